@@ -22,6 +22,12 @@ RCCL carries the config broadcast and the result gather.
   --scaling strong          : --total-problems problems in all (north_star: 8192 x 2048x128, 1024 x 2048x128)
 
 Prints ONE JSON line on rank 0.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: the headline, its
+config and the roofline of the timed steps' own HIP-event brackets.  `--full` adds everything else the line can carry: the
+CPU baseline and the parity sample, the per-kernel breakdown pass, the other policies, sizes and solver paths.
+`--dump-outputs DIR` writes what the last timed step returned (x, fvec, iteration info, status) as .npy files; the inputs
+depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -40,6 +46,34 @@ SEED0 = 12345
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (about 6.3 TB/s achievable)
 POLICY_NAMES = {0: "auto (J^T J MFMA + Cholesky, QR fallback)", 1: "householder-qr (tree reductions)",
                 2: "exact (lmfactor / lmpar in the reference's operation order)"}
+INFO_KEYS = ("iter_count", "fcn_count", "jacobian_count", "gradient_count", "converge_on_fcn", "converge_on_chng",
+             "converge_on_zero_diff")                  # nlh_iteration_behavior, in field order
+DUMP_LIMIT_BYTES = 64 * 10**6                          # --dump-outputs: array payload in all
+
+
+def dump_outputs(out_dir, arrays, seed=SEED0, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write each array (problems along axis 0, global problem order) as out_dir/<name>.npy in float64.
+    Arrays are cut to fit `limit` bytes in all, largest first, each to a sorted sample of its problems drawn by a generator
+    seeded with `seed` (the same problems from run to run); such an array's problem indices go to <name>_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name in sorted(arrays, key=lambda k: arrays[k].nbytes, reverse=True):
+        a = arrays[name]
+        if total <= limit:
+            break
+        nprob = a.shape[0]
+        row = a.nbytes // max(nprob, 1)
+        # the sample's own index file (8 bytes per kept problem) counts against the limit too
+        keep = max(0, min(nprob, (limit - (total - a.nbytes)) // (row + 8)))
+        idx = np.sort(np.random.default_rng(seed).choice(nprob, size=keep, replace=False))
+        arrays[name] = a[idx]
+        arrays[name + "_index"] = idx.astype(np.float64)
+        total += arrays[name].nbytes + 8 * keep - a.nbytes
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def fd_bytes(m, n):
@@ -949,14 +983,27 @@ def main():
     # ambiguous abbreviations of its options even behind the script name)
     ap.add_argument("--m", "--mrows", dest="m", type=int, default=M)
     ap.add_argument("--n", "--ncols", dest="n", type=int, default=N_VAR)
-    ap.add_argument("--cpu-sample", type=int, default=32,
-                    help="problems solved by the CPU oracle: the cpu_baseline timing and the parity sample (0 = skip)")
-    ap.add_argument("--extras", type=int, default=1,
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline as well: the CPU baseline and the parity sample, "
+                         "the per-kernel breakdown pass and the other policies, sizes and paths (the defaults of --cpu-sample, "
+                         "--extras and --other-paths become 32, 1 and 1).  Without it a run sets up, warms up, times the "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy (float64, "
+                         "problems in global order): x.npy, fvec.npy, iteration_info.npy (columns " + ", ".join(INFO_KEYS)
+                         + "), status.npy; an array cut to a seeded sample of its problems to stay within "
+                         f"{DUMP_LIMIT_BYTES // 10**6} MB in all comes with <name>_index.npy, the problems it holds")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="problems solved by the CPU oracle: the cpu_baseline timing and the parity sample (0 = skip; "
+                         "default 32 with --full, else 0)")
+    ap.add_argument("--extras", type=int, default=None,
                     help="0 = only the timed steps (profiles/capture_r06.sh: every launch rocprofv3 sees then belongs to a "
-                         "warm-up or timed step, so its per-kernel averages are the ones printed here)")
-    ap.add_argument("--other-paths", type=int, default=1,
+                         "warm-up or timed step, so its per-kernel averages are the ones printed here); default 1 with "
+                         "--full, else 0")
+    ap.add_argument("--other-paths", type=int, default=None,
                     help="1 = also time the Newton / quasi-Newton / bounded LSQ / BFGS / polynomial rows (SURVEY 8 a16-a24, "
-                         "f1-f4) on the GPU and on the CPU oracle and check the results bit for bit")
+                         "f1-f4) on the GPU and on the CPU oracle and check the results bit for bit; default 1 with --full, "
+                         "else 0")
     ap.add_argument("--policy", type=int, default=2,
                     help="factor policy of the timed steps: 2 exact (reference operation order, the parity-carrying one), "
                          "0 auto (J^T J + Cholesky), 1 QR with tree reductions")
@@ -964,6 +1011,11 @@ def main():
                     help="sub-batches in flight during the timed steps (1: per-kernel durations are those of one lock-step "
                          "batch; the library default -- several in flight -- is reported as `default_options`)")
     args = ap.parse_args()
+    for name, full_default in (("cpu_sample", 32), ("extras", 1), ("other_paths", 1)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -1048,7 +1100,7 @@ def main():
         njac += sum(ib["jacobian_count"] for ib in ibs)
         naccept += sum(ib["iter_count"] - 1 for ib in ibs)
         bad += sum(1 for s in status if s != 0)
-        last_ibs = ibs
+        last_ibs, last_status = ibs, status
     sync()
     elapsed = time.perf_counter() - t0
     gc.enable()
@@ -1061,14 +1113,22 @@ def main():
     elapsed = float(tt[0])
     njac_all, naccept_all, bad_all = (float(v) for v in cnt.tolist())
 
-    # per-problem counts in global problem order (reporting only; x and fvec were gathered inside the timed steps)
-    rows = torch.tensor([[ib["iter_count"], ib["fcn_count"], ib["jacobian_count"]] for ib in last_ibs],
-                        dtype=torch.float64, device=dev).reshape(B, 3)
+    # per-problem counts, flags and status in global problem order (reporting only; x and fvec were gathered inside the
+    # timed steps)
+    rows = torch.tensor([[ib[k] for k in INFO_KEYS] + [s] for ib, s in zip(last_ibs, last_status)],
+                        dtype=torch.float64, device=dev).reshape(B, len(INFO_KEYS) + 1)
     allrows = sharding.gather_results(rows, nprob_total, rank, world)
     gather_ok = None
     if gathered is not None:                                     # this rank's own rows came back where they belong
         mine = torch.tensor(sharding.shard_indices(nprob_total, rank, world), device=dev)
         gather_ok = bool(torch.equal(gathered[mine, :n], x)) and bool(torch.equal(gathered[mine, n:], fv[0]))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        xs, fs = (gathered[:, :n], gathered[:, n:]) if gathered is not None else (x, fv[0])
+        info = allrows.cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, {"x": xs.cpu().numpy(), "fvec": fs.cpu().numpy(),
+                                                  "iteration_info": info[:, :len(INFO_KEYS)],
+                                                  "status": info[:, len(INFO_KEYS)]})
 
     roof_ms, roof_launches = ds.h.timing(roof_kernel)
     roof_samples = ds.h.timing_samples(roof_kernel) if args.sub_batches == 1 else []
@@ -1152,6 +1212,8 @@ def main():
                 "avg_launch_ms": roof_ms / max(roof_launches, 1),
             },
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped                 # name -> shape of every array written under --dump-outputs
         if args.policy == 2:
             # The builder's own ceiling beside the spec peak: what the memory system delivers for THIS traffic shape, from the
             # stream microbenchmarks (profiles/ubench/rw_stream.hip, numbers in profiles/r04_ubench.txt: a read-only stream in

@@ -23,7 +23,7 @@ run_cfg c5auto --mrows 65536 --ncols 512 --batch 1 --policy 0   # config 5, norm
 run_cfg c2auto --batch 2048 --policy 0                  # the opt-in fast policy at the headline shape
 # config 5 under the normal-equations policy once more WITHOUT the profiler and with the per-kernel breakdown: the line's
 # kernel_rooflines (Gram against the fp64 MFMA peak, HIP events) is what DESIGN.md quotes next to the rocprofv3 averages
-timeout 600 python3 bench.py --steps 3 --warmup 1 --mrows 65536 --ncols 512 --batch 1 --policy 0 --cpu-sample 0 --other-paths 0 > "$OUT/r04_c5auto_bench_extras.json" 2> "$OUT/c5auto_extras.err"
+timeout 600 python3 bench.py --full --steps 3 --warmup 1 --mrows 65536 --ncols 512 --batch 1 --policy 0 --cpu-sample 0 --other-paths 0 > "$OUT/r04_c5auto_bench_extras.json" 2> "$OUT/c5auto_extras.err"
 # FETCH_SIZE calibration for the 8-byte-per-lane streaming pattern of k_qrx_pass (known byte count)
 ( cd profiles/ubench && hipcc -O3 --offload-arch=gfx950 -o fetch_calib fetch_calib.hip > /dev/null 2>&1 )
 timeout 120 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/calib" -o r04 -- profiles/ubench/fetch_calib > "$OUT/calib.log" 2>&1
@@ -50,6 +50,6 @@ ls -la "$OUT"
 # (added later in round 4) the other solvers' kernels after the latency work on LU, the Householder step, the BFGS pieces and
 # the triangular solves: one bench pass with only the other_paths rows, per-kernel stats; the LU of n = 1024 alone
 OUT=$PWD/gpurun_out/prof_r04; mkdir -p "$OUT"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/other.stats" -o r04 -- python3 bench.py --steps 1 --warmup 0 --batch 16 --m 1024 --n 64 --cpu-sample 0 --extras 0 > "$OUT/other.stats.log" 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/other.stats" -o r04 -- python3 bench.py --full --steps 1 --warmup 0 --batch 16 --m 1024 --n 64 --cpu-sample 0 --extras 0 > "$OUT/other.stats.log" 2>&1
 f=$(find "$OUT/other.stats" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$OUT/r04_other_paths_kernel_stats.csv"
 rm -rf "$OUT/other.stats"

@@ -22,8 +22,8 @@ pmc() {     # tag, bench args: FETCH_SIZE / WRITE_SIZE, one pass each
         timeout 600 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$OUT/$tag.$grp" -o r05 -- python3 bench.py --steps 1 --warmup 0 $COMMON "$@" > "$OUT/$tag.$grp.log" 2>&1
     done
 }
-# 1. the default bench line, no profiler (what the driver runs)
-python3 bench.py > "$OUT/r05_bench_default.json" 2> "$OUT/bench_default.err"
+# 1. the bench line with every block (--full), no profiler
+python3 bench.py --full > "$OUT/r05_bench_default.json" 2> "$OUT/bench_default.err"
 # 2. per-kernel stats + HBM counters of the BASELINE configs
 stats c2 python3 bench.py --steps 2 --warmup 1 $COMMON --batch 2048;                       pmc c2 --batch 2048
 stats c4 python3 bench.py --steps 2 --warmup 1 $COMMON --mrows 2048 --ncols 128 --batch 1024; pmc c4 --mrows 2048 --ncols 128 --batch 1024
@@ -31,7 +31,7 @@ stats c5 python3 bench.py --steps 2 --warmup 1 $COMMON --mrows 65536 --ncols 512
 stats c5auto python3 bench.py --steps 2 --warmup 1 $COMMON --mrows 65536 --ncols 512 --batch 1 --policy 0; pmc c5auto --mrows 65536 --ncols 512 --batch 1 --policy 0
 stats c2auto python3 bench.py --steps 2 --warmup 1 $COMMON --batch 2048 --policy 0
 # config 5 under the normal-equations policy WITHOUT the profiler, with the per-kernel breakdown (kernel_rooflines: Gram vs the fp64 MFMA peak)
-timeout 600 python3 bench.py --steps 3 --warmup 1 --mrows 65536 --ncols 512 --batch 1 --policy 0 --cpu-sample 0 --other-paths 0 > "$OUT/r05_c5auto_bench_extras.json" 2> "$OUT/c5auto_extras.err"
+timeout 600 python3 bench.py --full --steps 3 --warmup 1 --mrows 65536 --ncols 512 --batch 1 --policy 0 --cpu-sample 0 --other-paths 0 > "$OUT/r05_c5auto_bench_extras.json" 2> "$OUT/c5auto_extras.err"
 # MFMA-busy and effective clock of the Gram kernel (its own pass: counters only)
 timeout 600 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES --kernel-trace --output-format csv -d "$OUT/c5auto.MFMA" -o r05 -- python3 bench.py --steps 2 --warmup 1 $COMMON --mrows 65536 --ncols 512 --batch 1 --policy 0 > "$OUT/c5auto.MFMA.log" 2>&1
 python3 - "$OUT" <<'PY'
@@ -66,7 +66,7 @@ stats mid_4096x256_47 python3 profiles/sweep_mid.py 4096x256:47
 stats mid_2048x128_128 python3 profiles/sweep_mid.py 2048x128:128
 stats lone_4096x256 python3 profiles/sweep_mid.py 4096x256:1
 # 5. the other solvers' kernels (Newton, LU n = 1024, bounded least squares, BFGS, polynomial fits, mode H)
-stats other_paths python3 bench.py --steps 1 --warmup 0 --batch 16 --m 1024 --n 64 --cpu-sample 0 --extras 0
+stats other_paths python3 bench.py --full --steps 1 --warmup 0 --batch 16 --m 1024 --n 64 --cpu-sample 0 --extras 0
 stats lu_n1024 python3 profiles/lu_time.py 1024
 # FETCH_SIZE calibration for the 8-byte-per-lane streaming pattern of k_qrx_pass (known byte count)
 ( cd profiles/ubench && hipcc -O3 --offload-arch=gfx950 -o fetch_calib fetch_calib.hip > "$OUT/fetch_calib.build.log" 2>&1 )

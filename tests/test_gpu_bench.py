@@ -1,11 +1,12 @@
-"""GPU test of the bench.py contract: one JSON line with the driver's keys plus `roofline`, `cpu_baseline` and the
-parity check against the oracle, directly (the timed path is the parity-carrying exact policy) and under the torchrun
-launch line the driver uses for N > 1."""
+"""GPU test of the bench.py contract: one JSON line with the driver's keys plus `roofline`; under --full also
+`cpu_baseline` and the parity check against the oracle, directly (the timed path is the parity-carrying exact policy) and
+under the torchrun launch line the driver uses for N > 1; a plain run's line and its --dump-outputs files."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +31,7 @@ def _check(line, n_gpus, scaling="weak"):
 
 def test_bench_single_process():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--batch", "16",
-                          "--m", "1024", "--n", "64", "--cpu-sample", "4"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--m", "1024", "--n", "64", "--cpu-sample", "4", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _check(out.stdout.strip().splitlines()[-1], 1)
     assert "m=1024,n=64" in d["metric"]
@@ -107,3 +108,37 @@ def test_bench_strong_scaling_mode_one_rank():
     assert out.returncode == 0, out.stderr[-2000:]
     d = _check(out.stdout.strip().splitlines()[-1], 1, scaling="strong")
     assert d["config"]["problems_total"] == 24 and d["config"]["problems_rank0"] == 24
+
+
+FULL_ONLY = ("cpu_baseline", "parity", "kernel_ms_per_step", "kernel_rooflines", "default_options", "single_problem",
+             "auto_policy", "fd_jacobian_mode_h", "auto_policy_zero_residual", "predicted_scaling", "other_paths",
+             "device_vecfcn")
+
+
+def test_bench_plain_run_dumps_what_the_timed_path_returned(tmp_path, oracle):
+    """A plain run prints the headline line without any of --full's blocks, times exactly --steps steps, and
+    --dump-outputs writes the last step's x, fvec, iteration info and status: the CPU oracle's answers on the same seeds,
+    bit for bit."""
+    nprob, m, n, steps = 6, 512, 32, 2
+    dump = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                          "--batch", str(nprob), "--m", str(m), "--n", str(n), "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _check(out.stdout.strip().splitlines()[-1], 1)
+    assert d["steps"] == steps and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert not [k for k in FULL_ONLY if k in d]
+    assert d["roofline"]["launches"] > 0 and "event_bracketing" not in d["roofline"]
+    x, fvec = np.load(dump / "x.npy"), np.load(dump / "fvec.npy")
+    info, status = np.load(dump / "iteration_info.npy"), np.load(dump / "status.npy")
+    assert sorted(os.listdir(dump)) == ["fvec.npy", "iteration_info.npy", "status.npy", "x.npy"]     # nothing sampled
+    assert all(a.dtype == np.float64 for a in (x, fvec, info, status))
+    assert x.shape == (nprob, n) and fvec.shape == (nprob, m) and info.shape == (nprob, 7) and status.shape == (nprob,)
+    assert d["dumped_outputs"] == {"x": [nprob, n], "fvec": [nprob, m], "iteration_info": [nprob, 7], "status": [nprob]}
+    keys = ("iter_count", "fcn_count", "jacobian_count", "gradient_count", "converge_on_fcn", "converge_on_chng",
+            "converge_on_zero_diff")
+    for k in range(nprob):
+        A, b, xt, x0 = oracle.dq_generate(12345 + k, m, n, gamma=0.5, sigma=1e-3, spread=0.3)
+        rc, xo, fo, ibo = oracle.dq_lm_solve(A, b, 0.5, x0, opts=oracle.default_options(max_evals=500))[:4]
+        assert np.array_equal(x[k], xo) and np.array_equal(fvec[k], fo), k
+        assert info[k].tolist() == [ibo[q] for q in keys] and status[k] == rc, (k, info[k], ibo)
