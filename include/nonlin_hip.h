@@ -337,6 +337,29 @@ int nlh_bfgs_solve_batch_device(nlh_handle *h, const nlh_options *opts, int32_t 
 int nlh_bfgs_solve_batch_device_h(nlh_handle *h, const nlh_options *opts, int32_t nprob, int32_t n, nlh_device_vecfcn fcn,
                                   nlh_device_jacfcn gradfcn, void *ctx, double *x, double *fout, nlh_iteration_behavior *ib,
                                   int32_t *status);
+/* nelder_mead%solve -- nm_solve, src/nonlin_optimize.f90:104-340 (nm_extrapolate :343-399).  opts->max_evals =
+ * get_max_fcn_evals() (500, src/nonlin_multi_var.f90:62-66), opts->gtol = get_tolerance() (1e-12), opts->print_status (the
+ * block of :306-313 after every iteration); the other options are not read.  init_size: m_initSize (1.0).  simplex: [n+1][n]
+ * host (vertex-major: the reference's ndim x npts column-major matrix) or NULL; use_simplex = 1 starts from it (x is
+ * ignored), 0 builds it from x and init_size (:183-213); when non-NULL the final simplex is written back, so a second call
+ * with use_simplex = 1 continues where the first stopped, as the reference's object state does.  fout may be NULL.
+ * Returns 0 (x = the best vertex, :258-266) or NLH_CONVERGENCE_ERROR after max_evals (x untouched, fout = f of the initial
+ * vertex 1: :220, :316-337).  ib: iter_count counts the final convergence check (:230); fcn_count grows by n + 1 per shrink
+ * although a shrink evaluates n points (:299).  The callback runs on the calling thread; the simplex logic runs on the
+ * device (the machine of nlh_nelder_mead_solve_batch_device with one problem). */
+int nlh_nelder_mead_solve(nlh_handle *h, const nlh_options *opts, double init_size, int32_t n, nlh_fcnnvar fcn, void *ctx,
+                          double *x, double *simplex, int32_t use_simplex, double *fout, nlh_iteration_behavior *ib);
+/* ... on nprob problems of the USER'S device fcnnvar (an nlh_device_vecfcn called with m = 1: dF[npoints] = f at each
+ * point; a round asks for the points of every problem at once, in ascending problem order).  dx [nprob][n] and dsimplex
+ * [nprob][n+1][n] (or NULL: the library's own) DEVICE; fout / ib / status host [nprob] (NULL allowed); status[p] = 0 or
+ * NLH_CONVERGENCE_ERROR.  print_status is not honoured.  A problem's bits do not depend on the batch it is solved in. */
+int nlh_nelder_mead_solve_batch_device(nlh_handle *h, const nlh_options *opts, double init_size, int32_t nprob, int32_t n,
+                                       nlh_device_vecfcn fcn, void *ctx, double *dx, double *dsimplex, int32_t use_simplex,
+                                       double *fout, nlh_iteration_behavior *ib, int32_t *status);
+/* ... on a model of ONE function made by nlh_device_fcn_model_create (m = 1), host x [nprob][n] in/out, simplex built from
+ * x: what the Fortran shim's nelder_mead%solve_batch calls.  A dense-quadratic model or m > 1: NLH_INVALID_OPERATION_ERROR. */
+int nlh_dq_model_nelder_mead_solve(nlh_handle *h, const nlh_options *opts, double init_size, const nlh_dq_model *model,
+                                   double *x, double *fout, nlh_iteration_behavior *ib, int32_t *status);
 /* The same three behind HOST arrays x [nprob][n] in/out, fvec [nprob][m] out (what the Fortran shim's
  * vecfcn_helper%set_device_fcn + solver%solve / solve_batch call): staged through the handle's buffers. */
 int nlh_lm_solve_batch_device_h(nlh_handle *h, const nlh_options *opts, int32_t nprob, int32_t m, int32_t n,

@@ -609,3 +609,54 @@ class bfgs(line_search_optimizer):
         if rc:
             raise NonlinError(rc)                 # :765-767
         return fout.value
+
+
+class nelder_mead(equation_optimizer):
+    """src/nonlin_optimize.f90:24-41: the Nelder-Mead simplex method.  The simplex is object state: a second solve
+    continues from the final simplex of the first (:180-203)."""
+
+    def __init__(self):
+        super().__init__()
+        self._simplex = None                      # m_simplex (n x n+1, Fortran order), unallocated
+        self._init_size = 1.0                     # m_initSize
+
+    def get_simplex(self):                        # :402-418
+        return None if self._simplex is None else self._simplex.copy()
+
+    def set_simplex(self, x):                     # :421-437
+        self._simplex = None if x is None else np.array(x, dtype=np.float64, order="F", copy=True)
+
+    def get_initial_size(self): return self._init_size          # :440-451
+    def set_initial_size(self, x): self._init_size = float(x)   # :454-466
+
+    def solve(self, fcn, x, ib=None, args=None):
+        """nm_solve (:104-340).  x: initial estimate -> minimiser (in place; untouched when max evaluations stop the
+        solve).  Returns fout.  NonlinError(106) is raised after ib and the object's simplex are stored."""
+        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous):
+            raise ValueError("x must be a contiguous float64 numpy array (it is updated in place)")
+        if ib is not None:
+            ib._fill(_lib.IterationBehavior())    # :159-167
+        if not fcn.is_fcn_defined():
+            raise NonlinError(NL_UNDEFINED_FUNCTION_ERROR)   # :170
+        n = fcn.get_variable_count()
+        if x.shape != (n,):
+            raise NonlinError(NL_INVALID_INPUT_ERROR)        # :171
+        o = _lib.default_options()
+        o.max_evals = self._max_eval
+        o.gtol = self._tol
+        o.print_status = 1 if self._print else 0
+        h = self.handle or default_handle()
+        use = self._simplex is not None and self._simplex.shape == (n, n + 1)      # :176-188
+        # vertex-major [n+1][n] == the Fortran n x (n+1) matrix in column-major order
+        sim = np.ascontiguousarray(self._simplex.T) if use else np.zeros((n + 1, n))
+        cib = _lib.IterationBehavior()
+        fout = C.c_double(0.0)
+        rc = h.lib.nlh_nelder_mead_solve(h.ptr, C.byref(o), self._init_size, n, fcn._c_fcn(args), None, _dp(x), _dp(sim),
+                                         1 if use else 0, C.cast(C.byref(fout), _lib.c_double_p), C.byref(cib))
+        h.check(rc, "nlh_nelder_mead_solve")
+        self._simplex = np.asfortranarray(sim.T)
+        if ib is not None:
+            ib._fill(cib)
+        if rc:
+            raise NonlinError(rc)                 # :335-337
+        return fout.value

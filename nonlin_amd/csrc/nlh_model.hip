@@ -361,6 +361,16 @@ int nlh_dq_model_cls_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_mod
                      });
 }
 
+// nelder_mead%solve on every problem of a user's model of ONE function (the launcher is the fcnnvar, called with m = 1).
+// The dense-quadratic family has no Nelder-Mead form, and a vector launcher is not nelder_mead's plugin.
+int nlh_dq_model_nelder_mead_solve(nlh_handle *h, const nlh_options *o, double init_size, const nlh_dq_model *md, double *x,
+                                   double *fout, nlh_iteration_behavior *ib, int32_t *status)
+{
+    if (!md || !o) return NLH_INVALID_INPUT_ERROR;
+    if (!md->ufcn || md->m != 1) return NLH_INVALID_OPERATION_ERROR;
+    return nlh_nm_solve_batch_device_h(h, o, init_size, md->nprob, md->n, md->ufcn, md->uctx, x, fout, ib, status);
+}
+
 // bfgs%solve on 0.5 ||F(x)||^2 of every problem of the model (forward-difference gradient); fout [nprob]: the objective
 // at the solution, fvec [nprob][m]: F there.
 int nlh_dq_model_bfgs_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_model *md, double *x, double *fvec, double *fout,

@@ -243,6 +243,27 @@ class DeviceSolver:
             raise RuntimeError(f"nlh_bfgs_solve_batch_device returned {rc}")
         return [float(v) for v in fout], [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
 
+    def nelder_mead_solve_batch_device(self, fcn, ctx, x, simplex=None, init_size=1.0, opts=None):
+        """nelder_mead%solve for every problem with the USER'S device fcnnvar (fcn a launcher called with m = 1).  x [nprob][n]
+        device tensor, in place (the best vertex on convergence, untouched after max evaluations).  simplex: None (built
+        from x and init_size) or a [nprob][n+1][n] device tensor to start from (x ignored), updated in place to the final
+        simplex.  Returns (fout list, ib list, status list)."""
+        nprob, n = x.shape
+        _chk(x, (nprob, n), "x")
+        if simplex is not None:
+            _chk(simplex, (nprob, n + 1, n), "simplex")
+        ib = (_lib.IterationBehavior * nprob)()
+        status = (C.c_int32 * nprob)()
+        fout = (C.c_double * nprob)()
+        o = opts or self.options(max_evals=500)
+        rc = self.lib.nlh_nelder_mead_solve_batch_device(self.h.ptr, C.byref(o), float(init_size), nprob, n, self._devfcn(fcn),
+                                                         self._ctxp(ctx), x.data_ptr(), simplex.data_ptr() if simplex is not None else None,
+                                                         0 if simplex is None else 1, fout, ib, status)
+        self.h.check(rc, "nlh_nelder_mead_solve_batch_device")
+        if rc:
+            raise RuntimeError(f"nlh_nelder_mead_solve_batch_device returned {rc}")
+        return [float(v) for v in fout], [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+
     def fd_jacobian_device(self, fcn, ctx, m, x, fv=None, jac=None):
         """vecfcn_helper%jacobian of every problem of a user's device residual: J [nprob, n, m]."""
         nprob, n = x.shape

@@ -242,6 +242,33 @@ module nonlin_hip_c
             integer(c_int32_t), intent(out) :: status(*)
             integer(c_int) :: rc
         end function
+        function nlh_nelder_mead_solve(h, opts, init_size, n, fcn, ctx, x, simplex, use_simplex, fout, ib) &
+                bind(C, name="nlh_nelder_mead_solve") result(rc)
+            import :: c_ptr, c_funptr, c_int, c_int32_t, c_double, nlh_options, nlh_iteration_behavior
+            type(c_ptr), value :: h
+            type(nlh_options), intent(in) :: opts
+            real(c_double), value :: init_size
+            integer(c_int32_t), value :: n
+            type(c_funptr), value :: fcn
+            type(c_ptr), value :: ctx
+            real(c_double), intent(inout) :: x(*), simplex(*)
+            integer(c_int32_t), value :: use_simplex
+            real(c_double), intent(out) :: fout
+            type(nlh_iteration_behavior), intent(out) :: ib
+            integer(c_int) :: rc
+        end function
+        function nlh_dq_model_nelder_mead_solve(h, opts, init_size, model, x, fout, ib, status) &
+                bind(C, name="nlh_dq_model_nelder_mead_solve") result(rc)
+            import :: c_ptr, c_int, c_int32_t, c_double, nlh_options, nlh_iteration_behavior
+            type(c_ptr), value :: h, model
+            type(nlh_options), intent(in) :: opts
+            real(c_double), value :: init_size
+            real(c_double), intent(inout) :: x(*)
+            real(c_double), intent(out) :: fout(*)
+            type(nlh_iteration_behavior), intent(out) :: ib(*)
+            integer(c_int32_t), intent(out) :: status(*)
+            integer(c_int) :: rc
+        end function
         function nlh_dq_model_bfgs_solve(h, opts, model, x, fvec, fout, ib, status) &
                 bind(C, name="nlh_dq_model_bfgs_solve") result(rc)
             import :: c_ptr, c_int, c_int32_t, c_double, nlh_options, nlh_iteration_behavior

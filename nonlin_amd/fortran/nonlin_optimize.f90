@@ -1,6 +1,7 @@
-! line_search_optimizer and bfgs: the public types and bindings of src/nonlin_optimize.f90:44-72, 470-556.
-! bfgs%solve marshals to nlh_bfgs_solve (bfgs_solve behind the C ABI, :557-770); the line search is a parameter
-! record here.  nelder_mead is outside the hot path.
+! nelder_mead, line_search_optimizer and bfgs: the public types and bindings of src/nonlin_optimize.f90:24-72, 400-556.
+! nelder_mead%solve marshals to nlh_nelder_mead_solve (nm_solve behind the C ABI, :104-340; the simplex stays object
+! state here, as m_simplex does in the reference); bfgs%solve to nlh_bfgs_solve (bfgs_solve, :557-770); the line search
+! is a parameter record here.
 module nonlin_optimize
     use iso_fortran_env
     use, intrinsic :: iso_c_binding
@@ -13,8 +14,21 @@ module nonlin_optimize
     use nonlin_shim_support
     implicit none
     private
+    public :: nelder_mead
     public :: line_search_optimizer
     public :: bfgs
+
+    type, extends(equation_optimizer) :: nelder_mead
+        real(real64), private, allocatable, dimension(:,:) :: m_simplex
+        real(real64), private :: m_initSize = 1.0d0
+    contains
+        procedure, public :: solve => nm_solve_one
+        procedure, public :: solve_batch => nm_solve_many
+        procedure, public :: get_simplex => nm_get_simplex
+        procedure, public :: set_simplex => nm_set_simplex
+        procedure, public :: get_initial_size => nm_get_size
+        procedure, public :: set_initial_size => nm_set_size
+    end type
 
     type, abstract, extends(equation_optimizer) :: line_search_optimizer
         class(line_search), private, allocatable :: search_
@@ -39,6 +53,121 @@ module nonlin_optimize
     end type
 
 contains
+    pure function nm_get_simplex(this) result(p)               ! :402-416
+        class(nelder_mead), intent(in) :: this
+        real(real64), allocatable, dimension(:,:) :: p
+        if (allocated(this%m_simplex)) then
+            allocate(p(size(this%m_simplex, 1), size(this%m_simplex, 2)))
+            p = this%m_simplex
+        end if
+    end function
+
+    subroutine nm_set_simplex(this, x)                         ! :419-440
+        class(nelder_mead), intent(inout) :: this
+        real(real64), dimension(:,:) :: x
+        if (allocated(this%m_simplex)) deallocate(this%m_simplex)
+        allocate(this%m_simplex(size(x, 1), size(x, 2)))
+        this%m_simplex = x
+    end subroutine
+
+    pure function nm_get_size(this) result(x)                  ! :445-455
+        class(nelder_mead), intent(in) :: this
+        real(real64) :: x
+        x = this%m_initSize
+    end function
+
+    subroutine nm_set_size(this, x)                            ! :458-468
+        class(nelder_mead), intent(inout) :: this
+        real(real64), intent(in) :: x
+        this%m_initSize = x
+    end subroutine
+
+    !> nm_solve (:104-340): the simplex logic runs on the device, the objective on this thread through the trampoline.
+    !> An m_simplex of the right shape (ndim x npts) is the start and x is ignored (:176-188); otherwise the simplex is
+    !> built from x (:205-213).  Either way the final simplex is kept for the next call.
+    subroutine nm_solve_one(this, fcn, x, fout, ib, args)
+        class(nelder_mead), intent(inout) :: this
+        class(fcnnvar_helper), intent(in), target :: fcn
+        real(real64), intent(inout), dimension(:) :: x
+        real(real64), intent(out), optional :: fout
+        type(iteration_behavior), optional :: ib
+        class(*), intent(inout), optional, target :: args
+
+        type(nlh_options) :: opts
+        type(nlh_iteration_behavior) :: counters
+        type(nlh_scalar_ctx), target :: ctx
+        real(c_double), allocatable :: xwork(:)
+        real(c_double) :: fmin
+        integer(c_int) :: rc
+        integer(c_int32_t) :: use_simplex
+        integer(int32) :: n
+
+        n = fcn%get_variable_count()
+        if (present(ib)) call behavior_clear(ib)                                   ! :159-167
+        if (.not.fcn%is_fcn_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR    ! :170
+        if (size(x) /= n) error stop NL_INVALID_INPUT_ERROR                      ! :171
+        use_simplex = 0
+        if (allocated(this%m_simplex)) then                                        ! :176-188
+            if (size(this%m_simplex, 1) == n .and. size(this%m_simplex, 2) == n + 1) then
+                use_simplex = 1
+            else
+                deallocate(this%m_simplex)
+            end if
+        end if
+        if (.not.allocated(this%m_simplex)) allocate(this%m_simplex(n, n + 1))
+        call nlh_default_options(opts)
+        opts%max_evals = this%get_max_fcn_evals()
+        opts%gtol = this%get_tolerance()
+        opts%print_status = merge(1, 0, this%get_print_status())
+        ctx%helper => fcn
+        if (present(args)) ctx%args => args
+        allocate(xwork(n), source = x)
+        rc = nlh_nelder_mead_solve(nlh_default_handle(), opts, this%m_initSize, n, c_funloc(nlh_fcnnvar_trampoline), &
+            c_loc(ctx), xwork, this%m_simplex, use_simplex, fmin, counters)
+        if (rc < 0) error stop rc
+        x = xwork
+        if (present(fout)) fout = fmin                                             ! :333
+        if (present(ib)) call behavior_import(ib, counters)                        ! :322-330
+        if (rc /= 0) error stop rc                                                 ! :335-337
+    end subroutine
+
+    !> Extension: nelder_mead%solve on every problem of a batch created from the user's own device function with ONE
+    !> function per problem (device_model_batch%create_from_device_fcn, nfcn = 1): the launcher is the user's fcnnvar.
+    !> Each problem's simplex is built from its column of x(n, count) with get_initial_size() (the object's simplex is
+    !> neither read nor changed).  fout(count), status(count): the code each solve would have stopped with (0: converged).
+    subroutine nm_solve_many(this, model, x, fout, ib, status)
+        class(nelder_mead), intent(inout) :: this
+        class(device_model_batch), intent(in) :: model
+        real(real64), intent(inout), dimension(:,:) :: x
+        real(real64), intent(out), dimension(:), optional :: fout
+        type(iteration_behavior), intent(out), dimension(:), optional :: ib
+        integer(int32), intent(out), dimension(:), optional :: status
+
+        type(nlh_options) :: opts
+        type(nlh_iteration_behavior), allocatable :: counters(:)
+        integer(c_int32_t), allocatable :: outcome(:)
+        real(c_double), allocatable :: xwork(:,:), fmin(:)
+        integer(c_int) :: rc
+        integer(int32) :: n, count
+
+        if (.not.model%is_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR
+        n = model%get_variable_count()
+        count = model%get_problem_count()
+        if (any(shape(x) /= [n, count])) error stop NL_INVALID_INPUT_ERROR
+        call nlh_default_options(opts)
+        opts%max_evals = this%get_max_fcn_evals()
+        opts%gtol = this%get_tolerance()
+        allocate(counters(count), outcome(count), fmin(count))
+        allocate(xwork(n, count), source = x)
+        rc = nlh_dq_model_nelder_mead_solve(nlh_default_handle(), opts, this%m_initSize, model%c_handle(), xwork, fmin, &
+            counters, outcome)
+        if (rc /= 0) error stop rc
+        x = xwork
+        if (present(fout)) fout = fmin
+        if (present(status)) status = outcome
+        if (present(ib)) call behavior_import(ib, counters)
+    end subroutine
+
     pure logical function lsopt_has_search(this)
         class(line_search_optimizer), intent(in) :: this
         lsopt_has_search = allocated(this%search_)
