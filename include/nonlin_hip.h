@@ -43,9 +43,12 @@ extern "C" {
 #define NLH_UNDERDEFINED_PROBLEM_ERROR 212   /* (:37) */
 /* Size limits of this implementation (the reference has none); an entry point given a larger problem returns
  * NLH_ARRAY_SIZE_ERROR and touches nothing: quasi-Newton and BFGS n <= 8192 (columns per thread of the single-workgroup
- * rotation kernels); least squares under the opt-in NLH_FACTOR_AUTO / NLH_FACTOR_QR policies n <= 3000 (n-vectors in LDS).
- * Least squares under the default NLH_FACTOR_EXACT policy takes any n <= m (beyond 3000 columns lmpar's n-vectors live in
- * global memory); that is verified at n = 3008 -- the solver's own kernels have no bound in n, but the BUILT-IN
+ * rotation kernels); least squares under the opt-in NLH_FACTOR_AUTO / NLH_FACTOR_QR policies n <= 3000 (n-vectors in LDS);
+ * the stage-level nlh_lmpar n <= 3358 (its n-vectors in LDS).  Dynamic LDS is capped at 160 KiB - 2 KiB = 161,792 bytes
+ * per workgroup; no kernel is launched with more.  Least squares under the default NLH_FACTOR_EXACT policy takes any n <= m
+ * (beyond 2902 columns lmpar's n-vectors live in global memory; verified at n = 2903 - 3008), and Newton's LU solve
+ * (nlh_newton_solve*, nlh_lu_solve) any n (beyond 13137 its permuted right-hand side and pivots live in global memory;
+ * verified at n = 13138 - 13312) -- the solvers' own kernels have no bound in n, but the BUILT-IN
  * dense-quadratic family (the bench / test residual of nlh_dq_*, not part of the reference) keeps a point's x in LDS and
  * stops at n = 20000 (NLH_ARRAY_SIZE_ERROR from its launcher); a user's device function has whatever bound its own kernels
  * have.  Row counts are not limited: polynomial fits and bounded least squares beyond 18000 rows keep the

@@ -20,6 +20,24 @@ int ensure(nlh_handle *h, DevBuf &b, size_t bytes)
     return 0;
 }
 
+bool lds_fits(const void *kernel, size_t dyn)
+{
+    static std::mutex mu;
+    static std::vector<std::pair<const void *, size_t>> statics;      // (kernel, static LDS bytes), looked up once each
+    size_t st = 0;
+    {
+        std::lock_guard<std::mutex> g(mu);
+        auto it = std::find_if(statics.begin(), statics.end(), [&](const std::pair<const void *, size_t> &e) { return e.first == kernel; });
+        if (it != statics.end()) st = it->second;
+        else {
+            hipFuncAttributes a;
+            st = hipFuncGetAttributes(&a, kernel) == hipSuccess ? a.sharedSizeBytes : (size_t)NLH_LDS_MAX;   // (unknown: no launch)
+            statics.emplace_back(kernel, st);
+        }
+    }
+    return st + dyn <= (size_t)NLH_LDS_MAX;
+}
+
 int ensure_staging(nlh_handle *h, size_t bytes)
 {
     if (bytes <= h->staging_bytes) return 0;
@@ -105,7 +123,7 @@ int nlh_create(nlh_handle **out, int32_t device, void *hip_stream)
     h->device = device;
     h->stream = (hipStream_t)hip_stream;     // NULL = the device's default (null) stream
     // allow the single-workgroup kernels their full dynamic LDS (n-vectors live there)
-    const int lds_max = 160 * 1024 - 2048;
+    const int lds_max = NLH_LDS_MAX;
     qrx_init_device();
     nlh_lm_init_device(lds_max);
     nlh_square_init_device(lds_max);

@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <mutex>
 #include <thread>
 #include <atomic>
 #include <string>
@@ -51,7 +52,7 @@ struct nlh_handle {
     std::vector<DevBuf *> bufs;       // every workspace buffer, for destroy
     // named workspace buffers (grown on demand, reused across calls)
     DevBuf J, P, wa4, scratch, G, Gpart, vecs, ipvt, gvec, part, state, info, misc, lu, xdev, fdev, Adev, bdev, W2, R,
-           qnQ, qnR, qnV, bfB, bfR, bfV, qxV, lumv,
+           qnQ, qnR, qnV, bfB, bfR, bfV, qxV, lumv, lus,
            dvX, dvF, dvIdx, dvP;          // user device residuals: points, compact residuals, problem lists, panel chunk (nlh_devfcn.hip)
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -75,6 +76,11 @@ struct nlh_handle {
 
 
 int ensure(nlh_handle *h, DevBuf &b, size_t bytes);              // grow-on-demand device workspace, registered for destroy
+// The dynamic LDS nlh_create allows every single-workgroup kernel (hipFuncAttributeMaxDynamicSharedMemorySize).
+static const int NLH_LDS_MAX = 160 * 1024 - 2048;
+// Does a launch of `kernel` with `dyn` bytes of dynamic LDS fit NLH_LDS_MAX, the kernel's static LDS included?  Asked
+// before every launch whose dynamic LDS grows with n: a launch the runtime refuses would leave its problems where they are.
+bool lds_fits(const void *kernel, size_t dyn);
 int ensure_staging(nlh_handle *h, size_t bytes);
 int ensure_pinned(nlh_handle *h, size_t bytes);
 void timing_flush(nlh_handle *h);

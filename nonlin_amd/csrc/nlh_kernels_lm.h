@@ -707,7 +707,7 @@ k_lmpar(int m, int n, double *__restrict__ Rall, LmVecs v, double *__restrict__ 
         const double *__restrict__ Jall, double *__restrict__ W2all /* [nprob][n*n] scratch */,
         LmState *__restrict__ st, int want_stage, double *__restrict__ gv = nullptr, int ringcap = 0)
 {   // ringcap > 0: lmsolve's sweep on chip, its ring behind the other LDS vectors (lmsolve_ring_doubles(n, threads) doubles).
-    // GV: lmpar's n-vectors in [nprob][6 n + 8] doubles of global memory (gv) when they do not fit LDS (n > 3000; the
+    // GV: lmpar's n-vectors in [nprob][6 n + 8] doubles of global memory (gv) when they do not fit LDS (n > 2902; the
     // reference allocates for any n, src/nonlin_least_squares.f90:199-208): the same code through other pointers --
     // a workgroup's barriers order its own global accesses -- at L2 instead of LDS latency.  A compile-time switch: with
     // a run-time choice of the base the compiler loses the vectors' address space and every access to them becomes a

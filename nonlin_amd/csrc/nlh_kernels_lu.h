@@ -58,7 +58,9 @@ k_lu_factor(int n, double *__restrict__ Aall, int32_t *__restrict__ ipvt_all, in
     if (tid == 0 && info) info[p] = inf;
 }
 
-// Solve LU x = b in place (dynamic LDS: lu_solve_lds(n)).
+// Solve LU x = b in place (dynamic LDS: lu_solve_lds(n), n <= 13137; GV: lu_solve_lds_gv() -- P b and the pivots in
+// lu_solve_gv_doubles(n) doubles of global memory per problem, the same code through other pointers, barriers that also
+// wait for the workgroup's global stores).
 //
 // Round 4: BLOCKED substitution.  The straightforward form is 2 n barrier-separated steps of a sixteen-wave workgroup
 // (n = 1024: 0.85 ms, 0.4 us a step) after one thread has walked the n interchanges.  Here
@@ -71,17 +73,23 @@ k_lu_factor(int n, double *__restrict__ Aall, int32_t *__restrict__ ipvt_all, in
 // sequential loop skips (an exactly zero b(j)), and x(j) = b(j) / u(j,j) is the same IEEE division: the same bits.
 #define LUS_W 16
 static inline size_t lu_solve_lds(int n) { return sizeof(double) * ((size_t)n + 2 * LUS_W * LUS_W) + sizeof(int32_t) * ((size_t)n + 8 + 4); }
+static inline size_t lu_solve_lds_gv() { return sizeof(double) * (2 * LUS_W * LUS_W) + sizeof(int32_t) * 4; }
+__host__ __device__ inline size_t lu_solve_gv_doubles(int n) { return (size_t)n + ((size_t)n + 8 + 1) / 2; }
+template <bool GV>
+__device__ __forceinline__ void lus_barrier() { if (GV) __syncthreads(); else nlh_lds_barrier(); }
 
+template <bool GV>
 static __global__ void __launch_bounds__(1024)
 k_lu_solve(int n, const double *__restrict__ LUall, const int32_t *__restrict__ ipvt_all,
-           double *__restrict__ ball, const LmState *__restrict__ st, int want)
+           double *__restrict__ ball, const LmState *__restrict__ st, int want, double *__restrict__ gv)
 {
     constexpr int W = LUS_W;
-    extern __shared__ double bs[];
-    double *tri = bs + n;                                         // two buffers of tri[j * W + l] = a(jb + l, jb + j)
-    int32_t *ips = reinterpret_cast<int32_t *>(tri + 2 * W * W);
-    int32_t *flag = ips + n + 8;                                  // which of the block's back-substitution steps ran
+    extern __shared__ double smem[];
     const int p = blockIdx.x, tid = threadIdx.x, BS = blockDim.x, lane = tid & 63, wid = tid >> 6;
+    double *bs = GV ? gv + (size_t)p * lu_solve_gv_doubles(n) : smem;
+    double *tri = GV ? smem : bs + n;                             // two buffers of tri[j * W + l] = a(jb + l, jb + j)
+    int32_t *ips = reinterpret_cast<int32_t *>(GV ? bs + n : tri + 2 * W * W);
+    int32_t *flag = GV ? reinterpret_cast<int32_t *>(tri + 2 * W * W) : ips + n + 8;   // which of the block's back-substitution steps ran
     if (st && st[p].stage != want) return;                       // lock-step batches: only problems in this stage
     const double *a = LUall + (size_t)p * n * n;
     const int32_t *ipvt = ipvt_all + (size_t)p * n;
@@ -146,7 +154,7 @@ k_lu_solve(int n, const double *__restrict__ LUall, const int32_t *__restrict__ 
         const int w = n - jb < W ? n - jb : W;
         const int i0 = jb + W + tid;
         issue(k + 1);
-        nlh_lds_barrier();
+        lus_barrier<GV>();
         const double *tr = tri + buf * W * W;
         if (wid == 0) {
             double bl = (lane < w) ? bs[jb + lane] : 0.0;
@@ -161,7 +169,7 @@ k_lu_solve(int n, const double *__restrict__ LUall, const int32_t *__restrict__ 
             }
             if (lane < w) bs[jb + lane] = bl;
         }
-        nlh_lds_barrier();
+        lus_barrier<GV>();
         for (int i = i0; i < n; i += BS) {
             double bi = bs[i];
             if (i == i0) {
@@ -189,7 +197,7 @@ k_lu_solve(int n, const double *__restrict__ LUall, const int32_t *__restrict__ 
         const int jb = (2 * nblk - 1 - k) * W;
         const int w = n - jb < W ? n - jb : W;
         issue(k + 1);
-        nlh_lds_barrier();
+        lus_barrier<GV>();
         const double *tr = tri + buf * W * W;
         if (wid == 0) {
             const int l = lane & (W - 1);
@@ -212,7 +220,7 @@ k_lu_solve(int n, const double *__restrict__ LUall, const int32_t *__restrict__ 
             if (lane < w) bs[jb + lane] = bl;
             if (lane == 0) flag[0] = (int32_t)ran;
         }
-        nlh_lds_barrier();
+        lus_barrier<GV>();
         const unsigned ran = (unsigned)flag[0];
         for (int i = tid; i < jb; i += BS) {
             double bi = bs[i];

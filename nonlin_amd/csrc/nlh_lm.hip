@@ -191,8 +191,10 @@ static int launch_gram(nlh_handle *h, int nprob, int m, int n, const double *J, 
     return 0;
 }
 
-// up to here k_lmpar's six n-vectors (+ the exact reductions' scratch) fit 158 KB of LDS (NLH_LM_LDS_MAX_N: a smaller bound,
-// so that tests reach the global-memory form at small sizes)
+// up to here the normal-equations and tree-reduced QR policies keep k_lmpar's six n-vectors in LDS ((6 n + 72) doubles:
+// 144,576 B at n = 3000).  The exact policy's k_lmpar adds the exact reductions' scratch (2736 doubles at 1024 threads) and
+// keeps the vectors in LDS only where the whole request fits NLH_LDS_MAX (n <= 2902), in global memory beyond.
+// NLH_LM_LDS_MAX_N: a smaller bound, so that tests reach the global-memory form at small sizes.
 static const int LM_LDS_MAX_N = [] { const char *e = getenv("NLH_LM_LDS_MAX_N"); const int v = e ? atoi(e) : 3000; return v < 3000 ? v : 3000; }();
 
 // LDS of lmsolve's on-chip sweep for a k_lmpar launch (0 / *cap = 0: the global-memory wavefront).  NLH_LMSOLVE_GLOBAL=1
@@ -273,25 +275,33 @@ static int lm_factor_and_step(nlh_handle *h, const nlh_options *o, int nprob, in
             // 3,585 LM it/s for one lock-step batch of 2048 x 4096x256, 3,681 -> 3,511 with sub-batches; 47 x 4096x256 153.5 ->
             // 155.7 ms.  docs/lab_notebook.md.)
             Timed t(h, NLH_K_LMPAR);
-            if (n <= LM_LDS_MAX_N) {
-                int cap;
-                const size_t rb = lm_ring_bytes(n, lt_, &cap);
-                hipLaunchKernelGGL(k_lmpar<true>, dim3(nprob), dim3(lt_), shl + sizeof(double) * lmpar_scratch_doubles(lt_) + rb,
+            int cap;
+            const size_t rb = lm_ring_bytes(n, lt_, &cap);
+            const size_t lds = shl + sizeof(double) * lmpar_scratch_doubles(lt_) + rb;     // (the form in LDS: its real request)
+            if (n <= LM_LDS_MAX_N && lds_fits((const void *)k_lmpar<true>, lds)) {
+                hipLaunchKernelGGL(k_lmpar<true>, dim3(nprob), dim3(lt_), lds,
                                    h->stream, m, n, w.R, w.v, dx, w.wa4, w.P, w.J, w.W2, w.st, (int)ST_QR_READY, (double *)nullptr, cap);
             }
             else {                                              // lmpar's n-vectors in global memory (the misc buffer)
                 int rc2;
+                const size_t ldsg = sizeof(double) * (size_t)(64 + lmpar_scratch_doubles(ft));
+                if (!lds_fits((const void *)k_lmpar<true, true>, ldsg)) return NLH_ARRAY_SIZE_ERROR;
                 if ((rc2 = ensure(h, h->misc, sizeof(double) * (size_t)nprob * (6 * (size_t)n + 8)))) return rc2;
-                hipLaunchKernelGGL((k_lmpar<true, true>), dim3(nprob), dim3(ft), sizeof(double) * (size_t)(64 + lmpar_scratch_doubles(ft)),
+                hipLaunchKernelGGL((k_lmpar<true, true>), dim3(nprob), dim3(ft), ldsg,
                                    h->stream, m, n, w.R, w.v, dx, w.wa4, w.P, w.J, w.W2, w.st, (int)ST_QR_READY, (double *)h->misc.p);
             }
         }
+        HIPCHK(h, hipGetLastError());                           // a refused launch ends the solve now, not after max_evals rounds
         return 0;
     }
-    int rc = launch_gram(h, nprob, m, n, w.J, dfvec, w.G, w.g, w.st, ST_HAVE_JAC);
-    if (rc) return rc;
     int ringcap;                                                // lmsolve's on-chip sweep (the launches that can reach lmpar's iteration)
     const size_t ringb = lm_ring_bytes(n, lt_, &ringcap);
+    // (n <= LM_LDS_MAX_N, check_opts_lm: every launch below fits; asked all the same, before the first of them)
+    const size_t sh3 = sizeof(double) * (size_t)(3 * n + 64);
+    if (!lds_fits((const void *)k_lmpar<false>, shl + ringb) || !lds_fits((const void *)k_chol_factor, sh3) ||
+        !lds_fits((const void *)k_qr_factor, sh3)) return NLH_ARRAY_SIZE_ERROR;
+    int rc = launch_gram(h, nprob, m, n, w.J, dfvec, w.G, w.g, w.st, ST_HAVE_JAC);
+    if (rc) return rc;
     constexpr int NB = 16;
     {   // fast path: blocked Cholesky in natural order, G -> R
         Timed t(h, NLH_K_CHOL);
@@ -356,6 +366,7 @@ static int lm_factor_and_step(nlh_handle *h, const nlh_options *o, int nprob, in
         hipLaunchKernelGGL(k_lmpar<false>, dim3(nprob), dim3(lt_), shl + ringb, h->stream, m, n, w.R, w.v, dx, w.wa4, w.P,
                            w.J, w.W2, w.st, (int)ST_QR_READY, (double *)nullptr, ringcap);
     }
+    HIPCHK(h, hipGetLastError());
     return 0;
 }
 
@@ -850,14 +861,19 @@ int nlh_lmpar(nlh_handle *h, int32_t nprob, int32_t n, double *dR, int32_t ldr, 
               double *dpar, double *dxstep, double *dsdiag)
 {
     if (!h) return NLH_ERR_BAD_HANDLE;
+    if (nprob <= 0) return 0;
+    if (n < 1) return NLH_INVALID_INPUT_ERROR;
+    int cap;
+    const size_t rb = lm_ring_bytes(n, lmpar_threads(n), &cap);
+    const size_t sh = sizeof(double) * (size_t)(6 * n + 72) + rb;
+    // its n-vectors live in LDS only: n <= 3358 (a larger problem is the lock-step solver's, whose lmpar moves them to
+    // global memory)
+    if (!lds_fits((const void *)k_lmpar_standalone, sh)) return NLH_ARRAY_SIZE_ERROR;
     HIPCHK(h, hipSetDevice(h->device));
     int rc = ensure(h, h->misc, sizeof(double) * (size_t)nprob * n * n);
     if (rc) return rc;
     {
         Timed t(h, NLH_K_LMPAR);
-        int cap;
-        const size_t rb = lm_ring_bytes(n, lmpar_threads(n), &cap);
-        size_t sh = sizeof(double) * (size_t)(6 * n + 72) + rb;
         hipLaunchKernelGGL(k_lmpar_standalone, dim3(nprob), dim3(lmpar_threads(n)), sh, h->stream, n, dR, ldr, dipvt,
                            ddiag, dqtf, ddelta, dtailsq, dpar, dxstep, dsdiag, (double *)h->misc.p, cap);
     }

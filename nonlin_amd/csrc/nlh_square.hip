@@ -14,7 +14,7 @@ template <bool FAST> static void lu_panel_reg_attrs(int lds_max);
 
 void nlh_square_init_device(int lds_max)
 {
-    hipFuncSetAttribute((const void *)k_lu_solve, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    hipFuncSetAttribute((const void *)k_lu_solve<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     hipFuncSetAttribute((const void *)k_lu_panel_lds, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     broyden_kernel_attrs(lds_max);
     lu_panel_reg_attrs<false>(lds_max);
@@ -169,6 +169,22 @@ void launch_lu_factor(nlh_handle *h, int nprob, int n, double *dA, int32_t *dipv
     else lu_blocked<false>(h, nprob, n, dA, dipvt, dinfo, st, want, panel_mode);
 }
 
+// solve_lu for the problems of a batch in stage `want` (st == nullptr: all of them): P b and the pivots in LDS while
+// lu_solve_lds(n) fits (n <= 13137), in global memory (h->lus) beyond -- the same operations, the same bits.
+static int launch_lu_solve(nlh_handle *h, hipStream_t s, int nprob, int n, const double *dLU, const int32_t *dipvt, double *db,
+                           const LmState *st, int want)
+{
+    const dim3 grid(nprob), block(n >= 96 ? 1024 : 256);
+    if (lds_fits((const void *)k_lu_solve<false>, lu_solve_lds(n))) {
+        hipLaunchKernelGGL(k_lu_solve<false>, grid, block, lu_solve_lds(n), s, n, dLU, dipvt, db, st, want, (double *)nullptr);
+        return 0;
+    }
+    if (!lds_fits((const void *)k_lu_solve<true>, lu_solve_lds_gv())) return NLH_ARRAY_SIZE_ERROR;
+    int rc;
+    if ((rc = ensure(h, h->lus, sizeof(double) * lu_solve_gv_doubles(n) * (size_t)nprob))) return rc;
+    hipLaunchKernelGGL(k_lu_solve<true>, grid, block, lu_solve_lds_gv(), s, n, dLU, dipvt, db, st, want, (double *)h->lus.p);
+    return 0;
+}
 
 // ===========================================================================
 // Newton: ns_solve as a host loop; Jacobian, gradient, LU on the device.
@@ -279,8 +295,7 @@ static int newton_core(nlh_handle *h, const nlh_options *o, int n, NewtonEval &e
             launch_lu_factor(h, 1, n, dLU, dipvt, (int32_t *)nullptr);
             for (int i = 0; i < n; ++i) rhs[i] = -fvec[i];
             HIPCHK(h, hipMemcpyAsync(drhs, rhs.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(n >= 96 ? 1024 : 256), lu_solve_lds(n), s, n, (const double *)dLU, (const int32_t *)dipvt, drhs,
-                               (const LmState *)nullptr, -1);
+            if ((rc = launch_lu_solve(h, s, 1, n, dLU, dipvt, drhs, nullptr, -1))) break;
             HIPCHK(h, hipMemcpyAsync(dir.data(), drhs, sizeof(double) * n, hipMemcpyDeviceToHost, s));
             HIPCHK(h, hipMemcpyAsync(grad.data(), dgrad, sizeof(double) * n, hipMemcpyDeviceToHost, s));
             HIPCHK(h, hipStreamSynchronize(s));
@@ -698,8 +713,7 @@ static int square_lockstep(nlh_handle *h, const nlh_options *o, bool broyden, in
             hipLaunchKernelGGL(k_nt_rhs, dim3((n + 255) / 256, nprob), dim3(256), 0, s, n, (const double *)dfvec, ddir,
                                (const LmState *)st);
             launch_lu_factor(h, nprob, n, dJ, dipvt, nullptr, st, NT_NEED_JAC);          // :570
-            hipLaunchKernelGGL(k_lu_solve, dim3(nprob), dim3(n >= 96 ? 1024 : 256), lu_solve_lds(n), s, n, (const double *)dJ,
-                               (const int32_t *)dipvt, ddir, (const LmState *)st, (int)NT_NEED_JAC);   // :577
+            if ((rc = launch_lu_solve(h, s, nprob, n, dJ, dipvt, ddir, st, (int)NT_NEED_JAC))) return rc;   // :577
             hipLaunchKernelGGL(k_nt_step_begin, dim3(nprob), dim3(256), 0, s, n, no, (int)NT_NEED_JAC, dx, dxold, ddir, (const double *)dgrad,
                                (const double *)dfvec, (double *)nullptr, st, ns);
         }
@@ -918,8 +932,8 @@ int nlh_lu_solve(nlh_handle *h, int32_t nprob, int32_t n, const double *dLU, con
 {
     if (!h) return NLH_ERR_BAD_HANDLE;
     HIPCHK(h, hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_lu_solve, dim3(nprob), dim3(n >= 96 ? 1024 : 256), lu_solve_lds(n), h->stream, n, dLU, dipvt, db,
-                       (const LmState *)nullptr, -1);
+    int rc;
+    if ((rc = launch_lu_solve(h, h->stream, nprob, n, dLU, dipvt, db, nullptr, -1))) return rc;
     HIPCHK(h, hipGetLastError());
     return 0;
 }
