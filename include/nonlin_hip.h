@@ -55,7 +55,8 @@ extern "C" {
  * Householder reflector in global memory instead of LDS.
  * The number of problems of a batch is NOT limited: the lock-step drivers carry the problem index in a grid dimension
  * that holds 65535, and a larger batch is solved in slices of 65535 problems, one after the other, inside the entry point
- * (independent problems: the same bits). */
+ * (independent problems: the same bits).  The one-variable solvers' batches (brent_solver, newton_1var_solver) carry
+ * the problem index in the x dimension and are sliced at 2^28 problems, for their int32 point offsets. */
 /* library-level failures (not reference codes) */
 #define NLH_ERR_NO_DEVICE             -1
 #define NLH_ERR_HIP                   -2
@@ -363,6 +364,58 @@ int nlh_nelder_mead_solve_batch_device(nlh_handle *h, const nlh_options *opts, d
  * x: what the Fortran shim's nelder_mead%solve_batch calls.  A dense-quadratic model or m > 1: NLH_INVALID_OPERATION_ERROR. */
 int nlh_dq_model_nelder_mead_solve(nlh_handle *h, const nlh_options *opts, double init_size, const nlh_dq_model *model,
                                    double *x, double *fout, nlh_iteration_behavior *ib, int32_t *status);
+/* ---- equations of one variable: nonlin_single_var (src/nonlin_single_var.f90) + brent_solver / newton_1var_solver.
+ * fcn1var (:10-22) is an nlh_fcnnvar called with n = 1; fcn1var_helper%diff's user derivative (:154-200) likewise.
+ * equation_solver_1var's defaults (:45-54) are nlh_options' own: max_evals = get_max_fcn_evals() (100), ftol =
+ * get_fcn_tolerance() (1e-8), xtol = get_var_tolerance() (1e-12), gtol = get_diff_tolerance() (1e-12), print_status =
+ * get_print_status() (0); the other options are not read.  x1, x2: value_pair lim (src/nonlin_types.f90:31-36), in
+ * either order (both solvers sort them).  Returns 0, NLH_CONVERGENCE_ERROR (max_evals reached), NLH_INVALID_INPUT_ERROR
+ * (|x1 - x2| < epsilon, absolute: nothing is evaluated) or NLH_UNDEFINED_FUNCTION_ERROR (fcn NULL) -- the codes the
+ * reference error-stops with.  The callbacks run in list order on the calling thread; the solver's statements run on the
+ * device (the machine of the batch forms with one problem).  print_status prints the reference's blocks to stdout. */
+/* brent_solver%solve -- brent_solve, src/nonlin_solve.f90:643-835.  x is set to 0 before the input check (:691) and
+ * written only on convergence (:746, :751): a max-evaluations stop returns x = 0, f = fb and NLH_CONVERGENCE_ERROR.  f
+ * (NULL allowed) = fb (:820), 0 on invalid input.  ib: jacobian_count 0.  The a == c test is |a - c| < epsilon (:761);
+ * sign(tol1, xm) follows the sign of a negative zero (:802); status is printed after every evaluation, the last included
+ * (:808-810).  The first pass reads c, d and e unset when both sign tests of :726-727 fail -- fb == 0 exactly (reachable
+ * only with ftol <= 0) or fb NaN: they are 0. */
+int nlh_brent_solve(nlh_handle *h, const nlh_options *opts, nlh_fcnnvar fcn, void *ctx, double x1, double x2, double *x,
+                    double *f, nlh_iteration_behavior *ib);
+/* newton_1var_solver%solve -- newt1var_solve, src/nonlin_solve.f90:840-1032.  diff: the user's derivative, or NULL for
+ * f1h_diff_fcn's forward difference (h = sqrt(eps)|x|, sqrt(eps) when h < eps; f at x + h is evaluated and NOT counted;
+ * f' = (f(x + h) - f(x)) / h).  Every f + f' pair counts one evaluation and one derivative (ib->jacobian_count).  An
+ * endpoint with |f| < ftol returns at once: x = it, f = its value, fcn_count = 2, iter_count = 0, converge_on_fcn
+ * (:906-923).  The bisection / Newton-step exits (:953, :964) leave without evaluating at the new x.  f != NULL is the
+ * reference's "f present": one more evaluation at the final x, counted, its value discarded, f = the last ff
+ * (:1011-1017); f == NULL skips it.  Status is printed only on iterations that pass every test (:999-1001).  On invalid
+ * input x is left untouched. */
+int nlh_newton_1var_solve(nlh_handle *h, const nlh_options *opts, nlh_fcnnvar fcn, nlh_fcnnvar diff, void *ctx, double x1,
+                          double x2, double *x, double *f, nlh_iteration_behavior *ib);
+/* ... on nprob problems of the USER'S device fcn1var: an nlh_device_vecfcn called with n = 1, m = 1 (dF[q] = f at point
+ * dX[q]); newton's diff (NULL: forward differences, x and x + h in one round) an nlh_device_jacfcn with n = m = 1 (dJ[q]
+ * = f' at dX[q]), called once per round after fcn on the same list (entries of points that need no derivative -- a
+ * final evaluation -- are ignored).  A round asks every live problem for its points at once, in ascending problem
+ * order: brent 2 (a, b) then 1; newton 2 (x1, x2), then 2 per iteration (x, x + h) or 1 with diff, and 1 for the final
+ * evaluation when fout != NULL.  dlim [nprob][2], dx [nprob]: DEVICE; fout / ib / status: host [nprob], NULL allowed;
+ * fout != NULL is newton's "f present".  status[p] = 0, NLH_CONVERGENCE_ERROR or NLH_INVALID_INPUT_ERROR (a bad bracket
+ * in the batch: that problem evaluates nothing; the others are solved).  Any nprob (slices of 2^28 problems: int32
+ * point offsets); print_status is not honoured.  A problem's bits do not depend on the batch it is solved in. */
+int nlh_brent_solve_batch_device(nlh_handle *h, const nlh_options *opts, int32_t nprob, nlh_device_vecfcn fcn, void *ctx,
+                                 const double *dlim, double *dx, double *fout, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_newton_1var_solve_batch_device(nlh_handle *h, const nlh_options *opts, int32_t nprob, nlh_device_vecfcn fcn,
+                                       nlh_device_jacfcn diff, void *ctx, const double *dlim, double *dx, double *fout,
+                                       nlh_iteration_behavior *ib, int32_t *status);
+/* ... on a model made by nlh_device_fcn_model_create with n = m = 1 (its jacfcn, if any, is newton's derivative), host
+ * lim [nprob][2] and x [nprob]: what the Fortran shim's solve_batch calls.  n != 1, m != 1 or a dense-quadratic model:
+ * NLH_INVALID_OPERATION_ERROR. */
+int nlh_dq_model_brent_solve(nlh_handle *h, const nlh_options *opts, const nlh_dq_model *model, const double *lim, double *x,
+                             double *fout, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_dq_model_newton_1var_solve(nlh_handle *h, const nlh_options *opts, const nlh_dq_model *model, const double *lim,
+                                   double *x, double *fout, nlh_iteration_behavior *ib, int32_t *status);
+/* fcn1var_helper%diff -- f1h_diff_fcn, src/nonlin_single_var.f90:154-200: diff != NULL returns diff(x); otherwise the
+ * forward difference: f at x + h first, then f at x unless fv (f(x)) is given, df = (f(x + h) - f0) / h.  Host
+ * callbacks; needs no handle (like nlh_fd_gradient). */
+int nlh_fd_derivative(nlh_fcnnvar fcn, nlh_fcnnvar diff, void *ctx, double x, const double *fv, double *df);
 /* The same three behind HOST arrays x [nprob][n] in/out, fvec [nprob][m] out (what the Fortran shim's
  * vecfcn_helper%set_device_fcn + solver%solve / solve_batch call): staged through the handle's buffers. */
 int nlh_lm_solve_batch_device_h(nlh_handle *h, const nlh_options *opts, int32_t nprob, int32_t m, int32_t n,

@@ -155,6 +155,19 @@ SYMBOLS = {
                                                      c_int32_p]),
     "nlh_dq_model_nelder_mead_solve": (C.c_int, [_H, C.POINTER(Options), C.c_double, C.c_void_p, c_double_p, c_double_p,
                                                  C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_brent_solve": (C.c_int, [_H, C.POINTER(Options), FCNNVAR, C.c_void_p, C.c_double, C.c_double, c_double_p, c_double_p,
+                                  C.POINTER(IterationBehavior)]),
+    "nlh_newton_1var_solve": (C.c_int, [_H, C.POINTER(Options), FCNNVAR, FCNNVAR, C.c_void_p, C.c_double, C.c_double, c_double_p,
+                                        c_double_p, C.POINTER(IterationBehavior)]),
+    "nlh_brent_solve_batch_device": (C.c_int, [_H, C.POINTER(Options), C.c_int32, DEVFCN, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               c_double_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_newton_1var_solve_batch_device": (C.c_int, [_H, C.POINTER(Options), C.c_int32, DEVFCN, DEVFCN, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, c_double_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_dq_model_brent_solve": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, c_double_p, c_double_p, c_double_p,
+                                           C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_dq_model_newton_1var_solve": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, c_double_p, c_double_p, c_double_p,
+                                                 C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_fd_derivative": (C.c_int, [FCNNVAR, FCNNVAR, C.c_void_p, C.c_double, c_double_p, c_double_p]),
     "nlh_lm_solve_batch_device_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, DEVFCN, DEVFCN, C.c_void_p,
                                               c_double_p, c_double_p, C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_newton_solve_batch_device_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, DEVFCN, DEVFCN, C.c_void_p,

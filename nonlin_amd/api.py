@@ -660,3 +660,126 @@ class nelder_mead(equation_optimizer):
         if rc:
             raise NonlinError(rc)                 # :335-337
         return fout.value
+
+
+# ---------------------------------------------------------------------------------------------- equations of one variable
+class value_pair:
+    """src/nonlin_types.f90:31-36: a pair of values (the search limits of the one-variable solvers)."""
+
+    def __init__(self, x1=0.0, x2=0.0):
+        self.x1 = float(x1)
+        self.x2 = float(x2)
+
+
+class fcn1var_helper:
+    """src/nonlin_single_var.f90:25-43: holder of an equation of one variable fcn(x, args) -> float and, optionally, its
+    derivative diff(x, args) -> float."""
+
+    def __init__(self):
+        self._fcn = None
+        self._diff = None
+
+    def set_fcn(self, fcn): self._fcn = fcn                   # :132-141
+    def set_diff(self, diff): self._diff = diff               # :203-212
+    def is_fcn_defined(self): return self._fcn is not None    # :121-129
+    def is_derivative_defined(self): return self._diff is not None   # :143-152
+
+    def fcn(self, x, args=None):                              # :103-118 (silently 0 if unset)
+        return float(self._fcn(float(x), args)) if self._fcn is not None else 0.0
+
+    def diff(self, x, f=None, args=None):
+        """f1h_diff_fcn (:154-200): the user's derivative, or a forward difference (h = sqrt(eps)|x|, divided by h).  Runs
+        on the host through nlh_fd_derivative; needs no GPU."""
+        if f is not None:
+            fv = C.c_double(float(f))
+            fvp = C.cast(C.byref(fv), _lib.c_double_p)
+        else:
+            fvp = None
+        df = C.c_double(0.0)
+        rc = _lib.load().nlh_fd_derivative(self._c_fcn(args), self._c_diff(args), None, float(x), fvp,
+                                           C.cast(C.byref(df), _lib.c_double_p))
+        if rc:
+            raise NonlinError(rc)
+        return df.value
+
+    def _c_fcn(self, args):
+        f = self._fcn
+        if f is None:
+            return C.cast(None, _lib.FCNNVAR)
+        return _lib.FCNNVAR(lambda ctx, n, xp: float(f(xp[0], args)))
+
+    def _c_diff(self, args):
+        d = self._diff
+        if d is None:
+            return C.cast(None, _lib.FCNNVAR)
+        return _lib.FCNNVAR(lambda ctx, n, xp: float(d(xp[0], args)))
+
+
+class equation_solver_1var:
+    """src/nonlin_single_var.f90:45-69; defaults :47-54."""
+
+    def __init__(self):
+        self._max_eval = 100
+        self._fcn_tol = 1.0e-8
+        self._xtol = 1.0e-12
+        self._difftol = 1.0e-12
+        self._print = False
+        self.handle = None
+
+    def get_max_fcn_evals(self): return self._max_eval
+    def set_max_fcn_evals(self, n): self._max_eval = int(n)
+    def get_fcn_tolerance(self): return self._fcn_tol
+    def set_fcn_tolerance(self, x): self._fcn_tol = float(x)
+    def get_var_tolerance(self): return self._xtol
+    def set_var_tolerance(self, x): self._xtol = float(x)
+    def get_diff_tolerance(self): return self._difftol
+    def set_diff_tolerance(self, x): self._difftol = float(x)
+    def get_print_status(self): return self._print
+    def set_print_status(self, x): self._print = bool(x)
+
+    def _options(self):
+        o = _lib.default_options()
+        o.max_evals = self._max_eval
+        o.ftol = self._fcn_tol
+        o.xtol = self._xtol
+        o.gtol = self._difftol
+        o.print_status = 1 if self._print else 0
+        return o
+
+    def _solve(self, entry, fcn, lim, ib, args, with_diff):
+        """The reference's solve with f present.  Returns (x, f); NonlinError after ib is filled."""
+        if ib is not None:
+            ib._fill(_lib.IterationBehavior())
+        if not fcn.is_fcn_defined():
+            raise NonlinError(NL_UNDEFINED_FUNCTION_ERROR)
+        x1, x2 = (lim.x1, lim.x2) if isinstance(lim, value_pair) else (float(lim[0]), float(lim[1]))
+        h = self.handle or default_handle()
+        o = self._options()
+        x, f = C.c_double(0.0), C.c_double(0.0)
+        cib = _lib.IterationBehavior()
+        cargs = [fcn._c_fcn(args)] + ([fcn._c_diff(args)] if with_diff else [])
+        rc = getattr(h.lib, entry)(h.ptr, C.byref(o), *cargs, None, float(x1), float(x2), C.cast(C.byref(x), _lib.c_double_p),
+                                   C.cast(C.byref(f), _lib.c_double_p), C.byref(cib))
+        h.check(rc, entry)
+        if ib is not None:
+            ib._fill(cib)
+        if rc:
+            raise NonlinError(rc)
+        return x.value, f.value
+
+
+class brent_solver(equation_solver_1var):
+    """src/nonlin_solve.f90:69-76: Brent's method."""
+
+    def solve(self, fcn, lim, ib=None, args=None):
+        """brent_solve (:643-835).  lim: value_pair (or a pair).  Returns (x, f)."""
+        return self._solve("nlh_brent_solve", fcn, lim, ib, args, False)
+
+
+class newton_1var_solver(equation_solver_1var):
+    """src/nonlin_solve.f90:78-86: Newton's method for one variable, bracketed (bisection when a step leaves the bracket)."""
+
+    def solve(self, fcn, lim, ib=None, args=None):
+        """newt1var_solve (:840-1032) with f present (one more evaluation after the loop, its value discarded).  Returns
+        (x, f)."""
+        return self._solve("nlh_newton_1var_solve", fcn, lim, ib, args, True)

@@ -3,6 +3,7 @@
 // Units: nlh_core.hip (handle, options, timing, generator, residual / FD launches, worker handles), nlh_lm.hip
 // (least_squares_solver: lss_solve and its stages), nlh_square.hip (newton_solver, quasi_newton_solver, LU, the
 // Householder steps), nlh_cls.hip (constrained_least_squares_solver), nlh_bfgs.hip (bfgs, fcnnvar_helper%gradient), nlh_nm.hip (nelder_mead),
+// nlh_1var.hip (brent_solver, newton_1var_solver, fcn1var_helper%diff),
 // nlh_poly.hip (polynomial%fit), nlh_model.hip (device sets, device residual models behind host arrays), nlh_qrx.hip
 // (the exact lmfactor).  Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it
 // launches.
@@ -208,6 +209,11 @@ void nlh_bfgs_init_device(int lds_max);
 int nlh_nm_solve_batch_device_h(nlh_handle *h, const nlh_options *o, double init_size, int32_t nprob, int32_t n,
                                 nlh_device_vecfcn fcn, void *ctx, double *x, double *fout, nlh_iteration_behavior *ib,
                                 int32_t *status);
+// nlh_1var.hip: brent_solver (newton = 0) / newton_1var_solver (1) on a batch of the user's device fcn1var behind host
+// arrays lim [nprob][2], x [nprob]
+int nlh_root1v_solve_batch_device_h(nlh_handle *h, const nlh_options *o, int newton, int32_t nprob, nlh_device_vecfcn fcn,
+                                    nlh_device_jacfcn diff, void *ctx, const double *lim, double *x, double *fout,
+                                    nlh_iteration_behavior *ib, int32_t *status);
 void nlh_cls_init_device(int lds_max);
 void nlh_poly_init_device(int lds_max);
 void nlh_devfcn_init_device(int lds_max);        // nlh_devfcn.hip: the built-in family's launcher kernels keep x in LDS

@@ -371,6 +371,25 @@ int nlh_dq_model_nelder_mead_solve(nlh_handle *h, const nlh_options *o, double i
     return nlh_nm_solve_batch_device_h(h, o, init_size, md->nprob, md->n, md->ufcn, md->uctx, x, fout, ib, status);
 }
 
+// brent_solver%solve / newton_1var_solver%solve on every problem of a user's model of one equation in one unknown (the
+// launcher is the fcn1var, called with n = m = 1; newton's derivative is the model's jacfcn launcher, or forward
+// differences without one).  The dense-quadratic family has no such form.
+int nlh_dq_model_brent_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_model *md, const double *lim, double *x,
+                             double *fout, nlh_iteration_behavior *ib, int32_t *status)
+{
+    if (!md || !o) return NLH_INVALID_INPUT_ERROR;
+    if (!md->ufcn || md->m != 1 || md->n != 1) return NLH_INVALID_OPERATION_ERROR;
+    return nlh_root1v_solve_batch_device_h(h, o, 0, md->nprob, md->ufcn, nullptr, md->uctx, lim, x, fout, ib, status);
+}
+
+int nlh_dq_model_newton_1var_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_model *md, const double *lim, double *x,
+                                   double *fout, nlh_iteration_behavior *ib, int32_t *status)
+{
+    if (!md || !o) return NLH_INVALID_INPUT_ERROR;
+    if (!md->ufcn || md->m != 1 || md->n != 1) return NLH_INVALID_OPERATION_ERROR;
+    return nlh_root1v_solve_batch_device_h(h, o, 1, md->nprob, md->ufcn, md->ujac, md->uctx, lim, x, fout, ib, status);
+}
+
 // bfgs%solve on 0.5 ||F(x)||^2 of every problem of the model (forward-difference gradient); fout [nprob]: the objective
 // at the solution, fvec [nprob][m]: F there.
 int nlh_dq_model_bfgs_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_model *md, double *x, double *fvec, double *fout,

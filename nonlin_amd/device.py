@@ -7,9 +7,13 @@ A[p, j, i] = A_p(i, j)), b/fvec [nprob, m], x [nprob, n], all float64 on the GPU
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
+
+# nlh_iteration_behavior as a numpy structured dtype (the batch forms of the one-variable solvers return arrays of it)
+IB_DTYPE = np.dtype([(k, np.int32) for k, _ in _lib.IterationBehavior._fields_])
 
 
 def _chk(t, shape, name):
@@ -263,6 +267,34 @@ class DeviceSolver:
         if rc:
             raise RuntimeError(f"nlh_nelder_mead_solve_batch_device returned {rc}")
         return [float(v) for v in fout], [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+
+    def _root1v_batch(self, entry, fcns, ctx, lim, x, opts):
+        nprob = x.shape[0]
+        _chk(lim, (nprob, 2), "lim")
+        _chk(x, (nprob,), "x")
+        ibc = (_lib.IterationBehavior * nprob)()
+        ib = np.frombuffer(ibc, dtype=IB_DTYPE)             # a structured view on the ctypes buffer
+        status = np.zeros(nprob, dtype=np.int32)
+        fout = np.zeros(nprob, dtype=np.float64)
+        o = opts or self.options()
+        rc = getattr(self.lib, entry)(self.h.ptr, C.byref(o), nprob, *[self._devfcn(f) for f in fcns], self._ctxp(ctx),
+                                      lim.data_ptr(), x.data_ptr(), fout.ctypes.data_as(_lib.c_double_p), ibc,
+                                      status.ctypes.data_as(_lib.c_int32_p))
+        self.h.check(rc, entry)
+        if rc:
+            raise RuntimeError(f"{entry} returned {rc}")
+        return fout, status, ib
+
+    def brent_solve_batch_device(self, fcn, ctx, lim, x, opts=None):
+        """brent_solver%solve for every problem with the USER'S device fcn1var (fcn: a launcher called with n = m = 1).
+        lim [nprob, 2] and x [nprob]: float64 device tensors; x is written in place (0 unless the problem converged).
+        Returns numpy arrays (fout float64, status int32, ib: a structured array of the iteration_behavior fields)."""
+        return self._root1v_batch("nlh_brent_solve_batch_device", (fcn,), ctx, lim, x, opts)
+
+    def newton_1var_solve_batch_device(self, fcn, ctx, lim, x, diff=None, opts=None):
+        """newton_1var_solver%solve (with f present) for every problem: diff, the user's derivative launcher (n = m = 1),
+        or None for forward differences.  As brent_solve_batch_device."""
+        return self._root1v_batch("nlh_newton_1var_solve_batch_device", (fcn, diff), ctx, lim, x, opts)
 
     def fd_jacobian_device(self, fcn, ctx, m, x, fv=None, jac=None):
         """vecfcn_helper%jacobian of every problem of a user's device residual: J [nprob, n, m]."""

@@ -9,6 +9,7 @@ module nonlin
     use nonlin_polynomials
     use nonlin_multi_var
     use nonlin_optimize
+    use nonlin_single_var
     implicit none
     public
 end module

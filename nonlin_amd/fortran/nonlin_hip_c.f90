@@ -257,6 +257,64 @@ module nonlin_hip_c
             type(nlh_iteration_behavior), intent(out) :: ib
             integer(c_int) :: rc
         end function
+        function nlh_brent_solve(h, opts, fcn, ctx, x1, x2, x, f, ib) bind(C, name="nlh_brent_solve") result(rc)
+            import :: c_ptr, c_funptr, c_int, c_double, nlh_options, nlh_iteration_behavior
+            type(c_ptr), value :: h
+            type(nlh_options), intent(in) :: opts
+            type(c_funptr), value :: fcn
+            type(c_ptr), value :: ctx
+            real(c_double), value :: x1, x2
+            real(c_double), intent(inout) :: x
+            real(c_double), intent(out) :: f
+            type(nlh_iteration_behavior), intent(out) :: ib
+            integer(c_int) :: rc
+        end function
+        function nlh_newton_1var_solve(h, opts, fcn, diff, ctx, x1, x2, x, f, ib) &
+                bind(C, name="nlh_newton_1var_solve") result(rc)
+            import :: c_ptr, c_funptr, c_int, c_double, nlh_options, nlh_iteration_behavior
+            type(c_ptr), value :: h
+            type(nlh_options), intent(in) :: opts
+            type(c_funptr), value :: fcn, diff
+            type(c_ptr), value :: ctx
+            real(c_double), value :: x1, x2
+            real(c_double), intent(inout) :: x
+            type(c_ptr), value :: f
+            type(nlh_iteration_behavior), intent(out) :: ib
+            integer(c_int) :: rc
+        end function
+        function nlh_dq_model_brent_solve(h, opts, model, lim, x, fout, ib, status) &
+                bind(C, name="nlh_dq_model_brent_solve") result(rc)
+            import :: c_ptr, c_int, c_int32_t, c_double, nlh_options, nlh_iteration_behavior
+            type(c_ptr), value :: h, model
+            type(nlh_options), intent(in) :: opts
+            real(c_double), intent(in) :: lim(*)
+            real(c_double), intent(inout) :: x(*)
+            real(c_double), intent(out) :: fout(*)
+            type(nlh_iteration_behavior), intent(out) :: ib(*)
+            integer(c_int32_t), intent(out) :: status(*)
+            integer(c_int) :: rc
+        end function
+        function nlh_dq_model_newton_1var_solve(h, opts, model, lim, x, fout, ib, status) &
+                bind(C, name="nlh_dq_model_newton_1var_solve") result(rc)
+            import :: c_ptr, c_int, c_int32_t, c_double, nlh_options, nlh_iteration_behavior
+            type(c_ptr), value :: h, model
+            type(nlh_options), intent(in) :: opts
+            real(c_double), intent(in) :: lim(*)
+            real(c_double), intent(inout) :: x(*)
+            type(c_ptr), value :: fout
+            type(nlh_iteration_behavior), intent(out) :: ib(*)
+            integer(c_int32_t), intent(out) :: status(*)
+            integer(c_int) :: rc
+        end function
+        function nlh_fd_derivative(fcn, diff, ctx, x, fv, df) bind(C, name="nlh_fd_derivative") result(rc)
+            import :: c_ptr, c_funptr, c_int, c_double
+            type(c_funptr), value :: fcn, diff
+            type(c_ptr), value :: ctx
+            real(c_double), value :: x
+            type(c_ptr), value :: fv
+            real(c_double), intent(out) :: df
+            integer(c_int) :: rc
+        end function
         function nlh_dq_model_nelder_mead_solve(h, opts, init_size, model, x, fout, ib, status) &
                 bind(C, name="nlh_dq_model_nelder_mead_solve") result(rc)
             import :: c_ptr, c_int, c_int32_t, c_double, nlh_options, nlh_iteration_behavior

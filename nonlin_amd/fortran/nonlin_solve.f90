@@ -1,7 +1,9 @@
 ! line_search_solver, newton_solver and quasi_newton_solver: the public types and bindings of
 ! src/nonlin_solve.f90:20-67.  `solve` marshals to nlh_newton_solve / nlh_dq_model_newton_solve (ns_solve on
 ! the GPU, :452-638) and nlh_quasi_newton_solve (qns_solve, :156-427); the line search the solver owns is only
-! a parameter record here (nonlin_linesearch), the search runs behind the C ABI.
+! a parameter record here (nonlin_linesearch), the search runs behind the C ABI.  brent_solver and newton_1var_solver
+! (:69-86) marshal to nlh_brent_solve / nlh_newton_1var_solve (brent_solve :643-835, newt1var_solve :840-1032: the
+! solver's statements on the device, the user's function on this thread through the nonlin_single_var trampolines).
 module nonlin_solve
     use iso_fortran_env
     use, intrinsic :: iso_c_binding
@@ -11,11 +13,14 @@ module nonlin_solve
     use nonlin_types
     use nonlin_hip_c
     use nonlin_shim_support
+    use nonlin_single_var
     implicit none
     private
     public :: line_search_solver
     public :: newton_solver
     public :: quasi_newton_solver
+    public :: brent_solver
+    public :: newton_1var_solver
 
     type, abstract, extends(equation_solver) :: line_search_solver
         class(line_search), private, allocatable :: search_
@@ -43,6 +48,19 @@ module nonlin_solve
         procedure, public :: solve_batch => broyden_solve_many
         procedure, public :: get_jacobian_interval => broyden_refresh
         procedure, public :: set_jacobian_interval => broyden_put_refresh
+    end type
+
+
+    type, extends(equation_solver_1var) :: brent_solver
+    contains
+        procedure, public :: solve => brent_solve_one
+        procedure, public :: solve_batch => brent_solve_many
+    end type
+
+    type, extends(equation_solver_1var) :: newton_1var_solver
+    contains
+        procedure, public :: solve => newt1var_solve_one
+        procedure, public :: solve_batch => newt1var_solve_many
     end type
 
 contains
@@ -281,4 +299,172 @@ contains
         integer(int32), intent(in) :: n
         this%refresh_every_ = n
     end subroutine
+    ! ---- equations of one variable ----------------------------------------------------------------------------
+    function es1_options(this) result(opts)
+        class(equation_solver_1var), intent(in) :: this
+        type(nlh_options) :: opts
+        call nlh_default_options(opts)
+        opts%max_evals = this%get_max_fcn_evals()
+        opts%ftol = this%get_fcn_tolerance()
+        opts%xtol = this%get_var_tolerance()
+        opts%gtol = this%get_diff_tolerance()
+        opts%print_status = merge(1, 0, this%get_print_status())
+    end function
+
+    !> brent_solve (:643-835).  x = 0 unless the solve converged (:691, :746, :751); a failing solve error-stops with its
+    !> code after x, f and ib are stored.  The binding has the reference's dummies (nonlin_solver_1var); the work is done
+    !> by brent_solve_c, whose TARGET dummies the trampolines' context points at for the length of the call.
+    subroutine brent_solve_one(this, fcn, x, lim, f, ib, args)
+        class(brent_solver), intent(inout) :: this
+        class(fcn1var_helper), intent(in) :: fcn
+        real(real64), intent(inout) :: x
+        type(value_pair), intent(in) :: lim
+        real(real64), intent(out), optional :: f
+        type(iteration_behavior), optional :: ib
+        class(*), intent(inout), optional :: args
+        call brent_solve_c(this, fcn, x, lim, f, ib, args)
+    end subroutine
+
+    subroutine brent_solve_c(this, fcn, x, lim, f, ib, args)
+        class(brent_solver), intent(inout) :: this
+        class(fcn1var_helper), intent(in), target :: fcn
+        real(real64), intent(inout) :: x
+        type(value_pair), intent(in) :: lim
+        real(real64), intent(out), optional :: f
+        type(iteration_behavior), optional :: ib
+        class(*), intent(inout), optional, target :: args
+        type(nlh_iteration_behavior) :: counters
+        type(nlh_scalar1_ctx), target :: ctx
+        real(c_double) :: xv, fv
+        integer(c_int) :: rc
+        x = 0.0d0                                                                  ! :691
+        if (present(f)) f = 0.0d0                                                  ! :700
+        if (present(ib)) call behavior_clear(ib)                                   ! :701-709
+        if (.not.fcn%is_fcn_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR    ! :712
+        ctx%helper => fcn
+        if (present(args)) ctx%args => args
+        xv = 0.0d0
+        rc = nlh_brent_solve(nlh_default_handle(), es1_options(this), c_funloc(nlh_fcn1var_trampoline), c_loc(ctx), &
+            lim%x1, lim%x2, xv, fv, counters)
+        if (rc < 0) error stop rc
+        x = xv
+        if (present(f)) f = fv                                                     ! :820
+        if (present(ib)) call behavior_import(ib, counters)
+        if (rc /= 0) error stop rc                                                 ! :713, :832-834
+    end subroutine
+
+    !> newt1var_solve (:840-1032); f present: one more evaluation after the loop, its value discarded (:1011-1017).
+    !> The reference's dummies; the work is done by newt1var_solve_c (TARGET dummies, as brent_solve_c).
+    subroutine newt1var_solve_one(this, fcn, x, lim, f, ib, args)
+        class(newton_1var_solver), intent(inout) :: this
+        class(fcn1var_helper), intent(in) :: fcn
+        real(real64), intent(inout) :: x
+        type(value_pair), intent(in) :: lim
+        real(real64), intent(out), optional :: f
+        type(iteration_behavior), optional :: ib
+        class(*), intent(inout), optional :: args
+        call newt1var_solve_c(this, fcn, x, lim, f, ib, args)
+    end subroutine
+
+    subroutine newt1var_solve_c(this, fcn, x, lim, f, ib, args)
+        class(newton_1var_solver), intent(inout) :: this
+        class(fcn1var_helper), intent(in), target :: fcn
+        real(real64), intent(inout) :: x
+        type(value_pair), intent(in) :: lim
+        real(real64), intent(out), optional :: f
+        type(iteration_behavior), optional :: ib
+        class(*), intent(inout), optional, target :: args
+        type(nlh_iteration_behavior) :: counters
+        type(nlh_scalar1_ctx), target :: ctx
+        type(c_funptr) :: diff_entry
+        type(c_ptr) :: f_entry
+        real(c_double), target :: fv
+        real(c_double) :: xv
+        integer(c_int) :: rc
+        if (present(f)) f = 0.0d0                                                  ! :883
+        if (present(ib)) call behavior_clear(ib)                                   ! :884-892
+        if (.not.fcn%is_fcn_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR    ! :898
+        ctx%helper => fcn
+        if (present(args)) ctx%args => args
+        diff_entry = c_null_funptr
+        if (fcn%is_derivative_defined()) diff_entry = c_funloc(nlh_diff1var_trampoline)
+        f_entry = c_null_ptr
+        if (present(f)) f_entry = c_loc(fv)
+        xv = x
+        rc = nlh_newton_1var_solve(nlh_default_handle(), es1_options(this), c_funloc(nlh_fcn1var_trampoline), diff_entry, &
+            c_loc(ctx), lim%x1, lim%x2, xv, f_entry, counters)
+        if (rc < 0) error stop rc
+        x = xv
+        if (present(f)) f = fv                                                     ! :1017
+        if (present(ib)) call behavior_import(ib, counters)
+        if (rc /= 0) error stop rc                                                 ! :899, :1027-1029
+    end subroutine
+
+    !> Extension: brent_solver%solve on every problem of a batch created from the user's own device function of one
+    !> equation in one unknown (device_model_batch%create_from_device_fcn with nfcn = nvar = 1): lim(count), x(count),
+    !> f(count), status(count): the code each solve would have stopped with (0: converged).
+    subroutine brent_solve_many(this, model, lim, x, f, ib, status)
+        class(brent_solver), intent(inout) :: this
+        class(device_model_batch), intent(in) :: model
+        type(value_pair), intent(in), dimension(:) :: lim
+        real(real64), intent(inout), dimension(:) :: x
+        real(real64), intent(out), dimension(:), optional :: f
+        type(iteration_behavior), intent(out), dimension(:), optional :: ib
+        integer(int32), intent(out), dimension(:), optional :: status
+        call root1v_many(es1_options(this), 0, model, lim, x, f, ib, status)
+    end subroutine
+
+    !> Extension: newton_1var_solver%solve on every problem of such a batch (the model's Jacobian launcher, if any, is the
+    !> derivative; forward differences otherwise).  f present: the final evaluation of :1011-1014 is made.
+    subroutine newt1var_solve_many(this, model, lim, x, f, ib, status)
+        class(newton_1var_solver), intent(inout) :: this
+        class(device_model_batch), intent(in) :: model
+        type(value_pair), intent(in), dimension(:) :: lim
+        real(real64), intent(inout), dimension(:) :: x
+        real(real64), intent(out), dimension(:), optional :: f
+        type(iteration_behavior), intent(out), dimension(:), optional :: ib
+        integer(int32), intent(out), dimension(:), optional :: status
+        call root1v_many(es1_options(this), 1, model, lim, x, f, ib, status)
+    end subroutine
+
+    subroutine root1v_many(opts, newton, model, lim, x, f, ib, status)
+        type(nlh_options), intent(in) :: opts
+        integer, intent(in) :: newton
+        class(device_model_batch), intent(in) :: model
+        type(value_pair), intent(in), dimension(:) :: lim
+        real(real64), intent(inout), dimension(:) :: x
+        real(real64), intent(out), dimension(:), optional :: f
+        type(iteration_behavior), intent(out), dimension(:), optional :: ib
+        integer(int32), intent(out), dimension(:), optional :: status
+        type(nlh_iteration_behavior), allocatable :: counters(:)
+        integer(c_int32_t), allocatable :: outcome(:)
+        real(c_double), allocatable :: lw(:,:), xwork(:)
+        real(c_double), allocatable, target :: fw(:)
+        type(c_ptr) :: f_entry
+        integer(c_int) :: rc
+        integer(int32) :: count, k
+        if (.not.model%is_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR
+        count = model%get_problem_count()
+        if (size(lim) /= count .or. size(x) /= count) error stop NL_INVALID_INPUT_ERROR
+        allocate(counters(count), outcome(count), fw(count), lw(2, count))
+        allocate(xwork(count), source = x)
+        do k = 1, count
+            lw(1, k) = lim(k)%x1
+            lw(2, k) = lim(k)%x2
+        end do
+        if (newton == 0) then
+            rc = nlh_dq_model_brent_solve(nlh_default_handle(), opts, model%c_handle(), lw, xwork, fw, counters, outcome)
+        else
+            f_entry = c_null_ptr
+            if (present(f)) f_entry = c_loc(fw)
+            rc = nlh_dq_model_newton_1var_solve(nlh_default_handle(), opts, model%c_handle(), lw, xwork, f_entry, counters, &
+                outcome)
+        end if
+        if (rc /= 0) error stop rc
+        x = xwork
+        if (present(f)) f = fw
+        if (present(status)) status = outcome
+        if (present(ib)) call behavior_import(ib, counters)
+    end subroutine
+
 end module
