@@ -494,6 +494,46 @@ int nlh_qr_factor(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, double *dJ
 int nlh_lmfactor_exact(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, const double *dJ,
                        const double *df, double *dR, int32_t *dipvt, double *drdiag, double *dacnorm,
                        double *dqtf, double *dwa4);
+/* The launch plan of that factorisation: which kernels run at each of its n Householder steps for a batch of nprob
+ * m-by-n problems of which nact are expected to need factoring (<= 0: all; the LM solve passes its count, with
+ * have_stages = 1 for its per-problem stages).  Host code only -- no handle, no device -- walking the very stepper the
+ * factorisation walks, under the process's NLH_QRX_* environment.  Forms never change a result bit. */
+enum { NLH_QRX_SWEEP_COLUMN = 0,   /* a workgroup per trailing column, the update one step behind (a handful of problems) */
+       NLH_QRX_SWEEP_LANE = 1 };   /* a lane per trailing column, updates deferred to a flush every few steps */
+enum { NLH_QRX_INIT_SPLIT = 0,     /* initial column norms by a workgroup per column, in a launch of their own */
+       NLH_QRX_INIT_FUSED = 1 };   /* ... by a thread per column inside the init kernel */
+enum { NLH_QRX_PIVOT_FEW32 = 0,        /* k_qrx_pivot<32, false, true>: m <= 2048, a workgroup has its CU to itself */
+       NLH_QRX_PIVOT_BATCH32 = 1,      /* k_qrx_pivot<32>: four workgroups per CU */
+       NLH_QRX_PIVOT_FEW64 = 2,        /* k_qrx_pivot<64, false, true>: 4096-row NORM2 chunks, CU to itself */
+       NLH_QRX_PIVOT_BATCH64 = 3,      /* k_qrx_pivot<64> */
+       NLH_QRX_PIVOT_LONG = 4,         /* k_qrx_pivot<64, true>: columns of several chunks, pipelined NORM2, one launch */
+       NLH_QRX_PIVOT_LONG_SCALED = 5,  /* ... with the scaling of the reflector as a chip-wide launch of its own */
+       NLH_QRX_PIVOT_LONG_SPLIT = 6 }; /* ... and the gather too: search, gather, NORM2, scaling as four launches */
+enum { NLH_QRX_PASS_COLUMN = 0,        /* k_qrx_pass_col (the column sweep) */
+       NLH_QRX_PASS_WIDE = 1,          /* k_qrx_pass_rpw: sixteen waves per 64-column window, row-parallel */
+       NLH_QRX_PASS_WIDE_HALF = 2,     /* ... per 32-column half window */
+       NLH_QRX_PASS_FOUR_WAVE = 3,     /* k_qrx_pass_rp: four waves per window, row-parallel */
+       NLH_QRX_PASS_WAVE = 4,          /* k_qrx_pass: one wave per window, a workgroup each */
+       NLH_QRX_PASS_WAVE_SHARED = 5 }; /* ... the windows of a problem as the waves of one workgroup */
+typedef struct nlh_qrx_plan_head {
+    int32_t sweep, init;      /* NLH_QRX_SWEEP_*, NLH_QRX_INIT_* */
+    int32_t use_list, ny;     /* (problem, column) grids cover a compacted list of the ny problems that work, not the batch */
+    int32_t nact;             /* the count the plan was made for */
+} nlh_qrx_plan_head;
+typedef struct nlh_qrx_plan_step {
+    int32_t j, cur, np;       /* step, reflector bank, pending reflectors when the step starts */
+    int32_t lo;               /* lane sweep: first slot that can still hold live data (moves at a flush); column sweep: 0 */
+    int32_t flush, pf;        /* the pass writes the columns back and switches banks; the pivot kernel's flags
+                                 (1: this step's pass flushes, 2: the pass before did) */
+    int32_t pivot, pass;      /* NLH_QRX_PIVOT_*, NLH_QRX_PASS_*: the forms that are launched */
+    int32_t gwin;             /* what the pass's grid is built from, per problem: 64-column windows (wide_half: 32-column
+                                 half windows, column: trailing columns) */
+    int32_t lds, lds_max;     /* dynamic LDS bytes of the pass launch, and what its kernel is allowed */
+} nlh_qrx_plan_step;
+/* Fills *head and steps[0 .. min(n, cap)) (either may be NULL); returns n, -NLH_INVALID_INPUT_ERROR for nprob < 1,
+ * n < 1 or m < n, -NLH_INVALID_OPERATION_ERROR for a plan no kernel instance exists for (a defect of the library). */
+int32_t nlh_qrx_plan(int32_t nprob, int32_t m, int32_t n, int32_t nact, int32_t have_stages,
+                     nlh_qrx_plan_head *head, nlh_qrx_plan_step *steps, int32_t cap);
 /* lmpar (:394-566, including its two deviations from MINPACK) on an n-by-n R
  * (leading dimension ldr) for every problem.  dtailsq[k] = sum of squares of the
  * caller's wa4(n+1:m).  Outputs: dpar (in/out), dxstep [nprob][n], dsdiag [nprob][n]. */

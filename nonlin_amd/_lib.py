@@ -45,6 +45,16 @@ class Options(C.Structure):
                 ("sub_batches", C.c_int32)]
 
 
+class QrxPlanHead(C.Structure):
+    """nlh_qrx_plan_head."""
+    _fields_ = [(k, C.c_int32) for k in ("sweep", "init", "use_list", "ny", "nact")]
+
+
+class QrxPlanStep(C.Structure):
+    """nlh_qrx_plan_step."""
+    _fields_ = [(k, C.c_int32) for k in ("j", "cur", "np", "lo", "flush", "pf", "pivot", "pass", "gwin", "lds", "lds_max")]
+
+
 # every symbol include/nonlin_hip.h declares: name -> (restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = {
@@ -98,6 +108,8 @@ SYMBOLS = {
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_lmfactor_exact": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_qrx_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(QrxPlanHead),
+                                 C.POINTER(QrxPlanStep), C.c_int32]),
     "nlh_lmpar": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_lu_factor": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -48,6 +48,11 @@ static void qrx_time_end(nlh_handle *h, int, hipStream_t s)
     h->pending.push_back({h->qrx_a, h->qrx_b, h->qrx_kid});
     if (h->pending.size() > 65536) timing_flush(h);
 }
+static int qrx_no_launch(nlh_handle *h)      // qrx_factor met a planned step it has no kernel instance for
+{
+    h->err = "exact lmfactor: no kernel instance for a planned step";
+    return NLH_ERR_HIP;
+}
 // ---------------------------------------------------------------------------
 // small helper kernels of the drivers
 // ---------------------------------------------------------------------------
@@ -264,8 +269,9 @@ static int lm_factor_and_step(nlh_handle *h, const nlh_options *o, int nprob, in
             if ((rc = ensure(h, h->qxV, qrx_workspace_bytes(nprob, m, n)))) return rc;
             QrxTimer tm{h, [](void *c, int which, hipStream_t s) { qrx_time_begin((nlh_handle *)c, which, s); },
                         [](void *c, int which, hipStream_t s) { qrx_time_end((nlh_handle *)c, which, s); }};
-            qrx_factor(h->stream, nprob, m, n, jac_in_qrx_layout ? (const double *)nullptr : w.J, w.P, dfvec, w.R, w.v, w.wa4,
-                       w.scratch, dx, w.st, o->factor, o->gtol, h->qxV.p, &tm, nact);
+            if (qrx_factor(h->stream, nprob, m, n, jac_in_qrx_layout ? (const double *)nullptr : w.J, w.P, dfvec, w.R, w.v, w.wa4,
+                           w.scratch, dx, w.st, o->factor, o->gtol, h->qxV.p, &tm, nact))
+                return qrx_no_launch(h);
         }
         {
             // (Measured and dropped in round 5: lmpar's ITERATION -- the few problems whose Gauss-Newton step is not accepted; ten
@@ -825,8 +831,9 @@ int nlh_lmfactor_exact(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, const
     LmVecs v;
     memset(&v, 0, sizeof v);
     v.ipvt = dipvt; v.acnorm = dacnorm; v.qtf = dqtf; v.rdiag = drdiag;
-    qrx_factor(h->stream, nprob, m, n, dJ, (double *)h->P.p, df, dR, v, dwa4, dwa4, (const double *)nullptr, (LmState *)nullptr,
-               100.0, 0.0, h->qxV.p, (const QrxTimer *)nullptr, nprob);
+    if (qrx_factor(h->stream, nprob, m, n, dJ, (double *)h->P.p, df, dR, v, dwa4, dwa4, (const double *)nullptr, (LmState *)nullptr,
+                   100.0, 0.0, h->qxV.p, (const QrxTimer *)nullptr, nprob))
+        return qrx_no_launch(h);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -30,7 +30,8 @@ size_t qrx_workspace_bytes(int nprob, int m, int n);
 // T: row-major scratch (qrx_matrix_doubles); outputs: R (n x n column-major, upper + diagonal),
 // v.ipvt / acnorm / qtf / rdiag, wa4 = Q^T f, and -- when st != nullptr -- the outer-loop head (lm_head) with
 // stage -> ST_QR_READY / ST_DONE.  nact: how many of the nprob problems are expected to be at ST_NEED_QR (<= 0: all) --
-// only picks the kernel variant for nearly empty launches, never the result.
-void qrx_factor(hipStream_t stream, int nprob, int m, int n, const double *J, double *T, const double *fvec,
-                double *R, LmVecs v, double *wa4, double *scratch, const double *x, LmState *st, double factor,
-                double gtol, void *ws, const QrxTimer *tm, int nact);
+// only picks the kernel variant for nearly empty launches, never the result.  Which kernels run is the plan nlh_qrx_plan
+// (include/nonlin_hip.h) reports; returns 0, or -1 when that plan has a step no kernel instance exists for (a defect).
+int qrx_factor(hipStream_t stream, int nprob, int m, int n, const double *J, double *T, const double *fvec,
+               double *R, LmVecs v, double *wa4, double *scratch, const double *x, LmState *st, double factor,
+               double gtol, void *ws, const QrxTimer *tm, int nact);

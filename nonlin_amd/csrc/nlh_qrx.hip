@@ -44,7 +44,9 @@
 // (nlh_lm.hip, lm_sub_batches) so that one sub-batch's pivot kernels run under another's passes.
 #include "nlh_qrx.h"
 #include "nlh_common.h"
+#include "../../include/nonlin_hip.h"
 #include <type_traits>
+#include <cstdio>
 #include <cstdlib>
 #include <algorithm>
 
@@ -1260,9 +1262,8 @@ k_qrx_pass_rp(int p0, int nprob, int nwin, int lo, int m, int n, int ld, int cof
                                         // its producers read whole sectors per lane quad; ms per solve at 128 / 256 / 384 with them:
                                         // 44 x 4096x256 105.8 / 97.0 / 97.0, 64: 159 / 156 / 156, 128: 225 / 227 / 229, 256 x 2048x128 66.5 / 64.4 / 64.4)
 #endif
-#define QRX_RP_HALF 1632                // pass-form code: the wide form on 32-column half windows
 #ifndef QRX_RPWH_MAX_WG
-#define QRX_RPWH_MAX_WG 256             // ... while a launch has at most this many (problem, half window) pairs (ms per solve, off / 128 /
+#define QRX_RPWH_MAX_WG 256             // the wide form runs on 32-column half windows while a launch has at most this many (problem, half window) pairs (ms per solve, off / 128 /
                                         // 256 / 512: 13 x 4096x256 68.9 / 62.8 / 62.8 / 62.8, 24: 71.1 / 67.5 / 66.1 / 66.1, 32: 78.4 / 75.6 / 71.9 / 71.9,
                                         // 44: 91.9 / 91.0 / 88.0 / 91.9, 32 x 2048x128 23.2 / 21.6 / 21.6 / 21.6, 128: 34.6 / 34.2 / 34.1 / 36.6).  The gain is
                                         // small because the adder, not LDS bandwidth, sets the pace: ~7 ns per row whatever the column count
@@ -1874,74 +1875,286 @@ k_qrx_finish(int m, int n, int ld, int coff, size_t tst, size_t vst, int cur, in
     }
 }
 
-// two product buffers of 3 W / 4 * 8 rows x 64 lanes x 8 bytes (row pairs QRX_RPW_QSTR doubles apart), + the staged reflector entries
+// ---- The launch plan.  Which kernel runs at each Householder step is decided by host code that touches no device: QrxKnobs
+// (the NLH_QRX_* environment) and QrxPlanner, a stepper that qrx_factor and nlh_qrx_plan walk alike.  Its records are the C
+// ABI's (include/nonlin_hip.h): the form a shape reaches is a value to print, assert on and test without a GPU.
+
+// dynamic LDS of the wide form: two product buffers of 3 W / 4 * 8 rows x 64 lanes x 8 bytes (row pairs QRX_RPW_QSTR doubles
+// apart), + the staged reflector entries (120 KB at sixteen waves)
 static constexpr size_t qrx_rpw_lds(int W)
 {
     return sizeof(double) * ((size_t)(3 * W / 4) * QRX_RPW_G * QRX_RPW_QSTR + (size_t)QRX_RPW_NVB * (QRX_RPW_MAXNP + 1) * (3 * W / 4) * QRX_RPW_G);
 }
+// ... of the column form: two product buffers for columns of several chunks, one sized to the column otherwise
+static constexpr size_t QRX_COL_LDS_MAX = sizeof(double) * 2 * (64 * QRX_COL_EL + 128);
+static constexpr size_t qrx_col_lds(int m, int j)
+{
+    const int len = m - (j & ~7);
+    const int nrun = (((len + QRX_COL_EL - 1) / QRX_COL_EL) + 7) & ~7;                // the chain wave adds whole trips of eight runs
+    return len > 64 * QRX_COL_EL ? QRX_COL_LDS_MAX : sizeof(double) * (size_t)nrun * (QRX_COL_EL + 2);
+}
+// A pass with np pending updates; flushing ones exist for np = 1, 3, 4, 7 and QRX_C - 1 (flush periods 2, 4, 5, 8 and QRX_C).
+static constexpr bool qrx_can_flush(int np) { return np == 1 || np == 3 || np == QRX_RPW_MAXNP || (QRX_C > 8 && np == 7) || np == QRX_C - 1; }
+
+// The environment switches, for measurements (profiles/sweep_mid.py); none changes a result bit.  Read once per process;
+// a value that cannot be honoured is ignored, with one line on stderr, in favour of the built-in default.
+struct QrxKnobs {
+    long initn;        // NLH_QRX_INITN: most (problem, column) pairs whose initial norms take a workgroup per column while the
+                       // launch's chains would otherwise leave the chip idle (a thread per column walks its 4096 rows alone: 800 us
+                       // for 47 x 4096x256, whatever the count; k_qrx_init<true> is HBM-bound only from ~1000 problems on)
+    int period;        // NLH_QRX_PERIOD: steps between flushes, 1 .. QRX_C (0: the form's own); the flush comes at the first np
+                       // from period - 1 on that has a flushing instance
+    long rp_max;       // NLH_QRX_RP: most (problem, window) pairs of a row-parallel launch
+    long rpw16_max;    // NLH_QRX_RPW16: ... of the wide form
+    long rpwh_max;     // NLH_QRX_RPWH: most (problem, half window) pairs of the wide form on half windows
+    int col;           // NLH_QRX_COL: most active problems that take the column sweep (-1: by QRX_COL_MAX_WG pairs)
+    int few_max;       // NLH_QRX_FEW: most active problems that take the pivot kernel's FEW instances (NORM2's general runs out of
+                       // registers, at most two workgroups per CU: every launch whose workgroups are all resident at once anyway)
+    int piv32_maxm;    // NLH_QRX_PIV32_MAXM: rows up to which a BATCH takes the pivot kernel's 32-terms-per-lane instance (128
+                       // registers, four workgroups per CU; a column of more than 2048 rows then goes through its reflector slot
+                       // in memory and two NORM2 chunks).  Measured at 2048 x 4096x256 with the instance for 4096 rows too: 3,458 /
+                       // 3,428 against 3,458 / 3,500 LM it/s (same box, alternating runs): no gain, the default stays 2048.  (Also
+                       // built and measured: an instance whose threads gather whole 64-byte sectors -- sixteen consecutive elements
+                       // each, the column in registers from the gather to the scaling, two NORM2 chunks out of registers -- at
+                       // three / four workgroups per CU: 96 / 268 bytes of spills, 1.4 / 4.4 % SLOWER than the 64-term instance.)
+    int share;         // NLH_QRX_SHARE: 0 = the windows of a problem as separate workgroups
+    static long env(const char *name, long lo, long hi, long dflt)
+    {
+        const char *e = getenv(name);
+        if (!e) return dflt;
+        char *end;
+        const long v = strtol(e, &end, 10);
+        if (end != e && !*end && v >= lo && v <= hi) return v;
+        fprintf(stderr, "nonlin_hip: %s=%s ignored (not an integer in %ld .. %ld)\n", name, e, lo, hi);
+        return dflt;
+    }
+    QrxKnobs()
+    {
+        const long big = 0x7fffffff;
+        initn = std::max<long>(QRX_COL_MAX_WG, env("NLH_QRX_INITN", 0, big, 32768));
+        period = (int)env("NLH_QRX_PERIOD", 1, QRX_C, 0);
+        rp_max = env("NLH_QRX_RP", 0, big, QRX_RP_MAX_WG);
+        rpw16_max = std::min(rp_max, env("NLH_QRX_RPW16", 0, big, QRX_RPW16_MAX_WG));
+        rpwh_max = env("NLH_QRX_RPWH", 0, big, QRX_RPWH_MAX_WG);
+        col = (int)env("NLH_QRX_COL", 0, big, -1);
+        few_max = (int)env("NLH_QRX_FEW", 0, big, QRX_FEW_MAX);
+        piv32_maxm = (int)std::max<long>(2048, env("NLH_QRX_PIV32_MAXM", 0, big, QRX_PIV32_MAXM));
+        share = (int)env("NLH_QRX_SHARE", 0, 1, 1);
+    }
+};
+static const QrxKnobs &qrx_knobs() { static const QrxKnobs k; return k; }
+
+// A plan no kernel instance exists for is a defect of this file: -DNLH_DEBUG builds stop there, others report it.
+static int qrx_plan_bug(const nlh_qrx_plan_step &s)
+{
+    fprintf(stderr, "nonlin_hip: exact lmfactor: no launch for step %d (np %d, flush %d, pivot form %d, pass form %d)\n", s.j, s.np, s.flush, s.pivot, s.pass);
+#ifdef NLH_DEBUG
+    abort();
+#endif
+    return -1;
+}
+
+struct QrxPlanner {
+    const QrxKnobs &k;
+    const int m, n;
+    nlh_qrx_plan_head head;
+    int j = 0, cur = 0, np = 0, lo = 1;      // lo: first slot position that can still hold live data (step 0 moves physically)
+    bool prev_flushed = false;
+
+    QrxPlanner(int nprob, int m_, int n_, int nact, bool have_stages, const QrxKnobs &k_) : k(k_), m(m_), n(n_)
+    {
+        if (nact <= 0 || nact > nprob) nact = nprob;
+        const bool percol = (long)nact * n <= k.initn;
+        // launches with (columns x problems) grids cover the problems that work, not the batch (k_qrx_list)
+        head.use_list = have_stages && nact < nprob && percol;
+        head.ny = head.use_list ? nact : nprob;
+        head.init = percol ? NLH_QRX_INIT_SPLIT : NLH_QRX_INIT_FUSED;
+        head.sweep = (k.col >= 0 ? nact <= k.col : (long)nact * n <= QRX_COL_MAX_WG) ? NLH_QRX_SWEEP_COLUMN : NLH_QRX_SWEEP_LANE;
+        head.nact = nact;
+    }
+
+    // The pivot kernel's instance.  A long column (more than one NORM2 chunk, within the maxima the pipelined NORM2 keeps) of
+    // the column sweep has the scaling of its reflector as a launch of its own over the whole chip, and from step 1 on (no
+    // physical interchange, one update pending) the gather too: search and bookkeeping, gather, NORM2 as three launches --
+    // 218 -> ~200 us per 65536-row step.  The column sweep, a handful of problems by its nature, knows FEW instances only.
+    int pivot_form() const
+    {
+        const bool lng = m - j > 64 * 64 && m - j <= 64 * QRX_LONG_EL * QRX_LONG_MAXCH, few = head.nact <= k.few_max;
+        if (head.sweep == NLH_QRX_SWEEP_COLUMN)
+            return m <= 2048 ? NLH_QRX_PIVOT_FEW32 : lng ? (j >= 1 ? NLH_QRX_PIVOT_LONG_SPLIT : NLH_QRX_PIVOT_LONG_SCALED) : NLH_QRX_PIVOT_FEW64;
+        if (m <= 2048) return few ? NLH_QRX_PIVOT_FEW32 : NLH_QRX_PIVOT_BATCH32;
+        if (m <= k.piv32_maxm && !few) return NLH_QRX_PIVOT_BATCH32;
+        if (lng) return NLH_QRX_PIVOT_LONG;
+        return m - j <= 64 * 64 && few ? NLH_QRX_PIVOT_FEW64 : NLH_QRX_PIVOT_BATCH64;
+    }
+
+    // The lane sweep's pass: the form the launch's size asks for, whether it flushes, and the form that runs.
+    void pass_form(nlh_qrx_plan_step &s) const
+    {
+        const int nwin = (n + 1 - lo + 63) / 64, nhalf = (n + 1 - lo + 31) / 32;      // live physical columns coff + lo .. coff + n
+        const long nwg = (long)head.nact * nwin;
+        int f = nwg <= k.rpw16_max ? ((long)head.nact * nhalf <= k.rpwh_max ? NLH_QRX_PASS_WIDE_HALF : NLH_QRX_PASS_WIDE)
+                : nwg <= k.rp_max ? NLH_QRX_PASS_FOUR_WAVE : NLH_QRX_PASS_WAVE;
+        auto wide = [&] { return f == NLH_QRX_PASS_WIDE || f == NLH_QRX_PASS_WIDE_HALF; };
+        // the wide form keeps at most QRX_RPW_MAXNP pending reflectors (registers): a flush every 5th step; the four-wave
+        // form stages at most eight entries per row: every 8th; full launches every QRX_C-th
+        const int period = k.period ? k.period : wide() ? QRX_RPW_MAXNP + 1 : f == NLH_QRX_PASS_FOUR_WAVE ? std::min(QRX_C, 8) : QRX_C;
+        s.flush = qrx_can_flush(np) && np >= period - 1;
+        // a launch that inherits more pending updates than its form holds (a forced period) takes the next form until the flush
+        if (np >= 8) f = NLH_QRX_PASS_WAVE;
+        else if (np > QRX_RPW_MAXNP && wide()) f = NLH_QRX_PASS_FOUR_WAVE;
+        if (f == NLH_QRX_PASS_WAVE && k.share && nwin >= 2 && nwin <= QRX_SHARE_MAXWIN) f = NLH_QRX_PASS_WAVE_SHARED;
+        s.pass = f;
+        s.gwin = f == NLH_QRX_PASS_WIDE_HALF ? nhalf : nwin;
+        s.lds = wide() ? (int)qrx_rpw_lds(16) : 0;
+        s.lds_max = wide() ? s.lds : 65536;                     // no attribute is set for the others: the 64 KB every kernel may ask for
+    }
+
+    // 1: s is the next step; 0: past the last one (cur and np are k_qrx_finish's); -1: a step no launch exists for
+    int next(nlh_qrx_plan_step &s)
+    {
+        if (j >= n) return 0;
+        s.j = j; s.cur = cur;
+        s.pivot = pivot_form();
+        if (head.sweep == NLH_QRX_SWEEP_COLUMN) {
+            // a workgroup per trailing column, the update one step behind (k_qrx_pass_col): one pending reflector from
+            // step 1 on, a bank switch at every step, no physical move
+            s.np = s.flush = s.pf = j > 0;
+            s.lo = 0;
+            s.pass = NLH_QRX_PASS_COLUMN; s.gwin = n - j;
+            s.lds = (int)qrx_col_lds(m, j); s.lds_max = (int)QRX_COL_LDS_MAX;
+            np = 1;
+        } else {
+            s.np = np; s.lo = lo;
+            pass_form(s);
+            s.pf = (s.flush ? 1 : 0) | (prev_flushed ? 2 : 0);
+            const bool wide = s.pass == NLH_QRX_PASS_WIDE || s.pass == NLH_QRX_PASS_WIDE_HALF;
+            // what dispatch_pass and launch_pass have instances for
+            if (!(s.flush ? qrx_can_flush(np) : np <= QRX_C - 2) || (wide && np > QRX_RPW_MAXNP) || (s.pass == NLH_QRX_PASS_FOUR_WAVE && np >= 8))
+                return qrx_plan_bug(s);
+            prev_flushed = s.flush;
+            if (s.flush) { np = 1; lo = j + 1; } else np += 1;
+        }
+        if (s.flush) cur ^= 1;
+        ++j;
+        return 1;
+    }
+};
+
+extern "C" int32_t nlh_qrx_plan(int32_t nprob, int32_t m, int32_t n, int32_t nact, int32_t have_stages, nlh_qrx_plan_head *head,
+                                nlh_qrx_plan_step *steps, int32_t cap)
+{
+    if (nprob < 1 || n < 1 || m < n) return -NLH_INVALID_INPUT_ERROR;
+    QrxPlanner plan(nprob, m, n, nact, have_stages != 0, qrx_knobs());
+    if (head) *head = plan.head;
+    nlh_qrx_plan_step s;
+    int more;
+    while ((more = plan.next(s)) > 0)
+        if (steps && s.j < cap) steps[s.j] = s;
+    return more < 0 ? -NLH_INVALID_OPERATION_ERROR : n;
+}
+
+// ---- The launches: one switch per form enum.
+struct QrxLaunch {      // what the launches of one factorisation share
+    hipStream_t stream;
+    int nprob, m, n, ld, coff;
+    size_t tst, vst;
+    double *T, *R;
+    LmVecs v;
+    const LmState *st;
+    QrxWs w;
+};
+
+static bool launch_pivot(const QrxLaunch &a, const nlh_qrx_plan_step &s)
+{
+    auto pivot = [&](auto kernel, int threads, int pf) {
+        hipLaunchKernelGGL(kernel, dim3(a.nprob), dim3(threads), 0, a.stream, 0, a.m, a.n, a.ld, a.coff, a.tst, a.vst, s.j, s.cur, s.np, pf, a.T, a.w, a.R, a.v, a.st);
+    };
+    auto scale = [&] {
+        hipLaunchKernelGGL(k_qrx_scale_long, dim3((unsigned)(((a.m - s.j) / 2 + 1023) / 1024 + 1), a.nprob), dim3(256), 0, a.stream, a.m, a.vst, s.j, s.cur, s.np,
+                           s.pf, a.w, a.st);
+    };
+    // (Measured and dropped: the step as two lean launches -- a 102-register gather kernel, eight workgroups per CU,
+    // and a NORM2 kernel with ONE WAVE per problem working out of registers, so that all 2048 chains of a batch are in
+    // flight at once instead of 512 per round.  Bit-identical, but no faster: gather 98 us (HBM-bound: the column's
+    // sectors and np reflector vectors, ~210 KB per problem) + norm 88 us (46 us loading and preparing coefficients
+    // with a lane per 64-element run, 24 us the chains -- two per SIMD --, 24 us scaling: the column makes three more
+    // trips through memory than in the fused kernel) against 191 us for this kernel's four rounds.)
+    switch (s.pivot) {
+    case NLH_QRX_PIVOT_FEW32: pivot(k_qrx_pivot<32, false, true>, 256, s.pf); return true;
+    case NLH_QRX_PIVOT_BATCH32: pivot(k_qrx_pivot<32>, 256, s.pf); return true;
+    case NLH_QRX_PIVOT_FEW64: pivot(k_qrx_pivot<64, false, true>, 256, s.pf); return true;
+    case NLH_QRX_PIVOT_BATCH64: pivot(k_qrx_pivot<64>, 256, s.pf); return true;
+    case NLH_QRX_PIVOT_LONG: pivot(k_qrx_pivot<64, true>, QRX_LONG_THREADS, s.pf); return true;
+    case NLH_QRX_PIVOT_LONG_SCALED:                                     // flag 4: the scaling is left to k_qrx_scale_long
+        pivot(k_qrx_pivot<64, true>, QRX_LONG_THREADS, s.pf | 4);
+        scale();
+        return true;
+    case NLH_QRX_PIVOT_LONG_SPLIT:                                      // flag 8: gather and NORM2 too
+        pivot(k_qrx_pivot<64, true>, QRX_LONG_THREADS, s.pf | 4 | 8);
+        hipLaunchKernelGGL(k_qrx_gather_long, dim3((unsigned)(((a.m - (s.j & ~7)) / 2 + 1023) / 1024 + 1), a.nprob), dim3(256), 0, a.stream, a.m, a.ld, a.tst,
+                           a.vst, s.j, s.cur, s.np, s.pf, a.T, a.w, a.st);
+        hipLaunchKernelGGL(k_qrx_norm_long, dim3(a.nprob), dim3(QRX_NORM_THREADS), 0, a.stream, a.m, a.n, a.vst, s.j, s.cur, s.np, s.pf, a.w, a.st);
+        scale();
+        return true;
+    }
+    return false;
+}
 
 template <int NP, bool FLUSH>
-static void launch_pass(int rp, hipStream_t stream, int p0, int nprob, int lo, int m, int n, int ld, int coff, size_t tst, size_t vst, int j, int cur, double *T, const QrxWs &w,
-                        double *R, double *qtf, const LmState *st)
+static bool launch_pass(const QrxLaunch &a, const nlh_qrx_plan_step &s)
 {
     // One column per lane: measured against two and four columns per lane (fewer waves, the LDS row shared by more
     // elements) on 512 x 4096x256, 1024 x 2048x128 and a single problem, more waves won every time.
-    const int nwin = (n + 1 - lo + 63) / 64;                            // live physical columns coff + lo .. coff + n
-    const dim3 grid((unsigned)(((nprob + 7) / 8) * 8 * nwin));
-    // the row-parallel forms over the compacted problems when the factorisation has a list (qrx_factor)
-    const int npl = w.plist ? w.ny : nprob;
-    const int32_t *pls = w.plist;
-    const dim3 gridl((unsigned)(((npl + 7) / 8) * 8 * nwin));
-    if constexpr (NP >= 8) rp = 0;
-    // the wide row-parallel form holds at most QRX_RPW_MAXNP pending updates (registers); a launch that inherits more from the
-    // form before it takes the four-wave form until the next flush
-    if constexpr (NP > QRX_RPW_MAXNP) { if (rp == 16 || rp == QRX_RP_HALF || rp == 8) rp = 4; }
-    if constexpr (NP < 8) {
-    if constexpr (NP <= QRX_RPW_MAXNP) {
-    if (rp == 8)                                                        // eight waves (adder, stager, six producers), two workgroups per CU
-        hipLaunchKernelGGL((k_qrx_pass_rpw<NP, FLUSH, 8>), gridl, dim3(64 * 8), qrx_rpw_lds(8), stream, p0, npl, nwin, lo, m, n, ld, coff, tst, vst, j, cur,
-                           T, (const double *)w.V, w.tp, w.src, w.slotof, w.rdiag, w.wa, (const QrxStep *)w.step, R, qtf, st, pls);
-    else if (rp == QRX_RP_HALF) {                                       // the wide form on half windows
-        const int nsw = (n + 1 - lo + 31) / 32;
-        hipLaunchKernelGGL((k_qrx_pass_rpw<NP, FLUSH, 16, 32>), dim3((unsigned)(((npl + 7) / 8) * 8 * nsw)), dim3(64 * 16), qrx_rpw_lds(16), stream, p0, npl,
-                           nsw, lo, m, n, ld, coff, tst, vst, j, cur, T, (const double *)w.V, w.tp, w.src, w.slotof, w.rdiag, w.wa, (const QrxStep *)w.step, R, qtf, st, pls);
-    } else if (rp == 16)
-        hipLaunchKernelGGL((k_qrx_pass_rpw<NP, FLUSH, 16>), gridl, dim3(64 * 16), qrx_rpw_lds(16), stream, p0, npl, nwin, lo, m, n, ld, coff, tst, vst, j, cur,
-                           T, (const double *)w.V, w.tp, w.src, w.slotof, w.rdiag, w.wa, (const QrxStep *)w.step, R, qtf, st, pls);
+    // The row-parallel forms run over the compacted problems when the factorisation has a list; `list` is their last argument.
+    const int npl = a.w.plist ? a.w.ny : a.nprob;
+    auto pass = [&](auto kernel, int nprob, unsigned grid, int threads, auto... list) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), (size_t)s.lds, a.stream, 0, nprob, s.gwin, s.lo, a.m, a.n, a.ld, a.coff, a.tst, a.vst, s.j, s.cur,
+                           a.T, a.w.V, a.w.tp, a.w.src, a.w.slotof, a.w.rdiag, a.w.wa, a.w.step, a.R, a.v.qtf, a.st, list...);
+    };
+    auto tiles = [&](int nprob) { return (unsigned)(((nprob + 7) / 8) * 8 * s.gwin); };
+    switch (s.pass) {
+    case NLH_QRX_PASS_WIDE:
+        if constexpr (NP <= QRX_RPW_MAXNP) { pass(k_qrx_pass_rpw<NP, FLUSH, 16>, npl, tiles(npl), 64 * 16, a.w.plist); return true; }
+        break;
+    case NLH_QRX_PASS_WIDE_HALF:
+        if constexpr (NP <= QRX_RPW_MAXNP) { pass(k_qrx_pass_rpw<NP, FLUSH, 16, 32>, npl, tiles(npl), 64 * 16, a.w.plist); return true; }
+        break;
+    case NLH_QRX_PASS_FOUR_WAVE:
+        if constexpr (NP < 8) { pass(k_qrx_pass_rp<NP, FLUSH, 4>, npl, tiles(npl), 64 * 4, a.w.plist); return true; }
+        break;
+    case NLH_QRX_PASS_WAVE: pass(k_qrx_pass<NP, FLUSH, false>, a.nprob, tiles(a.nprob), 64); return true;
+    case NLH_QRX_PASS_WAVE_SHARED: pass(k_qrx_pass<NP, FLUSH, true>, a.nprob, (unsigned)a.nprob, 64 * s.gwin); return true;
     }
-    if (rp == 4)
-        hipLaunchKernelGGL((k_qrx_pass_rp<NP, FLUSH, 4>), gridl, dim3(64 * 4), 0, stream, p0, npl, nwin, lo, m, n, ld, coff, tst, vst, j, cur,
-                           T, (const double *)w.V, w.tp, w.src, w.slotof, w.rdiag, w.wa, (const QrxStep *)w.step, R, qtf, st, pls);
-    }
-    static const int share_env = [] { const char *e = getenv("NLH_QRX_SHARE"); return e ? atoi(e) : 1; }();
-    if (rp == 0 && share_env && nwin >= 2 && nwin <= QRX_SHARE_MAXWIN)
-        hipLaunchKernelGGL((k_qrx_pass<NP, FLUSH, true>), dim3((unsigned)nprob), dim3(64 * nwin), 0, stream, p0, nprob, nwin, lo, m, n, ld, coff,
-                           tst, vst, j, cur, T, (const double *)w.V, w.tp, w.src, w.slotof, w.rdiag, w.wa, (const QrxStep *)w.step, R, qtf, st);
-    else if (rp == 0)
-        hipLaunchKernelGGL((k_qrx_pass<NP, FLUSH, false>), grid, dim3(64), 0, stream, p0, nprob, nwin, lo, m, n, ld, coff, tst, vst, j, cur,
-                           T, (const double *)w.V, w.tp, w.src, w.slotof, w.rdiag, w.wa, (const QrxStep *)w.step, R, qtf, st);
+    return false;
 }
 
-// A pass with np pending updates; flushing ones exist for np = 1, 3 and QRX_C - 1 (flush periods 2, 4 and QRX_C).
-static constexpr bool qrx_can_flush(int np) { return np == 1 || np == 3 || np == QRX_RPW_MAXNP || (QRX_C > 8 && np == 7) || np == QRX_C - 1; }
-
-template <int NP>
-static void dispatch_pass(int np, bool flush, int rp, hipStream_t stream, int p0, int nprob, int lo, int m, int n, int ld, int coff, size_t tst, size_t vst,
-                          int j, int cur, double *T, const QrxWs &w, double *R, double *qtf, const LmState *st)
+// The run-time np becomes the template argument; false: no instance for (np, flush, form), nothing was launched.
+template <int NP = 0>
+static bool dispatch_pass(const QrxLaunch &a, const nlh_qrx_plan_step &s)
 {
-    if (np == NP) {
-        if (flush) {
-            if constexpr (qrx_can_flush(NP)) launch_pass<NP, true>(rp, stream, p0, nprob, lo, m, n, ld, coff, tst, vst, j, cur, T, w, R, qtf, st);
-        } else {
-            if constexpr (NP < QRX_C - 1) launch_pass<NP, false>(rp, stream, p0, nprob, lo, m, n, ld, coff, tst, vst, j, cur, T, w, R, qtf, st);
-        }
-    } else if constexpr (NP < QRX_C - 1) {
-        dispatch_pass<NP + 1>(np, flush, rp, stream, p0, nprob, lo, m, n, ld, coff, tst, vst, j, cur, T, w, R, qtf, st);
+    if (s.np == NP) {
+        if constexpr (qrx_can_flush(NP)) if (s.flush) return launch_pass<NP, true>(a, s);
+        if constexpr (NP < QRX_C - 1) if (!s.flush) return launch_pass<NP, false>(a, s);
+        return false;
     }
+    if constexpr (NP < QRX_C - 1) return dispatch_pass<NP + 1>(a, s);
+    return false;
 }
 
-// Per device (called when a handle is created on it): the column sweep of long columns asks for more than 64 KB of
-// dynamic LDS (two product buffers), which has to be allowed on every device the kernel is launched on.
+static bool launch_pass(const QrxLaunch &a, const nlh_qrx_plan_step &s)
+{
+    if (s.pass != NLH_QRX_PASS_COLUMN) return dispatch_pass(a, s);
+    auto col = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(s.gwin, a.w.ny), dim3(256), (size_t)s.lds, a.stream, a.m, a.n, a.ld, a.tst, a.vst, s.j, s.cur, a.T, a.w.V, a.w.tp,
+                           a.w.src, a.w.rdiag, a.w.wa, a.w.step, a.R, a.v.qtf, a.st, a.w.plist);
+    };
+    if (s.np) col(k_qrx_pass_col<true>); else col(k_qrx_pass_col<false>);
+    return true;
+}
+
+// Per device (called when a handle is created on it): the column sweep of long columns and the wide row-parallel pass ask
+// for more than 64 KB of dynamic LDS, which has to be allowed on every device the kernel is launched on.
 template <int NP>
 static void qrx_rpw_attr()
 {
@@ -1957,178 +2170,57 @@ static void qrx_rpw_attr()
 
 void qrx_init_device()
 {
-    const int lim = (int)(sizeof(double) * 2 * (64 * QRX_COL_EL + 128));
-    hipFuncSetAttribute((const void *)k_qrx_pass_col<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-    hipFuncSetAttribute((const void *)k_qrx_pass_col<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-    qrx_rpw_attr<0>();                                           // the sixteen-wave row-parallel pass: 120 KB
+    hipFuncSetAttribute((const void *)k_qrx_pass_col<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QRX_COL_LDS_MAX);
+    hipFuncSetAttribute((const void *)k_qrx_pass_col<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)QRX_COL_LDS_MAX);
+    qrx_rpw_attr<0>();
 }
 
-void qrx_factor(hipStream_t stream, int nprob, int m, int n, const double *J, double *T, const double *fvec,
-                double *R, LmVecs v, double *wa4, double *scratch, const double *x, LmState *st, double factor,
-                double gtol, void *ws, const QrxTimer *tm, int nact)
+int qrx_factor(hipStream_t stream, int nprob, int m, int n, const double *J, double *T, const double *fvec,
+               double *R, LmVecs v, double *wa4, double *scratch, const double *x, LmState *st, double factor,
+               double gtol, void *ws, const QrxTimer *tm, int nact)
 {
-    QrxWs w;
-    qrx_carve(ws, nprob, m, n, &w);
-    const int ld = qrx_ld(n), coff = qrx_coff(n);
-    const size_t tst = qrx_tstride(m, n), vst = qrx_vstride(m);
-    auto tb = [&](int which, hipStream_t s) { if (tm) tm->begin(tm->ctx, which, s); };
-    auto te = [&](int which, hipStream_t s) { if (tm) tm->end(tm->ctx, which, s); };
-    tb(2, stream);
+    QrxPlanner plan(nprob, m, n, nact, st != nullptr, qrx_knobs());
+    QrxLaunch a{stream, nprob, m, n, qrx_ld(n), qrx_coff(n), qrx_tstride(m, n), qrx_vstride(m), T, R, v, st, {}};
+    qrx_carve(ws, nprob, m, n, &a.w);
+    if (!plan.head.use_list) a.w.plist = nullptr;
+    a.w.ny = plan.head.ny;
+    const QrxWs &w = a.w;
+    auto tb = [&](int which) { if (tm) tm->begin(tm->ctx, which, stream); };
+    auto te = [&](int which) { if (tm) tm->end(tm->ctx, which, stream); };
+    tb(2);
     if (J) {
         const size_t total = (size_t)((m + 7) >> 3) * n;
         const unsigned gx = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_qrx_transpose, dim3(gx, nprob), dim3(256), 0, stream, m, n, ld, coff, tst, J, T, (const LmState *)st);
+        hipLaunchKernelGGL(k_qrx_transpose, dim3(gx, nprob), dim3(256), 0, stream, m, n, a.ld, a.coff, a.tst, J, T, (const LmState *)st);
     }
-    if (nact <= 0 || nact > nprob) nact = nprob;
-    // a workgroup per column for the initial norms while the launch's chains would otherwise leave the chip idle (a thread
-    // per column walks its 4096 rows alone: 800 us for 47 x 4096x256, whatever the count; k_qrx_init<true> is HBM-bound
-    // only from ~1000 problems on)
-    static const long initn_env = [] { const char *e = getenv("NLH_QRX_INITN"); return e ? atol(e) : 32768L; }();
-    // launches with (columns x problems) grids cover the problems that work, not the batch (k_qrx_list)
-    const bool use_list = st != nullptr && nact < nprob && (long)nact * n <= std::max<long>(QRX_COL_MAX_WG, initn_env);
-    const int ny = use_list ? nact : nprob;
-    if (use_list) hipLaunchKernelGGL(k_qrx_list, dim3(1), dim3(256), 0, stream, nprob, nact, st, w.plist);
-    else w.plist = nullptr;
-    w.ny = ny;
-    if ((long)nact * n <= std::max<long>(QRX_COL_MAX_WG, initn_env)) {
-        hipLaunchKernelGGL(k_qrx_init<false>, dim3(nprob), dim3(256), 0, stream, m, n, ld, coff, tst, T, fvec, w, v, (const LmState *)st);
-        hipLaunchKernelGGL(k_qrx_init_norms, dim3(n, ny), dim3(256), 0, stream, m, n, ld, coff, tst, (const double *)T, w, v,
+    if (plan.head.use_list) hipLaunchKernelGGL(k_qrx_list, dim3(1), dim3(256), 0, stream, nprob, plan.head.nact, st, w.plist);
+    if (plan.head.init == NLH_QRX_INIT_SPLIT) {
+        hipLaunchKernelGGL(k_qrx_init<false>, dim3(nprob), dim3(256), 0, stream, m, n, a.ld, a.coff, a.tst, T, fvec, w, v, (const LmState *)st);
+        hipLaunchKernelGGL(k_qrx_init_norms, dim3(n, w.ny), dim3(256), 0, stream, m, n, a.ld, a.coff, a.tst, (const double *)T, w, v,
                            (const LmState *)st);
     } else {
-        hipLaunchKernelGGL(k_qrx_init<true>, dim3(nprob), dim3(256), 0, stream, m, n, ld, coff, tst, T, fvec, w, v, (const LmState *)st);
+        hipLaunchKernelGGL(k_qrx_init<true>, dim3(nprob), dim3(256), 0, stream, m, n, a.ld, a.coff, a.tst, T, fvec, w, v, (const LmState *)st);
     }
-    te(2, stream);
+    te(2);
     // (Measured and dropped: the two halves of the batch on two streams, half B's pivot kernel under half A's pass, with
     // events keeping the passes from overlapping each other -- 1035 ms instead of 999 ms per 512 x 4096x256 solve; the
     // cross-stream event waits cost more than the pivot latency they hide.  Sub-batches on host threads, which need no
     // cross-stream ordering, do hide it: nlh_lm.hip, lm_sub_batches.)
-    static const int forced_period = [] { const char *e = getenv("NLH_QRX_PERIOD"); return e ? atoi(e) : 0; }();
-    static const long rp_env = [] { const char *e = getenv("NLH_QRX_RP"); return e ? atol(e) : -1L; }();
-    const long rp_max = rp_env >= 0 ? rp_env : QRX_RP_MAX_WG;
-    static const long rpw16_env = [] { const char *e = getenv("NLH_QRX_RPW16"); return e ? atol(e) : -1L; }();
-    const long rpw16_max = std::min(rp_max, rpw16_env >= 0 ? rpw16_env : (long)QRX_RPW16_MAX_WG);
-    static const int col_env = [] { const char *e = getenv("NLH_QRX_COL"); return e ? atoi(e) : -1; }();
-    if (col_env >= 0 ? nact <= col_env : (long)nact * n <= QRX_COL_MAX_WG) {
-        // two product buffers for columns of several chunks, one sized to the column otherwise
-        auto coll_lds = [](int m_, int j_) {
-            const int len = m_ - (j_ & ~7);
-            const int nrun = (((len + QRX_COL_EL - 1) / QRX_COL_EL) + 7) & ~7;        // the chain wave adds whole trips of eight runs
-            return sizeof(double) * (size_t)(len > 64 * QRX_COL_EL ? 2 * (64 * QRX_COL_EL + 128) : nrun * (QRX_COL_EL + 2));
-        };
-        auto pivot = [&](int j, int cur, int np, int pf) {
-            if (m <= 2048)
-                hipLaunchKernelGGL((k_qrx_pivot<32, false, true>), dim3(nprob), dim3(256), 0, stream, 0, m, n, ld, coff, tst, vst, j, cur, np, pf, T, w, R, v,
-                                   (const LmState *)st);
-            else if (m - j > 64 * 64 && m - j <= 64 * QRX_LONG_EL * QRX_LONG_MAXCH) {
-                // long column: the scaling of the reflector as a launch of its own over the whole chip (flush bit 2), and
-                // from step 1 on (no physical interchange, at most one update pending) the gather too: search and
-                // bookkeeping (flush bit 3), gather, NORM2 as three launches -- 218 -> ~200 us per 65536-row step
-                if (j >= 1 && np <= 1) {
-                    hipLaunchKernelGGL((k_qrx_pivot<64, true>), dim3(nprob), dim3(QRX_LONG_THREADS), 0, stream, 0, m, n, ld, coff, tst, vst, j, cur, np,
-                                       pf | 4 | 8, T, w, R, v, (const LmState *)st);
-                    hipLaunchKernelGGL(k_qrx_gather_long, dim3((unsigned)(((m - (j & ~7)) / 2 + 1023) / 1024 + 1), nprob), dim3(256), 0, stream, m, ld, tst, vst,
-                                       j, cur, np, pf, (const double *)T, w, (const LmState *)st);
-                    hipLaunchKernelGGL(k_qrx_norm_long, dim3(nprob), dim3(QRX_NORM_THREADS), 0, stream, m, n, vst, j, cur, np, pf, w, (const LmState *)st);
-                } else
-                hipLaunchKernelGGL((k_qrx_pivot<64, true>), dim3(nprob), dim3(QRX_LONG_THREADS), 0, stream, 0, m, n, ld, coff, tst, vst, j, cur, np, pf | 4, T, w,
-                                   R, v, (const LmState *)st);
-                hipLaunchKernelGGL(k_qrx_scale_long, dim3((unsigned)(((m - j) / 2 + 1023) / 1024 + 1), nprob), dim3(256), 0, stream, m, vst, j, cur, np, pf,
-                                   w, (const LmState *)st);
-            } else
-                hipLaunchKernelGGL((k_qrx_pivot<64, false, true>), dim3(nprob), dim3(256), 0, stream, 0, m, n, ld, coff, tst, vst, j, cur, np, pf, T, w, R, v,
-                                   (const LmState *)st);
-        };
-        {
-            // a workgroup per trailing column, the update one step behind (k_qrx_pass_col): one pending reflector from
-            // step 1 on, a bank switch at every step, no physical move
-            int cur = 0;
-            for (int j = 0; j < n; ++j) {
-                tb(0, stream);
-                pivot(j, cur, j > 0 ? 1 : 0, j > 0 ? 1 : 0);
-                te(0, stream);
-                tb(1, stream);
-                if (j == 0)
-                    hipLaunchKernelGGL(k_qrx_pass_col<false>, dim3(n - j, ny), dim3(256), coll_lds(m, j), stream, m, n, ld, tst, vst, j, cur, T,
-                                       (const double *)w.V, w.tp, (const int32_t *)w.src, w.rdiag, w.wa, (const QrxStep *)w.step, R, v.qtf,
-                                       (const LmState *)st, (const int32_t *)w.plist);
-                else
-                    hipLaunchKernelGGL(k_qrx_pass_col<true>, dim3(n - j, ny), dim3(256), coll_lds(m, j), stream, m, n, ld, tst, vst, j, cur, T,
-                                       (const double *)w.V, w.tp, (const int32_t *)w.src, w.rdiag, w.wa, (const QrxStep *)w.step, R, v.qtf,
-                                       (const LmState *)st, (const int32_t *)w.plist);
-                te(1, stream);
-                if (j > 0) cur ^= 1;
-            }
-            tb(2, stream);
-            hipLaunchKernelGGL(k_qrx_finish, dim3(nprob), dim3(256), 0, stream, m, n, ld, coff, tst, vst, cur, 1, (const double *)T, w, R, v,
-                               wa4, scratch, x, st, factor, gtol);
-            te(2, stream);
-            return;
-        }
+    nlh_qrx_plan_step s;
+    int more;
+    while ((more = plan.next(s)) > 0) {
+        tb(0);
+        bool ok = launch_pivot(a, s);
+        te(0);
+        tb(1);
+        ok = ok && launch_pass(a, s);
+        te(1);
+        if (!ok) return qrx_plan_bug(s);
     }
-    // the pivot kernel's instance for a handful of problems (NORM2's general runs out of registers, at most two workgroups
-    // per CU) also serves every launch whose workgroups are all resident at once anyway
-    static const int few_env = [] { const char *e = getenv("NLH_QRX_FEW"); return e ? atoi(e) : -1; }();
-    const int few_max = few_env >= 0 ? few_env : QRX_FEW_MAX;
-    // rows up to which a BATCH takes the pivot kernel's 32-terms-per-lane instance (128 registers, four workgroups per CU;
-    // a column of more than 2048 rows then goes through its reflector slot in memory and two NORM2 chunks).  Measured at
-    // 2048 x 4096x256 with the instance for 4096 rows too: 3,458 / 3,428 against 3,458 / 3,500 LM it/s (same box, alternating
-    // runs): no gain, the default stays 2048.  (Also built and measured: an
-    // instance whose threads gather whole 64-byte sectors -- sixteen consecutive elements each, the column in registers
-    // from the gather to the scaling, two NORM2 chunks out of registers -- at three / four workgroups per CU: 96 / 268
-    // bytes of spills, 1.4 / 4.4 % SLOWER than the 64-term instance.)
-    static const int piv32_env = [] { const char *e = getenv("NLH_QRX_PIV32_MAXM"); return e ? atoi(e) : -1; }();
-    const int piv32_maxm = std::max(2048, piv32_env >= 0 ? piv32_env : QRX_PIV32_MAXM);
-    bool prev_flushed = false;
-    int cur = 0, np = 0, lo = 1;             // lo: first slot position that can still hold live data (step 0 moves physically)
-    for (int j = 0; j < n; ++j) {
-        const int nwin = (n + 1 - lo + 63) / 64;
-        const long nwg = (long)nact * nwin;
-        // waves per workgroup of the row-parallel pass (16: the wide form, k_qrx_pass_rpw), 0: one wave per window
-        static const long rpwh_env = [] { const char *e = getenv("NLH_QRX_RPWH"); return e ? atol(e) : -1L; }();
-        const long nwgh = (long)nact * ((n + 1 - lo + 31) / 32);
-        // (NLH_QRX_RP8=<pairs>: the lane-quad form with EIGHT waves -- adder, stager, six producers, two workgroups per CU --
-        // instead of the four-wave form up to that many pairs.  Measured, ms per solve off / up to 512: 96 x 4096x256 197.9 /
-        // 192.3, 128: 218.1 / 231.5, 192: 321.8 / 317.8, 192 x 2048x128 55.6 / 53.5, 384: 94.8 / 90.9, 512: 104.8 / 104.3 --
-        // no consistent gain where launches are HBM-bound anyway; left off.)
-        static const long rp8_env = [] { const char *e = getenv("NLH_QRX_RP8"); return e ? atol(e) : 0L; }();
-        const int rp = nwg <= rpw16_max ? (nwgh <= (rpwh_env >= 0 ? rpwh_env : (long)QRX_RPWH_MAX_WG) ? QRX_RP_HALF : 16)
-                       : nwg <= rp_max ? (nwg <= rp8_env ? 8 : 4) : 0;
-        // the wide form keeps at most three pending reflectors (scalar registers): a flush every 4th step; the four-wave
-        // form every 8th; full launches every QRX_C-th
-        const int period = forced_period ? forced_period : ((rp == 16 || rp == QRX_RP_HALF || rp == 8) ? QRX_RPW_MAXNP + 1 : rp == 4 ? (QRX_C < 8 ? QRX_C : 8) : QRX_C);
-        const bool flush = qrx_can_flush(np) && np >= period - 1;
-        tb(0, stream);
-        const int pf = (flush ? 1 : 0) | (prev_flushed ? 2 : 0);
-        // (Measured and dropped: the step as two lean launches -- a 102-register gather kernel, eight workgroups per CU,
-        // and a NORM2 kernel with ONE WAVE per problem working out of registers, so that all 2048 chains of a batch are in
-        // flight at once instead of 512 per round.  Bit-identical, but no faster: gather 98 us (HBM-bound: the column's
-        // sectors and np reflector vectors, ~210 KB per problem) + norm 88 us (46 us loading and preparing coefficients
-        // with a lane per 64-element run, 24 us the chains -- two per SIMD --, 24 us scaling: the column makes three more
-        // trips through memory than in the fused kernel) against 191 us for this kernel's four rounds.)
-        if (m <= 2048 && nact <= few_max)
-            hipLaunchKernelGGL((k_qrx_pivot<32, false, true>), dim3(nprob), dim3(256), 0, stream, 0, m, n, ld, coff, tst, vst, j, cur, np, pf,
-                               T, w, R, v, (const LmState *)st);
-        else if (m <= piv32_maxm && (m <= 2048 || nact > few_max))
-            hipLaunchKernelGGL(k_qrx_pivot<32>, dim3(nprob), dim3(256), 0, stream, 0, m, n, ld, coff, tst, vst, j, cur, np, pf,
-                               T, w, R, v, (const LmState *)st);
-        else if (m - j <= 64 * 64 && nact <= few_max)
-            hipLaunchKernelGGL((k_qrx_pivot<64, false, true>), dim3(nprob), dim3(256), 0, stream, 0, m, n, ld, coff, tst, vst, j, cur, np, pf,
-                               T, w, R, v, (const LmState *)st);
-        else if (m - j > 64 * 64 && m - j <= 64 * QRX_LONG_EL * QRX_LONG_MAXCH)
-            hipLaunchKernelGGL((k_qrx_pivot<64, true>), dim3(nprob), dim3(QRX_LONG_THREADS), 0, stream, 0, m, n, ld, coff, tst, vst, j, cur, np, pf,
-                               T, w, R, v, (const LmState *)st);
-        else
-            hipLaunchKernelGGL(k_qrx_pivot<64>, dim3(nprob), dim3(256), 0, stream, 0, m, n, ld, coff, tst, vst, j, cur, np, pf,
-                               T, w, R, v, (const LmState *)st);
-        te(0, stream);
-        tb(1, stream);
-        dispatch_pass<0>(np, flush, rp, stream, 0, nprob, lo, m, n, ld, coff, tst, vst, j, cur, T, w, R, v.qtf, st);
-        te(1, stream);
-        prev_flushed = flush;
-        if (flush) { cur ^= 1; np = 1; lo = j + 1; } else { np += 1; }
-    }
-    tb(2, stream);
-    hipLaunchKernelGGL(k_qrx_finish, dim3(nprob), dim3(256), 0, stream, m, n, ld, coff, tst, vst, cur, np, (const double *)T, w, R, v,
+    if (more < 0) return more;
+    tb(2);
+    hipLaunchKernelGGL(k_qrx_finish, dim3(nprob), dim3(256), 0, stream, m, n, a.ld, a.coff, a.tst, a.vst, plan.cur, plan.np, (const double *)T, w, R, v,
                        wa4, scratch, x, st, factor, gtol);
-    te(2, stream);
+    te(2);
+    return 0;
 }

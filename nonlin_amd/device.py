@@ -22,6 +22,29 @@ def _chk(t, shape, name):
                          f"got {t.dtype} {tuple(t.shape)} cuda={t.is_cuda}")
 
 
+# names of the NLH_QRX_SWEEP_* / INIT_* / PIVOT_* / PASS_* values of include/nonlin_hip.h, in order
+QRX_SWEEPS = ("column", "lane")
+QRX_INITS = ("split", "fused")
+QRX_PIVOT_FORMS = ("few32", "batch32", "few64", "batch64", "long", "long_scaled", "long_split")
+QRX_PASS_FORMS = ("column", "wide", "wide_half", "four_wave", "wave", "wave_shared")
+
+
+def qrx_plan(nprob, m, n, nact=0, have_stages=False):
+    """The launch plan of the exact lmfactor (nlh_qrx_plan: host code, needs no GPU) for nprob m-by-n problems of which
+    nact need factoring (0: all), under this process's NLH_QRX_* environment.  Returns (head, steps): dicts of the
+    fields of nlh_qrx_plan_head / nlh_qrx_plan_step, one per Householder step, with the forms by name."""
+    head = _lib.QrxPlanHead()
+    steps = (_lib.QrxPlanStep * max(n, 1))()
+    rc = _lib.load().nlh_qrx_plan(nprob, m, n, nact, int(bool(have_stages)), C.byref(head), steps, n)
+    if rc != n:
+        raise ValueError(f"nlh_qrx_plan({nprob}, {m}, {n}, {nact}): error {rc}")
+    names = {"sweep": QRX_SWEEPS, "init": QRX_INITS, "pivot": QRX_PIVOT_FORMS, "pass": QRX_PASS_FORMS}
+
+    def rec(r):
+        return {k: names[k][getattr(r, k)] if k in names else int(getattr(r, k)) for k, _ in r._fields_}
+    return rec(head), [rec(steps[i]) for i in range(n)]
+
+
 class DeviceSolver:
     """Owns an nlh handle bound to torch's current stream on `device`."""
 

@@ -3,11 +3,19 @@ src/nonlin_least_squares.f90:569-667 / :241-253 in the reference's operation ord
 on matrices built to reach the corners the random LM problems rarely visit: graded rows (a new running maximum inside
 every NORM2 run), graded and permuted columns (non-trivial pivoting), duplicate columns (ties: lowest index wins), zero
 and dependent columns (zero reflectors), exact zeros, sizes on both sides of the kernels' internal limits (more than 256
-candidate columns, columns longer than one NORM2 chunk), and the same matrix in batches that select each of the three
-forms of the trailing pass (the wide sixteen-wave and the four-wave row-parallel form, one wave per window)."""
+candidate columns, columns longer than one NORM2 chunk), and the same matrix in batches that select each
+form of the trailing pass.  Which kernel forms a shape reaches is asserted through qrx_plan (tests/qrx_cases.py) before
+the bits are compared."""
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+import qrx_cases as QC
 
 pytestmark = pytest.mark.gpu
 
@@ -87,7 +95,7 @@ KINDS = ["random", "graded_rows", "graded_rows_down", "graded_cols", "duplicates
 
 
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("m,n", [(300, 37), (130, 129), (64, 64), (21, 4)])
+@pytest.mark.parametrize("m,n", QC.ADVERSARIAL)
 def test_lmfactor_exact_bitwise_adversarial(ds, oracle, kind, m, n):
     rng = np.random.default_rng(hash((kind, m, n)) % (2 ** 31))
     a = _matrix(kind, m, n, rng)
@@ -96,7 +104,7 @@ def test_lmfactor_exact_bitwise_adversarial(ds, oracle, kind, m, n):
 
 
 @pytest.mark.parametrize("kind", ["graded_rows", "duplicates", "graded_cols"])
-@pytest.mark.parametrize("m,n", [(4500, 40), (700, 300)])
+@pytest.mark.parametrize("m,n", QC.BEYOND_LIMITS)
 def test_lmfactor_exact_bitwise_beyond_internal_limits(ds, oracle, kind, m, n):
     """m - j > 4096: the pivot column does not fit one NORM2 chunk; n - j > 256: more candidate columns than threads."""
     rng = np.random.default_rng(7 + m + n)
@@ -106,14 +114,16 @@ def test_lmfactor_exact_bitwise_beyond_internal_limits(ds, oracle, kind, m, n):
 
 
 @pytest.mark.parametrize("kind", ["random", "graded_rows", "graded_rows_down", "duplicates", "zero_cols", "sparse"])
-@pytest.mark.parametrize("m,n,copies", [(9001, 24, 1), (12290, 17, 3), (4101, 30, 2), (8200, 12, 40), (2100, 33, 1), (4096, 70, 3)])
+@pytest.mark.parametrize("m,n,copies", list(QC.LONG_COLUMNS))
 def test_lmfactor_exact_bitwise_long_columns(ds, oracle, kind, m, n, copies):
     """Columns of several NORM2 chunks.  A handful of problems: the workgroup-per-column sweep with the update one step
     behind (k_qrx_pass_col: one pending reflector, a bank switch per step, chain wave + preparing waves) and the
     pipelined NORM2 of the pivot kernel (graded rows: a new maximum in every run, the general recurrence in every chunk;
     graded down: the maximum is the first element; m not a multiple of 8, m - n on both sides of 4096; single-chunk columns
-    of more than 2048 rows take the same sweep).  Forty problems:
-    the lane-per-column passes with up to nine pending reflectors under the long-column pivot kernel."""
+    of more than 2048 rows take the same sweep; so do forty problems of twelve columns).  520 problems: the
+    lane-per-column passes with up to nine pending reflectors under the long-column pivot kernel.  257 problems of 2100
+    rows: the 64-term pivot instance of a batch."""
+    QC.check_long_columns(m, n, copies)
     rng = np.random.default_rng(11 + m + n)
     a = _matrix(kind, m, n, rng)
     f = rng.standard_normal(m)
@@ -121,28 +131,56 @@ def test_lmfactor_exact_bitwise_long_columns(ds, oracle, kind, m, n, copies):
 
 
 @pytest.mark.parametrize("kind", ["random", "quantized", "plus_minus_one", "heavy_tail", "sparse", "graded_rows_down"])
-@pytest.mark.parametrize("m,n", [(40000, 6), (70001, 4)])
+@pytest.mark.parametrize("m,n", QC.CHAIN_FREE)
 def test_lmfactor_exact_long_columns_chain_free_norm2(ds, oracle, kind, m, n):
     """Columns of a dozen and more NORM2 chunks: from the third chunk on the running sum of squared ratios is formed
     WITHOUT the serial chain (ordered_possum_wave_int, nlh_common.h: per-binade exact additions with a two-state tie rule),
     falling back to the chain where the sum crosses a binade or a new maximum appears.  Quantized data puts the ratios on
-    exact ties, +-1 makes every ratio one, heavy tails move the maximum late; every bit must be the oracle's."""
+    exact ties, +-1 makes every ratio one, heavy tails move the maximum late; every bit must be the oracle's.
+    One problem: the column sweep, the pivot step split into search, gather, NORM2 and scaling launches from step 1 on."""
+    QC.check_column_sweep_of_long_columns(m, n)
     rng = np.random.default_rng(101 + m + n)
     a = _matrix(kind, m, n, rng)
     f = rng.standard_normal(m)
     _check(ds, oracle, a, f)
 
 
-@pytest.mark.parametrize("copies", [1, 20, 40, 60, 100, 120, 200, 300, 1100])
-def test_lmfactor_exact_every_pass_form(ds, oracle, copies):
-    """The same graded 520 x 70 matrix (two 64-column windows) in batches of 1 / 20 (<= 1536 (problem, column) pairs: the
-    workgroup-per-column sweep), 40, 60, 100 and 120 (80 / 120 / 200 / 240 (problem, window) pairs: the wide row-parallel form, sixteen
-    waves, producers reading whole sectors per lane quad, on 32-column half windows while those are at most 256 -- 60 copies
-    all the way, 100 once one window is left --; at most 256 pairs), 200 (400: four-wave; at most 512), 300 and 1100
-    (one wave per window, separate and as the waves of one workgroup); all the same bits."""
+def _pass_form_matrix():
     rng = np.random.default_rng(99)
-    a = _matrix("graded_rows", 520, 70, rng)
+    a = _matrix("graded_rows", QC.PASS_FORM_M, QC.PASS_FORM_N, rng)
     a[:, 5] = a[:, 3]
     a[:, 11] = 0.0
-    f = rng.standard_normal(520)
+    return a, rng.standard_normal(QC.PASS_FORM_M)
+
+
+@pytest.mark.parametrize("copies", list(QC.PASS_FORMS))
+def test_lmfactor_exact_every_pass_form(ds, oracle, copies):
+    """The same graded 520 x 70 matrix (two 64-column windows) in batches of 1 / 20 (<= 1536 (problem, column) pairs: the
+    workgroup-per-column sweep), 40, 60, 100 and 120 (at most 256 (problem, window) pairs: the wide row-parallel form, sixteen
+    waves, producers reading whole sectors per lane quad, on 32-column half windows while those are at most 256 -- 40 and 60
+    copies all the way, 100 and 120 once one window is left), 200 (400 pairs, at most 512: four-wave, then wide with
+    one window left), 300 and 1100 (one wave per window, as the waves of one workgroup while two windows are live; then
+    four-wave / a workgroup per window); all the same bits."""
+    QC.check_pass_forms(copies)
+    a, f = _pass_form_matrix()
     _check(ds, oracle, a, f, copies=copies)
+
+
+def test_lmfactor_exact_ignores_flush_period_without_instance(oracle):
+    """NLH_QRX_PERIOD=11 (QRX_C is 10) cannot be honoured: a fresh process says so on stderr, plans as it does without the
+    variable and factors 300 copies of the 520 x 70 matrix bit for bit."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, sys; sys.path[:0] = [%r, %r]\n"
+            "import test_gpu_lmfactor_exact as T\n"
+            "from nonlin_amd.device import DeviceSolver, qrx_plan\n"
+            "from oracle import pyoracle\n"
+            "pyoracle.lib()\n"
+            "a, f = T._pass_form_matrix()\n"
+            "T._check(DeviceSolver(0), pyoracle, a, f, copies=300)\n"
+            "print(json.dumps(qrx_plan(300, T.QC.PASS_FORM_M, T.QC.PASS_FORM_N)))\n") % (root, os.path.join(root, "tests"))
+    env = dict(os.environ, NLH_QRX_PERIOD="11")
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "NLH_QRX_PERIOD" in r.stderr
+    head, steps = json.loads(r.stdout.strip().splitlines()[-1])
+    assert [head, steps] == list(QC.qrx_plan(300, QC.PASS_FORM_M, QC.PASS_FORM_N))
