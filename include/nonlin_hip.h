@@ -39,6 +39,7 @@ extern "C" {
 #define NLH_DIVERGENT_BEHAVIOR_ERROR   206   /* (:23) */
 #define NLH_SPURIOUS_CONVERGENCE_ERROR 207   /* (:25) */
 #define NLH_TOLERANCE_TOO_SMALL_ERROR  208   /* (:27) */
+#define NLH_DIVIDE_BY_ZERO_ERROR       210   /* (:32) */
 #define NLH_UNDEFINED_FUNCTION_ERROR   211   /* (:34) */
 #define NLH_UNDERDEFINED_PROBLEM_ERROR 212   /* (:37) */
 /* Size limits of this implementation (the reference has none); an entry point given a larger problem returns
@@ -52,7 +53,8 @@ extern "C" {
  * dense-quadratic family (the bench / test residual of nlh_dq_*, not part of the reference) keeps a point's x in LDS and
  * stops at n = 20000 (NLH_ARRAY_SIZE_ERROR from its launcher); a user's device function has whatever bound its own kernels
  * have.  Row counts are not limited: polynomial fits and bounded least squares beyond 18000 rows keep the
- * Householder reflector in global memory instead of LDS.
+ * Householder reflector in global memory instead of LDS.  Polynomial roots: order <= 256 (one wave per polynomial on a
+ * dense window; the unblocked double-shift QR is not the method for larger orders).
  * The number of problems of a batch is NOT limited: the lock-step drivers carry the problem index in a grid dimension
  * that holds 65535, and a larger batch is solved in slices of 65535 problems, one after the other, inside the entry point
  * (independent problems: the same bits).  The one-variable solvers' batches (brent_solver, newton_1var_solver) carry
@@ -570,6 +572,29 @@ int nlh_poly_fit(nlh_handle *h, int32_t npts, int32_t order, int32_t thru_zero, 
 int nlh_poly_fit_batch(nlh_handle *h, int32_t nprob, int32_t npts, int32_t order, int32_t thru_zero,
                        const double *dx, const double *dy, double *dcoef);
 
+/* polynomial%roots (:357-381) for real polynomials of one order: the eigenvalues of the companion matrix of :346-353 by
+ * DGEBAL-style balancing and DLAHQR's double-shift QR (see DESIGN "Polynomial roots"); coef = c0 .. c_order.  Roots are
+ * interleaved (re, im), z [order][2] = complex(real64) / complex128, in the order DGEEV's WR / WI have: a complex pair as
+ * (re, +im), (re, -im), the exact zero roots of zero low coefficients last.  info (per polynomial): 0;
+ * NLH_CONVERGENCE_ERROR (the sweep limit: the roots that deflated are valid, the others NaN); NLH_DIVIDE_BY_ZERO_ERROR
+ * (leading coefficient exactly 0; roots NaN); NLH_INVALID_INPUT_ERROR (a coefficient, or a quotient -c_i / c_order, that
+ * is not finite; roots NaN).  The return value is non-zero only for bad arguments (order < 0: NLH_INVALID_INPUT_ERROR;
+ * order > 256: NLH_ARRAY_SIZE_ERROR, nothing launched) or a HIP error.  order == 0 returns 0 and writes nothing (:373).
+ * The batch form takes device arrays dcoef [nprob][order + 1], dz [nprob][order][2], dinfo [nprob].
+ * NLH_POLYROOTS_FORM = lane | wave | global (environment, read at each call) moves a call to a later form than the one
+ * its order selects (lane per polynomial: order <= 8; wave per polynomial on an LDS window: <= 128; on a global-memory
+ * window: <= 256); every form gives the same bits. */
+int nlh_poly_roots(nlh_handle *h, int32_t order, const double *coef, double *z, int32_t *info);
+int nlh_poly_roots_batch(nlh_handle *h, int32_t nprob, int32_t order, const double *dcoef, double *dz,
+                         int32_t *dinfo);
+/* polynomial%evaluate (:241-321), Horner from the top, for device arrays: dcoef [nprob][order + 1]; real points dx, dy
+ * [nprob][npts]; complex points dz, dy [nprob][npts][2] (the product y x is the four-multiply form, the real
+ * coefficient is added to the real part only). */
+int nlh_poly_eval_batch(nlh_handle *h, int32_t nprob, int32_t order, int32_t npts, const double *dcoef,
+                        const double *dx, double *dy);
+int nlh_poly_eval_complex_batch(nlh_handle *h, int32_t nprob, int32_t order, int32_t npts, const double *dcoef,
+                                const double *dz, double *dy);
+
 /* ---- per-kernel timing (HIP events on the handle's stream) ------------------ */
 #define NLH_K_DQ_RESIDUAL   0
 #define NLH_K_DQ_PANEL      1
@@ -585,7 +610,8 @@ int nlh_poly_fit_batch(nlh_handle *h, int32_t nprob, int32_t npts, int32_t order
 #define NLH_K_DQ_JACOBIAN  11
 #define NLH_K_QRX_PASS     12   /* exact lmfactor: trailing pass of a Householder step (nlh_qrx.hip) */
 #define NLH_K_QRX_PIVOT    13   /* exact lmfactor: pivot + reflector of a step */
-#define NLH_K_COUNT        14
+#define NLH_K_POLYROOTS    14   /* polynomial%roots: the one kernel of a nlh_poly_roots_batch call (nlh_polyroots.hip) */
+#define NLH_K_COUNT        15
 /* on: 0 = off, 1 = every kernel group, otherwise a mask with bit (k + 1) set for each group NLH_K_<k> to time
    (two HIP event records per timed launch on the handle's stream). */
 void nlh_timing_enable(nlh_handle *h, int32_t on);

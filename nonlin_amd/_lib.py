@@ -120,6 +120,10 @@ SYMBOLS = {
     "nlh_chol_rank1": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, c_int32_p]),
     "nlh_poly_fit": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p]),
     "nlh_poly_fit_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_poly_roots": (C.c_int, [_H, C.c_int32, c_double_p, c_double_p, C.POINTER(C.c_int32)]),
+    "nlh_poly_roots_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_poly_eval_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_poly_eval_complex_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_dq_model_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, C.c_double, C.POINTER(C.c_void_p)]),
     "nlh_device_set_create": (C.c_int, [C.POINTER(C.c_void_p), c_int32_p, C.c_int32]),
     "nlh_device_set_destroy": (None, [C.c_void_p]),
@@ -199,6 +203,7 @@ SYMBOLS = {
 KERNEL_IDS = {
     "dq_residual": 0, "dq_panel": 1, "fd_jacobian": 2, "gram": 3, "gram_reduce": 4, "jtf": 5,
     "chol": 6, "lmpar": 7, "qr": 8, "update": 9, "lu": 10, "dq_jacobian": 11, "qrx_pass": 12, "qrx_pivot": 13,
+    "polyroots": 14,
 }
 
 _lib = None

@@ -435,8 +435,13 @@ class newton_solver(line_search_solver):
 
 
 class polynomial:
-    """src/nonlin_polynomials.f90:39-62 -- the fitting front end only (initialize, order, fit, fit_thru_zero,
-    evaluate, get, get_all, set); roots / arithmetic are outside the hot path."""
+    """src/nonlin_polynomials.f90:39-72: initialize, order, fit, fit_thru_zero, evaluate (real and complex), companion_mtx,
+    roots, get, get_all, set, assignment (copy / assign), + - *, divide.  Coefficients are c(1) + c(2) x + ... as in the
+    reference (get / set are 1-based).  fit and roots run on the device; the arithmetic is host code that follows the
+    reference statement by statement, including where it is odd: for x of HIGHER order than y, x + y and x - y leave the
+    leading coefficient of the result 0 (:538, :593), and x - y with x uninitialised returns +y (:576-580).
+    roots() returns complex128 in the order LAPACK's DGEEV has them (a complex pair as (re, +im), (re, -im); the exact
+    zero roots of zero low coefficients last)."""
 
     def __init__(self, order=None):
         self._c = None
@@ -472,7 +477,9 @@ class polynomial:
     def fit(self, x, y, order): self._fit(x, y, order, False)                 # :146-190
     def fit_thru_zero(self, x, y, order): self._fit(x, y, order, True)        # :193-238
 
-    def evaluate(self, x):                                    # :241-268, Horner from the top
+    def evaluate(self, x):                                    # :241-321, Horner from the top
+        if np.iscomplexobj(x):
+            return self._evaluate_complex(np.asarray(x, dtype=np.complex128))
         x = np.asarray(x, dtype=np.float64)
         order = self.order()
         if order == -1:
@@ -484,9 +491,154 @@ class polynomial:
             y = y * x + self._c[j]
         return y
 
+    def _evaluate_complex(self, x):                           # :290-321: y x as (yr xr - yi xi, yr xi + yi xr), c to the real part
+        order = self.order()
+        if order == -1:
+            return np.zeros_like(x)
+        if order == 0:
+            return np.full_like(x, self._c[0])
+        xr, xi = x.real, x.imag
+        yr = self._c[order] * xr + self._c[order - 1]
+        yi = self._c[order] * xi
+        for j in range(order - 2, -1, -1):
+            tr = yr * xr - yi * xi
+            ti = yr * xi + yi * xr
+            yr = tr + self._c[j]
+            yi = ti
+        y = np.empty(x.shape, dtype=np.complex128)
+        y.real = yr
+        y.imag = yi
+        return y
+
+    def companion_mtx(self):                                  # :324-354
+        n = self.order()
+        if n == -1:
+            return np.zeros((0, 0))
+        c = np.zeros((n, n))
+        for i in range(n):
+            c[i, n - 1] = -self._c[i] / self._c[n]
+            if i < n - 1:
+                c[i + 1, i] = 1.0
+        return c
+
+    def roots(self):                                          # :357-381
+        n = self.order()
+        if n <= 0:
+            return np.zeros(0, dtype=np.complex128)           # :373
+        z = np.empty(n, dtype=np.complex128)
+        info = C.c_int32(0)
+        h = default_handle()
+        coef = np.ascontiguousarray(self._c, dtype=np.float64)
+        rc = h.lib.nlh_poly_roots(h.ptr, n, _dp(coef), z.ctypes.data_as(_lib.c_double_p), C.byref(info))
+        h.check(rc, "nlh_poly_roots")
+        if rc:
+            raise NonlinError(rc)
+        if info.value:
+            raise NonlinError(info.value)
+        return z
+
     def get(self, i): return float(self._c[i - 1])            # 1-based like the reference
     def get_all(self): return self._c.copy()
     def set(self, i, v): self._c[i - 1] = float(v)
+
+    # ---- assignment(=), :454-498 -------------------------------------------------------------------------------
+    def copy(self):                                           # poly_equals
+        z = polynomial()
+        if self._c is not None:
+            z._c = self._c.copy()
+        return z
+
+    def assign(self, y):
+        """x = y for y a polynomial (:454-470), a number (every coefficient, :473-488) or an array (:491-498)."""
+        if isinstance(y, polynomial):
+            self._c = None if y._c is None else y._c.copy()
+        elif np.ndim(y) == 0:
+            if self._c is not None:
+                self._c[:] = float(y)
+        else:
+            self.initialize(y)
+        return self
+
+    # ---- operators, :501-678 -----------------------------------------------------------------------------------
+    @staticmethod
+    def _of(c):
+        z = polynomial()
+        z._c = c
+        return z
+
+    def _add_sub(self, y, sub):                               # poly_poly_add :501-553, poly_poly_subtract :556-608
+        x_ord, y_ord = self.order(), y.order()
+        max_ord = max(x_ord, y_ord)
+        if x_ord == -1 and y_ord == -1:
+            return polynomial()
+        z = np.zeros(max_ord + 1)
+        if x_ord == -1:
+            z[:] = y._c                                       # :523, and :578 for subtract: +y
+        elif y_ord == -1:
+            z[:] = self._c
+        elif x_ord > y_ord:
+            lo = self._c[:y_ord + 1]
+            z[:y_ord + 1] = lo - y._c if sub else lo + y._c
+            z[y_ord + 1:x_ord] = self._c[y_ord + 1:x_ord]     # :538 / :593: do i = y_ord + 2, x_ord -- z(x_ord + 1) stays 0
+        elif x_ord < y_ord:
+            lo = y._c[:x_ord + 1]
+            z[:x_ord + 1] = self._c - lo if sub else self._c + lo
+            z[x_ord + 1:] = -y._c[x_ord + 1:] if sub else y._c[x_ord + 1:]
+        else:
+            z[:] = self._c - y._c if sub else self._c + y._c
+        return polynomial._of(z)
+
+    def __add__(self, y):
+        return self._add_sub(y, False) if isinstance(y, polynomial) else NotImplemented
+
+    def __sub__(self, y):
+        return self._add_sub(y, True) if isinstance(y, polynomial) else NotImplemented
+
+    def __mul__(self, y):
+        if isinstance(y, polynomial):                         # poly_poly_mult :611-636
+            n, m = self.order() + 1, y.order() + 1
+            if n + m - 2 < 0:
+                raise NonlinError(2)                          # initialize(order < 0)
+            z = np.zeros(n + m - 1)
+            for i in range(n):
+                for j in range(m):
+                    z[i + j] = z[i + j] + self._c[i] * y._c[j]
+            return polynomial._of(z)
+        if np.ndim(y) == 0 and not isinstance(y, complex):    # poly_dbl_mult :639-657
+            if self._c is None:
+                raise NonlinError(2)
+            return polynomial._of(self._c * float(y))
+        return NotImplemented
+
+    def __rmul__(self, x):                                    # dbl_poly_mult :660-678
+        return self.__mul__(x)
+
+    def divide(self, divisor):                                # poly_divide :681-779
+        """(quotient, remainder) of self / divisor."""
+        if self.order() == -1:
+            raise NonlinError(1)                              # :710
+        if divisor.order() == -1:
+            raise NonlinError(2)                              # :711
+        num, den = self._c, divisor._c
+        eps = np.finfo(np.float64).eps
+        lead = den[-1]
+        if abs(lead) <= eps:
+            raise NonlinError(NL_DIVIDE_BY_ZERO_ERROR)        # :717
+        n, m = num.size - 1, den.size - 1
+        if n < m:
+            return polynomial(0), polynomial._of(num.copy())  # :722-728
+        q = np.zeros(n - m + 1)
+        r = num.copy()
+        for i in range(n - m, -1, -1):
+            coeff = r[i + m] / lead
+            q[i] = coeff
+            for j in range(m + 1):
+                r[i + j] = r[i + j] - coeff * den[j]
+
+        def trim(v):                                          # :744-778
+            nz = np.nonzero(np.abs(v) > eps)[0]
+            return polynomial(0) if nz.size == 0 else polynomial._of(v[:nz[-1] + 1].copy())
+        return trim(q), trim(r)
 
 
 class fcnnvar_helper:

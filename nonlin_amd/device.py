@@ -472,6 +472,42 @@ class DeviceSolver:
             raise RuntimeError(f"nlh_poly_fit_batch returned {rc}")
         return coef
 
+    def poly_roots_batch(self, coef):
+        """polynomial%roots for every row of coef ([nprob, order + 1], constant first).  Returns (z complex128
+        [nprob, order], info int32 [nprob]): see nlh_poly_roots_batch in include/nonlin_hip.h for the order of the roots and
+        the per-row info codes.  A row's failure touches no other row and raises nothing."""
+        nprob, ncoef = coef.shape
+        _chk(coef, (nprob, ncoef), "coef")
+        order = ncoef - 1
+        z = torch.empty((nprob, order, 2), dtype=torch.float64, device=coef.device)
+        info = torch.zeros((nprob,), dtype=torch.int32, device=coef.device)
+        rc = self.lib.nlh_poly_roots_batch(self.h.ptr, nprob, order, coef.data_ptr(), z.data_ptr(), info.data_ptr())
+        self.h.check(rc, "nlh_poly_roots_batch")
+        if rc:
+            raise RuntimeError(f"nlh_poly_roots_batch returned {rc}")
+        return torch.view_as_complex(z), info
+
+    def poly_eval_batch(self, coef, x):
+        """polynomial%evaluate for every row: coef [nprob, order + 1], x [nprob, npts] float64 or complex128.  Returns y
+        like x."""
+        nprob, ncoef = coef.shape
+        _chk(coef, (nprob, ncoef), "coef")
+        npts = x.shape[1]
+        if x.dtype == torch.complex128:
+            if tuple(x.shape) != (nprob, npts) or not x.is_contiguous() or x.device != coef.device:
+                raise ValueError("x: expected a contiguous complex128 [nprob, npts] tensor on coef's device")
+            y = torch.empty_like(x)
+            rc = self.lib.nlh_poly_eval_complex_batch(self.h.ptr, nprob, ncoef - 1, npts, coef.data_ptr(), x.data_ptr(),
+                                                      y.data_ptr())
+        else:
+            _chk(x, (nprob, npts), "x")
+            y = torch.empty_like(x)
+            rc = self.lib.nlh_poly_eval_batch(self.h.ptr, nprob, ncoef - 1, npts, coef.data_ptr(), x.data_ptr(), y.data_ptr())
+        self.h.check(rc, "nlh_poly_eval_batch")
+        if rc:
+            raise RuntimeError(f"nlh_poly_eval_batch returned {rc}")
+        return y
+
     def chol_rank1(self, Rt, u, downdate=False):
         """In place on the row-major upper Cholesky factor Rt (n x n): R1^T R1 = R^T R +- u u^T.  Returns info."""
         n = Rt.shape[0]

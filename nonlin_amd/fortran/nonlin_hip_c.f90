@@ -106,6 +106,15 @@ module nonlin_hip_c
             real(c_double), intent(out) :: coef(*)
             integer(c_int) :: rc
         end function
+        function nlh_poly_roots(h, order, coef, z, info) bind(C, name="nlh_poly_roots") result(rc)
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: order
+            real(c_double), intent(in) :: coef(*)
+            real(c_double), intent(out) :: z(2, *)
+            integer(c_int32_t), intent(out) :: info
+            integer(c_int) :: rc
+        end function
         function nlh_cls_solve(h, opts, delta0, stepscale0, xl, xu, m, n, fcn, jacfcn, ctx, x, fvec, ib) &
                 bind(C, name="nlh_cls_solve") result(rc)
             import :: c_ptr, c_funptr, c_int, c_int32_t, c_double, nlh_options, nlh_iteration_behavior
