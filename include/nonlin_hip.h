@@ -595,6 +595,50 @@ int nlh_poly_eval_batch(nlh_handle *h, int32_t nprob, int32_t order, int32_t npt
 int nlh_poly_eval_complex_batch(nlh_handle *h, int32_t nprob, int32_t order, int32_t npts, const double *dcoef,
                                 const double *dz, double *dy);
 
+/* ---- parameter covariance of a least-squares fit (no counterpart in nonlin v2.2.0; MINPACK, whose lmder lss_solve
+ * modernises, ships it as `covar`).  For the problem min ||F(x)||^2 with Jacobian J at x:  cov = s^2 (J^T J)^-1, the
+ * standard errors sigma_i = sqrt(cov(i,i)) and the reduced chi-square s^2 = ||F(x)||^2 / (m - n). ----
+ * nlh_covar: MINPACK's covar, statement order kept, on the pivoted factor nlh_lmfactor_exact writes -- dR [nprob][n][n]
+ * column-major (upper triangle, diagonal = rdiag; the lower triangle is not read; dR is not modified), dipvt [nprob][n]
+ * 0-based.  tolr = tol |r(0,0)|; rank = number of leading k with |r(k,k)| > tolr (the first failure ends the count);
+ * the leading rank x rank block is inverted, (R^T R)^-1 formed and scattered to cov(ipvt(i), ipvt(j)), symmetric (exactly);
+ * rows and columns of the n - rank variables pivoted last are exactly 0 (they are not determined by the data to within
+ * tol).  tol <= 0 means machine epsilon.  dcov [nprob][n][n], drank [nprob].  Any n >= 1 and any nprob.  Three forms give
+ * the same bits (the plain sequential loops, -ffp-contract=off): a lane per problem (n <= 8), a workgroup per problem
+ * with the packed inverse in LDS (while nlh_covar_lds_bytes(n) fits the 161,792-byte cap: n <= 200), the same on a
+ * global-memory window of the handle (any n).  NLH_COVAR_FORM = lane | lds | global (environment, read at each call)
+ * forces a form for the sizes it can hold.  Switch points and rates: profiles/covar_rate.txt. */
+int nlh_covar(nlh_handle *h, int32_t nprob, int32_t n, const double *dR, const int32_t *dipvt, double tol,
+              double *dcov, int32_t *drank);
+/* Dynamic LDS bytes the workgroup form of nlh_covar asks for at n columns (host code, no device): the count the library
+ * compares with the cap before launching. */
+int64_t nlh_covar_lds_bytes(int32_t n);
+/* The covariance of nprob problems of the user's device family AT THE GIVEN x (dx [nprob][n], device, not modified):
+ * fvec = F(x) (one launcher call), J by vfh_jac_fcn's rule exactly as nlh_fd_jacobian_device (jacfcn, or forward
+ * differences), nlh_lmfactor_exact, nlh_covar with tol.  chi2 = (sum of f_i^2, i ascending, sequential) / (m - n);
+ * scaled = 1 multiplies every entry of cov once by chi2; sigma_i = sqrt(cov(i,i)) (after the scaling).  dcov [nprob][n][n];
+ * dsigma [nprob][n], drank [nprob], dchi2 [nprob] may be NULL.  scaled = 1 with m <= n: NLH_INVALID_INPUT_ERROR; m < n:
+ * NLH_UNDERDEFINED_PROBLEM_ERROR -- both before anything is evaluated (m == n with scaled = 0 is accepted; chi2 is then
+ * the IEEE quotient by zero).  A problem's bits do not depend on the batch it sits in; batches beyond 65535 problems
+ * run in slices.  Uses workspaces of the handle that no solver uses. */
+int nlh_lm_covariance_batch_device(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn,
+                                   nlh_device_jacfcn jacfcn, void *ctx, const double *dx, int32_t scaled, double tol,
+                                   double *dcov, double *dsigma, int32_t *drank, double *dchi2);
+/* ... behind HOST arrays x, cov, sigma, rank, chi2. */
+int nlh_lm_covariance_batch_device_h(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn,
+                                     nlh_device_jacfcn jacfcn, void *ctx, const double *x, int32_t scaled, double tol,
+                                     double *cov, double *sigma, int32_t *rank, double *chi2);
+/* ... for ONE problem with HOST callbacks: fcn at x, then vfh_jac_fcn's calls (jacfcn, or the n perturbed evaluations in
+ * ascending j; x is perturbed in place and restored), on the calling thread; the linear algebra runs on the device.
+ * cov [n][n], sigma [n] / rank / chi2 (NULL allowed): host. */
+int nlh_lm_covariance(nlh_handle *h, int32_t m, int32_t n, nlh_vecfcn fcn, nlh_jacfcn jacfcn, void *ctx, double *x,
+                      int32_t scaled, double tol, double *cov, double *sigma, int32_t *rank, double *chi2);
+/* ... for every problem of a model object (built-in family: forward differences, as its LM solve; a user-launcher model:
+ * its jacfcn if it has one), host arrays; a model on a device set is served share by share (handle may be NULL).  What
+ * the Fortran shim's least_squares_solver%covariance / covariance_batch call. */
+int nlh_dq_model_lm_covariance(nlh_handle *h, const nlh_dq_model *model, const double *x, int32_t scaled, double tol,
+                               double *cov, double *sigma, int32_t *rank, double *chi2);
+
 /* ---- per-kernel timing (HIP events on the handle's stream) ------------------ */
 #define NLH_K_DQ_RESIDUAL   0
 #define NLH_K_DQ_PANEL      1
@@ -611,7 +655,8 @@ int nlh_poly_eval_complex_batch(nlh_handle *h, int32_t nprob, int32_t order, int
 #define NLH_K_QRX_PASS     12   /* exact lmfactor: trailing pass of a Householder step (nlh_qrx.hip) */
 #define NLH_K_QRX_PIVOT    13   /* exact lmfactor: pivot + reflector of a step */
 #define NLH_K_POLYROOTS    14   /* polynomial%roots: the one kernel of a nlh_poly_roots_batch call (nlh_polyroots.hip) */
-#define NLH_K_COUNT        15
+#define NLH_K_COVAR       15   /* covar: the launches of one nlh_covar call, one bracket (nlh_covar.hip) */
+#define NLH_K_COUNT        16
 /* on: 0 = off, 1 = every kernel group, otherwise a mask with bit (k + 1) set for each group NLH_K_<k> to time
    (two HIP event records per timed launch on the handle's stream). */
 void nlh_timing_enable(nlh_handle *h, int32_t on);

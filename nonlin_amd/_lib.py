@@ -193,6 +193,16 @@ SYMBOLS = {
     "nlh_device_fcn_model_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
     "nlh_dq_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "nlh_dq_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_covar": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "nlh_covar_lds_bytes": (C.c_int64, [C.c_int32]),
+    "nlh_lm_covariance_batch_device": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, C.c_void_p,
+                                                 C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_lm_covariance_batch_device_h": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, c_double_p,
+                                                   C.c_int32, C.c_double, c_double_p, c_double_p, c_int32_p, c_double_p]),
+    "nlh_lm_covariance": (C.c_int, [_H, C.c_int32, C.c_int32, VECFCN, JACFCN, C.c_void_p, c_double_p, C.c_int32, C.c_double,
+                                    c_double_p, c_double_p, c_int32_p, c_double_p]),
+    "nlh_dq_model_lm_covariance": (C.c_int, [_H, C.c_void_p, c_double_p, C.c_int32, C.c_double, c_double_p, c_double_p, c_int32_p,
+                                             c_double_p]),
     "nlh_timing_enable": (None, [_H, C.c_int32]),
     "nlh_timing_reset": (None, [_H]),
     "nlh_timing_get": (C.c_int, [_H, C.c_int32, c_double_p, C.POINTER(C.c_int64)]),
@@ -203,7 +213,7 @@ SYMBOLS = {
 KERNEL_IDS = {
     "dq_residual": 0, "dq_panel": 1, "fd_jacobian": 2, "gram": 3, "gram_reduce": 4, "jtf": 5,
     "chol": 6, "lmpar": 7, "qr": 8, "update": 9, "lu": 10, "dq_jacobian": 11, "qrx_pass": 12, "qrx_pivot": 13,
-    "polyroots": 14,
+    "polyroots": 14, "covar": 15,
 }
 
 _lib = None

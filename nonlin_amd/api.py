@@ -241,6 +241,33 @@ class least_squares_solver(equation_solver):
             raise NonlinError(rc)                 # :388-390
 
 
+    def covariance(self, fcn, x, scaled=True, tol=None, args=None):
+        """Parameter covariance of the fit at x (extension; MINPACK's covar on a fresh lmfactor of the Jacobian at x --
+        NOT the last Jacobian of a solve).  fcn: the vecfcn_helper solve takes; x [n] is perturbed in place and restored.
+        Returns (cov [n, n], sigma [n], rank, chi2): cov = (J^T J)^-1, times chi2 = ||F(x)||^2 / (m - n) when scaled;
+        rows and columns of variables the data do not determine to within tol (default: machine epsilon, relative to the
+        largest pivot) are zero and rank < n."""
+        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.flags.c_contiguous):
+            raise ValueError("x must be a contiguous float64 numpy array")
+        if not fcn.is_fcn_defined():
+            raise NonlinError(NL_UNDEFINED_FUNCTION_ERROR)
+        m, n = fcn.get_equation_count(), fcn.get_variable_count()
+        if x.shape != (n,):
+            raise NonlinError(3)
+        h = self._handle()
+        cov = np.empty((n, n))
+        sigma = np.empty(n)
+        rank = C.c_int32(0)
+        chi2 = C.c_double(0.0)
+        cf, cj = fcn._c_fcn(args), fcn._c_jac(args)
+        rc = h.lib.nlh_lm_covariance(h.ptr, m, n, cf, cj, None, _dp(x), int(bool(scaled)), 0.0 if tol is None else float(tol),
+                                     _dp(cov), _dp(sigma), C.byref(rank), C.byref(chi2))
+        h.check(rc, "nlh_lm_covariance")
+        if rc:
+            raise NonlinError(rc)
+        return cov, sigma, int(rank.value), float(chi2.value)
+
+
 class constrained_equation_solver(least_squares_solver):
     """src/nonlin_least_squares.f90:33-53 (bounds holder)."""
 

@@ -62,7 +62,7 @@ int ensure_pinned(nlh_handle *h, size_t bytes)
 static const char *k_names[NLH_K_COUNT] = {
     "k_dq_residual", "k_dq_panel", "k_fd_jacobian", "k_gram_mfma", "k_gram_reduce", "k_jtf",
     "k_chol_factor", "k_lmpar", "k_qr_factor", "k_lm_update", "k_lu_factor", "k_dq_jacobian", "k_qrx_pass",
-    "k_qrx_pivot", "k_polyroots"};
+    "k_qrx_pivot", "k_polyroots", "k_covar"};
 
 void timing_flush(nlh_handle *h)
 {
@@ -131,6 +131,7 @@ int nlh_create(nlh_handle **out, int32_t device, void *hip_stream)
     nlh_bfgs_init_device(lds_max);
     nlh_poly_init_device(lds_max);
     nlh_polyroots_init_device(lds_max);
+    nlh_covar_init_device(lds_max);
     nlh_devfcn_init_device(lds_max);
     (void)hipFuncSetAttribute((const void *)k_dq_residual<RB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     (void)hipFuncSetAttribute((const void *)k_dq_residual2<RB / 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);

@@ -4,7 +4,7 @@
 // (least_squares_solver: lss_solve and its stages), nlh_square.hip (newton_solver, quasi_newton_solver, LU, the
 // Householder steps), nlh_cls.hip (constrained_least_squares_solver), nlh_bfgs.hip (bfgs, fcnnvar_helper%gradient), nlh_nm.hip (nelder_mead),
 // nlh_1var.hip (brent_solver, newton_1var_solver, fcn1var_helper%diff),
-// nlh_poly.hip (polynomial%fit), nlh_polyroots.hip (polynomial%roots, batched evaluate), nlh_model.hip (device sets, device residual models behind host arrays), nlh_qrx.hip
+// nlh_poly.hip (polynomial%fit), nlh_polyroots.hip (polynomial%roots, batched evaluate), nlh_covar.hip (parameter covariance), nlh_model.hip (device sets, device residual models behind host arrays), nlh_qrx.hip
 // (the exact lmfactor).  Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it
 // launches.
 #pragma once
@@ -54,7 +54,8 @@ struct nlh_handle {
     // named workspace buffers (grown on demand, reused across calls)
     DevBuf J, P, wa4, scratch, G, Gpart, vecs, ipvt, gvec, part, state, info, misc, lu, xdev, fdev, Adev, bdev, W2, R,
            qnQ, qnR, qnV, bfB, bfR, bfV, qxV, lumv, lus,
-           dvX, dvF, dvIdx, dvP;          // user device residuals: points, compact residuals, problem lists, panel chunk (nlh_devfcn.hip)
+           dvX, dvF, dvIdx, dvP,          // user device residuals: points, compact residuals, problem lists, panel chunk (nlh_devfcn.hip)
+           cvW, cvT, cvH;                 // covariance (nlh_covar.hip): the chain's arrays, the global-memory window, host-array staging
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     DevBuf cholmc;                     // side buffer of the multi-CU Cholesky (solved panels, bad-pivot flags)
@@ -217,6 +218,7 @@ int nlh_root1v_solve_batch_device_h(nlh_handle *h, const nlh_options *o, int new
 void nlh_cls_init_device(int lds_max);
 void nlh_poly_init_device(int lds_max);
 void nlh_polyroots_init_device(int lds_max);    // nlh_polyroots.hip (polynomial%roots, batched evaluate)
+void nlh_covar_init_device(int lds_max);        // nlh_covar.hip (covar, nlh_lm_covariance*)
 void nlh_devfcn_init_device(int lds_max);        // nlh_devfcn.hip: the built-in family's launcher kernels keep x in LDS
 // columns the built-in dense-quadratic family's kernels accept (x in LDS, lds_max of nlh_create): beyond it NLH_ARRAY_SIZE_ERROR
 static const int32_t NLH_DQ_MAX_N = 20000;

@@ -306,6 +306,48 @@ int nlh_dq_model_lm_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_mode
                      });
 }
 
+// Parameter covariance at x for every problem of the model (nlh_lm_covariance_batch_device_h on each share; the built-in
+// family through its launcher nlh_dq_device_fcn, forward differences as its LM solve uses).  Host arrays: x [nprob][n],
+// cov [nprob][n][n], sigma [nprob][n], rank / chi2 [nprob]; sigma, rank, chi2 may be NULL.
+int nlh_dq_model_lm_covariance(nlh_handle *h, const nlh_dq_model *md, const double *x, int32_t scaled, double tol, double *cov,
+                               double *sigma, int32_t *rank, double *chi2)
+{
+    if (!md || !x || !cov) return NLH_INVALID_INPUT_ERROR;
+    const int32_t m = md->m, n = md->n;
+    if (md->ufcn)
+        return nlh_lm_covariance_batch_device_h(h, md->nprob, m, n, md->ufcn, md->ujac, md->uctx, x, scaled, tol, cov, sigma, rank, chi2);
+    if (!md->set && !h) return NLH_ERR_BAD_HANDLE;
+    const size_t nn = (size_t)n * n;
+    for (const DqPart &pt : md->parts) {                         // the shares one after the other: each on its own handle
+        if (pt.cnt == 0) continue;
+        nlh_handle *ph = pt.h ? pt.h : h;
+        nlh_dq_device_ctx c;
+        c.dA = pt.dA; c.db = pt.db; c.gamma = md->gamma;
+        int rc;
+        if (pt.stride == 1) {
+            const size_t f = (size_t)pt.first;
+            rc = nlh_lm_covariance_batch_device_h(ph, pt.cnt, m, n, nlh_dq_device_fcn, nullptr, &c, x + f * n, scaled, tol, cov + f * nn,
+                                                  sigma ? sigma + f * n : nullptr, rank ? rank + f : nullptr, chi2 ? chi2 + f : nullptr);
+        } else {
+            const size_t cnt = (size_t)pt.cnt;
+            std::vector<double> xs(cnt * n), cs(cnt * nn), ss(cnt * n), qs(cnt);
+            std::vector<int32_t> rs(cnt);
+            for (size_t i = 0; i < cnt; ++i) memcpy(&xs[i * n], x + ((size_t)pt.first + i * pt.stride) * n, sizeof(double) * n);
+            rc = nlh_lm_covariance_batch_device_h(ph, pt.cnt, m, n, nlh_dq_device_fcn, nullptr, &c, xs.data(), scaled, tol, cs.data(),
+                                                  ss.data(), rs.data(), qs.data());
+            for (size_t i = 0; i < cnt && !rc; ++i) {
+                const size_t k = (size_t)pt.first + i * pt.stride;
+                memcpy(cov + k * nn, &cs[i * nn], sizeof(double) * nn);
+                if (sigma) memcpy(sigma + k * n, &ss[i * n], sizeof(double) * n);
+                if (rank) rank[k] = rs[i];
+                if (chi2) chi2[k] = qs[i];
+            }
+        }
+        if (rc) { if (md->set) md->set->err = ph->err; return rc; }
+    }
+    return 0;
+}
+
 // newton_solver%solve on every (square) problem of the model; analytic != 0: the model's own Jacobian
 // J(i,j) = (1 + 2 gamma u_i) A(i,j) plays the role of a jacobianfcn, otherwise forward differences.
 int nlh_dq_model_newton_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_model *md, int32_t analytic, double *x,

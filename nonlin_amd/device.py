@@ -508,6 +508,45 @@ class DeviceSolver:
             raise RuntimeError(f"nlh_poly_eval_batch returned {rc}")
         return y
 
+    def covar(self, R, ipvt, tol=None):
+        """MINPACK's covar on the pivoted factor lmfactor_exact returns: R [nprob, n, n] (column-major problems, upper
+        triangle with rdiag on the diagonal, not modified), ipvt [nprob, n] int32, 0-based.  tol: None or <= 0 means
+        machine epsilon.  Returns (cov [nprob, n, n], rank int32 [nprob]); rows and columns of the n - rank variables
+        pivoted last are exactly zero."""
+        nprob, n, _ = R.shape
+        _chk(R, (nprob, n, n), "R")
+        if not (ipvt.is_cuda and ipvt.dtype == torch.int32 and ipvt.is_contiguous() and tuple(ipvt.shape) == (nprob, n)):
+            raise ValueError("ipvt: expected a contiguous int32 GPU tensor of shape [nprob, n]")
+        cov = torch.empty((nprob, n, n), dtype=torch.float64, device=R.device)
+        rank = torch.empty((nprob,), dtype=torch.int32, device=R.device)
+        rc = self.lib.nlh_covar(self.h.ptr, nprob, n, R.data_ptr(), ipvt.data_ptr(), 0.0 if tol is None else float(tol),
+                                cov.data_ptr(), rank.data_ptr())
+        self.h.check(rc, "nlh_covar")
+        if rc:
+            raise RuntimeError(f"nlh_covar returned {rc}")
+        return cov, rank
+
+    def lm_covariance_batch_device(self, fcn, ctx, m, x, jac=None, scaled=True, tol=None):
+        """Parameter covariance of x.shape[0] least-squares problems of a USER'S device residual AT x ([nprob, n], not
+        modified): F(x), a fresh Jacobian (jac, or forward differences), the exact lmfactor, covar.  Returns (cov
+        [nprob, n, n], sigma [nprob, n], rank int32 [nprob], chi2 [nprob]); scaled: cov is multiplied by chi2 =
+        ||F(x)||^2 / (m - n).  Raises NonlinError-coded RuntimeError for m < n (212) and for scaled with m <= n (201)."""
+        nprob, n = x.shape
+        _chk(x, (nprob, n), "x")
+        dev = x.device
+        cov = torch.empty((nprob, n, n), dtype=torch.float64, device=dev)
+        sigma = torch.empty((nprob, n), dtype=torch.float64, device=dev)
+        rank = torch.empty((nprob,), dtype=torch.int32, device=dev)
+        chi2 = torch.empty((nprob,), dtype=torch.float64, device=dev)
+        rc = self.lib.nlh_lm_covariance_batch_device(self.h.ptr, nprob, int(m), n, self._devfcn(fcn), self._devfcn(jac),
+                                                     self._ctxp(ctx), x.data_ptr(), int(bool(scaled)),
+                                                     0.0 if tol is None else float(tol), cov.data_ptr(), sigma.data_ptr(),
+                                                     rank.data_ptr(), chi2.data_ptr())
+        self.h.check(rc, "nlh_lm_covariance_batch_device")
+        if rc:
+            raise RuntimeError(f"nlh_lm_covariance_batch_device returned {rc}")
+        return cov, sigma, rank, chi2
+
     def chol_rank1(self, Rt, u, downdate=False):
         """In place on the row-major upper Cholesky factor Rt (n x n): R1^T R1 = R^T R +- u u^T.  Returns info."""
         n = Rt.shape[0]
@@ -604,6 +643,26 @@ class HostModel:
         if rc != 0:
             raise RuntimeError(f"nlh_dq_model_bfgs_solve: {rc}")
         return x, f, fo, [ib[p].as_dict() for p in range(self.nprob)], [int(st[p]) for p in range(self.nprob)]
+
+    def lm_covariance(self, x, scaled=True, tol=None):
+        """Parameter covariance of every problem at x ([nprob, n] host array, not modified): returns numpy arrays (cov
+        [nprob, n, n], sigma [nprob, n], rank int32 [nprob], chi2 [nprob]).  See nlh_dq_model_lm_covariance."""
+        import numpy as np
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.nprob, self.n):
+            raise ValueError("x must be [nprob, n]")
+        cov = np.empty((self.nprob, self.n, self.n))
+        sigma = np.empty((self.nprob, self.n))
+        rank = np.empty(self.nprob, dtype=np.int32)
+        chi2 = np.empty(self.nprob)
+        dp = lambda a: a.ctypes.data_as(_lib.c_double_p)
+        hptr = None if isinstance(self.owner, DeviceSet) else self.owner.h.ptr
+        rc = self.lib.nlh_dq_model_lm_covariance(hptr, self._md, dp(x), int(bool(scaled)), 0.0 if tol is None else float(tol),
+                                                 dp(cov), dp(sigma), rank.ctypes.data_as(_lib.c_int32_p), dp(chi2))
+        self.owner.check(rc, "nlh_dq_model_lm_covariance")
+        if rc != 0:
+            raise RuntimeError(f"nlh_dq_model_lm_covariance: {rc}")
+        return cov, sigma, rank, chi2
 
     def close(self):
         if getattr(self, "_md", None) is not None and self._md.value:

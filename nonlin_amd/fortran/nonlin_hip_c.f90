@@ -214,6 +214,31 @@ module nonlin_hip_c
             integer(c_int32_t), intent(out) :: status(*)
             integer(c_int) :: rc
         end function
+        function nlh_lm_covariance(h, m, n, fcn, jacfcn, ctx, x, scaled, tol, cov, sigma, rank, chi2) &
+                bind(C, name="nlh_lm_covariance") result(rc)
+            import :: c_ptr, c_funptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: m, n
+            type(c_funptr), value :: fcn, jacfcn
+            type(c_ptr), value :: ctx
+            real(c_double), intent(inout) :: x(*)
+            integer(c_int32_t), value :: scaled
+            real(c_double), value :: tol
+            real(c_double), intent(out) :: cov(*), sigma(*), chi2(*)
+            integer(c_int32_t), intent(out) :: rank(*)
+            integer(c_int) :: rc
+        end function
+        function nlh_dq_model_lm_covariance(h, model, x, scaled, tol, cov, sigma, rank, chi2) &
+                bind(C, name="nlh_dq_model_lm_covariance") result(rc)
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h, model
+            real(c_double), intent(in) :: x(*)
+            integer(c_int32_t), value :: scaled
+            real(c_double), value :: tol
+            real(c_double), intent(out) :: cov(*), sigma(*), chi2(*)
+            integer(c_int32_t), intent(out) :: rank(*)
+            integer(c_int) :: rc
+        end function
         function nlh_dq_model_newton_solve(h, opts, model, analytic, x, fvec, ib, status) &
                 bind(C, name="nlh_dq_model_newton_solve") result(rc)
             import :: c_ptr, c_int, c_int32_t, c_double, nlh_options, nlh_iteration_behavior

@@ -24,6 +24,8 @@ module nonlin_least_squares
         procedure, public :: set_step_scaling_factor => lm_put_step_bound
         procedure, public :: solve => lm_solve_one
         procedure, public :: solve_batch => lm_solve_many
+        procedure, public :: covariance => lm_covariance_one
+        procedure, public :: covariance_batch => lm_covariance_many
     end type
 
     type, abstract, extends(least_squares_solver) :: constrained_equation_solver
@@ -153,6 +155,117 @@ contains
         fvec = fwork
         if (present(status)) status = outcome
         if (present(ib)) call behavior_import(ib, counters)
+    end subroutine
+
+    !> Extension: the parameter covariance of a least-squares fit AT x (typically the x a solve returned): F(x), a fresh
+    !> Jacobian by vecfcn_helper%jacobian's rule, lmfactor, MINPACK's covar (nlh_lm_covariance / nlh_dq_model_lm_covariance).
+    !> cov(n, n) = (J^T J)^-1, multiplied by chi2 = ||F(x)||^2 / (m - n) unless scaled = .false. (default .true.);
+    !> sigma(n) = sqrt of its diagonal; rank = number of variables the data determine to within tol (default: machine
+    !> epsilon, relative to the largest pivot) -- the rows and columns of the others are zero.  x is not changed.
+    subroutine lm_covariance_one(this, fcn, x, cov, sigma, rank, chi2, scaled, tol, args)
+        class(least_squares_solver), intent(inout) :: this
+        class(vecfcn_helper), intent(in), target :: fcn
+        real(real64), intent(in), dimension(:) :: x
+        real(real64), intent(out), dimension(:,:) :: cov
+        real(real64), intent(out), dimension(:), optional :: sigma
+        integer(int32), intent(out), optional :: rank
+        real(real64), intent(out), optional :: chi2
+        logical, intent(in), optional :: scaled
+        real(real64), intent(in), optional :: tol
+        class(*), intent(inout), optional, target :: args
+
+        type(nlh_callback_ctx), target :: ctx
+        type(device_model_batch) :: onchip
+        type(c_funptr) :: jac_entry
+        real(c_double), allocatable :: xwork(:), cwork(:,:), swork(:)
+        real(c_double) :: q(1), eps
+        integer(c_int32_t) :: r(1), sc
+        integer(c_int) :: rc
+        integer(int32) :: m, n
+
+        m = fcn%get_equation_count()
+        n = fcn%get_variable_count()
+        if (.not.fcn%is_fcn_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR
+        sc = 1
+        if (present(scaled)) sc = merge(1, 0, scaled)
+        if (sc == 1 .and. m <= n) error stop NL_INVALID_INPUT_ERROR
+        if (n > m) error stop NL_UNDERDEFINED_PROBLEM_ERROR
+        if (size(x) /= n) error stop 3
+        if (any(shape(cov) /= [n, n])) error stop 4
+        if (present(sigma)) then
+            if (size(sigma) /= n) error stop 5
+        end if
+        eps = 0.0d0
+        if (present(tol)) eps = tol
+        allocate(xwork(n), source = x)
+        allocate(cwork(n, n), swork(n))
+        if (fcn%is_device_model_defined()) then
+            onchip = fcn%device_model()
+            rc = nlh_dq_model_lm_covariance(nlh_default_handle(), onchip%c_handle(), xwork, sc, eps, cwork, swork, r, q)
+        else
+            ctx%helper => fcn
+            if (present(args)) ctx%args => args
+            jac_entry = c_null_funptr
+            if (fcn%is_jacobian_defined()) jac_entry = c_funloc(nlh_jacfcn_trampoline)
+            rc = nlh_lm_covariance(nlh_default_handle(), m, n, c_funloc(nlh_vecfcn_trampoline), jac_entry, c_loc(ctx), &
+                xwork, sc, eps, cwork, swork, r, q)
+        end if
+        if (rc /= 0) error stop rc
+        cov = cwork
+        if (present(sigma)) sigma = swork
+        if (present(rank)) rank = r(1)
+        if (present(chi2)) chi2 = q(1)
+    end subroutine
+
+    !> ... for every problem of a device model batch (built-in family or a user's device fcn): x(n, nprob),
+    !> cov(n, n, nprob), sigma(n, nprob), rank(nprob), chi2(nprob).
+    subroutine lm_covariance_many(this, model, x, cov, sigma, rank, chi2, scaled, tol)
+        class(least_squares_solver), intent(inout) :: this
+        class(device_model_batch), intent(in) :: model
+        real(real64), intent(in), dimension(:,:) :: x
+        real(real64), intent(out), dimension(:,:,:) :: cov
+        real(real64), intent(out), dimension(:,:), optional :: sigma
+        integer(int32), intent(out), dimension(:), optional :: rank
+        real(real64), intent(out), dimension(:), optional :: chi2
+        logical, intent(in), optional :: scaled
+        real(real64), intent(in), optional :: tol
+
+        real(c_double), allocatable :: xwork(:,:), cwork(:,:,:), swork(:,:), q(:)
+        integer(c_int32_t), allocatable :: r(:)
+        real(c_double) :: eps
+        integer(c_int32_t) :: sc
+        integer(c_int) :: rc
+        integer(int32) :: m, n, count
+
+        if (.not.model%is_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR
+        m = model%get_equation_count()
+        n = model%get_variable_count()
+        count = model%get_problem_count()
+        sc = 1
+        if (present(scaled)) sc = merge(1, 0, scaled)
+        if (sc == 1 .and. m <= n) error stop NL_INVALID_INPUT_ERROR
+        if (n > m) error stop NL_UNDERDEFINED_PROBLEM_ERROR
+        if (any(shape(x) /= [n, count])) error stop 3
+        if (any(shape(cov) /= [n, n, count])) error stop 4
+        if (present(sigma)) then
+            if (any(shape(sigma) /= [n, count])) error stop 5
+        end if
+        if (present(rank)) then
+            if (size(rank) /= count) error stop 6
+        end if
+        if (present(chi2)) then
+            if (size(chi2) /= count) error stop 7
+        end if
+        eps = 0.0d0
+        if (present(tol)) eps = tol
+        allocate(xwork(n, count), source = x)
+        allocate(cwork(n, n, count), swork(n, count), q(count), r(count))
+        rc = nlh_dq_model_lm_covariance(nlh_default_handle(), model%c_handle(), xwork, sc, eps, cwork, swork, r, q)
+        if (rc /= 0) error stop rc
+        cov = cwork
+        if (present(sigma)) sigma = swork
+        if (present(rank)) rank = r
+        if (present(chi2)) chi2 = q
     end subroutine
 
     ! ---- constrained_equation_solver: the box -------------------------------------------------------------------
