@@ -639,6 +639,83 @@ int nlh_lm_covariance(nlh_handle *h, int32_t m, int32_t n, nlh_vecfcn fcn, nlh_j
 int nlh_dq_model_lm_covariance(nlh_handle *h, const nlh_dq_model *model, const double *x, int32_t scaled, double tol,
                                double *cov, double *sigma, int32_t *rank, double *chi2);
 
+/* ---- built-in curve models (no counterpart in nonlin v2.2.0, which ships no model): sums of peaks or decays on a
+ * polynomial baseline, as library-owned launchers of the open device-residual path above, so that a curve fitter needs no
+ * device code of their own.  A model is a kind, ncomp = K >= 1 components and nbase = B in {-1, 0, .., 8}: the degree of a
+ * polynomial baseline, -1 for none.  It is fitted to data t, y [nprob][m] with optional weights w [nprob][m]; with
+ * shared_t != 0, t is one [m] array for every problem.  Parameters: the K components in order, then c_0 .. c_B, so
+ * n = P K + B + 1 with P = 3 for the peaks and 2 for the decay (n <= 8192).
+ * THE OPERATION ORDER IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation, the device library's
+ * exp -- so that a restatement in any IEEE language reproduces the exp-free kind bit for bit:
+ *   kind                        component k at abscissa t                              its partials, in parameter order
+ *   NLH_CURVE_GAUSS (a,mu,s)    d = (t - mu)/s; e = exp(-0.5*(d*d)); term = a*e        e;  g = ((a*e)*d)/s;  g*d
+ *   NLH_CURVE_LORENTZ (a,mu,w)  d = (t - mu)/w; q = 1.0 + d*d; term = a/q              1.0/q;  g = ((2.0*a)*d)/((w*q)*q);  g*d
+ *   NLH_CURVE_EXPDECAY (a,k)    e = exp(-(k*t)); term = a*e                            e;  -((a*t)*e)
+ *   model sum   s = 0;  s = s + term_k for k ascending
+ *   baseline    b = c_B;  b = b*t + c_j for j = B-1 .. 0;  s = s + b;      partials: p = 1; column = p; p = p*t, j ascending
+ *   residual    r = s - y;  then r = w*r when weights are given; every Jacobian entry is multiplied once by w then
+ * No sum crosses a row: a row's bits do not depend on the launch it is computed in.  Two workgroup forms give the same
+ * bits: a workgroup per (point, 256 rows), and -- while two points or more fit 256 threads, m <= 128 -- several points per
+ * workgroup; NLH_CURVE_FORM = row | flat (environment, read at each call) forces one for the sizes it can hold (flat:
+ * m <= 256).
+ * Weights and ragged data: rows with w = 0 are the way to pad spectra of different lengths to a common m (such a row's
+ * residual and Jacobian row are exactly 0).  When weights are given the degrees of freedom of a problem are
+ * dof = (number of rows with w != 0) - n, and nlh_curve_fit_batch reports chi2 = (sum of f_i^2, i ascending, sequential)
+ * / dof and multiplies every entry of cov once by (m - n) / dof before sigma_i = sqrt(cov(i,i)) is taken (with no zero
+ * weight both are what nlh_lm_covariance_batch_device returns, bit for bit).  A problem with dof <= 0 gets
+ * NLH_INVALID_INPUT_ERROR in status[p] before anything is evaluated for it; the others are solved. ---- */
+#define NLH_CURVE_GAUSS     0
+#define NLH_CURVE_LORENTZ   1
+#define NLH_CURVE_EXPDECAY  2
+#define NLH_CURVE_MAX_BASE  8
+#define NLH_CURVE_MAX_N  8192
+typedef struct nlh_curve_ctx {
+    int32_t kind, ncomp, nbase;
+    int32_t shared_t;     /* dt is [m], the same abscissae for every problem */
+    int32_t m;
+    const double *dt;     /* [nprob][m] (shared_t: [m]), device; the caller's */
+    const double *dy;     /* [nprob][m], device */
+    const double *dw;     /* [nprob][m], device, or NULL: no weights */
+} nlh_curve_ctx;
+/* The launchers (nlh_device_vecfcn / nlh_device_jacfcn, ctx = nlh_curve_ctx): they enqueue on the stream handed in, never
+ * synchronise and may be called from several host threads.  A malformed ctx -- unknown kind, K < 1, B outside -1 .. 8,
+ * n != P K + B + 1, m != ctx->m, a NULL array -- returns NLH_INVALID_INPUT_ERROR before any launch. */
+int nlh_curve_device_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX,
+                         int32_t m, double *dF);
+int nlh_curve_device_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX,
+                         int32_t m, double *dJ);
+/* n of a model (host code only); -1 for an unknown kind, ncomp < 1, nbase outside -1 .. 8 or n > 8192. */
+int32_t nlh_curve_nparams(int32_t kind, int32_t ncomp, int32_t nbase);
+/* A curve model as a MODEL object of the device-function kind, from HOST arrays t [nprob][m] (shared_t: [m]), y, w (NULL:
+ * no weights): the model owns its context and device copies, nlh_dq_model_destroy frees them.  analytic selects the
+ * Jacobian launcher; 0: forward differences, the reference's default.  nlh_dq_model_eval / _lm_solve / _cls_solve /
+ * _lm_covariance accept it as they accept any device-function model.  Errors (every nlh_curve_* entry point, in this
+ * order): NLH_ERR_BAD_HANDLE (NULL handle), NLH_INVALID_INPUT_ERROR (bad kind or counts, a NULL array),
+ * NLH_UNDERDEFINED_PROBLEM_ERROR (m < n). */
+int nlh_curve_model_create(nlh_handle *h, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m,
+                           const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic,
+                           nlh_dq_model **model);
+/* Model values -- no data term, no weights, the arithmetic above -- at arbitrary abscissae dt [nprob][npts] (shared_t:
+ * [npts]) for parameters dx [nprob][n]: dy [nprob][npts].  DEVICE pointers. */
+int nlh_curve_eval_batch(nlh_handle *h, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t npts,
+                         const double *dt, int32_t shared_t, const double *dx, double *dy);
+/* Fit + errors in one call, exactly this composition: nlh_lm_solve_batch_device (or, when xl or xu is given -- [n] host
+ * arrays, one box for every problem --, nlh_cls_solve_batch_device with delta0 = stepscale0 = 1) with the curve launchers;
+ * then, if any of dsigma, dcov, dchi2 is non-NULL, nlh_lm_covariance_batch_device at the solution with scaled = 1 and the
+ * default tol, and the degrees-of-freedom rule above when dw is given.  A problem whose status is not 0 gets NaN in
+ * sigma, cov and chi2 and rank -1.  dt, dy, dw (NULL: none), dx [nprob][n] in/out, dfvec [nprob][m], dsigma [nprob][n],
+ * dcov [nprob][n][n], dchi2 [nprob], drank [nprob]: DEVICE; ib, status: host [nprob], NULL allowed.  Asking for errors
+ * with m <= n: NLH_INVALID_INPUT_ERROR before anything is evaluated. */
+int nlh_curve_fit_batch(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                        int32_t m, const double *dt, int32_t shared_t, const double *dy, const double *dw, int32_t analytic,
+                        const double *xl, const double *xu, double *dx, double *dfvec, double *dsigma, double *dcov,
+                        double *dchi2, int32_t *drank, nlh_iteration_behavior *ib, int32_t *status);
+/* ... behind HOST arrays t, y, w, x, fvec, sigma, cov, chi2, rank. */
+int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                          int32_t m, const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic,
+                          const double *xl, const double *xu, double *x, double *fvec, double *sigma, double *cov,
+                          double *chi2, int32_t *rank, nlh_iteration_behavior *ib, int32_t *status);
+
 /* ---- per-kernel timing (HIP events on the handle's stream) ------------------ */
 #define NLH_K_DQ_RESIDUAL   0
 #define NLH_K_DQ_PANEL      1

@@ -35,6 +35,12 @@ class DqDeviceCtx(C.Structure):
     _fields_ = [("dA", C.c_void_p), ("db", C.c_void_p), ("gamma", C.c_double)]
 
 
+class CurveCtx(C.Structure):
+    """nlh_curve_ctx: a built-in curve model behind the launchers nlh_curve_device_fcn / nlh_curve_device_jac."""
+    _fields_ = [("kind", C.c_int32), ("ncomp", C.c_int32), ("nbase", C.c_int32), ("shared_t", C.c_int32), ("m", C.c_int32),
+                ("dt", C.c_void_p), ("dy", C.c_void_p), ("dw", C.c_void_p)]
+
+
 class Options(C.Structure):
     """nlh_options."""
     _fields_ = [("max_evals", C.c_int32), ("ftol", C.c_double), ("xtol", C.c_double),
@@ -203,6 +209,19 @@ SYMBOLS = {
                                     c_double_p, c_double_p, c_int32_p, c_double_p]),
     "nlh_dq_model_lm_covariance": (C.c_int, [_H, C.c_void_p, c_double_p, C.c_int32, C.c_double, c_double_p, c_double_p, c_int32_p,
                                              c_double_p]),
+    "nlh_curve_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_curve_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_curve_nparams": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "nlh_curve_model_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p,
+                                         c_double_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "nlh_curve_eval_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p]),
+    "nlh_curve_fit_batch": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_curve_fit_batch_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32,
+                                        c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                        c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_timing_enable": (None, [_H, C.c_int32]),
     "nlh_timing_reset": (None, [_H]),
     "nlh_timing_get": (C.c_int, [_H, C.c_int32, c_double_p, C.POINTER(C.c_int64)]),
@@ -251,6 +270,28 @@ def default_options():
     o = Options()
     load().nlh_default_options(C.byref(o))
     return o
+
+
+# kinds of the built-in curve models (include/nonlin_hip.h: NLH_CURVE_*), as constants and by name
+CURVE_GAUSS, CURVE_LORENTZ, CURVE_EXPDECAY = 0, 1, 2
+CURVE_KINDS = {"gauss": CURVE_GAUSS, "lorentz": CURVE_LORENTZ, "expdecay": CURVE_EXPDECAY}
+
+
+def curve_kind(kind):
+    """A curve kind as its NLH_CURVE_* value: one of the constants, or "gauss" / "lorentz" / "expdecay"."""
+    if isinstance(kind, str):
+        if kind not in CURVE_KINDS:
+            raise ValueError(f"unknown curve kind {kind!r}: one of {sorted(CURVE_KINDS)}")
+        return CURVE_KINDS[kind]
+    return int(kind)
+
+
+def curve_nparams(kind, ncomp=1, baseline=-1):
+    """n of a curve model (nlh_curve_nparams: host code, needs no GPU); raises ValueError for a bad kind or counts."""
+    n = load().nlh_curve_nparams(curve_kind(kind), int(ncomp), int(baseline))
+    if n < 0:
+        raise ValueError(f"no curve model of kind {kind!r} with {ncomp} components and baseline degree {baseline}")
+    return n
 
 
 class Handle:

@@ -84,6 +84,11 @@ struct nlh_dq_model {
     nlh_device_vecfcn ufcn = nullptr;
     nlh_device_jacfcn ujac = nullptr;
     void *uctx = nullptr;
+    // a built-in curve model (nlh_curve_model_create): uctx is this context, which the model owns together with the device
+    // copies of t, y, w behind it (one allocation, curve_base, on curve_device)
+    nlh_curve_ctx *curve = nullptr;
+    void *curve_base = nullptr;
+    int curve_device = 0;
 };
 
 int nlh_device_fcn_model_create(int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn, nlh_device_jacfcn jacfcn, void *ctx,
@@ -173,9 +178,48 @@ int nlh_dq_model_create_on(nlh_device_set *set, int32_t nprob, int32_t m, int32_
     return 0;
 }
 
+// A built-in curve model: device copies of the host arrays t [nprob][m] (shared_t: [m]), y, w (NULL: no weights) and the
+// context of the launchers nlh_curve_device_fcn / nlh_curve_device_jac (nlh_curve.hip), all owned by the model.
+int nlh_curve_model_create(nlh_handle *h, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m, const double *t,
+                           int32_t shared_t, const double *y, const double *w, int32_t analytic, nlh_dq_model **out)
+{
+    if (out) *out = nullptr;
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    const int32_t n = nlh_curve_nparams(kind, ncomp, nbase);
+    if (!out || n < 0 || nprob < 1 || m < 1 || !t || !y) return NLH_INVALID_INPUT_ERROR;
+    if (m < n) return NLH_UNDERDEFINED_PROBLEM_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t pm = (size_t)nprob * m, tm = shared_t ? (size_t)m : pm;
+    double *base = nullptr;
+    if (hipMalloc(&base, sizeof(double) * (tm + pm * (w ? 2 : 1))) != hipSuccess) {
+        h->err = "hipMalloc (curve model)";
+        return NLH_OUT_OF_MEMORY_ERROR;
+    }
+    hipError_t e = hipMemcpyAsync(base, t, sizeof(double) * tm, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + tm, y, sizeof(double) * pm, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && w) e = hipMemcpyAsync(base + tm + pm, w, sizeof(double) * pm, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        hipFree(base);
+        h->err = std::string("hipMemcpy (curve model): ") + hipGetErrorString(e);
+        return NLH_ERR_HIP;
+    }
+    nlh_curve_ctx *c = new nlh_curve_ctx();
+    c->kind = kind; c->ncomp = ncomp; c->nbase = nbase; c->shared_t = shared_t != 0; c->m = m;
+    c->dt = base; c->dy = base + tm; c->dw = w ? base + tm + pm : nullptr;
+    nlh_dq_model *md = new nlh_dq_model();
+    md->nprob = nprob; md->m = m; md->n = n; md->gamma = 0.0;
+    md->ufcn = nlh_curve_device_fcn; md->ujac = analytic ? nlh_curve_device_jac : nullptr; md->uctx = c;
+    md->curve = c; md->curve_base = base; md->curve_device = h->device;
+    *out = md;
+    return 0;
+}
+
 void nlh_dq_model_destroy(nlh_dq_model *md)
 {
     if (!md) return;
+    if (md->curve_base) { hipSetDevice(md->curve_device); hipFree(md->curve_base); }
+    delete md->curve;
     for (auto &pt : md->parts)
         if (pt.dA) { hipSetDevice(pt.device); hipFree(pt.dA); }
     device_set_release(md->set);

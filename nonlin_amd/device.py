@@ -16,6 +16,9 @@ from . import _lib
 IB_DTYPE = np.dtype([(k, np.int32) for k, _ in _lib.IterationBehavior._fields_])
 
 
+from ._lib import CURVE_GAUSS, CURVE_LORENTZ, CURVE_EXPDECAY, CURVE_KINDS, curve_kind, curve_nparams  # noqa: E402,F401
+
+
 def _chk(t, shape, name):
     if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
         raise ValueError(f"{name}: expected contiguous float64 GPU tensor of shape {tuple(shape)}, "
@@ -190,6 +193,88 @@ class DeviceSolver:
         points.  Keep the returned ctx (and A, b) alive while solving."""
         ctx = _lib.DqDeviceCtx(A.data_ptr(), b.data_ptr(), float(gamma))
         return (C.cast(self.lib.nlh_dq_device_fcn, _lib.DEVFCN), C.cast(self.lib.nlh_dq_device_jac, _lib.DEVFCN), ctx)
+
+    # -- built-in curve models ---------------------------------------------------
+    def _curve_data(self, t, y, weights):
+        """(nprob, m, shared_t) of the data tensors of a curve model, checked."""
+        nprob, m = y.shape
+        _chk(y, (nprob, m), "y")
+        shared = t.dim() == 1
+        _chk(t, (m,) if shared else (nprob, m), "t")
+        if weights is not None:
+            _chk(weights, (nprob, m), "weights")
+        return nprob, m, int(shared)
+
+    def curve_launchers(self, kind, ncomp, baseline, t, y, weights=None):
+        """A built-in curve model (kind: "gauss", "lorentz", "expdecay" or a CURVE_* constant; ncomp components; baseline:
+        degree of the polynomial baseline, -1 for none) on the data t, y [nprob, m] (t may be one shared [m] tensor) with
+        optional weights [nprob, m], as (fcn, jac, ctx) for lm_solve_batch_device, cls_solve_batch_device,
+        lm_covariance_batch_device and fd_jacobian_device.  Keep ctx alive while solving (it keeps the tensors)."""
+        nprob, m, shared = self._curve_data(t, y, weights)
+        k = curve_kind(kind)
+        curve_nparams(k, ncomp, baseline)
+        ctx = _lib.CurveCtx(k, int(ncomp), int(baseline), shared, m, t.data_ptr(), y.data_ptr(),
+                            weights.data_ptr() if weights is not None else None)
+        ctx._tensors = (t, y, weights)                                # the context holds addresses: the tensors live as long as it does
+        return (C.cast(self.lib.nlh_curve_device_fcn, _lib.DEVFCN), C.cast(self.lib.nlh_curve_device_jac, _lib.DEVFCN), ctx)
+
+    def curve_eval(self, kind, x, t, ncomp=1, baseline=-1):
+        """Model values (no data term, no weights) of x [nprob, n] at the abscissae t [nprob, npts] (or one shared [npts]
+        tensor): y [nprob, npts]."""
+        k = curve_kind(kind)
+        nprob, n = x.shape
+        _chk(x, (nprob, n), "x")
+        if n != curve_nparams(k, ncomp, baseline):
+            raise ValueError(f"x has {n} columns, the model {curve_nparams(k, ncomp, baseline)} parameters")
+        shared = t.dim() == 1
+        npts = t.shape[-1]
+        _chk(t, (npts,) if shared else (nprob, npts), "t")
+        y = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
+        rc = self.lib.nlh_curve_eval_batch(self.h.ptr, k, int(ncomp), int(baseline), nprob, npts, t.data_ptr(), int(shared),
+                                           x.data_ptr(), y.data_ptr())
+        self.h.check(rc, "nlh_curve_eval_batch")
+        if rc:
+            raise RuntimeError(f"nlh_curve_eval_batch returned {rc}")
+        return y
+
+    def curve_fit_batch(self, kind, t, y, x0, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
+                        covariance=True, opts=None):
+        """Fit + errors of y.shape[0] curves in one call (nlh_curve_fit_batch): least_squares_solver%solve -- or, with lower /
+        upper ([n], one box for every problem), constrained_least_squares_solver%solve -- from x0 [nprob, n] (not modified),
+        then the scaled parameter covariance at the solution.  Rows with weight 0 pad ragged data: they do not count as
+        degrees of freedom.  Returns (x, fvec, sigma, cov, chi2, rank, ibs, status); sigma, cov, chi2, rank are None with
+        covariance=False, NaN / -1 for a problem whose status is not 0."""
+        k = curve_kind(kind)
+        nprob, m, shared = self._curve_data(t, y, weights)
+        n = curve_nparams(k, ncomp, baseline)
+        _chk(x0, (nprob, n), "x0")
+        dev = y.device
+        x = x0.clone()
+        fvec = torch.empty((nprob, m), dtype=torch.float64, device=dev)
+        sigma = cov = chi2 = rank = None
+        if covariance:
+            sigma = torch.empty((nprob, n), dtype=torch.float64, device=dev)
+            cov = torch.empty((nprob, n, n), dtype=torch.float64, device=dev)
+            chi2 = torch.empty((nprob,), dtype=torch.float64, device=dev)
+            rank = torch.empty((nprob,), dtype=torch.int32, device=dev)
+        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64)
+        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
+        for b in (lo, hi):
+            if b is not None and b.shape != (n,):
+                raise ValueError(f"bounds: expected {n} entries")
+        ib = (_lib.IterationBehavior * nprob)()
+        status = (C.c_int32 * nprob)()
+        o = opts or self.options()
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        rc = self.lib.nlh_curve_fit_batch(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
+                                          y.data_ptr(), ptr(weights), int(bool(analytic)),
+                                          None if lo is None else lo.ctypes.data_as(_lib.c_double_p),
+                                          None if hi is None else hi.ctypes.data_as(_lib.c_double_p),
+                                          x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
+        self.h.check(rc, "nlh_curve_fit_batch")
+        if rc:
+            raise RuntimeError(f"nlh_curve_fit_batch returned {rc}")
+        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nprob)], [int(status[p]) for p in range(nprob)])
 
     def _ctxp(self, ctx):
         return ctx if isinstance(ctx, (int, C.c_void_p)) or ctx is None else C.cast(C.byref(ctx), C.c_void_p)

@@ -24,6 +24,8 @@ module nonlin_hip_c
     end type
 
     integer(c_int32_t), parameter :: NLH_FACTOR_AUTO = 0, NLH_FACTOR_QR = 1, NLH_FACTOR_EXACT = 2
+    ! kinds of the built-in curve models (include/nonlin_hip.h: NLH_CURVE_*)
+    integer(c_int32_t), parameter :: NLH_CURVE_GAUSS = 0, NLH_CURVE_LORENTZ = 1, NLH_CURVE_EXPDECAY = 2
 
     interface
         subroutine nlh_default_options(opts) bind(C, name="nlh_default_options")
@@ -152,6 +154,22 @@ module nonlin_hip_c
             real(c_double), value :: gamma
             type(c_ptr), intent(out) :: model
             integer(c_int) :: rc
+        end function
+        ! a built-in curve model on host data (include/nonlin_hip.h: nlh_curve_model_create; w: c_null_ptr for no weights)
+        function nlh_curve_model_create(h, kind, ncomp, nbase, nprob, m, t, shared_t, y, w, analytic, model) &
+                bind(C, name="nlh_curve_model_create") result(rc)
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: kind, ncomp, nbase, nprob, m, shared_t, analytic
+            real(c_double), intent(in) :: t(*), y(*)
+            type(c_ptr), value :: w
+            type(c_ptr), intent(out) :: model
+            integer(c_int) :: rc
+        end function
+        function nlh_curve_nparams(kind, ncomp, nbase) bind(C, name="nlh_curve_nparams") result(n)
+            import :: c_int32_t
+            integer(c_int32_t), value :: kind, ncomp, nbase
+            integer(c_int32_t) :: n
         end function
         ! a USER'S device residual (launchers, include/nonlin_hip.h: nlh_device_vecfcn / nlh_device_jacfcn) as a model object
         function nlh_device_fcn_model_create(nprob, m, n, fcn, jacfcn, ctx, model) &

@@ -18,6 +18,7 @@ module nonlin_multi_eqn_mult_var
     public :: nlh_callback_ctx
     public :: device_model_batch
     public :: NLH_MODEL_DENSE_QUADRATIC
+    public :: NLH_CURVE_GAUSS, NLH_CURVE_LORENTZ, NLH_CURVE_EXPDECAY   ! kinds of device_model_batch%create_curve (from nonlin_hip_c)
     public :: NLH_FACTOR_AUTO, NLH_FACTOR_QR, NLH_FACTOR_EXACT     ! values of equation_solver%factor_policy (from nonlin_hip_c)
     public :: nlh_use_devices
     public :: nlh_vecfcn_trampoline
@@ -55,6 +56,7 @@ module nonlin_multi_eqn_mult_var
     contains
         procedure, public :: create => dmb_create
         procedure, public :: create_from_device_fcn => dmb_create_fcn
+        procedure, public :: create_curve => dmb_create_curve
         procedure, public :: destroy => dmb_destroy
         procedure, public :: is_defined => dmb_defined
         procedure, public :: get_problem_count => dmb_nprob
@@ -74,6 +76,7 @@ module nonlin_multi_eqn_mult_var
     contains
         procedure, public :: set_device_model => helper_bind_model
         procedure, public :: set_device_fcn => helper_bind_device_fcn
+        procedure, public :: set_device_curve => helper_bind_curve
         procedure, public :: clear_device_model => helper_drop_model
         procedure, public :: is_device_model_defined => helper_has_model
         procedure, public :: device_model => helper_model
@@ -192,6 +195,25 @@ contains
         this%nvar_ = nvar
     end subroutine
 
+    !> Extension: the residual is a built-in curve model on ONE data set t(m), y(m), optional weights w(m) -- see
+    !> device_model_batch%create_curve.  solver%solve(obj, x, fvec, ib) and covariance then run on the GPU.
+    subroutine helper_bind_curve(this, kind, ncomp, baseline, t, y, w, analytic)
+        class(vecfcn_helper), intent(inout) :: this
+        integer(int32), intent(in) :: kind, ncomp, baseline
+        real(real64), intent(in), dimension(:) :: t, y
+        real(real64), intent(in), dimension(:), optional :: w
+        logical, intent(in), optional :: analytic
+        if (present(w)) then
+            call this%model_%create_curve(kind, ncomp, baseline, reshape(t, [size(t), 1]), reshape(y, [size(y), 1]), &
+                reshape(w, [size(w), 1]), analytic)
+        else
+            call this%model_%create_curve(kind, ncomp, baseline, reshape(t, [size(t), 1]), reshape(y, [size(y), 1]), &
+                analytic = analytic)
+        end if
+        this%neqn_ = this%model_%get_equation_count()
+        this%nvar_ = this%model_%get_variable_count()
+    end subroutine
+
     subroutine helper_drop_model(this)
         class(vecfcn_helper), intent(inout) :: this
         call this%model_%destroy()
@@ -260,6 +282,48 @@ contains
         this%nvar_ = nvar
         this%nprob_ = nprob
         this%analytic_ = c_associated(jentry)
+    end subroutine
+
+    !> A built-in curve model fitted to nprob data sets: kind NLH_CURVE_GAUSS (a, mu, sigma per component), NLH_CURVE_LORENTZ
+    !> (a, mu, w) or NLH_CURVE_EXPDECAY (a, k), ncomp components, baseline = degree of a polynomial baseline (-1: none);
+    !> the parameters of a problem are the components in order, then the baseline coefficients c_0 ...  t(m, nprob) --
+    !> or t(m, 1): the same abscissae for every problem --, y(m, nprob), optional weights w(m, nprob) (a row of weight 0
+    !> pads a shorter data set).  analytic (default .true.): the model's own Jacobian, otherwise forward differences.
+    !> The model owns device copies of the data; solve_batch, covariance_batch, evaluate and set_device_model take it as
+    !> they take any device model.
+    subroutine dmb_create_curve(this, kind, ncomp, baseline, t, y, w, analytic)
+        class(device_model_batch), intent(inout) :: this
+        integer(int32), intent(in) :: kind, ncomp, baseline
+        real(real64), intent(in), dimension(:,:) :: t, y
+        real(real64), intent(in), dimension(:,:), optional :: w
+        logical, intent(in), optional :: analytic
+        integer(c_int) :: rc
+        integer(c_int32_t) :: n, shared, use_jac
+        real(c_double), allocatable, target :: tc(:,:), yc(:,:), wc(:,:)
+        type(c_ptr) :: wp
+        n = nlh_curve_nparams(int(kind, c_int32_t), int(ncomp, c_int32_t), int(baseline, c_int32_t))
+        if (n < 0) error stop NL_INVALID_INPUT_ERROR
+        if (size(t, 1) /= size(y, 1) .or. (size(t, 2) /= size(y, 2) .and. size(t, 2) /= 1)) error stop NL_ARRAY_SIZE_ERROR
+        shared = 0
+        if (size(t, 2) == 1 .and. size(y, 2) /= 1) shared = 1
+        use_jac = 1
+        if (present(analytic)) use_jac = merge(1, 0, analytic)
+        call this%destroy()
+        tc = t                                               ! contiguous copies: the dummies may be sections
+        yc = y
+        wp = c_null_ptr
+        if (present(w)) then
+            if (any(shape(w) /= shape(y))) error stop NL_ARRAY_SIZE_ERROR
+            wc = w
+            wp = c_loc(wc)
+        end if
+        rc = nlh_curve_model_create(nlh_default_handle(), int(kind, c_int32_t), int(ncomp, c_int32_t), int(baseline, c_int32_t), &
+            int(size(y, 2), c_int32_t), int(size(y, 1), c_int32_t), tc, shared, yc, wp, use_jac, this%model_)
+        if (rc /= 0) error stop rc
+        this%neqn_ = size(y, 1)
+        this%nvar_ = n
+        this%nprob_ = size(y, 2)
+        this%analytic_ = use_jac /= 0
     end subroutine
 
     subroutine dmb_destroy(this)
