@@ -716,6 +716,120 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
                           const double *xl, const double *xu, double *x, double *fvec, double *sigma, double *cov,
                           double *chi2, int32_t *rank, nlh_iteration_behavior *ib, int32_t *status);
 
+/* ---- formula models (no counterpart in nonlin v2.2.0): the model is an expression the user writes as a string, e.g.
+ * "a*exp(-((t-mu)/s)^2/2)+c" with vars "t" and params "a,mu,s,c".  nlh_expr_compile (pure host code, needs no GPU) turns it
+ * into a small postfix program; the kernels behind nlh_expr_device_fcn / _jac interpret it, a thread per (point, row), so a
+ * curve fitter needs neither hipcc nor device code.
+ * GRAMMAR (blanks are ignored; operators are left-associative; -a^2 is -(a^2); a^2^3 is an error):
+ *   expr  := term (('+'|'-') term)*            term  := unary (('*'|'/') unary)*
+ *   unary := ('-'|'+') unary | power           power := atom ('^' ['-'] number)?
+ *   atom  := number | name | func '(' expr ')' | '(' expr ')'
+ * number: what strtod reads in the C locale from a digit or '.'; name: a variable, a parameter or pi (the only named
+ * constant); func: exp log sqrt sin cos tanh atan abs.  vars: 1 .. 4 comma-separated names; params: 1 .. 32, their order is
+ * the order of x.  A name is [A-Za-z_][A-Za-z0-9_]*, not pi and not a function.
+ * THE PROGRAM IS THE POSTFIX OF THE PARSE TREE: no constant folding, no reassociation, no sharing of common subexpressions
+ * (a unary '+' emits nothing; every literal and every pi is a constant of its own).  Instructions (op, arg):
+ *   CONST i (consts[i])   VAR v   PARAM k   NEG   ADD   SUB   MUL   DIV   (b on top of the stack, a below it)
+ *   IPOW k   an integer literal exponent, 2 <= |k| <= 16          POWC i   any other literal exponent c = consts[i]
+ *   EXP LOG SQRT SIN COS TANH ATAN ABS
+ * THE ARITHMETIC IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation, the device library's
+ * functions -- so that a restatement in any IEEE language reproduces an exp-free formula bit for bit:
+ *   values     the obvious operation per instruction;  POWC: pow(a, c);  NEG, ABS: sign operations;
+ *              IPOW k: v = a; v = v*a (|k| - 1 times in all); for k < 0 then v = 1.0/v
+ *   column j of the Jacobian: forward mode with STRUCTURAL zeros.  A node's tangent is absent (Z) or a double: CONST, VAR,
+ *   PARAM k != j are Z, PARAM j is 1.0; a Z operand is dropped, never multiplied (da, db: the tangents of a, b; v: the value)
+ *     ADD   da + db | da | db                       SUB   da - db | da | -db
+ *     MUL   da*b + a*db | da*b | a*db               DIV   q = a/b:  (da - q*db)/b | da/b | -((q*db)/b)
+ *     NEG   -da
+ *     IPOW  u = the product before the last multiplication (a itself for |k| = 2):
+ *           k > 0: ((double)k*u)*da                 k < 0: -((((double)|k|*u)*da)*(v*v))
+ *     POWC  (c*pow(a, c - 1.0))*da
+ *     EXP   v*da          LOG  da/a                 SQRT  da/(2.0*v)          SIN  cos(a)*da       COS  -(sin(a)*da)
+ *     TANH  (1.0 - v*v)*da                          ATAN  da/(1.0 + a*a)      ABS  a < 0 ? -da : da
+ *     a root that is Z writes +0.0
+ *   "structural": the compiler records per instruction the 32-bit mask of the parameters its subtree names; the tangent of a
+ *   node for column j is present exactly when bit j of that mask is set, whatever the values are.
+ *   residual   r = f - y;  then r = w*r when weights are given; every Jacobian entry is multiplied once by w then (a row of
+ *              weight 0 is exactly 0: the padding rule of the curve models)
+ * No sum crosses a row: a row's bits do not depend on the launch shape, the workgroup form (NLH_EXPR_FORM = row | flat,
+ * environment, read at each call, as NLH_CURVE_FORM), the number of Jacobian columns a pass carries, or the batch. ---- */
+#define NLH_EXPR_MAX_INSTR   256
+#define NLH_EXPR_MAX_CONST    64
+#define NLH_EXPR_MAX_DEPTH    16
+#define NLH_EXPR_MAX_VARS      4
+#define NLH_EXPR_MAX_PARAMS   32
+#define NLH_EXPR_CONST  0
+#define NLH_EXPR_VAR    1
+#define NLH_EXPR_PARAM  2
+#define NLH_EXPR_NEG    3
+#define NLH_EXPR_ADD    4
+#define NLH_EXPR_SUB    5
+#define NLH_EXPR_MUL    6
+#define NLH_EXPR_DIV    7
+#define NLH_EXPR_IPOW   8
+#define NLH_EXPR_POWC   9
+#define NLH_EXPR_EXP   10
+#define NLH_EXPR_LOG   11
+#define NLH_EXPR_SQRT  12
+#define NLH_EXPR_SIN   13
+#define NLH_EXPR_COS   14
+#define NLH_EXPR_TANH  15
+#define NLH_EXPR_ATAN  16
+#define NLH_EXPR_ABS   17
+typedef struct nlh_expr nlh_expr;
+/* Compile (host code only, thread-safe).  Errors -- a syntax error, an unknown name, a name in both lists, a duplicate or
+ * reserved name, an empty list or item, too many names, more than 256 instructions, 64 constants or a stack deeper than 16
+ * -- return NLH_INVALID_INPUT_ERROR, leave *e NULL and set the message nlh_expr_error() returns (thread-local), e.g.
+ * "col 17: unknown name 'foo'" (0-based column of the formula; "vars col 2: ..." / "params col 2: ..." for the lists). */
+int nlh_expr_compile(const char *formula, const char *vars, const char *params, nlh_expr **e);
+const char *nlh_expr_error(void);
+void nlh_expr_destroy(nlh_expr *e);
+/* Any of the outputs may be NULL.  depth: the deepest the evaluation stack gets. */
+void nlh_expr_shape(const nlh_expr *e, int32_t *nvar, int32_t *nparams, int32_t *ninstr, int32_t *nconst, int32_t *depth);
+/* Read-back, for restatements: op, arg [ninstr], consts [nconst] (any may be NULL).  The dependency masks: nlh_expr_masks. */
+int nlh_expr_program(const nlh_expr *e, int32_t *op, int32_t *arg, double *consts);
+int nlh_expr_masks(const nlh_expr *e, uint32_t *mask);
+typedef struct nlh_expr_ctx {
+    const nlh_expr *e;
+    int32_t shared_t;     /* dt is [nvar][m], the same abscissae for every problem */
+    int32_t m;
+    const double *dt;     /* [nvar][nprob][m] (shared_t: [nvar][m]), device; the caller's */
+    const double *dy;     /* [nprob][m], device */
+    const double *dw;     /* [nprob][m], device, or NULL: no weights */
+    int64_t dt_stride;    /* doubles from one variable's block of dt to the next: nprob*m (shared_t: m); 0 means that
+                           * value for shared_t and is allowed for one variable (it is never used then) */
+} nlh_expr_ctx;
+/* The launchers (nlh_device_vecfcn / nlh_device_jacfcn, ctx = nlh_expr_ctx): they enqueue on the stream handed in, never
+ * synchronise, allocate nothing (the program travels in the kernel arguments) and may be called from several host threads.
+ * A malformed ctx -- NULL e, n != nparams, m != ctx->m, a NULL array, two variables or more without a stride -- returns
+ * NLH_INVALID_INPUT_ERROR before any launch. */
+int nlh_expr_device_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX,
+                        int32_t m, double *dF);
+int nlh_expr_device_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX,
+                        int32_t m, double *dJ);
+/* A formula model as a MODEL object of the device-function kind, from HOST arrays t [nvar][nprob][m] (shared_t: [nvar][m]),
+ * y, w (NULL: no weights): the model owns a copy of the program, its context and device copies of the data (the caller may
+ * destroy e at once); nlh_dq_model_destroy frees them.  Errors (every entry point below, in this order):
+ * NLH_ERR_BAD_HANDLE (NULL handle), NLH_INVALID_INPUT_ERROR (NULL e or array, bad counts), NLH_UNDERDEFINED_PROBLEM_ERROR
+ * (m < n). */
+int nlh_expr_model_create(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32_t m, const double *t, int32_t shared_t,
+                          const double *y, const double *w, int32_t analytic, nlh_dq_model **model);
+/* Model values -- no data term, no weights -- at dt [nvar][nprob][npts] (shared_t: [nvar][npts]) for parameters
+ * dx [nprob][n]: dy [nprob][npts].  DEVICE pointers. */
+int nlh_expr_eval_batch(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32_t npts, const double *dt, int32_t shared_t,
+                        const double *dx, double *dy);
+/* Fit + errors in one call: exactly the composition nlh_curve_fit_batch documents (one helper runs both), with the formula
+ * launchers -- solve or bounded solve, covariance with scaled = 1, the zero-weight degrees-of-freedom rule, NaN and rank -1
+ * for a problem that did not solve.  The arguments are nlh_curve_fit_batch's, e for (kind, ncomp, nbase). */
+int nlh_expr_fit_batch(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+                       int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl,
+                       const double *xu, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2,
+                       int32_t *drank, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_expr_fit_batch_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+                         int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl,
+                         const double *xu, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+                         nlh_iteration_behavior *ib, int32_t *status);
+
 /* ---- per-kernel timing (HIP events on the handle's stream) ------------------ */
 #define NLH_K_DQ_RESIDUAL   0
 #define NLH_K_DQ_PANEL      1

@@ -41,6 +41,12 @@ class CurveCtx(C.Structure):
                 ("dt", C.c_void_p), ("dy", C.c_void_p), ("dw", C.c_void_p)]
 
 
+class ExprCtx(C.Structure):
+    """nlh_expr_ctx: a formula model behind the launchers nlh_expr_device_fcn / nlh_expr_device_jac."""
+    _fields_ = [("e", C.c_void_p), ("shared_t", C.c_int32), ("m", C.c_int32), ("dt", C.c_void_p), ("dy", C.c_void_p), ("dw", C.c_void_p),
+                ("dt_stride", C.c_int64)]
+
+
 class Options(C.Structure):
     """nlh_options."""
     _fields_ = [("max_evals", C.c_int32), ("ftol", C.c_double), ("xtol", C.c_double),
@@ -222,6 +228,23 @@ SYMBOLS = {
     "nlh_curve_fit_batch_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32,
                                         c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                         c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_compile": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "nlh_expr_error": (C.c_char_p, []),
+    "nlh_expr_destroy": (None, [C.c_void_p]),
+    "nlh_expr_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
+    "nlh_expr_program": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_double_p]),
+    "nlh_expr_masks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "nlh_expr_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_expr_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_expr_model_create": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32,
+                                        C.POINTER(C.c_void_p)]),
+    "nlh_expr_eval_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_expr_fit_batch": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_fit_batch_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p,
+                                       C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                       c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_timing_enable": (None, [_H, C.c_int32]),
     "nlh_timing_reset": (None, [_H]),
     "nlh_timing_get": (C.c_int, [_H, C.c_int32, c_double_p, C.POINTER(C.c_int64)]),
@@ -292,6 +315,57 @@ def curve_nparams(kind, ncomp=1, baseline=-1):
     if n < 0:
         raise ValueError(f"no curve model of kind {kind!r} with {ncomp} components and baseline degree {baseline}")
     return n
+
+
+# opcodes of a compiled formula (include/nonlin_hip.h: NLH_EXPR_*), in order
+EXPR_OPS = ("CONST", "VAR", "PARAM", "NEG", "ADD", "SUB", "MUL", "DIV", "IPOW", "POWC", "EXP", "LOG", "SQRT", "SIN", "COS", "TANH",
+            "ATAN", "ABS")
+
+
+def _names(v):
+    return ",".join(v) if isinstance(v, (tuple, list)) else str(v)
+
+
+class Expr:
+    """A formula model (nlh_expr_compile: host code, needs no GPU): formula is an expression over the variables vars (1 .. 4
+    names) and the parameters params (1 .. 32 names, in the order of x), e.g. Expr("a*exp(-k*t)+c", ("t",), ("a", "k", "c")).
+    Operators + - * / ^ (a literal exponent), functions exp log sqrt sin cos tanh atan abs, the constant pi.  Raises
+    ValueError with the compiler's message ("col 17: unknown name 'foo'").  close() frees it (so does garbage collection)."""
+
+    def __init__(self, formula, vars=("t",), params=()):
+        self.lib = load()
+        self.formula, self.vars, self.params = formula, _names(vars), _names(params)
+        self.ptr = C.c_void_p()
+        rc = self.lib.nlh_expr_compile(formula.encode(), self.vars.encode(), self.params.encode(), C.byref(self.ptr))
+        if rc:
+            self.ptr = C.c_void_p()
+            raise ValueError(self.lib.nlh_expr_error().decode())
+        s = [C.c_int32() for _ in range(5)]
+        self.lib.nlh_expr_shape(self.ptr, *[C.byref(v) for v in s])
+        self.nvar, self.nparams, self.ninstr, self.nconst, self.depth = (v.value for v in s)
+
+    def program(self):
+        """(op, arg, consts, mask): the postfix program as int32 arrays [ninstr], its constants [nconst] and per instruction
+        the uint32 mask of the parameters its subtree names."""
+        import numpy as np
+        op, arg = np.zeros(self.ninstr, dtype=np.int32), np.zeros(self.ninstr, dtype=np.int32)
+        consts, mask = np.zeros(self.nconst), np.zeros(self.ninstr, dtype=np.uint32)
+        rc = self.lib.nlh_expr_program(self.ptr, op.ctypes.data_as(c_int32_p), arg.ctypes.data_as(c_int32_p), consts.ctypes.data_as(c_double_p))
+        rc = rc or self.lib.nlh_expr_masks(self.ptr, mask.ctypes.data_as(C.POINTER(C.c_uint32)))
+        if rc:
+            raise RuntimeError(f"nlh_expr_program returned {rc}")
+        return op, arg, consts, mask
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.lib.nlh_expr_destroy(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Handle:

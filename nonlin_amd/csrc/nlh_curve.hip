@@ -112,16 +112,13 @@ int nlh_curve_eval_batch(nlh_handle *h, int32_t kind, int32_t ncomp, int32_t nba
 // ---------------------------------------------------------------------------------------------------------------------
 // fit + errors
 // ---------------------------------------------------------------------------------------------------------------------
-int nlh_curve_fit_batch(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m,
-                        const double *dt, int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl,
-                        const double *xu, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
-                        nlh_iteration_behavior *ib, int32_t *status)
+// The composition for any launcher pair (nlh_internal.h: nlh_fit_compose); nlh_curve_fit_batch and nlh_expr_fit_batch are it.
+int nlh_fit_compose(nlh_handle *h, const nlh_options *opts, int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn,
+                    nlh_device_jacfcn jac, void *ctx, const std::function<void(int32_t)> &at, const double *dw, const double *xl,
+                    const double *xu, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+                    nlh_iteration_behavior *ib, int32_t *status)
 {
-    int32_t n;
-    int rc = curve_shape_check(h, kind, ncomp, nbase, nprob, m, true, &n);
-    if (rc) return rc;
-    if (nprob == 0) return 0;
-    if (!opts || !dt || !dy || !dx || !dfvec) return NLH_INVALID_INPUT_ERROR;
+    int rc;
     const bool errors = dsigma || dcov || dchi2;
     if (errors && m <= n) return NLH_INVALID_INPUT_ERROR;        // no degree of freedom (nlh_lm_covariance_batch_device, scaled)
     HIPCHK(h, hipSetDevice(h->device));
@@ -141,25 +138,20 @@ int nlh_curve_fit_batch(nlh_handle *h, const nlh_options *opts, int32_t kind, in
         for (size_t p = 0; p < np; ++p)
             if (nz[p] - n <= 0) st[p] = NLH_INVALID_INPUT_ERROR;
     }
-    nlh_curve_ctx c;
-    c.kind = kind; c.ncomp = ncomp; c.nbase = nbase; c.shared_t = shared_t != 0; c.m = m;
-    nlh_device_jacfcn jac = analytic ? nlh_curve_device_jac : nullptr;
     // runs of consecutive problems that have degrees of freedom (all of them, as a rule): exactly the calls a user makes
     for (int32_t p0 = 0; p0 < nprob;) {
         if (st[p0]) { ++p0; continue; }
         int32_t p1 = p0;
         while (p1 < nprob && !st[p1]) ++p1;
         const int32_t cnt = p1 - p0;
-        c.dt = shared_t ? dt : dt + (size_t)p0 * m;
-        c.dy = dy + (size_t)p0 * m;
-        c.dw = dw ? dw + (size_t)p0 * m : nullptr;
+        at(p0);
         double *xs = dx + (size_t)p0 * n, *fs = dfvec + (size_t)p0 * m;
         nlh_iteration_behavior *ibs = ib ? ib + p0 : nullptr;
-        if (xl || xu) rc = nlh_cls_solve_batch_device(h, opts, 1.0, 1.0, xl, xu, cnt, m, n, nlh_curve_device_fcn, jac, &c, xs, fs, ibs, &st[p0]);
-        else rc = nlh_lm_solve_batch_device(h, opts, cnt, m, n, nlh_curve_device_fcn, jac, &c, xs, fs, ibs, &st[p0]);
+        if (xl || xu) rc = nlh_cls_solve_batch_device(h, opts, 1.0, 1.0, xl, xu, cnt, m, n, fcn, jac, ctx, xs, fs, ibs, &st[p0]);
+        else rc = nlh_lm_solve_batch_device(h, opts, cnt, m, n, fcn, jac, ctx, xs, fs, ibs, &st[p0]);
         if (rc) return rc;
         if (errors &&
-            (rc = nlh_lm_covariance_batch_device(h, cnt, m, n, nlh_curve_device_fcn, jac, &c, xs, 1, 0.0, cov + (size_t)p0 * nn,
+            (rc = nlh_lm_covariance_batch_device(h, cnt, m, n, fcn, jac, ctx, xs, 1, 0.0, cov + (size_t)p0 * nn,
                                                  dsigma ? dsigma + (size_t)p0 * n : nullptr, drank ? drank + p0 : nullptr,
                                                  dchi2 ? dchi2 + p0 : nullptr))) return rc;
         p0 = p1;
@@ -178,25 +170,42 @@ int nlh_curve_fit_batch(nlh_handle *h, const nlh_options *opts, int32_t kind, in
     return 0;
 }
 
-// ... behind HOST arrays: t [nprob][m] (or [m]), y, w, x, fvec, sigma, cov, chi2, rank
-int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m,
-                          const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl,
-                          const double *xu, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
-                          nlh_iteration_behavior *ib, int32_t *status)
+int nlh_curve_fit_batch(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m,
+                        const double *dt, int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl,
+                        const double *xu, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+                        nlh_iteration_behavior *ib, int32_t *status)
 {
     int32_t n;
     int rc = curve_shape_check(h, kind, ncomp, nbase, nprob, m, true, &n);
     if (rc) return rc;
     if (nprob == 0) return 0;
-    if (!opts || !t || !y || !x || !fvec) return NLH_INVALID_INPUT_ERROR;
+    if (!opts || !dt || !dy || !dx || !dfvec) return NLH_INVALID_INPUT_ERROR;
+    nlh_curve_ctx c;
+    c.kind = kind; c.ncomp = ncomp; c.nbase = nbase; c.shared_t = shared_t != 0; c.m = m;
+    auto at = [&](int32_t p0) {
+        c.dt = shared_t ? dt : dt + (size_t)p0 * m;
+        c.dy = dy + (size_t)p0 * m;
+        c.dw = dw ? dw + (size_t)p0 * m : nullptr;
+    };
+    return nlh_fit_compose(h, opts, nprob, m, n, nlh_curve_device_fcn, analytic ? nlh_curve_device_jac : nullptr, &c, at, dw, xl, xu, dx,
+                           dfvec, dsigma, dcov, dchi2, drank, ib, status);
+}
+
+// ... behind HOST arrays (nlh_internal.h: nlh_fit_compose_h): t (tm doubles), y, w, x, fvec, sigma, cov, chi2, rank
+int nlh_fit_compose_h(nlh_handle *h, const char *what, size_t tm, int32_t nprob, int32_t m, int32_t n, const double *t, const double *y,
+                      const double *w, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+                      const std::function<int(const double *, const double *, const double *, double *, double *, double *, double *,
+                                              double *, int32_t *)> &fit)
+{
+    int rc;
     if ((sigma || cov || chi2) && m <= n) return NLH_INVALID_INPUT_ERROR;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    const size_t np = (size_t)nprob, pm = np * m, tm = shared_t ? (size_t)m : pm, nn = (size_t)n * n;
+    const size_t np = (size_t)nprob, pm = np * m, nn = (size_t)n * n;
     const size_t doubles = tm + pm * (w ? 3 : 2) + np * n + (sigma ? np * n : 0) + (cov ? np * nn : 0) + (chi2 ? np : 0);
     double *base = nullptr;
     if (hipMalloc(&base, sizeof(double) * doubles + sizeof(int32_t) * np) != hipSuccess) {
-        h->err = "hipMalloc (curve fit)";
+        h->err = std::string("hipMalloc (") + what + ")";
         return NLH_OUT_OF_MEMORY_ERROR;
     }
     double *q = base;
@@ -214,8 +223,7 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
     if (e == hipSuccess && w) e = hipMemcpyAsync(dw, w, sizeof(double) * pm, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(dx, x, sizeof(double) * np * n, hipMemcpyHostToDevice, s);
     rc = 0;
-    if (e == hipSuccess)
-        rc = nlh_curve_fit_batch(h, opts, kind, ncomp, nbase, nprob, m, dt, shared_t, dy, dw, analytic, xl, xu, dx, df, ds, dc, dq, dr, ib, status);
+    if (e == hipSuccess) rc = fit(dt, dy, dw, dx, df, ds, dc, dq, dr);
     if (e == hipSuccess && !rc) {
         e = hipMemcpyAsync(x, dx, sizeof(double) * np * n, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(fvec, df, sizeof(double) * pm, hipMemcpyDeviceToHost, s);
@@ -228,8 +236,26 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
     (void)hipFree(base);
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) {
-        h->err = std::string("curve fit (host arrays): ") + hipGetErrorString(e);
+        h->err = std::string(what) + " (host arrays): " + hipGetErrorString(e);
         return NLH_ERR_HIP;
     }
     return rc;
+}
+
+int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m,
+                          const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl,
+                          const double *xu, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+                          nlh_iteration_behavior *ib, int32_t *status)
+{
+    int32_t n;
+    int rc = curve_shape_check(h, kind, ncomp, nbase, nprob, m, true, &n);
+    if (rc) return rc;
+    if (nprob == 0) return 0;
+    if (!opts || !t || !y || !x || !fvec) return NLH_INVALID_INPUT_ERROR;
+    return nlh_fit_compose_h(h, "curve fit", shared_t ? (size_t)m : (size_t)nprob * m, nprob, m, n, t, y, w, x, fvec, sigma, cov, chi2, rank,
+                             [&](const double *dt, const double *dy, const double *dw, double *dx, double *df, double *ds, double *dc,
+                                 double *dq, int32_t *dr) {
+                                 return nlh_curve_fit_batch(h, opts, kind, ncomp, nbase, nprob, m, dt, shared_t, dy, dw, analytic, xl, xu, dx,
+                                                            df, ds, dc, dq, dr, ib, status);
+                             });
 }

@@ -1,0 +1,395 @@
+// nlh_expr.hip -- formula models (include/nonlin_hip.h: nlh_expr_*): a model the user writes as an expression string.
+// First the compiler, pure host code that needs no GPU: a recursive-descent parser of the header's grammar that emits the
+// postfix of the parse tree as it goes -- no folding, no reassociation, no sharing -- with, per instruction, the mask of
+// the parameters its subtree names and the instruction that produced its left operand.  Then the launchers of the open
+// device-residual path (kernels and arithmetic: nlh_kernels_expr.h), which form a call runs and how many Jacobian
+// columns a pass carries, model values (nlh_expr_eval_batch) and the one-call fit + errors (nlh_expr_fit_batch: the
+// composition nlh_fit_compose of nlh_curve.hip).  The model object that owns its program and data is
+// nlh_expr_model_create (nlh_model.hip).
+#include "nlh_internal.h"
+#include "nlh_kernels_expr.h"
+
+#include <locale.h>
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the compiler
+// ---------------------------------------------------------------------------------------------------------------------
+static thread_local std::string expr_err;
+const char *nlh_expr_error(void) { return expr_err.c_str(); }
+
+static const char *const EXPR_FUNCS[] = {"exp", "log", "sqrt", "sin", "cos", "tanh", "atan", "abs"};   // NLH_EXPR_EXP ..
+
+namespace {
+struct ExprFail {};
+
+struct ExprParser {
+    const char *s;
+    size_t at = 0;
+    std::vector<std::string> vars, params;
+    ExprProg *P;
+    int nconst = 0, sp = 0;
+    int root[NLH_EXPR_MAX_DEPTH + 1];          // the instruction that produced each stack slot
+
+    [[noreturn]] void fail(size_t col, const std::string &msg)
+    {
+        expr_err = "col " + std::to_string(col) + ": " + msg;
+        throw ExprFail();
+    }
+    void blanks() { while (s[at] == ' ' || s[at] == '\t' || s[at] == '\n' || s[at] == '\r') ++at; }
+    char peek() { blanks(); return s[at]; }
+
+    void emit(size_t col, int op, int arg, int pops)
+    {
+        if (P->ninstr >= NLH_EXPR_MAX_INSTR) fail(col, "more than " + std::to_string(NLH_EXPR_MAX_INSTR) + " instructions");
+        const int pc = P->ninstr++;
+        uint32_t mask = op == NLH_EXPR_PARAM ? 1u << arg : 0u;
+        int aroot = 0;
+        if (pops == 2) { aroot = root[sp - 2]; mask = P->mask[aroot] | P->mask[root[sp - 1]]; }
+        else if (pops == 1) mask = P->mask[root[sp - 1]];
+        sp -= pops;
+        if (sp >= NLH_EXPR_MAX_DEPTH) fail(col, "the evaluation stack gets deeper than " + std::to_string(NLH_EXPR_MAX_DEPTH));
+        root[sp++] = pc;
+        if (sp > P->depth) P->depth = sp;
+        P->code[pc] = (uint32_t)op | ((uint32_t)(arg & 0xff) << 8) | ((uint32_t)aroot << 16);
+        P->mask[pc] = mask;
+    }
+    int constant(size_t col, double v)
+    {
+        if (nconst >= NLH_EXPR_MAX_CONST) fail(col, "more than " + std::to_string(NLH_EXPR_MAX_CONST) + " constants");
+        P->consts[nconst] = v;
+        return nconst++;
+    }
+    static bool digit(char c) { return c >= '0' && c <= '9'; }
+    static bool alpha(char c) { return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z') || c == '_'; }
+    double number(size_t *col)
+    {
+        blanks();
+        *col = at;
+        if (!(digit(s[at]) || (s[at] == '.' && digit(s[at + 1])))) fail(at, s[at] ? std::string("a number expected at '") + s[at] + "'" : "a number expected at the end");
+        static const locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+        char *end = nullptr;
+        const double v = strtod_l(s + at, &end, c_locale);
+        if (end == s + at) fail(at, "a number expected");
+        at = (size_t)(end - s);
+        return v;
+    }
+
+    void expr()
+    {
+        term();
+        for (char c = peek(); c == '+' || c == '-'; c = peek()) {
+            const size_t col = at++;
+            term();
+            emit(col, c == '+' ? NLH_EXPR_ADD : NLH_EXPR_SUB, 0, 2);
+        }
+    }
+    void term()
+    {
+        unary();
+        for (char c = peek(); c == '*' || c == '/'; c = peek()) {
+            const size_t col = at++;
+            unary();
+            emit(col, c == '*' ? NLH_EXPR_MUL : NLH_EXPR_DIV, 0, 2);
+        }
+    }
+    void unary()
+    {
+        const char c = peek();
+        if (c == '-' || c == '+') {
+            const size_t col = at++;
+            unary();
+            if (c == '-') emit(col, NLH_EXPR_NEG, 0, 1);
+            return;
+        }
+        power();
+    }
+    void power()
+    {
+        atom();
+        if (peek() != '^') return;
+        const size_t col = at++;
+        bool neg = false;
+        if (peek() == '-') { neg = true; ++at; }
+        size_t ncol;
+        const double v = number(&ncol);
+        if (v >= 2.0 && v <= 16.0 && v == (double)(int)v) emit(col, NLH_EXPR_IPOW, neg ? -(int)v : (int)v, 1);
+        else emit(col, NLH_EXPR_POWC, constant(ncol, neg ? -v : v), 1);
+        if (peek() == '^') fail(at, "a power of a power needs parentheses");
+    }
+    void atom()
+    {
+        const char c = peek();
+        const size_t col = at;
+        if (c == '(') {
+            ++at;
+            expr();
+            if (peek() != ')') fail(at, "')' expected");
+            ++at;
+            return;
+        }
+        if (digit(c) || c == '.') {
+            size_t ncol;
+            const double v = number(&ncol);
+            emit(col, NLH_EXPR_CONST, constant(col, v), 0);
+            return;
+        }
+        if (!alpha(c)) fail(at, c ? std::string("unexpected '") + c + "'" : "unexpected end of the formula");
+        size_t e = at;
+        while (alpha(s[e]) || digit(s[e])) ++e;
+        const std::string name(s + at, e - at);
+        at = e;
+        for (size_t f = 0; f < sizeof(EXPR_FUNCS) / sizeof(EXPR_FUNCS[0]); ++f)
+            if (name == EXPR_FUNCS[f]) {
+                if (peek() != '(') fail(at, "'(' expected after the function '" + name + "'");
+                ++at;
+                expr();
+                if (peek() != ')') fail(at, "')' expected");
+                ++at;
+                emit(col, NLH_EXPR_EXP + (int)f, 0, 1);
+                return;
+            }
+        if (name == "pi") { emit(col, NLH_EXPR_CONST, constant(col, 3.14159265358979323846), 0); return; }
+        for (size_t v = 0; v < vars.size(); ++v)
+            if (name == vars[v]) { emit(col, NLH_EXPR_VAR, (int)v, 0); return; }
+        for (size_t k = 0; k < params.size(); ++k)
+            if (name == params[k]) { emit(col, NLH_EXPR_PARAM, (int)k, 0); return; }
+        fail(col, "unknown name '" + name + "'");
+    }
+};
+
+// a comma-separated list of names; false with the message set
+bool expr_names(const char *what, const char *list, size_t most, const std::vector<std::string> &others, std::vector<std::string> &out)
+{
+    auto fail = [&](size_t col, const std::string &msg) {
+        expr_err = std::string(what) + " col " + std::to_string(col) + ": " + msg;
+        return false;
+    };
+    if (!list) return fail(0, "no list");
+    size_t at = 0;
+    for (;;) {
+        while (list[at] == ' ' || list[at] == '\t') ++at;
+        const size_t col = at;
+        if (!ExprParser::alpha(list[at])) return fail(col, list[at] && list[at] != ',' ? std::string("unexpected '") + list[at] + "'" : "a name expected");
+        while (ExprParser::alpha(list[at]) || ExprParser::digit(list[at])) ++at;
+        const std::string name(list + col, at - col);
+        if (name == "pi") return fail(col, "'pi' is the constant");
+        for (const char *f : EXPR_FUNCS)
+            if (name == f) return fail(col, "'" + name + "' is a function");
+        for (const auto &o : out)
+            if (name == o) return fail(col, "duplicate name '" + name + "'");
+        for (const auto &o : others)
+            if (name == o) return fail(col, "'" + name + "' is in both lists");
+        if (out.size() >= most) return fail(col, "more than " + std::to_string(most) + " names");
+        out.push_back(name);
+        while (list[at] == ' ' || list[at] == '\t') ++at;
+        if (!list[at]) return true;
+        if (list[at] != ',') return fail(at, std::string("unexpected '") + list[at] + "'");
+        ++at;
+    }
+}
+}   // namespace
+
+int nlh_expr_compile(const char *formula, const char *vars, const char *params, nlh_expr **e)
+{
+    if (e) *e = nullptr;
+    expr_err.clear();
+    if (!e || !formula) { expr_err = "col 0: no formula"; return NLH_INVALID_INPUT_ERROR; }
+    nlh_expr *x = new nlh_expr();
+    memset(x, 0, sizeof(*x));
+    ExprParser ps;
+    ps.s = formula; ps.P = &x->prog;
+    if (!expr_names("vars", vars, NLH_EXPR_MAX_VARS, {}, ps.vars) || !expr_names("params", params, NLH_EXPR_MAX_PARAMS, ps.vars, ps.params)) {
+        delete x;
+        return NLH_INVALID_INPUT_ERROR;
+    }
+    try {
+        ps.expr();
+        if (ps.peek()) ps.fail(ps.at, std::string("unexpected '") + ps.s[ps.at] + "'");
+    } catch (const ExprFail &) {
+        delete x;
+        return NLH_INVALID_INPUT_ERROR;
+    }
+    x->prog.nvar = (int32_t)ps.vars.size();
+    x->prog.nparams = (int32_t)ps.params.size();
+    x->nconst = ps.nconst;
+    *e = x;
+    return 0;
+}
+
+void nlh_expr_destroy(nlh_expr *e) { delete e; }
+
+void nlh_expr_shape(const nlh_expr *e, int32_t *nvar, int32_t *nparams, int32_t *ninstr, int32_t *nconst, int32_t *depth)
+{
+    if (nvar) *nvar = e ? e->prog.nvar : 0;
+    if (nparams) *nparams = e ? e->prog.nparams : 0;
+    if (ninstr) *ninstr = e ? e->prog.ninstr : 0;
+    if (nconst) *nconst = e ? e->nconst : 0;
+    if (depth) *depth = e ? e->prog.depth : 0;
+}
+
+int nlh_expr_program(const nlh_expr *e, int32_t *op, int32_t *arg, double *consts)
+{
+    if (!e) return NLH_INVALID_INPUT_ERROR;
+    for (int i = 0; i < e->prog.ninstr; ++i) {
+        if (op) op[i] = EXPR_OP(e->prog.code[i]);
+        if (arg) arg[i] = EXPR_ARG(e->prog.code[i]);
+    }
+    if (consts) memcpy(consts, e->prog.consts, sizeof(double) * e->nconst);
+    return 0;
+}
+
+int nlh_expr_masks(const nlh_expr *e, uint32_t *mask)
+{
+    if (!e || !mask) return NLH_INVALID_INPUT_ERROR;
+    memcpy(mask, e->prog.mask, sizeof(uint32_t) * e->prog.ninstr);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the launchers
+// ---------------------------------------------------------------------------------------------------------------------
+void nlh_expr_init_device(int lds_max)
+{
+    (void)hipFuncSetAttribute((const void *)k_expr_fcn<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)k_expr_fcn<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)k_expr_jac<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)k_expr_jac<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+}
+
+// The form a launch runs, as the curve models choose it: flat (several points per workgroup) while two points or more fit
+// a workgroup's 256 threads.  NLH_EXPR_FORM = row | flat (environment, read at every call; tests) forces a form for the
+// sizes it can hold (flat: m <= 256).
+static bool expr_flat(int m)
+{
+    if (m > 256) return false;
+    if (const char *e = getenv("NLH_EXPR_FORM")) {
+        if (!strcmp(e, "row")) return false;
+        if (!strcmp(e, "flat")) return true;
+    }
+    return 256 / m >= 2;
+}
+
+// Columns of the Jacobian a pass over the program carries.  A stack is depth * 256 doubles; a pass needs 1 + C of them
+// besides the x of the workgroup's points.  The most columns, 8 and n at most, with which that stays within half of
+// NLH_LDS_MAX, so that two workgroups share a compute unit; one column under the whole of it where even that does not fit
+// half (depth 16: 65,536 bytes of stacks).  NLH_EXPR_CHUNK (environment; tests) asks for fewer.
+static int expr_chunk(int depth, int n, size_t xbytes)
+{
+    const size_t stack = sizeof(double) * 256 * (size_t)depth, half = (size_t)NLH_LDS_MAX / 2;
+    int C = half > xbytes + stack ? (int)((half - xbytes) / stack) - 1 : 0;
+    C = std::max(1, std::min(C, std::min(n, 8)));
+    if (const char *e = getenv("NLH_EXPR_CHUNK")) {
+        const int want = atoi(e);
+        if (want >= 1 && want < C) C = want;
+    }
+    return C;
+}
+
+// Checks everything, launches nothing when anything is wrong.  y == nullptr: model values (no data term, no weights).
+static int expr_launch(bool jac, const nlh_expr *e, int shared_t, int m, int64_t stride, const double *t, const double *y, const double *w,
+                       int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, double *out, hipStream_t s)
+{
+    if (!e || e->prog.nparams != n || m < 1 || !t || !dX || !out) return NLH_INVALID_INPUT_ERROR;
+    if (stride == 0 && shared_t) stride = m;
+    if (e->prog.nvar > 1 && stride < m) return NLH_INVALID_INPUT_ERROR;
+    if (npoints <= 0) return 0;
+    if ((size_t)npoints * ((size_t)(m + 255) / 256) > 0x7fffffffu) return NLH_ARRAY_SIZE_ERROR;
+    ExprData ed;
+    ed.shared_t = shared_t != 0; ed.m = m; ed.tstride = stride; ed.t = t; ed.y = y; ed.w = w;
+    const bool flat = expr_flat(m);
+    const int ppw = flat ? 256 / m : 1, nblk = flat ? 1 : (m + 255) / 256;
+    const dim3 grid(flat ? (unsigned)((npoints + ppw - 1) / ppw) : (unsigned)((size_t)npoints * nblk));
+    const size_t xbytes = sizeof(double) * (size_t)ppw * n, stack = sizeof(double) * 256 * (size_t)e->prog.depth;
+    if (!jac) {
+        const size_t lds = xbytes + stack;
+        if (flat) hipLaunchKernelGGL(k_expr_fcn<true>, grid, dim3(256), lds, s, e->prog, ed, n, nblk, ppw, npoints, dprob, dX, out);
+        else hipLaunchKernelGGL(k_expr_fcn<false>, grid, dim3(256), lds, s, e->prog, ed, n, nblk, ppw, npoints, dprob, dX, out);
+        return 0;
+    }
+    const int C = expr_chunk(e->prog.depth, n, xbytes);
+    const size_t lds = xbytes + stack * (size_t)(1 + C);
+    if (flat) hipLaunchKernelGGL(k_expr_jac<true>, grid, dim3(256), lds, s, e->prog, ed, n, nblk, ppw, npoints, C, dprob, dX, out);
+    else hipLaunchKernelGGL(k_expr_jac<false>, grid, dim3(256), lds, s, e->prog, ed, n, nblk, ppw, npoints, C, dprob, dX, out);
+    return 0;
+}
+
+int nlh_expr_device_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m,
+                        double *dF)
+{
+    const nlh_expr_ctx *c = (const nlh_expr_ctx *)ctx;
+    if (!c || m != c->m || !c->dy || !dprob) return NLH_INVALID_INPUT_ERROR;
+    return expr_launch(false, c->e, c->shared_t, c->m, c->dt_stride, c->dt, c->dy, c->dw, npoints, dprob, n, dX, dF, (hipStream_t)hip_stream);
+}
+
+int nlh_expr_device_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m,
+                        double *dJ)
+{
+    const nlh_expr_ctx *c = (const nlh_expr_ctx *)ctx;
+    if (!c || m != c->m || !c->dy || !dprob) return NLH_INVALID_INPUT_ERROR;
+    return expr_launch(true, c->e, c->shared_t, c->m, c->dt_stride, c->dt, c->dy, c->dw, npoints, dprob, n, dX, dJ, (hipStream_t)hip_stream);
+}
+
+// the checks every entry point with (e, nprob, m) makes, in the documented order
+static int expr_shape_check(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32_t m, bool data, int32_t *n)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (!e || nprob < 0 || m < 1) return NLH_INVALID_INPUT_ERROR;
+    *n = e->prog.nparams;
+    if (data && m < *n) return NLH_UNDERDEFINED_PROBLEM_ERROR;
+    return 0;
+}
+
+int nlh_expr_eval_batch(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32_t npts, const double *dt, int32_t shared_t, const double *dx,
+                        double *dy)
+{
+    int32_t n;
+    int rc = expr_shape_check(h, e, nprob, npts, false, &n);
+    if (rc) return rc;
+    if (nprob == 0) return 0;
+    if (!dt || !dx || !dy) return NLH_INVALID_INPUT_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t stride = shared_t ? (int64_t)npts : (int64_t)nprob * npts;
+    if ((rc = expr_launch(false, e, shared_t, npts, stride, dt, nullptr, nullptr, nprob, nullptr, n, dx, dy, h->stream))) return rc;
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int nlh_expr_fit_batch(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+                       int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl, const double *xu,
+                       double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank, nlh_iteration_behavior *ib,
+                       int32_t *status)
+{
+    int32_t n;
+    int rc = expr_shape_check(h, e, nprob, m, true, &n);
+    if (rc) return rc;
+    if (nprob == 0) return 0;
+    if (!opts || !dt || !dy || !dx || !dfvec) return NLH_INVALID_INPUT_ERROR;
+    nlh_expr_ctx c;
+    c.e = e; c.shared_t = shared_t != 0; c.m = m;
+    c.dt_stride = shared_t ? (int64_t)m : (int64_t)nprob * m;      // (a run of problems keeps the whole batch's stride)
+    auto at = [&](int32_t p0) {
+        c.dt = shared_t ? dt : dt + (size_t)p0 * m;
+        c.dy = dy + (size_t)p0 * m;
+        c.dw = dw ? dw + (size_t)p0 * m : nullptr;
+    };
+    return nlh_fit_compose(h, opts, nprob, m, n, nlh_expr_device_fcn, analytic ? nlh_expr_device_jac : nullptr, &c, at, dw, xl, xu, dx,
+                           dfvec, dsigma, dcov, dchi2, drank, ib, status);
+}
+
+int nlh_expr_fit_batch_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+                         int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl, const double *xu, double *x,
+                         double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank, nlh_iteration_behavior *ib, int32_t *status)
+{
+    int32_t n;
+    int rc = expr_shape_check(h, e, nprob, m, true, &n);
+    if (rc) return rc;
+    if (nprob == 0) return 0;
+    if (!opts || !t || !y || !x || !fvec) return NLH_INVALID_INPUT_ERROR;
+    const size_t tm = (size_t)e->prog.nvar * (shared_t ? (size_t)m : (size_t)nprob * m);
+    return nlh_fit_compose_h(h, "formula fit", tm, nprob, m, n, t, y, w, x, fvec, sigma, cov, chi2, rank,
+                             [&](const double *dt, const double *dy, const double *dw, double *dx, double *df, double *ds, double *dc,
+                                 double *dq, int32_t *dr) {
+                                 return nlh_expr_fit_batch(h, opts, e, nprob, m, dt, shared_t, dy, dw, analytic, xl, xu, dx, df, ds, dc, dq,
+                                                           dr, ib, status);
+                             });
+}

@@ -4,7 +4,7 @@
 // (least_squares_solver: lss_solve and its stages), nlh_square.hip (newton_solver, quasi_newton_solver, LU, the
 // Householder steps), nlh_cls.hip (constrained_least_squares_solver), nlh_bfgs.hip (bfgs, fcnnvar_helper%gradient), nlh_nm.hip (nelder_mead),
 // nlh_1var.hip (brent_solver, newton_1var_solver, fcn1var_helper%diff),
-// nlh_poly.hip (polynomial%fit), nlh_polyroots.hip (polynomial%roots, batched evaluate), nlh_covar.hip (parameter covariance), nlh_curve.hip (built-in curve models), nlh_model.hip (device sets, device residual models behind host arrays), nlh_qrx.hip
+// nlh_poly.hip (polynomial%fit), nlh_polyroots.hip (polynomial%roots, batched evaluate), nlh_covar.hip (parameter covariance), nlh_curve.hip (built-in curve models, the fit + errors composition), nlh_expr.hip (formula models: compiler, launchers), nlh_model.hip (device sets, device residual models behind host arrays), nlh_qrx.hip
 // (the exact lmfactor).  Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it
 // launches.
 #pragma once
@@ -221,6 +221,36 @@ void nlh_poly_init_device(int lds_max);
 void nlh_polyroots_init_device(int lds_max);    // nlh_polyroots.hip (polynomial%roots, batched evaluate)
 void nlh_covar_init_device(int lds_max);        // nlh_covar.hip (covar, nlh_lm_covariance*)
 void nlh_devfcn_init_device(int lds_max);        // nlh_devfcn.hip: the built-in family's launcher kernels keep x in LDS
+void nlh_expr_init_device(int lds_max);          // nlh_expr.hip: the formula interpreter keeps its stacks in LDS
+
+// A compiled formula (nlh_expr.hip; include/nonlin_hip.h: nlh_expr_*).  ExprProg is what the kernels read, passed by value in
+// the kernel arguments: code[i] = op | (arg & 0xff) << 8 | aroot << 16, aroot the instruction that produced the operand a
+// of a binary instruction (b's is i - 1, as is a unary instruction's operand); mask[i]: the parameters instruction i's
+// subtree names.
+struct ExprProg {
+    int32_t ninstr, nvar, nparams, depth;
+    uint32_t code[NLH_EXPR_MAX_INSTR];
+    uint32_t mask[NLH_EXPR_MAX_INSTR];
+    double consts[NLH_EXPR_MAX_CONST];
+};
+struct nlh_expr {
+    ExprProg prog;
+    int32_t nconst;
+};
+
+// Fit + errors, the composition nlh_curve_fit_batch documents, for any launcher pair (nlh_curve.hip): solve (bounded when
+// xl or xu is given), covariance with scaled = 1 when any of dsigma, dcov, dchi2 is asked for, the degrees-of-freedom rule
+// of zero weights, NaN and rank -1 for problems that did not solve.  at(ctx, p0) points the context's data at problem p0
+// before each run of consecutive problems.  The caller has checked the shape; device pointers as nlh_curve_fit_batch's.
+int nlh_fit_compose(nlh_handle *h, const nlh_options *opts, int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn,
+                    nlh_device_jacfcn jac, void *ctx, const std::function<void(int32_t)> &at, const double *dw, const double *xl,
+                    const double *xu, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+                    nlh_iteration_behavior *ib, int32_t *status);
+// ... behind host arrays: t is tm doubles; fit(dt, dy, dw, dx, df, ds, dc, dq, dr) is the device-pointer entry point.
+int nlh_fit_compose_h(nlh_handle *h, const char *what, size_t tm, int32_t nprob, int32_t m, int32_t n, const double *t, const double *y,
+                      const double *w, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+                      const std::function<int(const double *, const double *, const double *, double *, double *, double *, double *,
+                                              double *, int32_t *)> &fit);
 // columns the built-in dense-quadratic family's kernels accept (x in LDS, lds_max of nlh_create): beyond it NLH_ARRAY_SIZE_ERROR
 static const int32_t NLH_DQ_MAX_N = 20000;
 

@@ -1,0 +1,221 @@
+// nlh_kernels_expr.h -- formula models (include/nonlin_hip.h: nlh_expr_*): the postfix program nlh_expr_compile makes of a
+// user's expression, interpreted by residual and Jacobian kernels behind the launchers nlh_expr_device_fcn / _jac.
+//
+// THE ARITHMETIC IS PART OF THE INTERFACE; the table is in include/nonlin_hip.h and expr_run below is it, line for line:
+// one IEEE operation per step (-ffp-contract=off), the device library's functions, tangents in forward mode with
+// structural zeros (an absent operand is dropped, never multiplied).  No sum crosses a row.
+//
+// Shape (nlh_kernels_curve.h's): a thread per (point, row); the point's x staged in LDS; the row's variables, y and w
+// loaded unconditionally (clamped index) ahead of the arithmetic; the Jacobian column-major with ld = m.  Two workgroup
+// forms, the same bits: row (a workgroup per (point, 256 rows)) and flat (256 / m points per workgroup, short m).
+//
+// The program is uniform across the launch and travels by value in the kernel arguments (ExprProg, 2.6 KB): instruction
+// fetch, dispatch, the stack pointer and every test of a dependency mask are scalar.  The stacks are indexed at run time, so
+// they live in LDS as [slot][thread] columns (a wave's 64 lanes read 64 consecutive doubles: no bank conflict), depth
+// slots deep -- the program's own depth, not the limit.  The Jacobian kernel carries the tangents of C consecutive columns
+// per pass over the program, in C more such stacks, and recomputes the values in every pass: values do not depend on C, and
+// a tangent only on its own column, so the bits are the table's for any C.  Which tangents exist is structural (the masks),
+// hence uniform: nothing per thread records it.
+#pragma once
+#include "nlh_internal.h"
+
+struct ExprData {                      // what the kernels read of an nlh_expr_ctx
+    int shared_t, m;
+    long long tstride;                 // doubles between the variables' blocks of t
+    const double *t, *y, *w;           // y, w may be null (model values: nlh_expr_eval_batch)
+};
+
+#define EXPR_OP(c)     ((int)((c) & 0xffu))
+#define EXPR_ARG(c)    ((int)(int8_t)(((c) >> 8) & 0xffu))
+#define EXPR_AROOT(c)  ((int)(((c) >> 16) & 0xffu))
+
+// thread -> (point q, row i, that point's x in LDS); false: nothing to do.  FLAT: ppw points per workgroup.
+template <bool FLAT>
+__device__ static inline bool expr_place(int m, int n, int nblk, int ppw, int npoints, const double *__restrict__ X, double *xs, int &q, int &i,
+                                         const double *&xq)
+{
+    if (FLAT) {
+        const int q0 = blockIdx.x * ppw, nq = min(ppw, npoints - q0);
+        for (int e = threadIdx.x; e < nq * n; e += 256) xs[e] = X[(size_t)q0 * n + e];
+        __syncthreads();
+        const int lp = threadIdx.x / m;
+        q = q0 + lp; i = threadIdx.x - lp * m; xq = xs + lp * n;
+        return lp < nq;
+    }
+    q = blockIdx.x / nblk;
+    const int rb = blockIdx.x - q * nblk;
+    for (int c = threadIdx.x; c < n; c += 256) xs[c] = X[(size_t)q * n + c];
+    __syncthreads();
+    i = rb * 256 + threadIdx.x; xq = xs;
+    return i < m;
+}
+
+// One pass over the program.  vs: this thread's column of the value stack (slot s at vs[s * 256]); ts: of the C tangent
+// stacks (column c, slot s at ts[(c * depth + s) * 256]), columns j0 .. j0 + C - 1 (C = 0: values only).  Returns the
+// root's value; the root's tangents are left in slot 0.
+template <bool TAN>
+__device__ static inline double expr_run(const ExprProg &P, const double *xq, const double (&tv)[NLH_EXPR_MAX_VARS], double *vs, double *ts,
+                                         int j0, int C)
+{
+    const int depth = P.depth;
+    const uint32_t cm = !TAN ? 0u : (C >= 32 ? 0xffffffffu : (1u << C) - 1u);   // (values only: every tangent test folds away)
+    int sp = 0;                                                   // slots in use (scalar)
+#define V(s) vs[(s) * 256]
+#define T(c, s) ts[((c) * depth + (s)) * 256]
+    for (int pc = 0; pc < P.ninstr; ++pc) {
+        const uint32_t code = P.code[pc];
+        const int op = EXPR_OP(code), arg = EXPR_ARG(code);
+        if (op <= NLH_EXPR_PARAM) {
+            double v;
+            if (op == NLH_EXPR_CONST) v = P.consts[arg];
+            else if (op == NLH_EXPR_VAR) v = arg == 0 ? tv[0] : (arg == 1 ? tv[1] : (arg == 2 ? tv[2] : tv[3]));
+            else {
+                v = xq[arg];
+                if (TAN && arg >= j0 && arg < j0 + C) T(arg - j0, sp) = 1.0;
+            }
+            V(sp) = v;
+            ++sp;
+            continue;
+        }
+        if (op >= NLH_EXPR_ADD && op <= NLH_EXPR_DIV) {           // binary: a below b
+            const double a = V(sp - 2), b = V(sp - 1);
+            const uint32_t ma = (P.mask[EXPR_AROOT(code)] >> j0) & cm, mb = (P.mask[pc - 1] >> j0) & cm;
+            double v, q = 0.0;
+            if (op == NLH_EXPR_ADD) v = a + b;
+            else if (op == NLH_EXPR_SUB) v = a - b;
+            else if (op == NLH_EXPR_MUL) v = a * b;
+            else { q = a / b; v = q; }
+            for (uint32_t mm = ma | mb; mm; mm &= mm - 1) {
+                const int c = __builtin_ctz(mm);
+                const bool ha = (ma >> c) & 1u, hb = (mb >> c) & 1u;
+                const double da = ha ? T(c, sp - 2) : 0.0, db = hb ? T(c, sp - 1) : 0.0;
+                double d;
+                if (op == NLH_EXPR_ADD) d = ha && hb ? da + db : (ha ? da : db);
+                else if (op == NLH_EXPR_SUB) d = ha && hb ? da - db : (ha ? da : -db);
+                else if (op == NLH_EXPR_MUL) d = ha && hb ? da * b + a * db : (ha ? da * b : a * db);
+                else d = ha && hb ? (da - q * db) / b : (ha ? da / b : -((q * db) / b));
+                T(c, sp - 2) = d;
+            }
+            V(sp - 2) = v;
+            --sp;
+            continue;
+        }
+        // unary: the operand is the instruction before
+        const double a = V(sp - 1);
+        const uint32_t ma = (P.mask[pc - 1] >> j0) & cm;
+        double v, g = 0.0;                                        // the tangent is g * da (or the op's own form below)
+        switch (op) {
+        case NLH_EXPR_NEG: v = -a; break;
+        case NLH_EXPR_IPOW: {
+            const int k = arg < 0 ? -arg : arg;
+            double u = a;
+            v = a;
+            for (int r = 1; r < k; ++r) { u = v; v = v * a; }
+            g = (double)k * u;
+            if (arg < 0) v = 1.0 / v;
+            break;
+        }
+        case NLH_EXPR_POWC: {
+            const double c = P.consts[arg];
+            v = pow(a, c);
+            if (ma) g = c * pow(a, c - 1.0);
+            break;
+        }
+        case NLH_EXPR_EXP: v = exp(a); break;
+        case NLH_EXPR_LOG: v = log(a); break;
+        case NLH_EXPR_SQRT: v = sqrt(a); break;
+        case NLH_EXPR_SIN: v = sin(a); if (ma) g = cos(a); break;
+        case NLH_EXPR_COS: v = cos(a); if (ma) g = sin(a); break;
+        case NLH_EXPR_TANH: v = tanh(a); break;
+        case NLH_EXPR_ATAN: v = atan(a); break;
+        default: v = fabs(a); break;                              // NLH_EXPR_ABS
+        }
+        for (uint32_t mm = ma; mm; mm &= mm - 1) {
+            const int c = __builtin_ctz(mm);
+            const double da = T(c, sp - 1);
+            double d;
+            switch (op) {
+            case NLH_EXPR_NEG: d = -da; break;
+            case NLH_EXPR_IPOW: d = arg > 0 ? g * da : -((g * da) * (v * v)); break;
+            case NLH_EXPR_POWC: d = g * da; break;
+            case NLH_EXPR_EXP: d = v * da; break;
+            case NLH_EXPR_LOG: d = da / a; break;
+            case NLH_EXPR_SQRT: d = da / (2.0 * v); break;
+            case NLH_EXPR_SIN: d = g * da; break;
+            case NLH_EXPR_COS: d = -(g * da); break;
+            case NLH_EXPR_TANH: d = (1.0 - v * v) * da; break;
+            case NLH_EXPR_ATAN: d = da / (1.0 + a * a); break;
+            default: d = a < 0.0 ? -da : da; break;
+            }
+            T(c, sp - 1) = d;
+        }
+        V(sp - 1) = v;
+    }
+    return V(0);
+#undef V
+#undef T
+}
+
+// the row's variables, loaded whether or not the thread has a row (clamped index)
+__device__ static inline void expr_load_vars(const ExprData &ed, int nvar, size_t at, int ic, double (&tv)[NLH_EXPR_MAX_VARS])
+{
+    const size_t o = ed.shared_t ? (size_t)ic : at;
+#pragma unroll
+    for (int v = 0; v < NLH_EXPR_MAX_VARS; ++v) tv[v] = ed.t[v < nvar ? o + (size_t)v * (size_t)ed.tstride : o];
+}
+
+template <bool FLAT>
+static __global__ void __launch_bounds__(256)
+k_expr_fcn(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints, const int32_t *__restrict__ dprob,
+           const double *__restrict__ X, double *__restrict__ F)
+{
+    extern __shared__ double lds[];                               // x of the workgroup's points, then the value stack
+    int q, i;
+    const double *xq;
+    const bool on = expr_place<FLAT>(ed.m, n, nblk, ppw, npoints, X, lds, q, i, xq);
+    const int qc = min(q, npoints - 1), ic = min(i, ed.m - 1);
+    const int p = dprob ? dprob[qc] : qc;
+    const size_t at = (size_t)p * ed.m + ic;
+    double tv[NLH_EXPR_MAX_VARS];
+    expr_load_vars(ed, P.nvar, at, ic, tv);
+    const double y = ed.y ? ed.y[at] : 0.0;
+    const double w = ed.w ? ed.w[at] : 1.0;
+    if (!on) return;
+    double *vs = lds + (FLAT ? ppw : 1) * n + threadIdx.x;
+    double r = expr_run<false>(P, xq, tv, vs, vs, 0, 0);
+    if (ed.y) r = r - y;
+    if (ed.w) r = w * r;
+    F[(size_t)q * ed.m + i] = r;
+}
+
+template <bool FLAT>
+static __global__ void __launch_bounds__(256)
+k_expr_jac(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints, int C, const int32_t *__restrict__ dprob,
+           const double *__restrict__ X, double *__restrict__ J)
+{
+    extern __shared__ double lds[];                               // x, the value stack, C tangent stacks
+    int q, i;
+    const double *xq;
+    const bool on = expr_place<FLAT>(ed.m, n, nblk, ppw, npoints, X, lds, q, i, xq);
+    const int qc = min(q, npoints - 1), ic = min(i, ed.m - 1);
+    const int p = dprob ? dprob[qc] : qc;
+    const size_t at = (size_t)p * ed.m + ic;
+    double tv[NLH_EXPR_MAX_VARS];
+    expr_load_vars(ed, P.nvar, at, ic, tv);
+    const double w = ed.w ? ed.w[at] : 1.0;
+    if (!on) return;
+    const size_t m = (size_t)ed.m;
+    const bool hw = ed.w != nullptr;
+    double *vs = lds + (FLAT ? ppw : 1) * n + threadIdx.x;
+    double *ts = vs + P.depth * 256;
+    double *Jq = J + (size_t)q * m * n + i;
+    const uint32_t root = P.mask[P.ninstr - 1];
+    for (int j0 = 0; j0 < n; j0 += C) {
+        const int cc = min(C, n - j0);
+        if ((root >> j0) & (cc >= 32 ? 0xffffffffu : (1u << cc) - 1u)) expr_run<true>(P, xq, tv, vs, ts, j0, cc);
+        for (int c = 0; c < cc; ++c) {
+            const double d = (root >> (j0 + c)) & 1u ? ts[(c * P.depth) * 256] : 0.0;
+            Jq[(size_t)(j0 + c) * m] = hw ? w * d : d;
+        }
+    }
+}

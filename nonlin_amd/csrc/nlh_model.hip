@@ -89,6 +89,10 @@ struct nlh_dq_model {
     nlh_curve_ctx *curve = nullptr;
     void *curve_base = nullptr;
     int curve_device = 0;
+    // a formula model (nlh_expr_model_create): uctx is this context; the model owns it, the copy of the program behind it
+    // and the device copies of t, y, w (curve_base on curve_device, as the curve model's)
+    nlh_expr_ctx *expr = nullptr;
+    nlh_expr *expr_prog = nullptr;
 };
 
 int nlh_device_fcn_model_create(int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn, nlh_device_jacfcn jacfcn, void *ctx,
@@ -215,9 +219,48 @@ int nlh_curve_model_create(nlh_handle *h, int32_t kind, int32_t ncomp, int32_t n
     return 0;
 }
 
+// A formula model: the same, with a copy of the compiled program (the caller's nlh_expr may be destroyed at once).
+int nlh_expr_model_create(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32_t m, const double *t, int32_t shared_t, const double *y,
+                          const double *w, int32_t analytic, nlh_dq_model **out)
+{
+    if (out) *out = nullptr;
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (!out || !e || nprob < 1 || m < 1 || !t || !y) return NLH_INVALID_INPUT_ERROR;
+    const int32_t n = e->prog.nparams;
+    if (m < n) return NLH_UNDERDEFINED_PROBLEM_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t pm = (size_t)nprob * m, stride = shared_t ? (size_t)m : pm, tm = stride * e->prog.nvar;
+    double *base = nullptr;
+    if (hipMalloc(&base, sizeof(double) * (tm + pm * (w ? 2 : 1))) != hipSuccess) {
+        h->err = "hipMalloc (formula model)";
+        return NLH_OUT_OF_MEMORY_ERROR;
+    }
+    hipError_t er = hipMemcpyAsync(base, t, sizeof(double) * tm, hipMemcpyHostToDevice, h->stream);
+    if (er == hipSuccess) er = hipMemcpyAsync(base + tm, y, sizeof(double) * pm, hipMemcpyHostToDevice, h->stream);
+    if (er == hipSuccess && w) er = hipMemcpyAsync(base + tm + pm, w, sizeof(double) * pm, hipMemcpyHostToDevice, h->stream);
+    if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
+    if (er != hipSuccess) {
+        hipFree(base);
+        h->err = std::string("hipMemcpy (formula model): ") + hipGetErrorString(er);
+        return NLH_ERR_HIP;
+    }
+    nlh_dq_model *md = new nlh_dq_model();
+    md->expr_prog = new nlh_expr(*e);
+    nlh_expr_ctx *c = new nlh_expr_ctx();
+    c->e = md->expr_prog; c->shared_t = shared_t != 0; c->m = m; c->dt_stride = (int64_t)stride;
+    c->dt = base; c->dy = base + tm; c->dw = w ? base + tm + pm : nullptr;
+    md->nprob = nprob; md->m = m; md->n = n; md->gamma = 0.0;
+    md->ufcn = nlh_expr_device_fcn; md->ujac = analytic ? nlh_expr_device_jac : nullptr; md->uctx = c;
+    md->expr = c; md->curve_base = base; md->curve_device = h->device;
+    *out = md;
+    return 0;
+}
+
 void nlh_dq_model_destroy(nlh_dq_model *md)
 {
     if (!md) return;
+    delete md->expr;
+    delete md->expr_prog;
     if (md->curve_base) { hipSetDevice(md->curve_device); hipFree(md->curve_base); }
     delete md->curve;
     for (auto &pt : md->parts)

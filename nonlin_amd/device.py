@@ -17,6 +17,7 @@ IB_DTYPE = np.dtype([(k, np.int32) for k, _ in _lib.IterationBehavior._fields_])
 
 
 from ._lib import CURVE_GAUSS, CURVE_LORENTZ, CURVE_EXPDECAY, CURVE_KINDS, curve_kind, curve_nparams  # noqa: E402,F401
+from ._lib import Expr  # noqa: E402,F401
 
 
 def _chk(t, shape, name):
@@ -274,6 +275,92 @@ class DeviceSolver:
         self.h.check(rc, "nlh_curve_fit_batch")
         if rc:
             raise RuntimeError(f"nlh_curve_fit_batch returned {rc}")
+        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nprob)], [int(status[p]) for p in range(nprob)])
+
+    # -- formula models ----------------------------------------------------------
+    @staticmethod
+    def _expr_t(expr, t, nprob, m):
+        """shared_t of the abscissae t of a formula model, checked: [nvar, nprob, m], or shared [nvar, m]; with one variable
+        [nprob, m] or shared [m] will do."""
+        if expr.nvar == 1 and t.dim() == 2 and tuple(t.shape) == (nprob, m):
+            shape, shared = (nprob, m), 0
+        elif t.dim() == 3:
+            shape, shared = (expr.nvar, nprob, m), 0
+        elif t.dim() == 1:
+            shape, shared = (m,) if expr.nvar == 1 else (expr.nvar, m), 1
+        else:
+            shape, shared = (expr.nvar, m), 1
+        _chk(t, shape, "t")
+        return shared
+
+    def _expr_data(self, expr, t, y, weights):
+        """(nprob, m, shared_t) of the data tensors of a formula model, checked."""
+        nprob, m = y.shape
+        _chk(y, (nprob, m), "y")
+        shared = self._expr_t(expr, t, nprob, m)
+        if weights is not None:
+            _chk(weights, (nprob, m), "weights")
+        return nprob, m, shared
+
+    def expr_launchers(self, expr, t, y, weights=None):
+        """A formula model (nonlin_amd.Expr) on the data t [nvar, nprob, m] (or shared [nvar, m]; one variable: [nprob, m] or
+        [m]), y [nprob, m] with optional weights [nprob, m], as (fcn, jac, ctx) for lm_solve_batch_device,
+        cls_solve_batch_device, lm_covariance_batch_device and fd_jacobian_device.  Keep ctx alive while solving (it keeps
+        the tensors and the expression)."""
+        nprob, m, shared = self._expr_data(expr, t, y, weights)
+        ctx = _lib.ExprCtx(expr.ptr, shared, m, t.data_ptr(), y.data_ptr(), weights.data_ptr() if weights is not None else None,
+                           m if shared else nprob * m)
+        ctx._keep = (expr, t, y, weights)                             # the context holds addresses: they live as long as it does
+        return (C.cast(self.lib.nlh_expr_device_fcn, _lib.DEVFCN), C.cast(self.lib.nlh_expr_device_jac, _lib.DEVFCN), ctx)
+
+    def expr_eval(self, expr, x, t):
+        """Model values (no data term, no weights) of x [nprob, n] at t [nvar, nprob, npts] (or shared [nvar, npts]; one
+        variable: [nprob, npts] or [npts]): y [nprob, npts]."""
+        nprob, n = x.shape
+        _chk(x, (nprob, n), "x")
+        if n != expr.nparams:
+            raise ValueError(f"x has {n} columns, the formula {expr.nparams} parameters")
+        npts = t.shape[-1]
+        shared = self._expr_t(expr, t, nprob, npts)
+        y = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
+        rc = self.lib.nlh_expr_eval_batch(self.h.ptr, expr.ptr, nprob, npts, t.data_ptr(), int(shared), x.data_ptr(), y.data_ptr())
+        self.h.check(rc, "nlh_expr_eval_batch")
+        if rc:
+            raise RuntimeError(f"nlh_expr_eval_batch returned {rc}")
+        return y
+
+    def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None):
+        """Fit + errors of y.shape[0] data sets to a formula in one call (nlh_expr_fit_batch): curve_fit_batch with an Expr in
+        the place of (kind, ncomp, baseline).  Returns (x, fvec, sigma, cov, chi2, rank, ibs, status)."""
+        nprob, m, shared = self._expr_data(expr, t, y, weights)
+        n = expr.nparams
+        _chk(x0, (nprob, n), "x0")
+        dev = y.device
+        x = x0.clone()
+        fvec = torch.empty((nprob, m), dtype=torch.float64, device=dev)
+        sigma = cov = chi2 = rank = None
+        if covariance:
+            sigma = torch.empty((nprob, n), dtype=torch.float64, device=dev)
+            cov = torch.empty((nprob, n, n), dtype=torch.float64, device=dev)
+            chi2 = torch.empty((nprob,), dtype=torch.float64, device=dev)
+            rank = torch.empty((nprob,), dtype=torch.int32, device=dev)
+        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64)
+        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
+        for b in (lo, hi):
+            if b is not None and b.shape != (n,):
+                raise ValueError(f"bounds: expected {n} entries")
+        ib = (_lib.IterationBehavior * nprob)()
+        status = (C.c_int32 * nprob)()
+        o = opts or self.options()
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        rc = self.lib.nlh_expr_fit_batch(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(), ptr(weights),
+                                         int(bool(analytic)),
+                                         None if lo is None else lo.ctypes.data_as(_lib.c_double_p),
+                                         None if hi is None else hi.ctypes.data_as(_lib.c_double_p),
+                                         x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
+        self.h.check(rc, "nlh_expr_fit_batch")
+        if rc:
+            raise RuntimeError(f"nlh_expr_fit_batch returned {rc}")
         return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nprob)], [int(status[p]) for p in range(nprob)])
 
     def _ctxp(self, ctx):

@@ -166,6 +166,36 @@ module nonlin_hip_c
             type(c_ptr), intent(out) :: model
             integer(c_int) :: rc
         end function
+        ! formula models (include/nonlin_hip.h: nlh_expr_*): compile on the host, then a model object on host data
+        function nlh_expr_compile(formula, vars, params, e) bind(C, name="nlh_expr_compile") result(rc)
+            import :: c_ptr, c_int, c_char
+            character(kind=c_char), intent(in) :: formula(*), vars(*), params(*)
+            type(c_ptr), intent(out) :: e
+            integer(c_int) :: rc
+        end function
+        function nlh_expr_error() bind(C, name="nlh_expr_error") result(msg)
+            import :: c_ptr
+            type(c_ptr) :: msg
+        end function
+        subroutine nlh_expr_destroy(e) bind(C, name="nlh_expr_destroy")
+            import :: c_ptr
+            type(c_ptr), value :: e
+        end subroutine
+        subroutine nlh_expr_shape(e, nvar, nparams, ninstr, nconst, depth) bind(C, name="nlh_expr_shape")
+            import :: c_ptr, c_int32_t
+            type(c_ptr), value :: e
+            integer(c_int32_t), intent(out) :: nvar, nparams, ninstr, nconst, depth
+        end subroutine
+        function nlh_expr_model_create(h, e, nprob, m, t, shared_t, y, w, analytic, model) &
+                bind(C, name="nlh_expr_model_create") result(rc)
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h, e
+            integer(c_int32_t), value :: nprob, m, shared_t, analytic
+            real(c_double), intent(in) :: t(*), y(*)
+            type(c_ptr), value :: w
+            type(c_ptr), intent(out) :: model
+            integer(c_int) :: rc
+        end function
         function nlh_curve_nparams(kind, ncomp, nbase) bind(C, name="nlh_curve_nparams") result(n)
             import :: c_int32_t
             integer(c_int32_t), value :: kind, ncomp, nbase

@@ -57,6 +57,7 @@ module nonlin_multi_eqn_mult_var
         procedure, public :: create => dmb_create
         procedure, public :: create_from_device_fcn => dmb_create_fcn
         procedure, public :: create_curve => dmb_create_curve
+        procedure, public :: create_expr => dmb_create_expr
         procedure, public :: destroy => dmb_destroy
         procedure, public :: is_defined => dmb_defined
         procedure, public :: get_problem_count => dmb_nprob
@@ -77,6 +78,7 @@ module nonlin_multi_eqn_mult_var
         procedure, public :: set_device_model => helper_bind_model
         procedure, public :: set_device_fcn => helper_bind_device_fcn
         procedure, public :: set_device_curve => helper_bind_curve
+        procedure, public :: set_device_expr => helper_bind_expr
         procedure, public :: clear_device_model => helper_drop_model
         procedure, public :: is_device_model_defined => helper_has_model
         procedure, public :: device_model => helper_model
@@ -214,6 +216,26 @@ contains
         this%nvar_ = this%model_%get_variable_count()
     end subroutine
 
+    !> Extension: the residual is a formula (see device_model_batch%create_expr) on ONE data set: t(m, nvar) -- a column per
+    !> variable --, y(m), optional weights w(m).  solver%solve(obj, x, fvec, ib) and covariance then run on the GPU.
+    subroutine helper_bind_expr(this, formula, vars, params, t, y, w, analytic)
+        class(vecfcn_helper), intent(inout) :: this
+        character(len=*), intent(in) :: formula, vars, params
+        real(real64), intent(in), dimension(:,:) :: t
+        real(real64), intent(in), dimension(:) :: y
+        real(real64), intent(in), dimension(:), optional :: w
+        logical, intent(in), optional :: analytic
+        if (present(w)) then
+            call this%model_%create_expr(formula, vars, params, reshape(t, [size(t, 1), 1, size(t, 2)]), reshape(y, [size(y), 1]), &
+                reshape(w, [size(w), 1]), analytic)
+        else
+            call this%model_%create_expr(formula, vars, params, reshape(t, [size(t, 1), 1, size(t, 2)]), reshape(y, [size(y), 1]), &
+                analytic = analytic)
+        end if
+        this%neqn_ = this%model_%get_equation_count()
+        this%nvar_ = this%model_%get_variable_count()
+    end subroutine
+
     subroutine helper_drop_model(this)
         class(vecfcn_helper), intent(inout) :: this
         call this%model_%destroy()
@@ -319,6 +341,66 @@ contains
         end if
         rc = nlh_curve_model_create(nlh_default_handle(), int(kind, c_int32_t), int(ncomp, c_int32_t), int(baseline, c_int32_t), &
             int(size(y, 2), c_int32_t), int(size(y, 1), c_int32_t), tc, shared, yc, wp, use_jac, this%model_)
+        if (rc /= 0) error stop rc
+        this%neqn_ = size(y, 1)
+        this%nvar_ = n
+        this%nprob_ = size(y, 2)
+        this%analytic_ = use_jac /= 0
+    end subroutine
+
+    !> A formula model fitted to nprob data sets: formula is an expression over the variables vars and the parameters params
+    !> (comma-separated names; the order of params is the order of a problem's x), e.g. "a*exp(-k*t)+c", "t", "a,k,c" --
+    !> operators + - * / ^ (a literal exponent), exp log sqrt sin cos tanh atan abs, pi (INTEGRATION.md 6h has the grammar and
+    !> the stated arithmetic).  t(m, nprob, nvar) -- or t(m, 1, nvar): the same abscissae for every problem --, y(m, nprob),
+    !> optional weights w(m, nprob) (a row of weight 0 pads a shorter data set).  analytic (default .true.): the formula's
+    !> own forward-mode Jacobian, otherwise forward differences.  A formula the compiler refuses stops the program with
+    !> NL_INVALID_INPUT_ERROR after printing the compiler's message (the column is 0-based).  The model owns the compiled
+    !> program and device copies of the data.
+    subroutine dmb_create_expr(this, formula, vars, params, t, y, w, analytic)
+        class(device_model_batch), intent(inout) :: this
+        character(len=*), intent(in) :: formula, vars, params
+        real(real64), intent(in), dimension(:,:,:) :: t
+        real(real64), intent(in), dimension(:,:) :: y
+        real(real64), intent(in), dimension(:,:), optional :: w
+        logical, intent(in), optional :: analytic
+        integer(c_int) :: rc
+        integer(c_int32_t) :: nvar, n, ninstr, nconst, depth, shared, use_jac
+        real(c_double), allocatable, target :: tc(:,:,:), yc(:,:), wc(:,:)
+        type(c_ptr) :: wp, e, msg
+        character(kind=c_char), pointer :: text(:)
+        integer :: k
+        rc = nlh_expr_compile(trim(formula)//c_null_char, trim(vars)//c_null_char, trim(params)//c_null_char, e)
+        if (rc /= 0) then
+            msg = nlh_expr_error()
+            call c_f_pointer(msg, text, [512])
+            k = 1
+            do while (k < 512 .and. text(k) /= c_null_char)
+                k = k + 1
+            end do
+            write(error_unit, '(A,512A1)') "formula: ", text(1:k - 1)
+            error stop NL_INVALID_INPUT_ERROR
+        end if
+        call nlh_expr_shape(e, nvar, n, ninstr, nconst, depth)
+        if (size(t, 3) /= nvar .or. size(t, 1) /= size(y, 1) .or. (size(t, 2) /= size(y, 2) .and. size(t, 2) /= 1)) then
+            call nlh_expr_destroy(e)
+            error stop NL_ARRAY_SIZE_ERROR
+        end if
+        shared = 0
+        if (size(t, 2) == 1 .and. size(y, 2) /= 1) shared = 1
+        use_jac = 1
+        if (present(analytic)) use_jac = merge(1, 0, analytic)
+        call this%destroy()
+        tc = t                                               ! contiguous copies: the dummies may be sections
+        yc = y
+        wp = c_null_ptr
+        if (present(w)) then
+            if (any(shape(w) /= shape(y))) error stop NL_ARRAY_SIZE_ERROR
+            wc = w
+            wp = c_loc(wc)
+        end if
+        rc = nlh_expr_model_create(nlh_default_handle(), e, int(size(y, 2), c_int32_t), int(size(y, 1), c_int32_t), tc, shared, yc, wp, &
+            use_jac, this%model_)
+        call nlh_expr_destroy(e)                             ! (the model keeps its own copy of the program)
         if (rc /= 0) error stop rc
         this%neqn_ = size(y, 1)
         this%nvar_ = n
