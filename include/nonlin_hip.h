@@ -830,6 +830,118 @@ int nlh_expr_fit_batch_h(nlh_handle *h, const nlh_options *opts, const nlh_expr 
                          const double *xu, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
                          nlh_iteration_behavior *ib, int32_t *status);
 
+/* ---- parameter maps (no counterpart in nonlin v2.2.0): fixed and tied parameters for ANY device model.  The model keeps
+ * its N FULL parameters; the solver sees n <= N FREE unknowns.  Each full parameter k is free, fixed at a per-problem
+ * value, or tied to another parameter: p_k = scale_k*p_src + offset_k.  The map is a pair of wrapping launchers around any
+ * inner launcher pair (built-in curve, formula, a user's own), so everything that takes launchers works through it:
+ * nlh_lm_solve_batch_device, nlh_cls_solve_batch_device, nlh_lm_covariance_batch_device, nlh_fd_jacobian_device and the
+ * model objects.  With forward differences the library then builds n + 1 points per Jacobian instead of N + 1.
+ * Free parameters are numbered in ascending full index: free unknown j is the j-th free full parameter.
+ * THE ARITHMETIC IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation:
+ *   expand    (free x[n] -> full p[N])  first every free p_k = x[index_k] and every fixed p_k = full_k (full: the caller's
+ *             array of full parameters); then, tied k ascending:  u = scale_k*p_src;  p_k = u + offset_k
+ *   gather    (full -> free)  x[j] = full[free_to_full[j]]
+ *   contract  (inner Jacobian Jf, m x N -> J, m x n)  for each free j:  v = Jf[:, free_to_full[j]];  then, for every tied k
+ *             in ascending k whose source is that parameter:  v = v + scale_k*Jf[:, k].  Columns of fixed parameters, and
+ *             of parameters tied to fixed ones, are not read.
+ *   covariance of the full parameters from the free one: the factor g_k is 1.0 for a free parameter, scale_k for a tie to a
+ *             free source and absent otherwise (j_k: the free number of k, or of its source);
+ *             cov_full[k][l] = (g_k*cov[j_k][j_l])*g_l;  sigma_full[k] = fabs(g_k)*sigma[j_k];  rows, columns and sigmas of
+ *             parameters without a factor are +0.0.  A problem that did not solve has NaN in every entry (and rank -1).
+ * No sum crosses a row: a row's bits do not depend on the launch, the batch or the workgroup form. ---- */
+#define NLH_PMAP_FREE  0
+#define NLH_PMAP_FIXED 1
+#define NLH_PMAP_TIED  2
+#define NLH_PMAP_MAX_N 8192            /* = NLH_CURVE_MAX_N */
+typedef struct nlh_pmap nlh_pmap;
+/* The map object (host code, needs no GPU; nlh_pmap_gather_batch, _expand_batch and _cov_batch keep a device copy of its
+ * tables in it from their first use, which nlh_pmap_destroy frees).
+ * kind [nfull]: NLH_PMAP_*; src, scale, offset [nfull] are read only at tied positions, and all three may be NULL when nothing is tied.  Refused with NLH_INVALID_INPUT_ERROR, *pm left NULL:
+ * nfull < 1 or > NLH_PMAP_MAX_N; a kind outside 0 .. 2; a tie whose source is out of range, is itself, or is itself tied
+ * (no chains); a scale or offset that is not finite; a tie with scale 0.0 (that is a fixed parameter: say so); no free
+ * parameter at all.  A tie to a FIXED source is allowed: a derived constant. */
+int  nlh_pmap_create(int32_t nfull, const int32_t *kind, const int32_t *src, const double *scale, const double *offset, nlh_pmap **pm);
+void nlh_pmap_destroy(nlh_pmap *pm);
+void nlh_pmap_shape(const nlh_pmap *pm, int32_t *nfull, int32_t *nfree, int32_t *ntied);     /* any output may be NULL */
+/* Read-back, for restatements (any output may be NULL): kind, index, scale, offset [nfull], free_to_full [nfree].
+ * index[k]: the free number for a free k, the source's full index for a tied k, -1 for a fixed k; scale / offset are
+ * 1.0 / 0.0 where k is not tied. */
+int  nlh_pmap_tables(const nlh_pmap *pm, int32_t *kind, int32_t *index, double *scale, double *offset, int32_t *free_to_full);
+/* The wrapping launchers.  nlh_pmap_wrap makes their context on the handle's device: device copies of the tables, scratch,
+ * the inner pair (fcn, jac -- NULL: none --, inner_ctx; all stay the caller's and must outlive the context).  dfull is a
+ * DEVICE array [nprob][N], or [N] with shared_full != 0, the caller's, read at fixed positions only: point q reads row
+ * dprob[q] (a NULL dprob means q itself).
+ *   nlh_pmap_device_fcn  expand into scratch P [npoints][N]; the inner fcn with n = N straight into the caller's dF
+ *   nlh_pmap_device_jac  expand; the inner jac into scratch Jf [npoints][N][m]; contract into dJ.  With a NULL inner jac it
+ *                        returns an error: pass a NULL jacfcn to the solver instead (forward differences over the n free
+ *                        unknowns).
+ * Both enqueue only on the stream handed in, never synchronise and may be called from several host threads on different
+ * streams.  A malformed context, n != nfree or m < 1 returns non-zero before any launch.  An inner error comes back as it
+ * is, with no further launch; the inner launcher is called after the expansion of its points has been enqueued, so by then
+ * the context's own scratch has been written, and nothing of the caller's.
+ * Scratch belongs to the context: one buffer per stream, grown on demand, reused, kept until nlh_pmap_unwrap, at most
+ * 1 GiB per call and so per stream (a context called on s streams -- the handle's and a solver's sub-batch workers -- holds
+ * up to s GiB).  A call that needs more runs in slices of points, each calling the inner launcher with offset dprob, dX and
+ * dJ -- the same bits.  Growing a buffer frees and allocates device memory, which waits for the device: it happens in the
+ * first calls on a stream, not in every call.
+ * NLH_PMAP_SCRATCH = bytes (environment, read at each call; tests) lowers the cap.  The contraction runs a thread per
+ * (point, row) in the two workgroup forms of the curve kernels -- a workgroup per (point, 256 rows), or several points per
+ * workgroup while two or more fit 256 threads; NLH_PMAP_FORM = row | flat forces one for the sizes it can hold (flat:
+ * m <= 256) -- and splits the free columns over a second grid dimension while the launch would otherwise be fewer than four
+ * workgroups per compute unit (NLH_PMAP_SPLIT = number of column groups overrides; tests). */
+typedef struct nlh_pmap_ctx nlh_pmap_ctx;
+int  nlh_pmap_wrap(nlh_handle *h, const nlh_pmap *pm, nlh_device_vecfcn fcn, nlh_device_jacfcn jac, void *inner_ctx,
+                   const double *dfull, int32_t shared_full, nlh_pmap_ctx **out);
+void nlh_pmap_unwrap(nlh_pmap_ctx *c);
+int  nlh_pmap_device_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dF);
+int  nlh_pmap_device_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dJ);
+/* The three small steps around a solve made through the launchers by hand, on DEVICE arrays (the handle's stream):
+ *   gather   dfull [nprob][N] -> dx [nprob][n]
+ *   expand   dx [nprob][n], dfull [nprob][N] (shared_full: [N]) -> dp [nprob][N] (dp may not alias dfull; dfull may be
+ *            NULL for a map without a fixed parameter, as for nlh_pmap_wrap)
+ *   cov      dcov [nprob][n][n], dsigma [nprob][n] -> dcov_full [nprob][N][N], dsigma_full [nprob][N]; either pair may be
+ *            NULL; dfail [nprob] int32 or NULL: a non-zero entry marks a problem that did not solve (NaN in every entry). */
+int  nlh_pmap_gather_batch(nlh_handle *h, const nlh_pmap *pm, int32_t nprob, const double *dfull, double *dx);
+int  nlh_pmap_expand_batch(nlh_handle *h, const nlh_pmap *pm, int32_t nprob, const double *dx, const double *dfull,
+                           int32_t shared_full, double *dp);
+int  nlh_pmap_cov_batch(nlh_handle *h, const nlh_pmap *pm, int32_t nprob, const double *dcov, const double *dsigma,
+                        const int32_t *dfail, double *dcov_full, double *dsigma_full);
+/* One-call fits through a map: nlh_curve_fit_batch / nlh_expr_fit_batch plus pm (NULL: exactly the old entry points, bit
+ * for bit).  Everything the caller sees is FULL: dx [nprob][N] in and out, dsigma [nprob][N], dcov [nprob][N][N], host xl / xu
+ * [N].  On entry a fixed parameter keeps the value dx holds for that problem (the values may differ per problem; the entry
+ * point works on a private copy); tied positions of dx are ignored on entry; on exit dx is the expansion of the solution, for
+ * every problem: one that is refused on its degrees of freedom keeps its free and fixed values, and its tied positions
+ * hold the ties evaluated at them.
+ * Bound entries at fixed and tied positions are not read.  The composition: gather; the solve over the n = nfree free
+ * unknowns with the wrapping launchers; the covariance at the solution; expand; the covariance of the full parameters.
+ * The degrees of freedom, m >= n (NLH_UNDERDEFINED_PROBLEM_ERROR otherwise), m > n for errors and (m - n) / dof all use
+ * n = nfree; everything else is the old composition, zero-weight padding rule included.  Errors, in this order: the old
+ * entry point's for the handle and the model; NLH_INVALID_INPUT_ERROR for a map whose nfull is not the model's N;
+ * NLH_UNDERDEFINED_PROBLEM_ERROR (m < nfree); NLH_INVALID_INPUT_ERROR (a NULL array; errors asked for with m <= nfree). */
+int nlh_curve_fit_batch_pmap(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                             int32_t m, const double *dt, int32_t shared_t, const double *dy, const double *dw, int32_t analytic,
+                             const double *xl, const double *xu, const nlh_pmap *pm, double *dx, double *dfvec, double *dsigma,
+                             double *dcov, double *dchi2, int32_t *drank, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_curve_fit_batch_pmap_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                               int32_t m, const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic,
+                               const double *xl, const double *xu, const nlh_pmap *pm, double *x, double *fvec, double *sigma,
+                               double *cov, double *chi2, int32_t *rank, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_expr_fit_batch_pmap(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+                            int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl,
+                            const double *xu, const nlh_pmap *pm, double *dx, double *dfvec, double *dsigma, double *dcov,
+                            double *dchi2, int32_t *drank, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_expr_fit_batch_pmap_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+                              int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl,
+                              const double *xu, const nlh_pmap *pm, double *x, double *fvec, double *sigma, double *cov,
+                              double *chi2, int32_t *rank, nlh_iteration_behavior *ib, int32_t *status);
+/* A device-function MODEL of nfree unknowns over a launcher-backed inner model (device-function, curve or formula; a
+ * dense-quadratic model: NLH_INVALID_INPUT_ERROR), which must outlive it.  full: HOST [nprob][N], or [N] with shared_full;
+ * the model owns its device copy and its wrapping context.  Every nlh_dq_model_* solver and nlh_dq_model_lm_covariance
+ * then takes it (x [nprob][nfree]).  Errors: NLH_ERR_BAD_HANDLE, then NLH_INVALID_INPUT_ERROR (a NULL argument, a
+ * dense-quadratic inner model, nfull != the inner model's n), NLH_UNDERDEFINED_PROBLEM_ERROR is left to the solvers. */
+int nlh_pmap_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_pmap *pm, const double *full, int32_t shared_full,
+                          nlh_dq_model **model);
+
 /* ---- per-kernel timing (HIP events on the handle's stream) ------------------ */
 #define NLH_K_DQ_RESIDUAL   0
 #define NLH_K_DQ_PANEL      1

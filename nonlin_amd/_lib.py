@@ -245,6 +245,32 @@ SYMBOLS = {
     "nlh_expr_fit_batch_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p,
                                        C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                        c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_pmap_create": (C.c_int, [C.c_int32, c_int32_p, c_int32_p, c_double_p, c_double_p, C.POINTER(C.c_void_p)]),
+    "nlh_pmap_destroy": (None, [C.c_void_p]),
+    "nlh_pmap_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p]),
+    "nlh_pmap_tables": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_int32_p]),
+    "nlh_pmap_wrap": (C.c_int, [_H, C.c_void_p, DEVFCN, DEVFCN, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "nlh_pmap_unwrap": (None, [C.c_void_p]),
+    "nlh_pmap_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_pmap_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_pmap_gather_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_pmap_expand_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_pmap_cov_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_curve_fit_batch_pmap": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior),
+                                           c_int32_p]),
+    "nlh_curve_fit_batch_pmap_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p,
+                                             C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, c_double_p,
+                                             c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior),
+                                             c_int32_p]),
+    "nlh_expr_fit_batch_pmap": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_fit_batch_pmap_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p,
+                                            c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p,
+                                            c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_pmap_model_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, c_double_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "nlh_timing_enable": (None, [_H, C.c_int32]),
     "nlh_timing_reset": (None, [_H]),
     "nlh_timing_get": (C.c_int, [_H, C.c_int32, c_double_p, C.POINTER(C.c_int64)]),
@@ -359,6 +385,78 @@ class Expr:
     def close(self):
         if getattr(self, "ptr", None) is not None and self.ptr.value:
             self.lib.nlh_expr_destroy(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# kinds of a parameter of a map (include/nonlin_hip.h: NLH_PMAP_*)
+PMAP_FREE, PMAP_FIXED, PMAP_TIED = 0, 1, 2
+
+
+class ParamMap:
+    """A parameter map (nlh_pmap_create: host code, needs no GPU): which of a model's nfull parameters are free, fixed at a
+    per-problem value, or tied to another one by p_k = scale * p_src + offset.  fixed: the indices of the fixed parameters;
+    tied: {k: (src, scale, offset)}.  E.g. ParamMap(7, fixed=(6,), tied={5: (2, 1.25, 0.0)}).  Raises ValueError for what the
+    library refuses (an index out of range, a chain of ties, a tie with scale 0, no free parameter, ...).  Free unknown j
+    is the j-th free parameter in ascending index.  close() frees it (so does garbage collection)."""
+
+    def __init__(self, nfull, fixed=(), tied=None):
+        import numpy as np
+        self.lib = load()
+        self.ptr = C.c_void_p()
+        nfull = int(nfull)
+        tied = dict(tied or {})
+        fixed = [int(k) for k in fixed]
+        if nfull < 1 or any(not 0 <= int(k) < nfull for k in list(fixed) + list(tied)) or set(fixed) & set(int(k) for k in tied):
+            raise ValueError(f"ParamMap: bad nfull ({nfull}), an index outside 0 .. nfull - 1, or a parameter both fixed and tied")
+        kind = np.zeros(nfull, dtype=np.int32)
+        src = np.zeros(nfull, dtype=np.int32)
+        scale, offset = np.ones(nfull), np.zeros(nfull)
+        kind[fixed] = PMAP_FIXED
+        for k, (sk, sc, of) in tied.items():
+            kind[int(k)], src[int(k)], scale[int(k)], offset[int(k)] = PMAP_TIED, int(sk), float(sc), float(of)
+        rc = self.lib.nlh_pmap_create(nfull, kind.ctypes.data_as(c_int32_p), src.ctypes.data_as(c_int32_p),
+                                      scale.ctypes.data_as(c_double_p), offset.ctypes.data_as(c_double_p), C.byref(self.ptr))
+        if rc:
+            self.ptr = C.c_void_p()
+            raise ValueError(f"ParamMap: the library refuses this map (nlh_pmap_create returned {rc}): a tie must name a free or "
+                             "fixed source other than itself, with a finite non-zero scale and a finite offset, and at least one "
+                             f"parameter must stay free (nfull <= {8192})")
+        s = [C.c_int32() for _ in range(3)]
+        self.lib.nlh_pmap_shape(self.ptr, *[C.byref(v) for v in s])
+        self.nfull, self.nfree, self.ntied = (v.value for v in s)
+
+    @classmethod
+    def for_expr(cls, expr, fixed=(), tied=None):
+        """The same by the parameter names of an Expr: ParamMap.for_expr(e, fixed=("b",), tied={"w2": ("w1", 1.25, 0.0)})."""
+        names = [v.strip() for v in expr.params.split(",")]
+
+        def at(name):
+            if name not in names:
+                raise ValueError(f"ParamMap: {name!r} is not a parameter of the formula ({', '.join(names)})")
+            return names.index(name)
+        return cls(len(names), fixed=[at(k) for k in fixed], tied={at(k): (at(v[0]), v[1], v[2]) for k, v in (tied or {}).items()})
+
+    def tables(self):
+        """(kind, index, scale, offset, free_to_full): the read-back of nlh_pmap_tables as numpy arrays."""
+        import numpy as np
+        kind, index = np.zeros(self.nfull, dtype=np.int32), np.zeros(self.nfull, dtype=np.int32)
+        scale, offset = np.zeros(self.nfull), np.zeros(self.nfull)
+        f2f = np.zeros(self.nfree, dtype=np.int32)
+        rc = self.lib.nlh_pmap_tables(self.ptr, kind.ctypes.data_as(c_int32_p), index.ctypes.data_as(c_int32_p),
+                                      scale.ctypes.data_as(c_double_p), offset.ctypes.data_as(c_double_p), f2f.ctypes.data_as(c_int32_p))
+        if rc:
+            raise RuntimeError(f"nlh_pmap_tables returned {rc}")
+        return kind, index, scale, offset, f2f
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.lib.nlh_pmap_destroy(self.ptr)
             self.ptr = C.c_void_p()
 
     def __del__(self):

@@ -195,10 +195,10 @@ int nlh_curve_fit_batch(nlh_handle *h, const nlh_options *opts, int32_t kind, in
 int nlh_fit_compose_h(nlh_handle *h, const char *what, size_t tm, int32_t nprob, int32_t m, int32_t n, const double *t, const double *y,
                       const double *w, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
                       const std::function<int(const double *, const double *, const double *, double *, double *, double *, double *,
-                                              double *, int32_t *)> &fit)
+                                              double *, int32_t *)> &fit, int32_t nfree)
 {
     int rc;
-    if ((sigma || cov || chi2) && m <= n) return NLH_INVALID_INPUT_ERROR;
+    if ((sigma || cov || chi2) && m <= (nfree >= 0 ? nfree : n)) return NLH_INVALID_INPUT_ERROR;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const size_t np = (size_t)nprob, pm = np * m, nn = (size_t)n * n;

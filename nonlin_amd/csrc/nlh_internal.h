@@ -4,7 +4,7 @@
 // (least_squares_solver: lss_solve and its stages), nlh_square.hip (newton_solver, quasi_newton_solver, LU, the
 // Householder steps), nlh_cls.hip (constrained_least_squares_solver), nlh_bfgs.hip (bfgs, fcnnvar_helper%gradient), nlh_nm.hip (nelder_mead),
 // nlh_1var.hip (brent_solver, newton_1var_solver, fcn1var_helper%diff),
-// nlh_poly.hip (polynomial%fit), nlh_polyroots.hip (polynomial%roots, batched evaluate), nlh_covar.hip (parameter covariance), nlh_curve.hip (built-in curve models, the fit + errors composition), nlh_expr.hip (formula models: compiler, launchers), nlh_model.hip (device sets, device residual models behind host arrays), nlh_qrx.hip
+// nlh_poly.hip (polynomial%fit), nlh_polyroots.hip (polynomial%roots, batched evaluate), nlh_covar.hip (parameter covariance), nlh_curve.hip (built-in curve models, the fit + errors composition), nlh_pmap.hip (parameter maps: fixed and tied parameters), nlh_expr.hip (formula models: compiler, launchers), nlh_model.hip (device sets, device residual models behind host arrays), nlh_qrx.hip
 // (the exact lmfactor).  Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it
 // launches.
 #pragma once
@@ -247,10 +247,12 @@ int nlh_fit_compose(nlh_handle *h, const nlh_options *opts, int32_t nprob, int32
                     const double *xu, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
                     nlh_iteration_behavior *ib, int32_t *status);
 // ... behind host arrays: t is tm doubles; fit(dt, dy, dw, dx, df, ds, dc, dq, dr) is the device-pointer entry point.
+// nfree >= 0 (a fit through a parameter map, nlh_pmap.hip: the arrays have the n full parameters, the solve nfree
+// unknowns): the count the degrees of freedom are checked with.
 int nlh_fit_compose_h(nlh_handle *h, const char *what, size_t tm, int32_t nprob, int32_t m, int32_t n, const double *t, const double *y,
                       const double *w, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
                       const std::function<int(const double *, const double *, const double *, double *, double *, double *, double *,
-                                              double *, int32_t *)> &fit);
+                                              double *, int32_t *)> &fit, int32_t nfree = -1);
 // columns the built-in dense-quadratic family's kernels accept (x in LDS, lds_max of nlh_create): beyond it NLH_ARRAY_SIZE_ERROR
 static const int32_t NLH_DQ_MAX_N = 20000;
 

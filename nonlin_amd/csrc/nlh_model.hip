@@ -93,6 +93,9 @@ struct nlh_dq_model {
     // and the device copies of t, y, w (curve_base on curve_device, as the curve model's)
     nlh_expr_ctx *expr = nullptr;
     nlh_expr *expr_prog = nullptr;
+    // a mapped model (nlh_pmap_model_create): uctx is this wrapping context around another model's launchers; the model owns
+    // it and the device copy of the full parameters behind it (curve_base on curve_device)
+    nlh_pmap_ctx *pmap = nullptr;
 };
 
 int nlh_device_fcn_model_create(int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn, nlh_device_jacfcn jacfcn, void *ctx,
@@ -256,9 +259,45 @@ int nlh_expr_model_create(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32
     return 0;
 }
 
+// A model of the free unknowns of a parameter map over a launcher-backed inner model (nlh_pmap.hip: the wrapping launchers).
+int nlh_pmap_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_pmap *pm, const double *full, int32_t shared_full,
+                          nlh_dq_model **out)
+{
+    if (out) *out = nullptr;
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (!out || !inner || !pm || !full || !inner->ufcn) return NLH_INVALID_INPUT_ERROR;
+    int32_t N, n;
+    nlh_pmap_shape(pm, &N, &n, nullptr);
+    if (N != inner->n) return NLH_INVALID_INPUT_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t cnt = (shared_full ? 1 : (size_t)inner->nprob) * N;
+    double *base = nullptr;
+    if (hipMalloc(&base, sizeof(double) * cnt) != hipSuccess) {
+        h->err = "hipMalloc (mapped model)";
+        return NLH_OUT_OF_MEMORY_ERROR;
+    }
+    hipError_t e = hipMemcpyAsync(base, full, sizeof(double) * cnt, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        hipFree(base);
+        h->err = std::string("hipMemcpy (mapped model): ") + hipGetErrorString(e);
+        return NLH_ERR_HIP;
+    }
+    nlh_pmap_ctx *pc = nullptr;
+    const int rc = nlh_pmap_wrap(h, pm, inner->ufcn, inner->ujac, inner->uctx, base, shared_full, &pc);
+    if (rc) { hipFree(base); return rc; }
+    nlh_dq_model *md = new nlh_dq_model();
+    md->nprob = inner->nprob; md->m = inner->m; md->n = n; md->gamma = 0.0;
+    md->ufcn = nlh_pmap_device_fcn; md->ujac = inner->ujac ? nlh_pmap_device_jac : nullptr; md->uctx = pc;
+    md->pmap = pc; md->curve_base = base; md->curve_device = h->device;
+    *out = md;
+    return 0;
+}
+
 void nlh_dq_model_destroy(nlh_dq_model *md)
 {
     if (!md) return;
+    nlh_pmap_unwrap(md->pmap);
     delete md->expr;
     delete md->expr_prog;
     if (md->curve_base) { hipSetDevice(md->curve_device); hipFree(md->curve_base); }

@@ -18,6 +18,7 @@ IB_DTYPE = np.dtype([(k, np.int32) for k, _ in _lib.IterationBehavior._fields_])
 
 from ._lib import CURVE_GAUSS, CURVE_LORENTZ, CURVE_EXPDECAY, CURVE_KINDS, curve_kind, curve_nparams  # noqa: E402,F401
 from ._lib import Expr  # noqa: E402,F401
+from ._lib import ParamMap  # noqa: E402,F401
 
 
 def _chk(t, shape, name):
@@ -47,6 +48,24 @@ def qrx_plan(nprob, m, n, nact=0, have_stages=False):
     def rec(r):
         return {k: names[k][getattr(r, k)] if k in names else int(getattr(r, k)) for k, _ in r._fields_}
     return rec(head), [rec(steps[i]) for i in range(n)]
+
+
+class _PmapCtx:
+    """The context of a map's wrapping launchers (nlh_pmap_ctx), with everything it points at kept alive."""
+
+    def __init__(self, lib, ptr, keep):
+        self.lib, self.ptr, self._keep = lib, ptr, keep
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.lib.nlh_pmap_unwrap(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DeviceSolver:
@@ -239,16 +258,21 @@ class DeviceSolver:
         return y
 
     def curve_fit_batch(self, kind, t, y, x0, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
-                        covariance=True, opts=None):
+                        covariance=True, opts=None, pmap=None):
         """Fit + errors of y.shape[0] curves in one call (nlh_curve_fit_batch): least_squares_solver%solve -- or, with lower /
         upper ([n], one box for every problem), constrained_least_squares_solver%solve -- from x0 [nprob, n] (not modified),
         then the scaled parameter covariance at the solution.  Rows with weight 0 pad ragged data: they do not count as
         degrees of freedom.  Returns (x, fvec, sigma, cov, chi2, rank, ibs, status); sigma, cov, chi2, rank are None with
-        covariance=False, NaN / -1 for a problem whose status is not 0."""
+        covariance=False, NaN / -1 for a problem whose status is not 0.
+        pmap (a ParamMap over the model's n parameters): fixed and tied parameters (nlh_curve_fit_batch_pmap).  Every array
+        keeps its full size; a fixed parameter keeps the value x0 holds for its problem, tied positions of x0 are ignored,
+        bound entries at fixed and tied positions are not read, and sigma / cov are those of the full parameters."""
         k = curve_kind(kind)
         nprob, m, shared = self._curve_data(t, y, weights)
         n = curve_nparams(k, ncomp, baseline)
         _chk(x0, (nprob, n), "x0")
+        if pmap is not None and pmap.nfull != n:
+            raise ValueError(f"pmap maps {pmap.nfull} parameters, the model has {n}")
         dev = y.device
         x = x0.clone()
         fvec = torch.empty((nprob, m), dtype=torch.float64, device=dev)
@@ -267,14 +291,20 @@ class DeviceSolver:
         status = (C.c_int32 * nprob)()
         o = opts or self.options()
         ptr = lambda a: a.data_ptr() if a is not None else None
-        rc = self.lib.nlh_curve_fit_batch(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
-                                          y.data_ptr(), ptr(weights), int(bool(analytic)),
-                                          None if lo is None else lo.ctypes.data_as(_lib.c_double_p),
-                                          None if hi is None else hi.ctypes.data_as(_lib.c_double_p),
-                                          x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        self.h.check(rc, "nlh_curve_fit_batch")
+        plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
+        phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
+        if pmap is None:
+            rc = self.lib.nlh_curve_fit_batch(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
+                                              y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
+                                              x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
+        else:
+            rc = self.lib.nlh_curve_fit_batch_pmap(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
+                                                   y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr,
+                                                   x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
+        name = "nlh_curve_fit_batch" if pmap is None else "nlh_curve_fit_batch_pmap"
+        self.h.check(rc, name)
         if rc:
-            raise RuntimeError(f"nlh_curve_fit_batch returned {rc}")
+            raise RuntimeError(f"{name} returned {rc}")
         return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nprob)], [int(status[p]) for p in range(nprob)])
 
     # -- formula models ----------------------------------------------------------
@@ -329,12 +359,16 @@ class DeviceSolver:
             raise RuntimeError(f"nlh_expr_eval_batch returned {rc}")
         return y
 
-    def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None):
+    def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None,
+                       pmap=None):
         """Fit + errors of y.shape[0] data sets to a formula in one call (nlh_expr_fit_batch): curve_fit_batch with an Expr in
-        the place of (kind, ncomp, baseline).  Returns (x, fvec, sigma, cov, chi2, rank, ibs, status)."""
+        the place of (kind, ncomp, baseline), pmap (e.g. ParamMap.for_expr(expr, ...)) included.  Returns (x, fvec, sigma, cov,
+        chi2, rank, ibs, status)."""
         nprob, m, shared = self._expr_data(expr, t, y, weights)
         n = expr.nparams
         _chk(x0, (nprob, n), "x0")
+        if pmap is not None and pmap.nfull != n:
+            raise ValueError(f"pmap maps {pmap.nfull} parameters, the formula has {n}")
         dev = y.device
         x = x0.clone()
         fvec = torch.empty((nprob, m), dtype=torch.float64, device=dev)
@@ -353,17 +387,85 @@ class DeviceSolver:
         status = (C.c_int32 * nprob)()
         o = opts or self.options()
         ptr = lambda a: a.data_ptr() if a is not None else None
-        rc = self.lib.nlh_expr_fit_batch(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(), ptr(weights),
-                                         int(bool(analytic)),
-                                         None if lo is None else lo.ctypes.data_as(_lib.c_double_p),
-                                         None if hi is None else hi.ctypes.data_as(_lib.c_double_p),
-                                         x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        self.h.check(rc, "nlh_expr_fit_batch")
+        plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
+        phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
+        if pmap is None:
+            rc = self.lib.nlh_expr_fit_batch(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(), ptr(weights),
+                                             int(bool(analytic)), plo, phi,
+                                             x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
+        else:
+            rc = self.lib.nlh_expr_fit_batch_pmap(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(),
+                                                  ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr,
+                                                  x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
+        name = "nlh_expr_fit_batch" if pmap is None else "nlh_expr_fit_batch_pmap"
+        self.h.check(rc, name)
         if rc:
-            raise RuntimeError(f"nlh_expr_fit_batch returned {rc}")
+            raise RuntimeError(f"{name} returned {rc}")
         return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nprob)], [int(status[p]) for p in range(nprob)])
 
+    # -- parameter maps ------------------------------------------------------------
+    def pmap_launchers(self, pmap, fcn, jac, ctx, full):
+        """Fixed and tied parameters for any launcher pair: wraps (fcn, jac, ctx) -- of curve_launchers, expr_launchers,
+        dq_launchers or a user's own -- in the map's launchers (nlh_pmap_wrap) and returns (fcn, jac, ctx) for
+        lm_solve_batch_device, cls_solve_batch_device, lm_covariance_batch_device and fd_jacobian_device, which then work on
+        x [nprob, pmap.nfree].  full: the full parameters [nprob, pmap.nfull], or one shared [pmap.nfull] tensor; it is read at
+        fixed positions only.  jac is None without an inner Jacobian launcher (pass jac=None to the solver: forward
+        differences over the free unknowns).  Keep the returned ctx alive while solving; ctx.close() frees it (so does
+        garbage collection)."""
+        shared = full.dim() == 1
+        _chk(full, (pmap.nfull,) if shared else (full.shape[0], pmap.nfull), "full")
+        out = C.c_void_p()
+        rc = self.lib.nlh_pmap_wrap(self.h.ptr, pmap.ptr, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), full.data_ptr(),
+                                    int(shared), C.byref(out))
+        self.h.check(rc, "nlh_pmap_wrap")
+        if rc:
+            raise RuntimeError(f"nlh_pmap_wrap returned {rc}")
+        wrapped = _PmapCtx(self.lib, out, (pmap, fcn, jac, ctx, full))
+        return (C.cast(self.lib.nlh_pmap_device_fcn, _lib.DEVFCN),
+                C.cast(self.lib.nlh_pmap_device_jac, _lib.DEVFCN) if jac is not None else None, wrapped)
+
+    def pmap_gather(self, pmap, full):
+        """The free unknowns x [nprob, nfree] of full parameters [nprob, nfull] (nlh_pmap_gather_batch)."""
+        nprob = full.shape[0]
+        _chk(full, (nprob, pmap.nfull), "full")
+        x = torch.empty((nprob, pmap.nfree), dtype=torch.float64, device=full.device)
+        rc = self.lib.nlh_pmap_gather_batch(self.h.ptr, pmap.ptr, nprob, full.data_ptr(), x.data_ptr())
+        self.h.check(rc, "nlh_pmap_gather_batch")
+        if rc:
+            raise RuntimeError(f"nlh_pmap_gather_batch returned {rc}")
+        return x
+
+    def pmap_expand(self, pmap, x, full):
+        """The full parameters [nprob, nfull] of the free unknowns x [nprob, nfree]: fixed values from full ([nprob, nfull] or
+        one shared [nfull] tensor), ties evaluated (nlh_pmap_expand_batch)."""
+        nprob = x.shape[0]
+        _chk(x, (nprob, pmap.nfree), "x")
+        shared = full.dim() == 1
+        _chk(full, (pmap.nfull,) if shared else (nprob, pmap.nfull), "full")
+        p = torch.empty((nprob, pmap.nfull), dtype=torch.float64, device=x.device)
+        rc = self.lib.nlh_pmap_expand_batch(self.h.ptr, pmap.ptr, nprob, x.data_ptr(), full.data_ptr(), int(shared), p.data_ptr())
+        self.h.check(rc, "nlh_pmap_expand_batch")
+        if rc:
+            raise RuntimeError(f"nlh_pmap_expand_batch returned {rc}")
+        return p
+
+    def pmap_cov(self, pmap, cov, sigma, fail=None):
+        """Covariance [nprob, nfull, nfull] and standard errors [nprob, nfull] of the full parameters from those of the free
+        unknowns (nlh_pmap_cov_batch); fail: int32 [nprob], non-zero for a problem that did not solve (NaN everywhere)."""
+        nprob = cov.shape[0]
+        _chk(cov, (nprob, pmap.nfree, pmap.nfree), "cov"); _chk(sigma, (nprob, pmap.nfree), "sigma")
+        cf = torch.empty((nprob, pmap.nfull, pmap.nfull), dtype=torch.float64, device=cov.device)
+        sf = torch.empty((nprob, pmap.nfull), dtype=torch.float64, device=cov.device)
+        rc = self.lib.nlh_pmap_cov_batch(self.h.ptr, pmap.ptr, nprob, cov.data_ptr(), sigma.data_ptr(),
+                                         fail.data_ptr() if fail is not None else None, cf.data_ptr(), sf.data_ptr())
+        self.h.check(rc, "nlh_pmap_cov_batch")
+        if rc:
+            raise RuntimeError(f"nlh_pmap_cov_batch returned {rc}")
+        return cf, sf
+
     def _ctxp(self, ctx):
+        if isinstance(ctx, _PmapCtx):
+            return ctx.ptr
         return ctx if isinstance(ctx, (int, C.c_void_p)) or ctx is None else C.cast(C.byref(ctx), C.c_void_p)
 
     def lm_solve_batch_device(self, fcn, ctx, m, x, jac=None, opts=None):

@@ -26,6 +26,8 @@ module nonlin_hip_c
     integer(c_int32_t), parameter :: NLH_FACTOR_AUTO = 0, NLH_FACTOR_QR = 1, NLH_FACTOR_EXACT = 2
     ! kinds of the built-in curve models (include/nonlin_hip.h: NLH_CURVE_*)
     integer(c_int32_t), parameter :: NLH_CURVE_GAUSS = 0, NLH_CURVE_LORENTZ = 1, NLH_CURVE_EXPDECAY = 2
+    ! kinds of a parameter of a map (include/nonlin_hip.h: NLH_PMAP_*)
+    integer(c_int32_t), parameter :: NLH_PMAP_FREE = 0, NLH_PMAP_FIXED = 1, NLH_PMAP_TIED = 2
 
     interface
         subroutine nlh_default_options(opts) bind(C, name="nlh_default_options")
@@ -193,6 +195,33 @@ module nonlin_hip_c
             integer(c_int32_t), value :: nprob, m, shared_t, analytic
             real(c_double), intent(in) :: t(*), y(*)
             type(c_ptr), value :: w
+            type(c_ptr), intent(out) :: model
+            integer(c_int) :: rc
+        end function
+        ! parameter maps (include/nonlin_hip.h: nlh_pmap_*): the map object (host code), and a model of its free unknowns
+        ! over a launcher-backed model (src is 0-based here)
+        function nlh_pmap_create(nfull, kind, src, scale, offset, pm) bind(C, name="nlh_pmap_create") result(rc)
+            import :: c_ptr, c_int, c_int32_t, c_double
+            integer(c_int32_t), value :: nfull
+            integer(c_int32_t), intent(in) :: kind(*), src(*)
+            real(c_double), intent(in) :: scale(*), offset(*)
+            type(c_ptr), intent(out) :: pm
+            integer(c_int) :: rc
+        end function
+        subroutine nlh_pmap_destroy(pm) bind(C, name="nlh_pmap_destroy")
+            import :: c_ptr
+            type(c_ptr), value :: pm
+        end subroutine
+        subroutine nlh_pmap_shape(pm, nfull, nfree, ntied) bind(C, name="nlh_pmap_shape")
+            import :: c_ptr, c_int32_t
+            type(c_ptr), value :: pm
+            integer(c_int32_t), intent(out) :: nfull, nfree, ntied
+        end subroutine
+        function nlh_pmap_model_create(h, inner, pm, full, shared_full, model) bind(C, name="nlh_pmap_model_create") result(rc)
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h, inner, pm
+            real(c_double), intent(in) :: full(*)
+            integer(c_int32_t), value :: shared_full
             type(c_ptr), intent(out) :: model
             integer(c_int) :: rc
         end function

@@ -19,6 +19,7 @@ module nonlin_multi_eqn_mult_var
     public :: device_model_batch
     public :: NLH_MODEL_DENSE_QUADRATIC
     public :: NLH_CURVE_GAUSS, NLH_CURVE_LORENTZ, NLH_CURVE_EXPDECAY   ! kinds of device_model_batch%create_curve (from nonlin_hip_c)
+    public :: NLH_PMAP_FREE, NLH_PMAP_FIXED, NLH_PMAP_TIED             ! kinds of a parameter, device_model_batch%create_mapped
     public :: NLH_FACTOR_AUTO, NLH_FACTOR_QR, NLH_FACTOR_EXACT     ! values of equation_solver%factor_policy (from nonlin_hip_c)
     public :: nlh_use_devices
     public :: nlh_vecfcn_trampoline
@@ -58,6 +59,7 @@ module nonlin_multi_eqn_mult_var
         procedure, public :: create_from_device_fcn => dmb_create_fcn
         procedure, public :: create_curve => dmb_create_curve
         procedure, public :: create_expr => dmb_create_expr
+        procedure, public :: create_mapped => dmb_create_mapped
         procedure, public :: destroy => dmb_destroy
         procedure, public :: is_defined => dmb_defined
         procedure, public :: get_problem_count => dmb_nprob
@@ -406,6 +408,49 @@ contains
         this%nvar_ = n
         this%nprob_ = size(y, 2)
         this%analytic_ = use_jac /= 0
+    end subroutine
+
+    !> Fixed and tied parameters for a launcher-backed model (create_curve, create_expr, create_from_device_fcn): a model of
+    !> the FREE unknowns of a parameter map over inner, which must outlive it.  kind(N): NLH_PMAP_FREE, NLH_PMAP_FIXED or
+    !> NLH_PMAP_TIED per full parameter of inner; a tied parameter k is p(k) = scale(k) * p(src(k)) + offset(k), src 1-based
+    !> (src, scale, offset are read at tied positions only); full(N, nprob) -- or full(N, 1): the same for every problem --
+    !> holds the values of the fixed parameters.  The free unknowns are numbered in ascending full index
+    !> (get_variable_count() of them); solve_batch, covariance_batch and evaluate take x(nfree, nprob).  A map the library
+    !> refuses (INTEGRATION.md 6i) stops the program with NL_INVALID_INPUT_ERROR.
+    subroutine dmb_create_mapped(this, inner, kind, src, scale, offset, full)
+        class(device_model_batch), intent(inout) :: this
+        class(device_model_batch), intent(in) :: inner
+        integer(int32), intent(in), dimension(:) :: kind, src
+        real(real64), intent(in), dimension(:) :: scale, offset
+        real(real64), intent(in), dimension(:,:) :: full
+        integer(c_int) :: rc
+        integer(c_int32_t) :: nfull, nfree, ntied, shared
+        integer(c_int32_t), allocatable :: kc(:), sc(:)
+        real(c_double), allocatable :: fc(:,:), scl(:), off(:)
+        type(c_ptr) :: pm
+        if (.not.inner%is_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR
+        nfull = inner%nvar_
+        if (size(kind) /= nfull .or. size(src) /= nfull .or. size(scale) /= nfull .or. size(offset) /= nfull) &
+            error stop NL_ARRAY_SIZE_ERROR
+        if (size(full, 1) /= nfull .or. (size(full, 2) /= inner%nprob_ .and. size(full, 2) /= 1)) error stop NL_ARRAY_SIZE_ERROR
+        shared = 0
+        if (size(full, 2) == 1 .and. inner%nprob_ /= 1) shared = 1
+        kc = kind
+        sc = src - 1
+        scl = scale
+        off = offset
+        fc = full
+        rc = nlh_pmap_create(nfull, kc, sc, scl, off, pm)
+        if (rc /= 0) error stop NL_INVALID_INPUT_ERROR
+        call nlh_pmap_shape(pm, nfull, nfree, ntied)
+        call this%destroy()
+        rc = nlh_pmap_model_create(nlh_default_handle(), inner%model_, pm, fc, shared, this%model_)
+        call nlh_pmap_destroy(pm)                            ! (the model keeps its own copies of the tables)
+        if (rc /= 0) error stop rc
+        this%neqn_ = inner%neqn_
+        this%nvar_ = nfree
+        this%nprob_ = inner%nprob_
+        this%analytic_ = inner%analytic_
     end subroutine
 
     subroutine dmb_destroy(this)
