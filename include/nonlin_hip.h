@@ -561,6 +561,16 @@ int nlh_solve_upper(nlh_handle *h, int32_t nprob, int32_t n, const double *dRt, 
  * src/nonlin_optimize.f90:721-722): R1^T R1 = R^T R +- u u^T in place on the ROW-major upper factor dRt;
  * du is consumed; *hinfo = 1 if the downdate would lose positive definiteness. */
 int nlh_chol_rank1(nlh_handle *h, int32_t n, int32_t downdate, double *dRt, double *du, int32_t *hinfo);
+/* cholesky_factor(b, .true.) and solve_cholesky(.true., r, x) stand-ins (call sites src/nonlin_optimize.f90:724, 727),
+ * through the launches of bfgs%solve.  dB [nprob][n][n] symmetric; dRt [nprob][n][n] the ROW-major upper factors, zeros
+ * below the diagonal; hinfo [nprob] (host): 0, or the 1-based row of a non-positive pivot (the rows above it are
+ * factored, the others hold B).  dx [nprob][n] in place.  nlh_bf_chol_form(n): the form the factorisation takes --
+ * G = 4, 2, 1: the blocked kernel with G thread groups per column (while its LDS fits: n <= 608); -4, -8: the column
+ * form with that many columns per thread; 0 for an n no form exists for.  It asks the runtime for the kernel's static
+ * LDS: call it on a thread whose device is set (any handle created), or it reports the column form. */
+int nlh_bf_chol_factor(nlh_handle *h, int32_t nprob, int32_t n, const double *dB, double *dRt, int32_t *hinfo);
+int nlh_bf_solve_cholesky(nlh_handle *h, int32_t nprob, int32_t n, const double *dRt, double *dx);
+int32_t nlh_bf_chol_form(int32_t n);
 
 /* polynomial%fit / polynomial%fit_thru_zero (src/nonlin_polynomials.f90:146-238): least-squares polynomial of
  * the given order through npts points; coef = c0 .. c_order (c0 = 0 for thru_zero).  Returns 4 where the

@@ -130,6 +130,9 @@ SYMBOLS = {
     "nlh_qr_rank1_update": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_solve_upper": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "nlh_chol_rank1": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, c_int32_p]),
+    "nlh_bf_chol_factor": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, c_int32_p]),
+    "nlh_bf_solve_cholesky": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_bf_chol_form": (C.c_int32, [C.c_int32]),
     "nlh_poly_fit": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p]),
     "nlh_poly_fit_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_poly_roots": (C.c_int, [_H, C.c_int32, c_double_p, c_double_p, C.POINTER(C.c_int32)]),

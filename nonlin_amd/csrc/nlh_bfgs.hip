@@ -7,13 +7,29 @@
 #include "nlh_kernels_bfgs.h"
 #include "nlh_kernels_bfgs_batch.h"
 
-// The blocked Cholesky of the Hessian approximation: as many thread groups per column as 1024 threads allow.
-static void launch_bf_chol_blocked(hipStream_t s, int nprob, int n, const double *dB, double *dR, int *dinfo, const LmState *st, int want)
+// R = chol(B) (:724): the one place that chooses a form.  The blocked kernel, with as many thread groups per column as
+// 1024 threads allow, wherever its LDS fits (lds_fits: n <= 608); beyond, the column form, which has the same bits by
+// construction (k_bf_chol_factor<4> with 1024 threads serves any n <= 4096).  G > 0: blocked with G groups; -NC: the
+// column form with NC columns per thread.
+static int bf_chol_form(int n)
 {
     const int CT = ((n + 63) / 64) * 64;
-    if (CT * 4 <= 1024) hipLaunchKernelGGL(k_bf_chol_blocked<4>, dim3(nprob), dim3(CT * 4), bf_chol_lds(n), s, n, dB, dR, dinfo, st, want);
-    else if (CT * 2 <= 1024) hipLaunchKernelGGL(k_bf_chol_blocked<2>, dim3(nprob), dim3(CT * 2), bf_chol_lds(n), s, n, dB, dR, dinfo, st, want);
-    else hipLaunchKernelGGL(k_bf_chol_blocked<1>, dim3(nprob), dim3(CT), bf_chol_lds(n), s, n, dB, dR, dinfo, st, want);
+    const int G = CT * 4 <= 1024 ? 4 : CT * 2 <= 1024 ? 2 : 1;
+    const void *blocked = G == 4 ? (const void *)k_bf_chol_blocked<4> : G == 2 ? (const void *)k_bf_chol_blocked<2> : (const void *)k_bf_chol_blocked<1>;
+    if (n <= 1024 && lds_fits(blocked, bf_chol_lds(n))) return G;
+    return qn_nc8(n) ? -8 : -4;
+}
+
+static void launch_bf_chol(hipStream_t s, int nprob, int n, const double *dB, double *dR, int *dinfo, const LmState *st, int want)
+{
+    const int CT = ((n + 63) / 64) * 64;
+    switch (bf_chol_form(n)) {
+    case 4: hipLaunchKernelGGL(k_bf_chol_blocked<4>, dim3(nprob), dim3(CT * 4), bf_chol_lds(n), s, n, dB, dR, dinfo, st, want); break;
+    case 2: hipLaunchKernelGGL(k_bf_chol_blocked<2>, dim3(nprob), dim3(CT * 2), bf_chol_lds(n), s, n, dB, dR, dinfo, st, want); break;
+    case 1: hipLaunchKernelGGL(k_bf_chol_blocked<1>, dim3(nprob), dim3(CT), bf_chol_lds(n), s, n, dB, dR, dinfo, st, want); break;
+    case -8: hipLaunchKernelGGL(k_bf_chol_factor<8>, dim3(nprob), dim3(1024), sizeof(double) * n, s, n, dB, dR, dinfo, st, want); break;
+    default: hipLaunchKernelGGL(k_bf_chol_factor<4>, dim3(nprob), dim3(1024), sizeof(double) * n, s, n, dB, dR, dinfo, st, want); break;
+    }
 }
 
 void nlh_bfgs_init_device(int lds_max)
@@ -177,9 +193,8 @@ static int bfgs_core(nlh_handle *h, const nlh_options *o, int n, BfgsEval &ev, d
                 hipLaunchKernelGGL(k_bf_downdate_rot, dim3(1), dim3(64), 0, s, n, du, dc, dinfo, (const LmState *)nullptr, -1);
                 hipLaunchKernelGGL(k_bf_downdate_apply, dim3((n + 255) / 256), dim3(256), sizeof(double) * 2 * n, s, n, dR, dc, du, dinfo, (const LmState *)nullptr, -1);
             } else {
-                if (n <= 1024) launch_bf_chol_blocked(s, 1, n, dB, dR, dinfo, nullptr, -1);
-                else if (qn_nc8(n)) hipLaunchKernelGGL(k_bf_chol_factor<8>, dim3(1), dim3(1024), sizeof(double) * n, s, n, dB, dR, dinfo, (const LmState *)nullptr, -1);
-                else hipLaunchKernelGGL(k_bf_chol_factor<4>, dim3(1), dim3(1024), sizeof(double) * n, s, n, dB, dR, dinfo, (const LmState *)nullptr, -1);
+                launch_bf_chol(s, 1, n, dB, dR, dinfo, nullptr, -1);
+                HIPCHK(h, hipGetLastError());                   // a refused launch would leave the old factor in place
             }
             // dx = -(R^T R)^-1 g (:727)
             for (int i = 0; i < n; ++i) u[i] = -g[i];
@@ -346,9 +361,7 @@ static int bfgs_lockstep(nlh_handle *h, const nlh_options *o, int32_t nprob, int
                                (const double *)dv, (const int *)dinfo, cst, (int)BF_UPD_RANK);
             hipLaunchKernelGGL(k_nt_advance, dim3(pb), dim3(256), 0, s, nprob, st, (int)BF_UPD_RANK, (int)BF_DIR);
             // :724: R = chol(B)
-            if (n <= 1024) launch_bf_chol_blocked(s, nprob, n, (const double *)dB, dR, dinfo, cst, (int)BF_UPD_FACTOR);
-            else if (qn_nc8(n)) hipLaunchKernelGGL(k_bf_chol_factor<8>, dim3(nprob), dim3(1024), sizeof(double) * n, s, n, (const double *)dB, dR, dinfo, cst, (int)BF_UPD_FACTOR);
-                else hipLaunchKernelGGL(k_bf_chol_factor<4>, dim3(nprob), dim3(1024), sizeof(double) * n, s, n, (const double *)dB, dR, dinfo, cst, (int)BF_UPD_FACTOR);
+            launch_bf_chol(s, nprob, n, (const double *)dB, dR, dinfo, cst, (int)BF_UPD_FACTOR);
             hipLaunchKernelGGL(k_nt_advance, dim3(pb), dim3(256), 0, s, nprob, st, (int)BF_UPD_FACTOR, (int)BF_DIR);
             // :727: dx = -(R^T R)^-1 g
             hipLaunchKernelGGL(k_bfl_neg, dim3((n + 255) / 256, nprob), dim3(256), 0, s, n, (const double *)dg, dw, cst);
@@ -531,6 +544,49 @@ int nlh_chol_rank1(nlh_handle *h, int32_t n, int32_t downdate, double *dRt, doub
     }
     HIPCHK(h, hipStreamSynchronize(s));
     if (hinfo) *hinfo = info;
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// cholesky_factor(b, .true.) stand-in (call site src/nonlin_optimize.f90:724) through launch_bf_chol, the dispatch of the
+// solver, every problem taking part: dB [nprob][n][n] symmetric, dRt the row-major upper factors, hinfo [nprob] (host).
+int nlh_bf_chol_factor(nlh_handle *h, int32_t nprob, int32_t n, const double *dB, double *dRt, int32_t *hinfo)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (nprob < 1 || n < 1 || !dB || !dRt || !hinfo) return NLH_INVALID_INPUT_ERROR;
+    if (n > QN_MAX_N || nprob > NLH_MAX_LOCKSTEP) return NLH_ARRAY_SIZE_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = ensure(h, h->bfV, sizeof(int32_t) * (size_t)nprob))) return rc;
+    int *dinfo = (int *)h->bfV.p;
+    hipStream_t s = h->stream;
+    launch_bf_chol(s, nprob, n, dB, dRt, dinfo, nullptr, -1);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hinfo, dinfo, sizeof(int32_t) * (size_t)nprob, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// The form launch_bf_chol takes for n (0: no form, n out of range).
+int32_t nlh_bf_chol_form(int32_t n)
+{
+    if (n < 1 || n > QN_MAX_N) return 0;
+    return bf_chol_form(n);
+}
+
+// solve_cholesky(.true., r, x) stand-in (call site :727): x <- R^-T x, then x <- R^-1 x, the solver's two launches.
+int nlh_bf_solve_cholesky(nlh_handle *h, int32_t nprob, int32_t n, const double *dRt, double *dx)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (nprob < 1 || n < 1 || !dRt || !dx) return NLH_INVALID_INPUT_ERROR;
+    if (n > QN_MAX_N || nprob > NLH_MAX_LOCKSTEP) return NLH_ARRAY_SIZE_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const int bs1 = std::min(1024, ((n + 63) / 64) * 64);
+    hipLaunchKernelGGL(k_bf_solve_upper_t, dim3(nprob), dim3(bs1), sizeof(double) * n, s, n, dRt, dx, (const LmState *)nullptr, -1);
+    hipLaunchKernelGGL(k_qn_solve_upper, dim3(nprob), dim3(bs1), sizeof(double) * n, s, n, dRt, dx, (size_t)n * n, (size_t)n, (const LmState *)nullptr, -1);
+    HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
     return 0;
 }

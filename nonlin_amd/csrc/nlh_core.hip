@@ -31,7 +31,8 @@ bool lds_fits(const void *kernel, size_t dyn)
         if (it != statics.end()) st = it->second;
         else {
             hipFuncAttributes a;
-            st = hipFuncGetAttributes(&a, kernel) == hipSuccess ? a.sharedSizeBytes : (size_t)NLH_LDS_MAX;   // (unknown: no launch)
+            if (hipFuncGetAttributes(&a, kernel) != hipSuccess) return false;   // (unknown: no launch; asked again next time)
+            st = a.sharedSizeBytes;
             statics.emplace_back(kernel, st);
         }
     }

@@ -208,7 +208,9 @@ k_bf_chol_factor(int n, const double *__restrict__ B, double *__restrict__ Rt, i
 // columns finishes the BFC_W x BFC_W diagonal block with v_readlane broadcasts (no barrier either), and everybody else
 // solves its BFC_W rows against that block from LDS.  Every element still receives a(j,c) - sum_k r(k,j) r(k,c) with k
 // ascending, a separate multiply and subtract per term, then the division by r(j,j): the bits of the loop above.
-// A non-positive pivot stops at the same row with the same rows written.  Dynamic LDS: bf_chol_lds(n).
+// A non-positive pivot stops at the same row with the same rows written.  Dynamic LDS: bf_chol_lds(n), and no static LDS.
+// bf_chol_lds(608) = 161,792 bytes = NLH_LDS_MAX: n = 608 is the largest size this form can be launched for (609: 161,920
+// bytes; from 624 more than the 160 KB a workgroup can have).  launch_bf_chol asks lds_fits and takes the column form beyond.
 #define BFC_W 16
 static inline size_t bf_chol_lds(int n) { return sizeof(double) * ((size_t)n * BFC_W + BFC_W * BFC_W + (size_t)(((n + 63) / 64) * 64) * BFC_W); }
 
@@ -225,7 +227,10 @@ k_bf_chol_blocked(int n, const double *__restrict__ B, double *__restrict__ Rt, 
     double *pre = bfc_sm;                            // pre[k * W + jj] = r(k, jb + jj), k < jb
     double *P = bfc_sm + (size_t)n * W;              // P[kk * W + jj] = r(jb + kk, jb + jj)
     double *colbuf = P + W * W;                      // colbuf[c * W + jj]: the panel rows of column c after the prefix phase
-    __shared__ int bad;
+    // the bad-pivot flag: rows k < jb <= n - 1 of pre are all that is ever filled or read, so row n - 1 is free -- a static
+    // __shared__ int would put n = 608, whose dynamic LDS is NLH_LDS_MAX to the byte, out of reach.  n = 608 DEPENDS on
+    // this alias: a change to the prefix phase that touches row n - 1 of pre must give the flag another home.
+    int &bad = *(int *)(pre + (size_t)(n - 1) * W);
     const int tid = threadIdx.x, BS = blockDim.x, p = blockIdx.x, CT = BS / G, c = tid % CT, g = tid / CT, lane = tid & 63;
     if (gst && gst[p].stage != gwant) return;                    // lock-step batches: only problems in this stage
     B += (size_t)p * n * n; Rt += (size_t)p * n * n; info += p;
@@ -251,6 +256,7 @@ k_bf_chol_blocked(int n, const double *__restrict__ B, double *__restrict__ Rt, 
 #pragma unroll
         for (int q = 0; q < RW; ++q) { const int jj = g * RW + q; part[q] = B[(size_t)cc_ * n + jb + (jj < w ? jj : w - 1)]; }
         __syncthreads();                            // the rows of the earlier panels are in memory
+        // rows 0 .. jb - 1 of pre, jb <= n - 1: row n - 1 is RESERVED for the bad-pivot flag (above) -- never fill or read it
         for (int e0 = tid; e0 < jb * W; e0 += 4 * BS) {
             double v[4];
 #pragma unroll

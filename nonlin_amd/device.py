@@ -830,6 +830,34 @@ class DeviceSolver:
                      "nlh_chol_rank1")
         return int(info.value)
 
+    def bf_chol_factor(self, B):
+        """R = chol(B) as bfgs%solve forms it: B [nprob, n, n] symmetric.  Returns (Rt [nprob, n, n] row-major upper
+        factors, info list: 0 or the 1-based row of a non-positive pivot)."""
+        nprob, n, _ = B.shape
+        _chk(B, (nprob, n, n), "B")
+        Rt = torch.empty_like(B)
+        info = (C.c_int32 * nprob)()
+        rc = self.lib.nlh_bf_chol_factor(self.h.ptr, nprob, n, B.data_ptr(), Rt.data_ptr(), info)
+        self.h.check(rc, "nlh_bf_chol_factor")
+        if rc:
+            raise RuntimeError(f"nlh_bf_chol_factor returned {rc}")
+        return Rt, [int(v) for v in info]
+
+    def bf_chol_form(self, n):
+        """The form bf_chol_factor takes for n: 4, 2, 1 blocked with that many thread groups per column; -4, -8 the column
+        form with that many columns per thread."""
+        return int(self.lib.nlh_bf_chol_form(int(n)))
+
+    def bf_solve_cholesky(self, Rt, x):
+        """x <- (R^T R)^-1 x in place, Rt [nprob, n, n] row-major upper factors, x [nprob, n]."""
+        nprob, n, _ = Rt.shape
+        _chk(Rt, (nprob, n, n), "Rt"); _chk(x, (nprob, n), "x")
+        rc = self.lib.nlh_bf_solve_cholesky(self.h.ptr, nprob, n, Rt.data_ptr(), x.data_ptr())
+        self.h.check(rc, "nlh_bf_solve_cholesky")
+        if rc:
+            raise RuntimeError(f"nlh_bf_solve_cholesky returned {rc}")
+        return x
+
     def lu_solve(self, LU, ipvt, b):
         nprob, n, _ = LU.shape
         self.h.check(self.lib.nlh_lu_solve(self.h.ptr, nprob, n, LU.data_ptr(), ipvt.data_ptr(), b.data_ptr()),

@@ -1667,6 +1667,12 @@ static int nlo_line_search_scalar(const nlo_options *opt, nlo_fcnnvar fcn, void 
     return flag ? NLO_CONVERGENCE_ERROR : 0;
 }
 
+/* How often nlo_bfgs_solve has refactorised (:724) in an iteration after its first since the last reset: the branch
+ * y . dx <= 1e-10 (steps that have become tiny, or negative curvature), the only place where a DENSE B is factored.
+ * Tests use it to show that an input takes it. */
+static long g_bfgs_refactors = 0;
+long nlo_bfgs_refactor_count(int reset) { long v = g_bfgs_refactors; if (reset) g_bfgs_refactors = 0; return v; }
+
 /* bfgs_solve, src/nonlin_optimize.f90:557-770.  opt->max_evals = get_max_fcn_evals() (500), opt->gtol =
  * get_tolerance() (1e-12), opt->xtol = get_var_tolerance() (1e-12); ib->gradient_count is filled. */
 int nlo_bfgs_solve(const nlo_options *opt, nlo_fcnnvar fcn, nlo_gradfcn grad_or_null, void *ctx, int32_t n,
@@ -1745,6 +1751,7 @@ int nlo_bfgs_solve(const nlo_options *opt, nlo_fcnnvar fcn, nlo_gradfcn grad_or_
                 nlo_chol_update(n, r, u);
                 if (nlo_chol_downdate(n, r, v)) { rc = NLO_INVALID_OPERATION_ERROR; break; }   /* linalg raises LA_MATRIX_FORMAT_ERROR */
             } else {
+                if (iter > 1) g_bfgs_refactors += 1;
                 if (nlo_chol_factor_upper(n, b, r)) { rc = NLO_INVALID_OPERATION_ERROR; break; }
             }
             for (int32_t i = 0; i < n; ++i) dx[i] = -g[i];   /* :727 dx = solve_cholesky(.true., r, -g) */

@@ -187,6 +187,7 @@ void nlo_chol_update(int32_t n, double *r, double *u);
 int nlo_chol_downdate(int32_t n, double *r, double *u);
 int nlo_chol_factor_upper(int32_t n, const double *b, double *r);
 void nlo_solve_cholesky_upper(int32_t n, const double *r, double *x);
+long nlo_bfgs_refactor_count(int reset);   /* refactorisations (:724) after the first iteration since the last reset */
 int nlo_bfgs_solve(const nlo_options *opt, nlo_fcnnvar fcn, nlo_gradfcn grad_or_null, void *ctx, int32_t n,
                    double *x, double *fout, nlo_iteration_behavior *ib);
 

@@ -108,6 +108,8 @@ def lib():
         L.nlo_qr_factor_rhs.argtypes = [C.c_int32, C.c_int32, dp, dp]
         L.nlo_bfgs_solve.argtypes = [C.POINTER(Options), FCNNVAR, GRADFCN, C.c_void_p, C.c_int32, dp, dp,
                                      C.POINTER(IterationBehavior)]
+        L.nlo_bfgs_refactor_count.argtypes = [C.c_int]
+        L.nlo_bfgs_refactor_count.restype = C.c_long
         L.nlo_dq_bfgs_solve.argtypes = [C.POINTER(Options), C.POINTER(DqProblem), dp, dp, C.POINTER(IterationBehavior)]
         L.nlo_fd_gradient.argtypes = [FCNNVAR, GRADFCN, C.c_void_p, C.c_int32, dp, dp, dp]
         L.nlo_rtr.argtypes = [C.c_int32, dp, dp]
@@ -276,6 +278,11 @@ def bfgs_solve(fcn, n, x0, grad=None, opts=None):
     cf, cg = _wrap_scalar(fcn), _wrap_grad(grad)
     rc = lib().nlo_bfgs_solve(C.byref(o), cf, cg, None, n, _dp(x), C.cast(C.byref(fout), C.POINTER(C.c_double)), C.byref(ib))
     return rc, x, fout.value, ib.as_dict()
+
+
+def bfgs_refactor_count(reset=False):
+    """How often bfgs has refactorised R = chol(B) (:724) in an iteration after its first since the last reset."""
+    return int(lib().nlo_bfgs_refactor_count(int(bool(reset))))
 
 
 def fd_gradient(fcn, x, fv=None):
