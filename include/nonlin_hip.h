@@ -952,6 +952,104 @@ int nlh_expr_fit_batch_pmap_h(nlh_handle *h, const nlh_options *opts, const nlh_
 int nlh_pmap_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_pmap *pm, const double *full, int32_t shared_full,
                           nlh_dq_model **model);
 
+/* ---- robust losses (no counterpart in nonlin v2.2.0): Huber, soft-L1 and Cauchy fits for ANY device model.  A measured
+ * spectrum with a cosmic-ray spike or a dead bin pulls a plain least-squares fit; a robust loss rho bounds what one residual
+ * can contribute.  Like a parameter map, a loss is a pair of wrapping launchers around any inner launcher pair (built-in
+ * curve, formula, a user's own, a map's), so everything that takes launchers works through it unchanged:
+ * nlh_lm_solve_batch_device, nlh_cls_solve_batch_device, nlh_lm_covariance_batch_device, nlh_fd_jacobian_device, the model
+ * objects and the maps.  The wrapped residual is  rho~(r) = c*sign(r)*sqrt(rho((r/c)^2)),  so ||rho~||^2 = c^2 * sum rho and
+ * the unchanged solver minimises the robust cost itself; a forward-difference Jacobian of the wrapped function is the right
+ * Jacobian.  c > 0 is the scale: residuals well inside it are treated as least squares treats them.
+ * THE ARITHMETIC IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation.  r the inner residual,
+ * u = r / c, a = fabs(u):
+ *   kind                               out                                                      g (row factor of J)      wgt = rho'
+ *   NLH_LOSS_LINEAR                    r                                                        1.0                      1.0
+ *   NLH_LOSS_HUBER    a <= 1.0         r (bit for bit)                                          1.0                      1.0
+ *                     else (NaN too)   v = 2.0*a; v = v - 1.0; s = sqrt(v); c*copysign(s, u)    1.0/s                    1.0/a
+ *   NLH_LOSS_SOFT_L1                   z = u*u; s = sqrt(1.0 + z); k = sqrt(2.0/(s + 1.0));
+ *                                      c*(u*k)                                                  1.0/(s*k)                1.0/s
+ *   NLH_LOSS_CAUCHY   z = u*u == 0.0   r                                                        1.0                      1.0
+ *                     else             l = log1p(z); s = sqrt(l); c*copysign(s, u)              q = 1.0 + z; wgt = 1.0/q;
+ *                                                                                               g = (wgt*a)/s            wgt
+ * The Jacobian rule is J'[i][j] = g_i * J[i][j], one multiply per entry, g_i from the inner residual at the same point.  No
+ * sum crosses a row: a row's bits do not depend on the launch, the batch or the workgroup form.  Huber and soft-L1 use only
+ * + - * / sqrt and are reproducible bit for bit; Cauchy carries the device library's log1p.  A row with r = +-0 stays +-0
+ * under every kind, so zero-weight padding keeps working.  Documented domain: |r| < 1e150 * c.
+ * The scale is per problem, dscale [nprob] on the DEVICE -- point q reads dscale[dprob[q]] (a NULL dprob means q itself) --,
+ * or one value with shared_scale != 0.  On device arrays a scale that is not finite or not positive makes every residual,
+ * g and wgt of that problem NaN (every kind but LINEAR, which reads no scale: dscale may then be NULL); entry points that
+ * take HOST scales refuse one with NLH_INVALID_INPUT_ERROR. ---- */
+#define NLH_LOSS_LINEAR  0
+#define NLH_LOSS_HUBER   1
+#define NLH_LOSS_SOFT_L1 2
+#define NLH_LOSS_CAUCHY  3
+/* The wrapping launchers.  nlh_loss_wrap makes their context on the handle's device; the inner pair (fcn, jac -- NULL: none
+ * --, inner_ctx) and dscale stay the caller's and must outlive the context.
+ *   nlh_loss_device_fcn  the inner fcn straight into the caller's dF; then the table's out, in place.  Needs no scratch
+ *                        beyond a problem list when dprob is NULL.
+ *   nlh_loss_device_jac  the inner fcn into scratch R [npoints][m]; the inner jac straight into the caller's dJ; then
+ *                        every row of dJ times its g, in place.  With a NULL inner jac it returns an error: pass a NULL
+ *                        jacfcn to the solver instead (forward differences of the wrapped residual).
+ * Both enqueue only on the stream handed in, never synchronise and may be called from several host threads on different
+ * streams.  A malformed context, n < 1 or m < 1 returns non-zero before any launch.  An inner error comes back as it is,
+ * with no further launch.  NLH_LOSS_LINEAR launches no kernel of the table and calls no inner fcn for a Jacobian: the inner
+ * pair's output is the caller's as it is.  Every kind, LINEAR included, hands the inner launcher a problem list of its own when
+ * dprob is NULL (the built-in launchers want one), so a wrapped pair takes the same calls whatever its kind.
+ * Scratch belongs to the context, exactly as a parameter map's: one buffer per stream, grown on demand, reused, kept
+ * until nlh_loss_unwrap, at most 1 GiB per call and so per stream; a call that needs more runs in slices of points -- the
+ * same bits.  NLH_LOSS_SCRATCH = bytes (environment, read at each call; tests) lowers the cap.  The row scaling runs a
+ * thread per (point, row) in the two workgroup forms of the curve kernels -- a workgroup per (point, 256 rows), or several
+ * points per workgroup while two or more fit 256 threads (m <= 128); NLH_LOSS_FORM = row | flat forces one for the sizes
+ * it can hold (flat: m <= 256) -- and splits the columns over a second grid dimension while the launch would otherwise be
+ * fewer than four workgroups per compute unit (NLH_LOSS_SPLIT = number of column groups overrides; tests). */
+typedef struct nlh_loss_ctx nlh_loss_ctx;
+int  nlh_loss_wrap(nlh_handle *h, int32_t kind, const double *dscale, int32_t shared_scale, nlh_device_vecfcn fcn,
+                   nlh_device_jacfcn jac, void *inner_ctx, nlh_loss_ctx **out);
+void nlh_loss_unwrap(nlh_loss_ctx *c);
+int  nlh_loss_device_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dF);
+int  nlh_loss_device_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dJ);
+/* The table applied to raw residuals dr [nprob][m] on the DEVICE (the handle's stream): dout, dg, dwgt [nprob][m], each
+ * may be NULL; dout may be dr itself.  wgt = rho' is 1.0 for a residual the loss leaves alone and falls towards 0.0 for an
+ * outlier: it is what a user thresholds to flag outliers. */
+int  nlh_loss_apply_batch(nlh_handle *h, int32_t kind, int32_t nprob, int32_t m, const double *dscale, int32_t shared_scale,
+                          const double *dr, double *dout, double *dg, double *dwgt);
+/* One-call fits with a loss: the _pmap entry points plus (loss, dscale, shared_scale) after pm.  NLH_LOSS_LINEAR is the
+ * _pmap entry point, bit for bit (dscale is not read).  The composition is fixed, and the bits depend on its order: the
+ * loss wraps the model's launchers directly, and the map, if any, wraps the result.  What comes back is that of the
+ * TRANSFORMED problem: dfvec is rho~ (not the raw residual: nlh_curve_eval_batch / nlh_expr_eval_batch give the model, and
+ * nlh_loss_apply_batch the weights), dchi2 is sum rho~^2 / dof = c^2 * sum rho / dof, and dsigma / dcov are the scaled
+ * covariance of the transformed problem, (J'^T J')^-1 * chi2.  Errors, in this order: the _pmap entry point's up to
+ * NLH_UNDERDEFINED_PROBLEM_ERROR; NLH_INVALID_INPUT_ERROR for a loss outside 0 .. 3; then the _pmap entry point's for NULL
+ * arrays (dscale, or scale, included).  The _h forms take HOST scale [nprob] (or [1]) and refuse, with
+ * NLH_INVALID_INPUT_ERROR, one that is not finite or not positive. */
+int nlh_curve_fit_batch_loss(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                             int32_t m, const double *dt, int32_t shared_t, const double *dy, const double *dw, int32_t analytic,
+                             const double *xl, const double *xu, const nlh_pmap *pm, int32_t loss, const double *dscale,
+                             int32_t shared_scale, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2,
+                             int32_t *drank, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_curve_fit_batch_loss_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                               int32_t m, const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic,
+                               const double *xl, const double *xu, const nlh_pmap *pm, int32_t loss, const double *scale,
+                               int32_t shared_scale, double *x, double *fvec, double *sigma, double *cov, double *chi2,
+                               int32_t *rank, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_expr_fit_batch_loss(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+                            int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl,
+                            const double *xu, const nlh_pmap *pm, int32_t loss, const double *dscale, int32_t shared_scale,
+                            double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+                            nlh_iteration_behavior *ib, int32_t *status);
+int nlh_expr_fit_batch_loss_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+                              int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl,
+                              const double *xu, const nlh_pmap *pm, int32_t loss, const double *scale, int32_t shared_scale,
+                              double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+                              nlh_iteration_behavior *ib, int32_t *status);
+/* A device-function MODEL with a loss over a launcher-backed inner model (device-function, curve, formula or mapped; a
+ * dense-quadratic model: NLH_INVALID_INPUT_ERROR), which must outlive it.  scale: HOST [nprob], or [1] with shared_scale
+ * (NULL allowed for NLH_LOSS_LINEAR); the model owns its device copy and its wrapping context.  Every nlh_dq_model_* solver
+ * and nlh_dq_model_lm_covariance then takes it.  Errors: NLH_ERR_BAD_HANDLE, then NLH_INVALID_INPUT_ERROR (a NULL
+ * argument, a dense-quadratic inner model, a kind outside 0 .. 3, a scale that is not finite or not positive). */
+int nlh_loss_model_create(nlh_handle *h, const nlh_dq_model *inner, int32_t kind, const double *scale, int32_t shared_scale,
+                          nlh_dq_model **model);
+
 /* ---- per-kernel timing (HIP events on the handle's stream) ------------------ */
 #define NLH_K_DQ_RESIDUAL   0
 #define NLH_K_DQ_PANEL      1

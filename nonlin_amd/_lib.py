@@ -274,6 +274,29 @@ SYMBOLS = {
                                             c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p,
                                             c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_pmap_model_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, c_double_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "nlh_loss_wrap": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "nlh_loss_unwrap": (None, [C.c_void_p]),
+    "nlh_loss_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_loss_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_loss_apply_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "nlh_curve_fit_batch_loss": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_curve_fit_batch_loss_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p,
+                                             C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32,
+                                             c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
+                                             C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_fit_batch_loss": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_fit_batch_loss_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p,
+                                            c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, c_double_p, C.c_int32,
+                                            c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
+                                            C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_loss_model_create": (C.c_int, [_H, C.c_void_p, C.c_int32, c_double_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "nlh_timing_enable": (None, [_H, C.c_int32]),
     "nlh_timing_reset": (None, [_H]),
     "nlh_timing_get": (C.c_int, [_H, C.c_int32, c_double_p, C.POINTER(C.c_int64)]),
@@ -467,6 +490,45 @@ class ParamMap:
             self.close()
         except Exception:
             pass
+
+
+# kinds of a robust loss (include/nonlin_hip.h: NLH_LOSS_*)
+LOSS_LINEAR, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY = 0, 1, 2, 3
+LOSS_KINDS = {"linear": LOSS_LINEAR, "huber": LOSS_HUBER, "soft_l1": LOSS_SOFT_L1, "cauchy": LOSS_CAUCHY}
+
+
+class Loss:
+    """A robust loss (include/nonlin_hip.h: nlh_loss_*; host data only, needs no GPU): kind -- "linear", "huber", "soft_l1",
+    "cauchy" or a LOSS_* constant -- and the scale c: one positive finite number for every problem, or a sequence with one
+    per problem.  Residuals well inside c are treated as least squares treats them; far outside, their pull is bounded.
+    E.g. Loss("huber", 3 * sigma_noise).  Raises ValueError for an unknown kind and for a scale that is not finite or not
+    positive (what the library's host-array entry points refuse); "linear" ignores the scale."""
+
+    def __init__(self, kind, scale=1.0):
+        import numpy as np
+        if isinstance(kind, str):
+            if kind.lower() not in LOSS_KINDS:
+                raise ValueError(f"Loss: unknown kind {kind!r} (one of {', '.join(LOSS_KINDS)})")
+            kind = LOSS_KINDS[kind.lower()]
+        if isinstance(kind, bool) or not isinstance(kind, (int, np.integer)) or not LOSS_LINEAR <= int(kind) <= LOSS_CAUCHY:
+            raise ValueError(f"Loss: unknown kind {kind!r}")
+        self.kind = int(kind)
+        try:
+            sc = np.array(scale, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"Loss: the scale must be a number or a sequence of numbers, not {scale!r}") from None
+        if sc.ndim > 1 or sc.size == 0:
+            raise ValueError("Loss: the scale is one number, or one number per problem")
+        if not (np.isfinite(sc).all() and (sc > 0.0).all()):
+            raise ValueError("Loss: the scale must be finite and positive")
+        self.shared = sc.ndim == 0
+        self.scale = np.ascontiguousarray(sc.reshape(-1))
+
+    def scale_for(self, nprob):
+        """The host scales a call on nprob problems passes: ([1], shared = 1) or ([nprob], shared = 0)."""
+        if not self.shared and len(self.scale) != nprob:
+            raise ValueError(f"Loss: {len(self.scale)} scales for {nprob} problems")
+        return self.scale, int(self.shared)
 
 
 class Handle:

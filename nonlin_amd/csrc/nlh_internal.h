@@ -4,7 +4,7 @@
 // (least_squares_solver: lss_solve and its stages), nlh_square.hip (newton_solver, quasi_newton_solver, LU, the
 // Householder steps), nlh_cls.hip (constrained_least_squares_solver), nlh_bfgs.hip (bfgs, fcnnvar_helper%gradient), nlh_nm.hip (nelder_mead),
 // nlh_1var.hip (brent_solver, newton_1var_solver, fcn1var_helper%diff),
-// nlh_poly.hip (polynomial%fit), nlh_polyroots.hip (polynomial%roots, batched evaluate), nlh_covar.hip (parameter covariance), nlh_curve.hip (built-in curve models, the fit + errors composition), nlh_pmap.hip (parameter maps: fixed and tied parameters), nlh_expr.hip (formula models: compiler, launchers), nlh_model.hip (device sets, device residual models behind host arrays), nlh_qrx.hip
+// nlh_poly.hip (polynomial%fit), nlh_polyroots.hip (polynomial%roots, batched evaluate), nlh_covar.hip (parameter covariance), nlh_curve.hip (built-in curve models, the fit + errors composition), nlh_pmap.hip (parameter maps: fixed and tied parameters), nlh_loss.hip (robust losses), nlh_expr.hip (formula models: compiler, launchers), nlh_model.hip (device sets, device residual models behind host arrays), nlh_qrx.hip
 // (the exact lmfactor).  Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it
 // launches.
 #pragma once
@@ -253,6 +253,17 @@ int nlh_fit_compose_h(nlh_handle *h, const char *what, size_t tm, int32_t nprob,
                       const double *w, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
                       const std::function<int(const double *, const double *, const double *, double *, double *, double *, double *,
                                               double *, int32_t *)> &fit, int32_t nfree = -1);
+// ... through a parameter map (nlh_pmap.hip): nlh_fit_compose over the free unknowns, between a gather and an expansion; every
+// array of the caller's has the map's full size.  nlh_loss.hip hands it a loss's wrapping launchers.
+int nlh_fit_compose_pmap(nlh_handle *h, const nlh_options *opts, const nlh_pmap *pm, int32_t nprob, int32_t m, nlh_device_vecfcn fcn,
+                     nlh_device_jacfcn jac, void *ctx, const std::function<void(int32_t)> &at, const double *dw, const double *xl,
+                     const double *xu, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+                     nlh_iteration_behavior *ib, int32_t *status);
+// robust losses (nlh_loss.hip): a kind of the header's table; HOST scales finite and positive, every one of cnt (LINEAR reads
+// none); the same check and then a device copy of them, the caller's to hipFree (LINEAR: none, *dscale NULL)
+bool nlh_loss_kind_ok(int32_t kind);
+bool nlh_loss_scale_ok(int32_t kind, const double *scale, size_t cnt);
+int nlh_loss_scale_upload(nlh_handle *h, int32_t kind, const double *scale, size_t cnt, double **dscale);
 // columns the built-in dense-quadratic family's kernels accept (x in LDS, lds_max of nlh_create): beyond it NLH_ARRAY_SIZE_ERROR
 static const int32_t NLH_DQ_MAX_N = 20000;
 

@@ -96,6 +96,9 @@ struct nlh_dq_model {
     // a mapped model (nlh_pmap_model_create): uctx is this wrapping context around another model's launchers; the model owns
     // it and the device copy of the full parameters behind it (curve_base on curve_device)
     nlh_pmap_ctx *pmap = nullptr;
+    // a model with a loss (nlh_loss_model_create): uctx is this wrapping context around another model's launchers; the model
+    // owns it and the device copy of the scales behind it (curve_base on curve_device)
+    nlh_loss_ctx *loss = nullptr;
 };
 
 int nlh_device_fcn_model_create(int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn, nlh_device_jacfcn jacfcn, void *ctx,
@@ -294,10 +297,32 @@ int nlh_pmap_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_pm
     return 0;
 }
 
+// A model with a robust loss over a launcher-backed inner model (nlh_loss.hip: the wrapping launchers).
+int nlh_loss_model_create(nlh_handle *h, const nlh_dq_model *inner, int32_t kind, const double *scale, int32_t shared_scale,
+                          nlh_dq_model **out)
+{
+    if (out) *out = nullptr;
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (!out || !inner || !inner->ufcn || !nlh_loss_kind_ok(kind)) return NLH_INVALID_INPUT_ERROR;
+    double *base = nullptr;
+    const int urc = nlh_loss_scale_upload(h, kind, scale, shared_scale ? 1 : (size_t)inner->nprob, &base);
+    if (urc) return urc;
+    nlh_loss_ctx *lc = nullptr;
+    const int rc = nlh_loss_wrap(h, kind, base, shared_scale, inner->ufcn, inner->ujac, inner->uctx, &lc);
+    if (rc) { hipFree(base); return rc; }
+    nlh_dq_model *md = new nlh_dq_model();
+    md->nprob = inner->nprob; md->m = inner->m; md->n = inner->n; md->gamma = 0.0;
+    md->ufcn = nlh_loss_device_fcn; md->ujac = inner->ujac ? nlh_loss_device_jac : nullptr; md->uctx = lc;
+    md->loss = lc; md->curve_base = base; md->curve_device = h->device;
+    *out = md;
+    return 0;
+}
+
 void nlh_dq_model_destroy(nlh_dq_model *md)
 {
     if (!md) return;
     nlh_pmap_unwrap(md->pmap);
+    nlh_loss_unwrap(md->loss);
     delete md->expr;
     delete md->expr_prog;
     if (md->curve_base) { hipSetDevice(md->curve_device); hipFree(md->curve_base); }

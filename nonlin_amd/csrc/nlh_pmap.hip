@@ -371,7 +371,7 @@ int nlh_pmap_cov_batch(nlh_handle *h, const nlh_pmap *pm, int32_t nprob, const d
 // ---------------------------------------------------------------------------------------------------------------------
 // fit + errors through a map: nlh_fit_compose over the free unknowns, between a gather and an expansion
 // ---------------------------------------------------------------------------------------------------------------------
-static int fit_compose_pmap(nlh_handle *h, const nlh_options *opts, const nlh_pmap *pm, int32_t nprob, int32_t m, nlh_device_vecfcn fcn,
+int nlh_fit_compose_pmap(nlh_handle *h, const nlh_options *opts, const nlh_pmap *pm, int32_t nprob, int32_t m, nlh_device_vecfcn fcn,
                             nlh_device_jacfcn jac, void *ctx, const std::function<void(int32_t)> &at, const double *dw, const double *xl,
                             const double *xu, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
                             nlh_iteration_behavior *ib, int32_t *status)
@@ -459,7 +459,7 @@ int nlh_curve_fit_batch_pmap(nlh_handle *h, const nlh_options *opts, int32_t kin
         c.dy = dy + (size_t)p0 * m;
         c.dw = dw ? dw + (size_t)p0 * m : nullptr;
     };
-    return fit_compose_pmap(h, opts, pm, nprob, m, nlh_curve_device_fcn, analytic ? nlh_curve_device_jac : nullptr, &c, at, dw, xl, xu, dx, dfvec,
+    return nlh_fit_compose_pmap(h, opts, pm, nprob, m, nlh_curve_device_fcn, analytic ? nlh_curve_device_jac : nullptr, &c, at, dw, xl, xu, dx, dfvec,
                             dsigma, dcov, dchi2, drank, ib, status);
 }
 
@@ -505,7 +505,7 @@ int nlh_expr_fit_batch_pmap(nlh_handle *h, const nlh_options *opts, const nlh_ex
         c.dy = dy + (size_t)p0 * m;
         c.dw = dw ? dw + (size_t)p0 * m : nullptr;
     };
-    return fit_compose_pmap(h, opts, pm, nprob, m, nlh_expr_device_fcn, analytic ? nlh_expr_device_jac : nullptr, &c, at, dw, xl, xu, dx, dfvec,
+    return nlh_fit_compose_pmap(h, opts, pm, nprob, m, nlh_expr_device_fcn, analytic ? nlh_expr_device_jac : nullptr, &c, at, dw, xl, xu, dx, dfvec,
                             dsigma, dcov, dchi2, drank, ib, status);
 }
 

@@ -19,6 +19,7 @@ IB_DTYPE = np.dtype([(k, np.int32) for k, _ in _lib.IterationBehavior._fields_])
 from ._lib import CURVE_GAUSS, CURVE_LORENTZ, CURVE_EXPDECAY, CURVE_KINDS, curve_kind, curve_nparams  # noqa: E402,F401
 from ._lib import Expr  # noqa: E402,F401
 from ._lib import ParamMap  # noqa: E402,F401
+from ._lib import Loss  # noqa: E402,F401
 
 
 def _chk(t, shape, name):
@@ -66,6 +67,15 @@ class _PmapCtx:
             self.close()
         except Exception:
             pass
+
+
+class _LossCtx(_PmapCtx):
+    """The context of a loss's wrapping launchers (nlh_loss_ctx), with everything it points at kept alive."""
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.lib.nlh_loss_unwrap(self.ptr)
+            self.ptr = C.c_void_p()
 
 
 class DeviceSolver:
@@ -258,7 +268,7 @@ class DeviceSolver:
         return y
 
     def curve_fit_batch(self, kind, t, y, x0, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
-                        covariance=True, opts=None, pmap=None):
+                        covariance=True, opts=None, pmap=None, loss=None):
         """Fit + errors of y.shape[0] curves in one call (nlh_curve_fit_batch): least_squares_solver%solve -- or, with lower /
         upper ([n], one box for every problem), constrained_least_squares_solver%solve -- from x0 [nprob, n] (not modified),
         then the scaled parameter covariance at the solution.  Rows with weight 0 pad ragged data: they do not count as
@@ -266,7 +276,10 @@ class DeviceSolver:
         covariance=False, NaN / -1 for a problem whose status is not 0.
         pmap (a ParamMap over the model's n parameters): fixed and tied parameters (nlh_curve_fit_batch_pmap).  Every array
         keeps its full size; a fixed parameter keeps the value x0 holds for its problem, tied positions of x0 are ignored,
-        bound entries at fixed and tied positions are not read, and sigma / cov are those of the full parameters."""
+        bound entries at fixed and tied positions are not read, and sigma / cov are those of the full parameters.
+        loss (a Loss): a robust fit (nlh_curve_fit_batch_loss), with or without pmap.  fvec is then the transformed residual
+        rho~, chi2 = sum rho~^2 / dof, and sigma / cov are those of the transformed problem; loss_apply on the raw residuals
+        gives the weights that flag outliers.  None calls exactly what is called without it."""
         k = curve_kind(kind)
         nprob, m, shared = self._curve_data(t, y, weights)
         n = curve_nparams(k, ncomp, baseline)
@@ -293,7 +306,13 @@ class DeviceSolver:
         ptr = lambda a: a.data_ptr() if a is not None else None
         plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
         phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
-        if pmap is None:
+        if loss is not None:
+            dscale, sh = self._loss_scale(loss, nprob, dev)
+            rc = self.lib.nlh_curve_fit_batch_loss(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
+                                                   y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
+                                                   pmap.ptr if pmap is not None else None, loss.kind, dscale.data_ptr(), sh,
+                                                   x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
+        elif pmap is None:
             rc = self.lib.nlh_curve_fit_batch(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
                                               y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
                                               x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
@@ -301,7 +320,7 @@ class DeviceSolver:
             rc = self.lib.nlh_curve_fit_batch_pmap(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
                                                    y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr,
                                                    x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        name = "nlh_curve_fit_batch" if pmap is None else "nlh_curve_fit_batch_pmap"
+        name = "nlh_curve_fit_batch_loss" if loss is not None else "nlh_curve_fit_batch" if pmap is None else "nlh_curve_fit_batch_pmap"
         self.h.check(rc, name)
         if rc:
             raise RuntimeError(f"{name} returned {rc}")
@@ -360,10 +379,10 @@ class DeviceSolver:
         return y
 
     def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None,
-                       pmap=None):
+                       pmap=None, loss=None):
         """Fit + errors of y.shape[0] data sets to a formula in one call (nlh_expr_fit_batch): curve_fit_batch with an Expr in
-        the place of (kind, ncomp, baseline), pmap (e.g. ParamMap.for_expr(expr, ...)) included.  Returns (x, fvec, sigma, cov,
-        chi2, rank, ibs, status)."""
+        the place of (kind, ncomp, baseline), pmap (e.g. ParamMap.for_expr(expr, ...)) and loss (a Loss) included.  Returns
+        (x, fvec, sigma, cov, chi2, rank, ibs, status)."""
         nprob, m, shared = self._expr_data(expr, t, y, weights)
         n = expr.nparams
         _chk(x0, (nprob, n), "x0")
@@ -389,7 +408,13 @@ class DeviceSolver:
         ptr = lambda a: a.data_ptr() if a is not None else None
         plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
         phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
-        if pmap is None:
+        if loss is not None:
+            dscale, sh = self._loss_scale(loss, nprob, dev)
+            rc = self.lib.nlh_expr_fit_batch_loss(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(),
+                                                  ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr if pmap is not None else None,
+                                                  loss.kind, dscale.data_ptr(), sh,
+                                                  x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
+        elif pmap is None:
             rc = self.lib.nlh_expr_fit_batch(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(), ptr(weights),
                                              int(bool(analytic)), plo, phi,
                                              x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
@@ -397,7 +422,7 @@ class DeviceSolver:
             rc = self.lib.nlh_expr_fit_batch_pmap(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(),
                                                   ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr,
                                                   x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        name = "nlh_expr_fit_batch" if pmap is None else "nlh_expr_fit_batch_pmap"
+        name = "nlh_expr_fit_batch_loss" if loss is not None else "nlh_expr_fit_batch" if pmap is None else "nlh_expr_fit_batch_pmap"
         self.h.check(rc, name)
         if rc:
             raise RuntimeError(f"{name} returned {rc}")
@@ -462,6 +487,45 @@ class DeviceSolver:
         if rc:
             raise RuntimeError(f"nlh_pmap_cov_batch returned {rc}")
         return cf, sf
+
+    # -- robust losses -------------------------------------------------------------
+    def _loss_scale(self, loss, nprob, dev=None):
+        """(device tensor of the scales of a Loss for nprob problems, shared flag)."""
+        sc, sh = loss.scale_for(nprob)
+        return torch.from_numpy(sc).to(dev if dev is not None else self.device), sh
+
+    def loss_launchers(self, loss, fcn, jac, ctx, nprob=None):
+        """A robust loss for any launcher pair: wraps (fcn, jac, ctx) -- of curve_launchers, expr_launchers, dq_launchers,
+        pmap_launchers or a user's own -- in the loss's launchers (nlh_loss_wrap) and returns (fcn, jac, ctx) for
+        lm_solve_batch_device, cls_solve_batch_device, lm_covariance_batch_device, fd_jacobian_device and pmap_launchers.
+        A Loss with one scale per problem fixes the number of problems (nprob, when given, is checked against it).  jac is
+        None without an inner Jacobian launcher (pass jac=None to the solver: forward differences of the wrapped residual).
+        Keep the returned ctx alive while solving; ctx.close() frees it (so does garbage collection)."""
+        dscale, sh = self._loss_scale(loss, len(loss.scale) if nprob is None or loss.shared else nprob)
+        out = C.c_void_p()
+        rc = self.lib.nlh_loss_wrap(self.h.ptr, loss.kind, dscale.data_ptr(), sh, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx),
+                                    C.byref(out))
+        self.h.check(rc, "nlh_loss_wrap")
+        if rc:
+            raise RuntimeError(f"nlh_loss_wrap returned {rc}")
+        wrapped = _LossCtx(self.lib, out, (loss, fcn, jac, ctx, dscale))
+        return (C.cast(self.lib.nlh_loss_device_fcn, _lib.DEVFCN),
+                C.cast(self.lib.nlh_loss_device_jac, _lib.DEVFCN) if jac is not None else None, wrapped)
+
+    def loss_apply(self, loss, r):
+        """(out, g, wgt) of raw residuals r [nprob, m] under a Loss (nlh_loss_apply_batch): the transformed residual rho~, the
+        row factor of the Jacobian, and the weight rho' -- 1.0 for a residual the loss leaves alone, towards 0.0 for an
+        outlier: threshold it to flag outliers."""
+        nprob, m = r.shape
+        _chk(r, (nprob, m), "r")
+        dscale, sh = self._loss_scale(loss, nprob, r.device)
+        out, g, wgt = (torch.empty_like(r) for _ in range(3))
+        rc = self.lib.nlh_loss_apply_batch(self.h.ptr, loss.kind, nprob, m, dscale.data_ptr(), sh, r.data_ptr(), out.data_ptr(),
+                                           g.data_ptr(), wgt.data_ptr())
+        self.h.check(rc, "nlh_loss_apply_batch")
+        if rc:
+            raise RuntimeError(f"nlh_loss_apply_batch returned {rc}")
+        return out, g, wgt
 
     def _ctxp(self, ctx):
         if isinstance(ctx, _PmapCtx):

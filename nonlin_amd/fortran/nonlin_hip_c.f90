@@ -28,6 +28,8 @@ module nonlin_hip_c
     integer(c_int32_t), parameter :: NLH_CURVE_GAUSS = 0, NLH_CURVE_LORENTZ = 1, NLH_CURVE_EXPDECAY = 2
     ! kinds of a parameter of a map (include/nonlin_hip.h: NLH_PMAP_*)
     integer(c_int32_t), parameter :: NLH_PMAP_FREE = 0, NLH_PMAP_FIXED = 1, NLH_PMAP_TIED = 2
+    ! kinds of a robust loss (include/nonlin_hip.h: NLH_LOSS_*)
+    integer(c_int32_t), parameter :: NLH_LOSS_LINEAR = 0, NLH_LOSS_HUBER = 1, NLH_LOSS_SOFT_L1 = 2, NLH_LOSS_CAUCHY = 3
 
     interface
         subroutine nlh_default_options(opts) bind(C, name="nlh_default_options")
@@ -222,6 +224,16 @@ module nonlin_hip_c
             type(c_ptr), value :: h, inner, pm
             real(c_double), intent(in) :: full(*)
             integer(c_int32_t), value :: shared_full
+            type(c_ptr), intent(out) :: model
+            integer(c_int) :: rc
+        end function
+        ! robust losses (include/nonlin_hip.h: nlh_loss_*): a model with a loss over a launcher-backed model
+        function nlh_loss_model_create(h, inner, kind, scale, shared_scale, model) bind(C, name="nlh_loss_model_create") result(rc)
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h, inner
+            integer(c_int32_t), value :: kind
+            real(c_double), intent(in) :: scale(*)
+            integer(c_int32_t), value :: shared_scale
             type(c_ptr), intent(out) :: model
             integer(c_int) :: rc
         end function

@@ -20,6 +20,7 @@ module nonlin_multi_eqn_mult_var
     public :: NLH_MODEL_DENSE_QUADRATIC
     public :: NLH_CURVE_GAUSS, NLH_CURVE_LORENTZ, NLH_CURVE_EXPDECAY   ! kinds of device_model_batch%create_curve (from nonlin_hip_c)
     public :: NLH_PMAP_FREE, NLH_PMAP_FIXED, NLH_PMAP_TIED             ! kinds of a parameter, device_model_batch%create_mapped
+    public :: NLH_LOSS_LINEAR, NLH_LOSS_HUBER, NLH_LOSS_SOFT_L1, NLH_LOSS_CAUCHY   ! kinds of device_model_batch%create_robust
     public :: NLH_FACTOR_AUTO, NLH_FACTOR_QR, NLH_FACTOR_EXACT     ! values of equation_solver%factor_policy (from nonlin_hip_c)
     public :: nlh_use_devices
     public :: nlh_vecfcn_trampoline
@@ -60,6 +61,7 @@ module nonlin_multi_eqn_mult_var
         procedure, public :: create_curve => dmb_create_curve
         procedure, public :: create_expr => dmb_create_expr
         procedure, public :: create_mapped => dmb_create_mapped
+        procedure, public :: create_robust => dmb_create_robust
         procedure, public :: destroy => dmb_destroy
         procedure, public :: is_defined => dmb_defined
         procedure, public :: get_problem_count => dmb_nprob
@@ -449,6 +451,34 @@ contains
         if (rc /= 0) error stop rc
         this%neqn_ = inner%neqn_
         this%nvar_ = nfree
+        this%nprob_ = inner%nprob_
+        this%analytic_ = inner%analytic_
+    end subroutine
+
+    !> A robust loss for a launcher-backed model (create_curve, create_expr, create_from_device_fcn, create_mapped): a model
+    !> of the same unknowns over inner, which must outlive it, whose residuals are transformed so that the unchanged solvers
+    !> minimise the robust cost (INTEGRATION.md 6j).  kind: NLH_LOSS_LINEAR, NLH_LOSS_HUBER, NLH_LOSS_SOFT_L1 or
+    !> NLH_LOSS_CAUCHY; scale(nprob) -- or scale(1): the same for every problem -- is the residual size beyond which the loss
+    !> bends, finite and positive.  solve_batch then returns the transformed residuals, covariance_batch the errors of the
+    !> transformed problem.  A kind or a scale the library refuses stops the program with NL_INVALID_INPUT_ERROR.
+    subroutine dmb_create_robust(this, inner, kind, scale)
+        class(device_model_batch), intent(inout) :: this
+        class(device_model_batch), intent(in) :: inner
+        integer(int32), intent(in) :: kind
+        real(real64), intent(in), dimension(:) :: scale
+        integer(c_int) :: rc
+        integer(c_int32_t) :: shared
+        real(c_double), allocatable :: sc(:)
+        if (.not.inner%is_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR
+        if (size(scale) /= inner%nprob_ .and. size(scale) /= 1) error stop NL_ARRAY_SIZE_ERROR
+        shared = 0
+        if (size(scale) == 1 .and. inner%nprob_ /= 1) shared = 1
+        sc = scale
+        call this%destroy()
+        rc = nlh_loss_model_create(nlh_default_handle(), inner%model_, kind, sc, shared, this%model_)
+        if (rc /= 0) error stop rc
+        this%neqn_ = inner%neqn_
+        this%nvar_ = inner%nvar_
         this%nprob_ = inner%nprob_
         this%analytic_ = inner%analytic_
     end subroutine
