@@ -3,10 +3,11 @@
 // postfix of the parse tree as it goes -- no folding, no reassociation, no sharing -- with, per instruction, the mask of
 // the parameters its subtree names and the instruction that produced its left operand.  Then the launchers of the open
 // device-residual path (kernels and arithmetic: nlh_kernels_expr.h), which form a call runs and how many Jacobian
-// columns a pass carries, model values (nlh_expr_eval_batch) and the one-call fit + errors (nlh_expr_fit_batch: the
-// composition nlh_fit_compose of nlh_curve.hip).  The model object that owns its program and data is
-// nlh_expr_model_create (nlh_model.hip).
+// columns a pass carries, model values (nlh_expr_eval_batch) and the six one-call fits nlh_expr_fit_batch*: a formula as
+// the FitSource of the pipeline (nlh_fit.hip).  The model object that owns its program and data is nlh_expr_model_create
+// (nlh_model.hip).
 #include "nlh_internal.h"
+#include "nlh_launch.h"
 #include "nlh_kernels_expr.h"
 
 #include <locale.h>
@@ -259,15 +260,7 @@ void nlh_expr_init_device(int lds_max)
 // The form a launch runs, as the curve models choose it: flat (several points per workgroup) while two points or more fit
 // a workgroup's 256 threads.  NLH_EXPR_FORM = row | flat (environment, read at every call; tests) forces a form for the
 // sizes it can hold (flat: m <= 256).
-static bool expr_flat(int m)
-{
-    if (m > 256) return false;
-    if (const char *e = getenv("NLH_EXPR_FORM")) {
-        if (!strcmp(e, "row")) return false;
-        if (!strcmp(e, "flat")) return true;
-    }
-    return 256 / m >= 2;
-}
+static bool expr_flat(int m) { return launch_flat("NLH_EXPR_FORM", m); }
 
 // Columns of the Jacobian a pass over the program carries.  A stack is depth * 256 doubles; a pass needs 1 + C of them
 // besides the x of the workgroup's points.  The most columns, 8 and n at most, with which that stays within half of
@@ -329,23 +322,14 @@ int nlh_expr_device_jac(void *ctx, void *hip_stream, int32_t npoints, const int3
     return expr_launch(true, c->e, c->shared_t, c->m, c->dt_stride, c->dt, c->dy, c->dw, npoints, dprob, n, dX, dJ, (hipStream_t)hip_stream);
 }
 
-// the checks every entry point with (e, nprob, m) makes, in the documented order
-static int expr_shape_check(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32_t m, bool data, int32_t *n)
-{
-    if (!h) return NLH_ERR_BAD_HANDLE;
-    if (!e || nprob < 0 || m < 1) return NLH_INVALID_INPUT_ERROR;
-    *n = e->prog.nparams;
-    if (data && m < *n) return NLH_UNDERDEFINED_PROBLEM_ERROR;
-    return 0;
-}
-
 int nlh_expr_eval_batch(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32_t npts, const double *dt, int32_t shared_t, const double *dx,
                         double *dy)
 {
-    int32_t n;
-    int rc = expr_shape_check(h, e, nprob, npts, false, &n);
-    if (rc) return rc;
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (!e || nprob < 0 || npts < 1) return NLH_INVALID_INPUT_ERROR;
+    const int32_t n = e->prog.nparams;
     if (nprob == 0) return 0;
+    int rc;
     if (!dt || !dx || !dy) return NLH_INVALID_INPUT_ERROR;
     HIPCHK(h, hipSetDevice(h->device));
     const int64_t stride = shared_t ? (int64_t)npts : (int64_t)nprob * npts;
@@ -354,42 +338,77 @@ int nlh_expr_eval_batch(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32_t
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// fit + errors: the pipeline of nlh_fit.hip on a formula
+// ---------------------------------------------------------------------------------------------------------------------
+static void expr_bind(void *ctx, const double *dt, const double *dy, const double *dw, int32_t p0)
+{
+    nlh_expr_ctx *c = (nlh_expr_ctx *)ctx;
+    const size_t at = (size_t)p0 * c->m;
+    c->dt = c->shared_t ? dt : dt + at;
+    c->dy = dy + at;
+    c->dw = dw ? dw + at : nullptr;
+}
+
+static int expr_fit(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t analytic, const FitArgs &a, bool host)
+{
+    nlh_expr_ctx c;                                               // (its data pointers: expr_bind, before every run of problems)
+    c.e = e; c.shared_t = a.shared_t != 0; c.m = a.m;
+    c.dt_stride = a.shared_t ? (int64_t)a.m : (int64_t)a.nprob * a.m;   // (a run of problems keeps the whole batch's stride)
+    const FitSource src = {e ? e->prog.nparams : -1, e ? (size_t)e->prog.nvar : 0, "formula fit", nlh_expr_device_fcn,
+                           analytic ? nlh_expr_device_jac : nullptr, &c, expr_bind};
+    return nlh_fit_run(h, opts, src, a, host);
+}
+
 int nlh_expr_fit_batch(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
                        int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl, const double *xu,
                        double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank, nlh_iteration_behavior *ib,
                        int32_t *status)
 {
-    int32_t n;
-    int rc = expr_shape_check(h, e, nprob, m, true, &n);
-    if (rc) return rc;
-    if (nprob == 0) return 0;
-    if (!opts || !dt || !dy || !dx || !dfvec) return NLH_INVALID_INPUT_ERROR;
-    nlh_expr_ctx c;
-    c.e = e; c.shared_t = shared_t != 0; c.m = m;
-    c.dt_stride = shared_t ? (int64_t)m : (int64_t)nprob * m;      // (a run of problems keeps the whole batch's stride)
-    auto at = [&](int32_t p0) {
-        c.dt = shared_t ? dt : dt + (size_t)p0 * m;
-        c.dy = dy + (size_t)p0 * m;
-        c.dw = dw ? dw + (size_t)p0 * m : nullptr;
-    };
-    return nlh_fit_compose(h, opts, nprob, m, n, nlh_expr_device_fcn, analytic ? nlh_expr_device_jac : nullptr, &c, at, dw, xl, xu, dx,
-                           dfvec, dsigma, dcov, dchi2, drank, ib, status);
+    return expr_fit(h, opts, e, analytic, {nprob, m, dt, shared_t, dy, dw, xl, xu, nullptr, NLH_LOSS_LINEAR, nullptr, 0, dx, dfvec, dsigma, dcov,
+                                           dchi2, drank, ib, status}, false);
 }
 
 int nlh_expr_fit_batch_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
                          int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl, const double *xu, double *x,
                          double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank, nlh_iteration_behavior *ib, int32_t *status)
 {
-    int32_t n;
-    int rc = expr_shape_check(h, e, nprob, m, true, &n);
-    if (rc) return rc;
-    if (nprob == 0) return 0;
-    if (!opts || !t || !y || !x || !fvec) return NLH_INVALID_INPUT_ERROR;
-    const size_t tm = (size_t)e->prog.nvar * (shared_t ? (size_t)m : (size_t)nprob * m);
-    return nlh_fit_compose_h(h, "formula fit", tm, nprob, m, n, t, y, w, x, fvec, sigma, cov, chi2, rank,
-                             [&](const double *dt, const double *dy, const double *dw, double *dx, double *df, double *ds, double *dc,
-                                 double *dq, int32_t *dr) {
-                                 return nlh_expr_fit_batch(h, opts, e, nprob, m, dt, shared_t, dy, dw, analytic, xl, xu, dx, df, ds, dc, dq,
-                                                           dr, ib, status);
-                             });
+    return expr_fit(h, opts, e, analytic, {nprob, m, t, shared_t, y, w, xl, xu, nullptr, NLH_LOSS_LINEAR, nullptr, 0, x, fvec, sigma, cov, chi2,
+                                           rank, ib, status}, true);
+}
+
+int nlh_expr_fit_batch_pmap(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+                            int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl, const double *xu,
+                            const nlh_pmap *pm, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+                            nlh_iteration_behavior *ib, int32_t *status)
+{
+    return expr_fit(h, opts, e, analytic, {nprob, m, dt, shared_t, dy, dw, xl, xu, pm, NLH_LOSS_LINEAR, nullptr, 0, dx, dfvec, dsigma, dcov,
+                                           dchi2, drank, ib, status}, false);
+}
+
+int nlh_expr_fit_batch_pmap_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+                              int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl, const double *xu,
+                              const nlh_pmap *pm, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+                              nlh_iteration_behavior *ib, int32_t *status)
+{
+    return expr_fit(h, opts, e, analytic, {nprob, m, t, shared_t, y, w, xl, xu, pm, NLH_LOSS_LINEAR, nullptr, 0, x, fvec, sigma, cov, chi2, rank,
+                                           ib, status}, true);
+}
+
+int nlh_expr_fit_batch_loss(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+                            int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl, const double *xu,
+                            const nlh_pmap *pm, int32_t loss, const double *dscale, int32_t shared_scale, double *dx, double *dfvec,
+                            double *dsigma, double *dcov, double *dchi2, int32_t *drank, nlh_iteration_behavior *ib, int32_t *status)
+{
+    return expr_fit(h, opts, e, analytic, {nprob, m, dt, shared_t, dy, dw, xl, xu, pm, loss, dscale, shared_scale, dx, dfvec, dsigma, dcov, dchi2,
+                                           drank, ib, status}, false);
+}
+
+int nlh_expr_fit_batch_loss_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+                              int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl, const double *xu,
+                              const nlh_pmap *pm, int32_t loss, const double *scale, int32_t shared_scale, double *x, double *fvec,
+                              double *sigma, double *cov, double *chi2, int32_t *rank, nlh_iteration_behavior *ib, int32_t *status)
+{
+    return expr_fit(h, opts, e, analytic, {nprob, m, t, shared_t, y, w, xl, xu, pm, loss, scale, shared_scale, x, fvec, sigma, cov, chi2, rank,
+                                           ib, status}, true);
 }

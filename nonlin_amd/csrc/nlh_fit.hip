@@ -1,0 +1,251 @@
+// nlh_fit.hip -- the one-call fit + errors pipeline behind the twelve entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss}{,_h}
+// (nlh_internal.h: nlh_fit_run).  A model kind hands it a FitSource -- its launchers, a context and how to point that context
+// at a run of problems -- and the rest of the entry point's arguments as a FitArgs; here are the documented ladder of checks,
+// the staging of host arrays, the composition (the loss wraps the model's launchers, the parameter map, if any, wraps the
+// result), the solve and covariance of every run of consecutive problems that have degrees of freedom, and the rule of
+// zero-weight padding.  Nothing here knows what a curve or a formula is.  Kernels: nlh_kernels_fit.h.
+#include "nlh_internal.h"
+#include "nlh_kernels_fit.h"
+
+namespace {
+// The launchers a solve sees -- the model's, inside the loss's, inside the map's -- and what each run of consecutive
+// problems re-points: a run counts its dprob from its first problem.
+struct FitRun {
+    nlh_handle *h;
+    const nlh_options *opts;
+    const FitSource *src;
+    const FitArgs *a;                  // device pointers
+    int32_t N;                         // the model's parameters
+    nlh_device_vecfcn fcn;
+    nlh_device_jacfcn jac;
+    void *ctx;
+    nlh_loss_ctx *lc = nullptr;
+    nlh_pmap_ctx *pc = nullptr;
+    const double *fullc = nullptr;     // the map's private copy of the full parameters
+    void bind(int32_t p0) const
+    {
+        src->bind(src->ctx, a->t, a->y, a->w, p0);
+        if (lc) loss_ctx_rebind(lc, a->shared_scale ? a->scale : a->scale + p0);
+        if (pc) pmap_ctx_rebind(pc, fullc + (size_t)p0 * N);
+    }
+};
+}   // namespace
+
+// Solve (bounded when xl or xu is given), covariance with scaled = 1 when any of dsigma, dcov, the caller's chi2 is asked for,
+// the degrees-of-freedom rule of zero weights, NaN and rank -1 for problems that did not solve: over n unknowns -- the
+// model's parameters, or the free ones of a map, whose arrays xl .. status these then are.
+static int fit_solve(const FitRun &r, int32_t n, const double *xl, const double *xu, double *dx, double *dsigma, double *dcov, int32_t *status)
+{
+    nlh_handle *h = r.h;
+    const FitArgs &a = *r.a;
+    const int32_t nprob = a.nprob, m = a.m;
+    const double *dw = a.w;
+    double *dfvec = a.fvec, *dchi2 = a.chi2;
+    int32_t *drank = a.rank;
+    nlh_iteration_behavior *ib = a.ib;
+    int rc;
+    const bool errors = dsigma || dcov || dchi2;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t np = (size_t)nprob, nn = (size_t)n * n;
+    // the handle's own buffer for this entry point: status and non-zero-weight counts, a cov when the caller wants none
+    const size_t ints = 2 * np + 2;
+    if ((rc = ensure(h, h->crv, sizeof(int32_t) * ints + sizeof(double) * (errors && !dcov ? np * nn : 0) + 64))) return rc;
+    int32_t *dstat = (int32_t *)h->crv.p, *dnz = dstat + np;
+    double *cov = dcov ? dcov : (double *)(dstat + (ints & ~(size_t)1));
+    std::vector<int32_t> st(np, 0), nz;
+    if (dw) {                                                    // degrees of freedom, before anything is evaluated
+        nz.resize(np);
+        hipLaunchKernelGGL(k_fit_count, dim3((nprob + 63) / 64), dim3(64), 0, s, nprob, m, dw, dnz);
+        HIPCHK(h, hipMemcpyAsync(nz.data(), dnz, sizeof(int32_t) * np, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        for (size_t p = 0; p < np; ++p)
+            if (nz[p] - n <= 0) st[p] = NLH_INVALID_INPUT_ERROR;
+    }
+    // runs of consecutive problems that have degrees of freedom (all of them, as a rule): exactly the calls a user makes
+    for (int32_t p0 = 0; p0 < nprob;) {
+        if (st[p0]) { ++p0; continue; }
+        int32_t p1 = p0;
+        while (p1 < nprob && !st[p1]) ++p1;
+        const int32_t cnt = p1 - p0;
+        r.bind(p0);
+        double *xs = dx + (size_t)p0 * n, *fs = dfvec + (size_t)p0 * m;
+        nlh_iteration_behavior *ibs = ib ? ib + p0 : nullptr;
+        if (xl || xu) rc = nlh_cls_solve_batch_device(h, r.opts, 1.0, 1.0, xl, xu, cnt, m, n, r.fcn, r.jac, r.ctx, xs, fs, ibs, &st[p0]);
+        else rc = nlh_lm_solve_batch_device(h, r.opts, cnt, m, n, r.fcn, r.jac, r.ctx, xs, fs, ibs, &st[p0]);
+        if (rc) return rc;
+        if (errors &&
+            (rc = nlh_lm_covariance_batch_device(h, cnt, m, n, r.fcn, r.jac, r.ctx, xs, 1, 0.0, cov + (size_t)p0 * nn,
+                                                 dsigma ? dsigma + (size_t)p0 * n : nullptr, drank ? drank + p0 : nullptr,
+                                                 dchi2 ? dchi2 + p0 : nullptr))) return rc;
+        p0 = p1;
+    }
+    if (errors) {
+        HIPCHK(h, hipMemcpyAsync(dstat, st.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_fit_post, dim3((nprob + 63) / 64), dim3(64), 0, s, nprob, m, n, (const int32_t *)dstat,
+                           dw ? (const int32_t *)dnz : (const int32_t *)nullptr, (const double *)dfvec, cov, dsigma, dchi2, drank);
+        HIPCHK(h, hipStreamSynchronize(s));                      // (st is a host vector)
+    }
+    if (status) memcpy(status, st.data(), sizeof(int32_t) * np);
+    if (ib)
+        for (size_t p = 0; p < np; ++p)
+            if (st[p] == NLH_INVALID_INPUT_ERROR && nz.size() && nz[p] - n <= 0) ib[p] = nlh_iteration_behavior{};
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// ... through a parameter map: fit_solve over the n free unknowns with the map's launchers around r's, between a gather and
+// an expansion; every array of the caller's has the map's full size.
+static int fit_mapped(FitRun r, int32_t n)
+{
+    nlh_handle *h = r.h;
+    const FitArgs &a = *r.a;
+    const size_t N = (size_t)r.N, nf = (size_t)n, np = (size_t)a.nprob;
+    if ((np * (a.cov ? N * N : N) + 255) / 256 > 0x7fffffffu) return NLH_ARRAY_SIZE_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    int rc = 0;
+    // a private copy of the full parameters (the fixed values), the free unknowns, the free sigma and cov, the failure flags
+    const size_t doubles = np * N + np * nf + (a.sigma ? np * nf : 0) + (a.cov ? np * nf * nf : 0);
+    double *base = nullptr;
+    if (hipMalloc(&base, sizeof(double) * doubles + sizeof(int32_t) * np) != hipSuccess) {
+        h->err = "hipMalloc (fit through a parameter map)";
+        return NLH_OUT_OF_MEMORY_ERROR;
+    }
+    double *q = base;
+    double *fullc = q; q += np * N;
+    double *xf = q; q += np * nf;
+    double *sf = a.sigma ? q : nullptr; q += a.sigma ? np * nf : 0;
+    double *cf = a.cov ? q : nullptr; q += a.cov ? np * nf * nf : 0;
+    int32_t *dfail = (int32_t *)q;
+    std::vector<int32_t> f2f(nf);
+    nlh_pmap_tables(a.pm, nullptr, nullptr, nullptr, nullptr, f2f.data());
+    std::vector<double> lo, hi;
+    if (a.xl) { lo.resize(nf); for (size_t j = 0; j < nf; ++j) lo[j] = a.xl[f2f[j]]; }
+    if (a.xu) { hi.resize(nf); for (size_t j = 0; j < nf; ++j) hi[j] = a.xu[f2f[j]]; }
+    std::vector<int32_t> st(np, 0);
+    nlh_pmap_ctx *pc = nullptr;                                   // its copy of the tables serves the steps here too
+    hipError_t e = hipSuccess;
+    rc = nlh_pmap_wrap(h, a.pm, r.fcn, r.jac, r.ctx, fullc, 0, &pc);
+    if (!rc) e = hipMemcpyAsync(fullc, a.x, sizeof(double) * np * N, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && !rc) {
+        pmap_gather(pmap_ctx_tables(pc), s, a.nprob, fullc, xf);
+        r.fcn = nlh_pmap_device_fcn; r.jac = r.jac ? nlh_pmap_device_jac : nullptr; r.ctx = pc;
+        r.pc = pc; r.fullc = fullc;
+        rc = fit_solve(r, n, a.xl ? lo.data() : nullptr, a.xu ? hi.data() : nullptr, xf, sf, cf, st.data());
+    }
+    if (e == hipSuccess && !rc) {
+        // every problem, also one that was refused on its degrees of freedom and kept its x: on exit x obeys the map
+        pmap_expand(pmap_ctx_tables(pc), s, a.nprob, xf, fullc, 0, a.x);
+        if (a.sigma || a.cov) {
+            e = hipMemcpyAsync(dfail, st.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) pmap_cov(pmap_ctx_tables(pc), s, a.nprob, cf, sf, dfail, a.cov, a.sigma);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(s);                // (st is a host vector; the buffers go)
+    nlh_pmap_unwrap(pc);
+    (void)hipFree(base);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) {
+        h->err = std::string("fit through a parameter map: ") + hipGetErrorString(e);
+        return NLH_ERR_HIP;
+    }
+    if (!rc && a.status) memcpy(a.status, st.data(), sizeof(int32_t) * np);
+    return rc;
+}
+
+// The composition on device pointers: the loss wraps the model's launchers (NLH_LOSS_LINEAR: no context, no kernel of the
+// loss), the map, if any, wraps the result.  n: the unknowns of the solve.
+static int fit_device(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, int32_t n)
+{
+    FitRun r{h, opts, &src, &a, src.N, src.fcn, src.jac, src.ctx};
+    auto run = [&]() { return a.pm ? fit_mapped(r, n) : fit_solve(r, n, a.xl, a.xu, a.x, a.sigma, a.cov, a.status); };
+    if (a.loss == NLH_LOSS_LINEAR) return run();
+    int rc = nlh_loss_wrap(h, a.loss, a.scale, a.shared_scale, src.fcn, src.jac, src.ctx, &r.lc);
+    if (rc) return rc;
+    r.fcn = nlh_loss_device_fcn; r.jac = src.jac ? nlh_loss_device_jac : nullptr; r.ctx = r.lc;
+    rc = run();
+    const hipError_t e = hipStreamSynchronize(h->stream);         // (the context's scratch goes)
+    nlh_loss_unwrap(r.lc);
+    if (!rc && e != hipSuccess) {
+        h->err = std::string("fit with a loss: ") + hipGetErrorString(e);
+        return NLH_ERR_HIP;
+    }
+    return rc;
+}
+
+// ... behind HOST arrays t, y, w, x, fvec, sigma, cov, chi2, rank (and the scales, which dscale is the device copy of): one
+// allocation, the copies in, fit_device, the copies out.
+static int fit_staged(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, int32_t n, const double *dscale)
+{
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t N = (size_t)src.N, np = (size_t)a.nprob, pm = np * a.m, nn = N * N;
+    const size_t tm = src.tdoubles * (a.shared_t ? (size_t)a.m : pm);
+    const size_t doubles = tm + pm * (a.w ? 3 : 2) + np * N + (a.sigma ? np * N : 0) + (a.cov ? np * nn : 0) + (a.chi2 ? np : 0);
+    double *base = nullptr;
+    if (hipMalloc(&base, sizeof(double) * doubles + sizeof(int32_t) * np) != hipSuccess) {
+        h->err = std::string("hipMalloc (") + src.what + ")";
+        return NLH_OUT_OF_MEMORY_ERROR;
+    }
+    FitArgs d = a;
+    double *q = base;
+    double *dt = q; q += tm;
+    double *dy = q; q += pm;
+    double *dw = a.w ? q : nullptr; q += a.w ? pm : 0;
+    d.fvec = q; q += pm;
+    d.x = q; q += np * N;
+    d.sigma = a.sigma ? q : nullptr; q += a.sigma ? np * N : 0;
+    d.cov = a.cov ? q : nullptr; q += a.cov ? np * nn : 0;
+    d.chi2 = a.chi2 ? q : nullptr; q += a.chi2 ? np : 0;
+    d.rank = a.rank ? (int32_t *)q : nullptr;
+    d.t = dt; d.y = dy; d.w = dw; d.scale = dscale;
+    hipError_t e = hipMemcpyAsync(dt, a.t, sizeof(double) * tm, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dy, a.y, sizeof(double) * pm, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && a.w) e = hipMemcpyAsync(dw, a.w, sizeof(double) * pm, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d.x, a.x, sizeof(double) * np * N, hipMemcpyHostToDevice, s);
+    int rc = 0;
+    if (e == hipSuccess) rc = fit_device(h, opts, src, d, n);
+    if (e == hipSuccess && !rc) {
+        e = hipMemcpyAsync(a.x, d.x, sizeof(double) * np * N, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(a.fvec, d.fvec, sizeof(double) * pm, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && a.sigma) e = hipMemcpyAsync(a.sigma, d.sigma, sizeof(double) * np * N, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && a.cov) e = hipMemcpyAsync(a.cov, d.cov, sizeof(double) * np * nn, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && a.chi2) e = hipMemcpyAsync(a.chi2, d.chi2, sizeof(double) * np, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && a.rank) e = hipMemcpyAsync(a.rank, d.rank, sizeof(int32_t) * np, hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t e2 = hipStreamSynchronize(s);
+    (void)hipFree(base);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) {
+        h->err = std::string(src.what) + " (host arrays): " + hipGetErrorString(e);
+        return NLH_ERR_HIP;
+    }
+    return rc;
+}
+
+// The checks of every one of the twelve entry points, in the documented order, and then the fit.
+int nlh_fit_run(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, bool host)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (src.N < 0 || a.nprob < 0 || a.m < 1) return NLH_INVALID_INPUT_ERROR;
+    int32_t n = src.N;                                            // the unknowns: the free parameters of a map
+    if (a.pm) {
+        int32_t nfull;
+        nlh_pmap_shape(a.pm, &nfull, &n, nullptr);
+        if (nfull != src.N) return NLH_INVALID_INPUT_ERROR;
+    }
+    if (a.m < n) return NLH_UNDERDEFINED_PROBLEM_ERROR;
+    if (!nlh_loss_kind_ok(a.loss)) return NLH_INVALID_INPUT_ERROR;
+    if (a.nprob == 0) return 0;
+    if (!opts || !a.t || !a.y || !a.x || !a.fvec || (a.loss != NLH_LOSS_LINEAR && !a.scale)) return NLH_INVALID_INPUT_ERROR;
+    if ((a.sigma || a.cov || a.chi2) && a.m <= n) return NLH_INVALID_INPUT_ERROR;   // no degree of freedom for errors
+    if (!host) return fit_device(h, opts, src, a, n);
+    double *dscale = nullptr;                                     // checks the host scales: finite, positive (LINEAR: none, NULL)
+    int rc = nlh_loss_scale_upload(h, a.loss, a.scale, a.shared_scale ? 1 : (size_t)a.nprob, &dscale);
+    if (rc) return rc;
+    rc = fit_staged(h, opts, src, a, n, dscale);
+    if (dscale) (void)hipFree(dscale);
+    return rc;
+}

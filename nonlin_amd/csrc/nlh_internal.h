@@ -1,12 +1,26 @@
 // nlh_internal.h -- what the translation units of libnonlin_hip.so share: the handle, the error macro, the event
 // brackets of a kernel group, and the helpers one unit defines for the others (nlh_core.hip unless noted).
-// Units: nlh_core.hip (handle, options, timing, generator, residual / FD launches, worker handles), nlh_lm.hip
-// (least_squares_solver: lss_solve and its stages), nlh_square.hip (newton_solver, quasi_newton_solver, LU, the
-// Householder steps), nlh_cls.hip (constrained_least_squares_solver), nlh_bfgs.hip (bfgs, fcnnvar_helper%gradient), nlh_nm.hip (nelder_mead),
-// nlh_1var.hip (brent_solver, newton_1var_solver, fcn1var_helper%diff),
-// nlh_poly.hip (polynomial%fit), nlh_polyroots.hip (polynomial%roots, batched evaluate), nlh_covar.hip (parameter covariance), nlh_curve.hip (built-in curve models, the fit + errors composition), nlh_pmap.hip (parameter maps: fixed and tied parameters), nlh_loss.hip (robust losses), nlh_expr.hip (formula models: compiler, launchers), nlh_model.hip (device sets, device residual models behind host arrays), nlh_qrx.hip
-// (the exact lmfactor).  Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it
-// launches.
+// Units:
+//   nlh_core.hip       handle, options, timing, generator, residual / FD launches, worker handles
+//   nlh_lm.hip         least_squares_solver: lss_solve and its stages
+//   nlh_square.hip     newton_solver, quasi_newton_solver, LU, the Householder steps
+//   nlh_cls.hip        constrained_least_squares_solver
+//   nlh_bfgs.hip       bfgs, fcnnvar_helper%gradient
+//   nlh_nm.hip         nelder_mead
+//   nlh_1var.hip       brent_solver, newton_1var_solver, fcn1var_helper%diff
+//   nlh_poly.hip       polynomial%fit
+//   nlh_polyroots.hip  polynomial%roots, batched evaluate
+//   nlh_covar.hip      parameter covariance
+//   nlh_devfcn.hip     user device residuals: the open launcher path, the built-in family as launchers
+//   nlh_curve.hip      built-in curve models: launchers, values, the six nlh_curve_fit_batch* entry points
+//   nlh_expr.hip       formula models: compiler, launchers, values, the six nlh_expr_fit_batch* entry points
+//   nlh_fit.hip        the fit + errors pipeline behind those twelve (nlh_fit_run below)
+//   nlh_pmap.hip       parameter maps: the map object, the wrapping launchers, gather / expand / covariance
+//   nlh_loss.hip       robust losses: the wrapping launchers, apply, the upload of host scales
+//   nlh_model.hip      device sets, device residual models behind host arrays
+//   nlh_qrx.hip        the exact lmfactor
+// Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it launches.  nlh_launch.h:
+// the host side of the (point, row) kernels' two workgroup forms and what the two pairs of wrapping launchers share.
 #pragma once
 #include "../../include/nonlin_hip.h"
 
@@ -19,6 +33,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <thread>
 #include <atomic>
@@ -56,7 +71,7 @@ struct nlh_handle {
            qnQ, qnR, qnV, bfB, bfR, bfV, qxV, lumv, lus,
            dvX, dvF, dvIdx, dvP,          // user device residuals: points, compact residuals, problem lists, panel chunk (nlh_devfcn.hip)
            cvW, cvT, cvH,                 // covariance (nlh_covar.hip): the chain's arrays, the global-memory window, host-array staging
-           crv;                           // curve fits (nlh_curve.hip): status, non-zero-weight counts, a covariance nobody asked to keep
+           crv;                           // one-call fits (nlh_fit.hip): status, non-zero-weight counts, a covariance nobody asked to keep
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     DevBuf cholmc;                     // side buffer of the multi-CU Cholesky (solved panels, bad-pivot flags)
@@ -238,27 +253,52 @@ struct nlh_expr {
     int32_t nconst;
 };
 
-// Fit + errors, the composition nlh_curve_fit_batch documents, for any launcher pair (nlh_curve.hip): solve (bounded when
-// xl or xu is given), covariance with scaled = 1 when any of dsigma, dcov, dchi2 is asked for, the degrees-of-freedom rule
-// of zero weights, NaN and rank -1 for problems that did not solve.  at(ctx, p0) points the context's data at problem p0
-// before each run of consecutive problems.  The caller has checked the shape; device pointers as nlh_curve_fit_batch's.
-int nlh_fit_compose(nlh_handle *h, const nlh_options *opts, int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn,
-                    nlh_device_jacfcn jac, void *ctx, const std::function<void(int32_t)> &at, const double *dw, const double *xl,
-                    const double *xu, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
-                    nlh_iteration_behavior *ib, int32_t *status);
-// ... behind host arrays: t is tm doubles; fit(dt, dy, dw, dx, df, ds, dc, dq, dr) is the device-pointer entry point.
-// nfree >= 0 (a fit through a parameter map, nlh_pmap.hip: the arrays have the n full parameters, the solve nfree
-// unknowns): the count the degrees of freedom are checked with.
-int nlh_fit_compose_h(nlh_handle *h, const char *what, size_t tm, int32_t nprob, int32_t m, int32_t n, const double *t, const double *y,
-                      const double *w, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
-                      const std::function<int(const double *, const double *, const double *, double *, double *, double *, double *,
-                                              double *, int32_t *)> &fit, int32_t nfree = -1);
-// ... through a parameter map (nlh_pmap.hip): nlh_fit_compose over the free unknowns, between a gather and an expansion; every
-// array of the caller's has the map's full size.  nlh_loss.hip hands it a loss's wrapping launchers.
-int nlh_fit_compose_pmap(nlh_handle *h, const nlh_options *opts, const nlh_pmap *pm, int32_t nprob, int32_t m, nlh_device_vecfcn fcn,
-                     nlh_device_jacfcn jac, void *ctx, const std::function<void(int32_t)> &at, const double *dw, const double *xl,
-                     const double *xu, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
-                     nlh_iteration_behavior *ib, int32_t *status);
+// The one-call fit + errors of the twelve entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss}{,_h} (nlh_fit.hip).
+// FitSource: what a model kind hands the pipeline.  bind points the context's data at problem p0 of dt, dy, dw (the whole
+// batch's device arrays) before each run of consecutive problems; whatever else the context holds stays the whole batch's.
+struct FitSource {
+    int32_t N;                         // parameters of the model; < 0: the model is refused
+    size_t tdoubles;                   // doubles of t per abscissa: 1 for a curve, nvar for a formula
+    const char *what;                  // the label of error texts: "curve fit"
+    nlh_device_vecfcn fcn;
+    nlh_device_jacfcn jac;             // NULL: forward differences
+    void *ctx;
+    void (*bind)(void *ctx, const double *dt, const double *dy, const double *dw, int32_t p0);
+};
+// FitArgs: the rest of an entry point's arguments, as the header documents them, for the device-pointer form and the
+// host-array form alike.  A plain fit is pm = NULL, loss = NLH_LOSS_LINEAR (which reads no scale).
+struct FitArgs {
+    int32_t nprob, m;
+    const double *t;
+    int32_t shared_t;
+    const double *y, *w, *xl, *xu;
+    const nlh_pmap *pm;
+    int32_t loss;
+    const double *scale;
+    int32_t shared_scale;
+    double *x, *fvec, *sigma, *cov, *chi2;
+    int32_t *rank;
+    nlh_iteration_behavior *ib;
+    int32_t *status;
+};
+// The documented ladder of checks, then: solve (bounded when xl or xu is given), covariance with scaled = 1 when any of sigma,
+// cov, chi2 is asked for, the degrees-of-freedom rule of zero weights, NaN and rank -1 for problems that did not solve.  The
+// loss wraps the model's launchers; the map, if any, wraps the result.  host: the arrays are host arrays (the scales too).
+int nlh_fit_run(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, bool host);
+// what the pipeline needs of a wrapping context besides the public nlh_*_wrap / _unwrap: where a run of problems starts in
+// the caller's arrays (nlh_loss.hip, nlh_pmap.hip), and the map's three small launches on the context's copy of the tables
+struct PmapTables;                     // nlh_kernels_pmap.h
+void loss_ctx_rebind(nlh_loss_ctx *c, const double *dscale);
+void pmap_ctx_rebind(nlh_pmap_ctx *c, const double *dfull);
+const PmapTables *pmap_ctx_tables(const nlh_pmap_ctx *c);
+void pmap_gather(const PmapTables *T, hipStream_t s, int nprob, const double *full, double *x);
+void pmap_expand(const PmapTables *T, hipStream_t s, int nprob, const double *x, const double *full, int shared_full, double *p);
+void pmap_cov(const PmapTables *T, hipStream_t s, int nprob, const double *cov, const double *sigma, const int32_t *fail, double *covf,
+              double *sigf);
+// Host arrays, one after the other, into ONE device allocation on the handle's device, the caller's to hipFree; synchronised.
+// Errors name `what` in h->err: "hipMalloc (what)", "hipMemcpy (what): ...".  A part of 0 bytes is skipped.  (nlh_model.hip)
+struct HostPart { const void *p; size_t bytes; };
+int nlh_upload(nlh_handle *h, const char *what, std::initializer_list<HostPart> parts, void **base);
 // robust losses (nlh_loss.hip): a kind of the header's table; HOST scales finite and positive, every one of cnt (LINEAR reads
 // none); the same check and then a device copy of them, the caller's to hipFree (LINEAR: none, *dscale NULL)
 bool nlh_loss_kind_ok(int32_t kind);

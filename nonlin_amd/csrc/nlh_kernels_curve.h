@@ -23,6 +23,7 @@
 // column-major (ld = m): consecutive threads write consecutive rows of a column.
 #pragma once
 #include "nlh_internal.h"
+#include "nlh_kernels_place.h"
 
 struct CurveData {                     // what the kernels read: nlh_curve_ctx without the kind
     int K, B, shared_t, m;
@@ -59,27 +60,6 @@ __device__ static inline double curve_value(int K, int B, const double *x, doubl
     return s;
 }
 
-// thread -> (point q, row i, that point's x in LDS); false: nothing to do.  FLAT: ppw points per workgroup.
-template <bool FLAT>
-__device__ static inline bool curve_place(int m, int n, int nblk, int ppw, int npoints, const double *__restrict__ X, double *xs, int &q, int &i,
-                                          const double *&xq)
-{
-    if (FLAT) {
-        const int q0 = blockIdx.x * ppw, nq = min(ppw, npoints - q0);
-        for (int e = threadIdx.x; e < nq * n; e += 256) xs[e] = X[(size_t)q0 * n + e];
-        __syncthreads();
-        const int lp = threadIdx.x / m;
-        q = q0 + lp; i = threadIdx.x - lp * m; xq = xs + lp * n;
-        return lp < nq;
-    }
-    q = blockIdx.x / nblk;
-    const int rb = blockIdx.x - q * nblk;
-    for (int c = threadIdx.x; c < n; c += 256) xs[c] = X[(size_t)q * n + c];
-    __syncthreads();
-    i = rb * 256 + threadIdx.x; xq = xs;
-    return i < m;
-}
-
 template <int KIND, bool FLAT>
 static __global__ void __launch_bounds__(256)
 k_curve_fcn(CurveData cd, int n, int nblk, int ppw, int npoints, const int32_t *__restrict__ dprob, const double *__restrict__ X,
@@ -88,7 +68,7 @@ k_curve_fcn(CurveData cd, int n, int nblk, int ppw, int npoints, const int32_t *
     extern __shared__ double xs[];
     int q, i;
     const double *xq;
-    const bool on = curve_place<FLAT>(cd.m, n, nblk, ppw, npoints, X, xs, q, i, xq);
+    const bool on = place_staged<FLAT>(cd.m, n, nblk, ppw, npoints, X, xs, q, i, xq);
     const int qc = min(q, npoints - 1), ic = min(i, cd.m - 1);
     const int p = dprob ? dprob[qc] : qc;
     const size_t at = (size_t)p * cd.m + ic;
@@ -110,7 +90,7 @@ k_curve_jac(CurveData cd, int n, int nblk, int ppw, int npoints, const int32_t *
     extern __shared__ double xs[];
     int q, i;
     const double *xq;
-    const bool on = curve_place<FLAT>(cd.m, n, nblk, ppw, npoints, X, xs, q, i, xq);
+    const bool on = place_staged<FLAT>(cd.m, n, nblk, ppw, npoints, X, xs, q, i, xq);
     const int qc = min(q, npoints - 1), ic = min(i, cd.m - 1);
     const int p = dprob ? dprob[qc] : qc;
     const size_t at = (size_t)p * cd.m + ic;
@@ -154,50 +134,4 @@ k_curve_jac(CurveData cd, int n, int nblk, int ppw, int npoints, const int32_t *
         Jb[(size_t)j * m] = hw ? w * pw : pw;
         pw = pw * t;
     }
-}
-
-// rows with w != 0 of every problem (the degrees of freedom of a fit on zero-padded data are that count minus n)
-static __global__ void __launch_bounds__(64)
-k_curve_count(int nprob, int m, const double *__restrict__ w, int32_t *__restrict__ cnt)
-{
-    const int p = blockIdx.x * 64 + threadIdx.x;
-    if (p >= nprob) return;
-    int c = 0;
-    for (int i = 0; i < m; ++i) c += w[(size_t)p * m + i] != 0.0;
-    cnt[p] = c;
-}
-
-// What nlh_curve_fit_batch does after the covariance chain, a thread per problem: a problem that did not solve gets NaN
-// and rank -1; with weights, chi2 = (sum of f_i^2, i ascending, sequential) / dof and every entry of cov is multiplied
-// once by (m - n) / dof before sigma_i = sqrt(cov(i,i)) is taken.  Any of cov, sigma, chi2, rank may be null.
-static __global__ void __launch_bounds__(64)
-k_curve_post(int nprob, int m, int n, const int32_t *__restrict__ status, const int32_t *__restrict__ nz, const double *__restrict__ f,
-             double *__restrict__ cov, double *__restrict__ sigma, double *__restrict__ chi2, int32_t *__restrict__ rank)
-{
-    const int p = blockIdx.x * 64 + threadIdx.x;
-    if (p >= nprob) return;
-    const size_t nn = (size_t)n * n;
-    if (status[p] != 0) {
-        const double nan = __longlong_as_double(0x7ff8000000000000ll);
-        if (cov) for (size_t e = 0; e < nn; ++e) cov[p * nn + e] = nan;
-        if (sigma) for (int j = 0; j < n; ++j) sigma[(size_t)p * n + j] = nan;
-        if (chi2) chi2[p] = nan;
-        if (rank) rank[p] = -1;
-        return;
-    }
-    if (!nz) return;
-    const double dof = (double)(nz[p] - n);
-    if (chi2) {
-        const double *fp = f + (size_t)p * m;
-        double s = 0.0;
-        for (int i = 0; i < m; ++i) s = s + fp[i] * fp[i];
-        chi2[p] = s / dof;
-    }
-    const double scale = (double)(m - n) / dof;
-    if (cov)
-        for (size_t e = 0; e < nn; ++e) {
-            const double v = cov[p * nn + e] * scale;
-            cov[p * nn + e] = v;
-            if (sigma && e / n == e % n) sigma[(size_t)p * n + e / n] = sqrt(v);
-        }
 }

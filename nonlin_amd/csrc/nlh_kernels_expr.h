@@ -18,6 +18,7 @@
 // hence uniform: nothing per thread records it.
 #pragma once
 #include "nlh_internal.h"
+#include "nlh_kernels_place.h"
 
 struct ExprData {                      // what the kernels read of an nlh_expr_ctx
     int shared_t, m;
@@ -28,27 +29,6 @@ struct ExprData {                      // what the kernels read of an nlh_expr_c
 #define EXPR_OP(c)     ((int)((c) & 0xffu))
 #define EXPR_ARG(c)    ((int)(int8_t)(((c) >> 8) & 0xffu))
 #define EXPR_AROOT(c)  ((int)(((c) >> 16) & 0xffu))
-
-// thread -> (point q, row i, that point's x in LDS); false: nothing to do.  FLAT: ppw points per workgroup.
-template <bool FLAT>
-__device__ static inline bool expr_place(int m, int n, int nblk, int ppw, int npoints, const double *__restrict__ X, double *xs, int &q, int &i,
-                                         const double *&xq)
-{
-    if (FLAT) {
-        const int q0 = blockIdx.x * ppw, nq = min(ppw, npoints - q0);
-        for (int e = threadIdx.x; e < nq * n; e += 256) xs[e] = X[(size_t)q0 * n + e];
-        __syncthreads();
-        const int lp = threadIdx.x / m;
-        q = q0 + lp; i = threadIdx.x - lp * m; xq = xs + lp * n;
-        return lp < nq;
-    }
-    q = blockIdx.x / nblk;
-    const int rb = blockIdx.x - q * nblk;
-    for (int c = threadIdx.x; c < n; c += 256) xs[c] = X[(size_t)q * n + c];
-    __syncthreads();
-    i = rb * 256 + threadIdx.x; xq = xs;
-    return i < m;
-}
 
 // One pass over the program.  vs: this thread's column of the value stack (slot s at vs[s * 256]); ts: of the C tangent
 // stacks (column c, slot s at ts[(c * depth + s) * 256]), columns j0 .. j0 + C - 1 (C = 0: values only).  Returns the
@@ -172,7 +152,7 @@ k_expr_fcn(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints,
     extern __shared__ double lds[];                               // x of the workgroup's points, then the value stack
     int q, i;
     const double *xq;
-    const bool on = expr_place<FLAT>(ed.m, n, nblk, ppw, npoints, X, lds, q, i, xq);
+    const bool on = place_staged<FLAT>(ed.m, n, nblk, ppw, npoints, X, lds, q, i, xq);
     const int qc = min(q, npoints - 1), ic = min(i, ed.m - 1);
     const int p = dprob ? dprob[qc] : qc;
     const size_t at = (size_t)p * ed.m + ic;
@@ -196,7 +176,7 @@ k_expr_jac(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints,
     extern __shared__ double lds[];                               // x, the value stack, C tangent stacks
     int q, i;
     const double *xq;
-    const bool on = expr_place<FLAT>(ed.m, n, nblk, ppw, npoints, X, lds, q, i, xq);
+    const bool on = place_staged<FLAT>(ed.m, n, nblk, ppw, npoints, X, lds, q, i, xq);
     const int qc = min(q, npoints - 1), ic = min(i, ed.m - 1);
     const int p = dprob ? dprob[qc] : qc;
     const size_t at = (size_t)p * ed.m + ic;

@@ -21,6 +21,7 @@
 // loads are issued before the first store, unconditionally on a clamped (point, row).
 #pragma once
 #include "nlh_internal.h"
+#include "nlh_kernels_place.h"
 
 struct LossArgs {
     int kind;                          // NLH_LOSS_*
@@ -72,13 +73,6 @@ static __device__ __forceinline__ void loss_eval(int kind, double c, double r, d
     }
 }
 
-// q0 .. q0 + cnt as a problem list (a caller that passed no dprob, for the inner launcher)
-static __global__ void __launch_bounds__(256) k_loss_iota(int cnt, int q0, int32_t *__restrict__ list)
-{
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q < cnt) list[q] = q0 + q;
-}
-
 // in place on the inner launcher's F [npoints][m]: a thread per (point, row)
 static __global__ void __launch_bounds__(256) k_loss_fcn(LossArgs A, int m, int npoints, double *__restrict__ F)
 {
@@ -111,14 +105,7 @@ static __global__ void __launch_bounds__(256)
 k_loss_jac(LossArgs A, int m, int n, int nblk, int ppw, int cpg, int npoints, const double *__restrict__ R, double *J)
 {
     int q, i;
-    if (FLAT) {
-        const int lp = threadIdx.x / m;
-        q = blockIdx.x * ppw + lp; i = threadIdx.x - lp * m;
-        if (lp >= ppw) q = npoints;
-    } else {
-        q = blockIdx.x / nblk;
-        i = (blockIdx.x - q * nblk) * 256 + threadIdx.x;
-    }
+    place_row<FLAT>(m, nblk, ppw, npoints, q, i);
     const bool on = q < npoints && i < m;
     const int qc = min(q, npoints - 1), ic = min(i, m - 1);
     const size_t ms = (size_t)m;

@@ -18,6 +18,7 @@
 // the current one.
 #pragma once
 #include "nlh_internal.h"
+#include "nlh_kernels_place.h"
 
 struct PmapTables {                    // device copies, owned by a context, or by the map for its three batch steps
     int N, n;
@@ -58,27 +59,13 @@ k_pmap_gather(PmapTables T, int nprob, const double *__restrict__ full, double *
     if (T.kind[k] == NLH_PMAP_FREE) x[(size_t)p * T.n + T.index[k]] = full[e];
 }
 
-// q0 .. q0 + cnt as a problem list (a caller that passed no dprob, for the inner launcher)
-static __global__ void __launch_bounds__(256) k_pmap_iota(int cnt, int q0, int32_t *__restrict__ list)
-{
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q < cnt) list[q] = q0 + q;
-}
-
 // The contraction.  grid.x: workgroups over (point, row block) -- FLAT: ppw points each --, grid.y: groups of cpg free columns.
 template <bool FLAT>
 static __global__ void __launch_bounds__(256)
 k_pmap_jac(PmapTables T, int m, int nblk, int ppw, int cpg, int npoints, const double *__restrict__ Jf, double *__restrict__ J)
 {
     int q, i;
-    if (FLAT) {
-        const int lp = threadIdx.x / m;
-        q = blockIdx.x * ppw + lp; i = threadIdx.x - lp * m;
-        if (lp >= ppw) q = npoints;
-    } else {
-        q = blockIdx.x / nblk;
-        i = (blockIdx.x - q * nblk) * 256 + threadIdx.x;
-    }
+    place_row<FLAT>(m, nblk, ppw, npoints, q, i);
     const bool on = q < npoints && i < m;
     const int qc = min(q, npoints - 1), ic = min(i, m - 1);
     const size_t ms = (size_t)m;

@@ -84,22 +84,48 @@ struct nlh_dq_model {
     nlh_device_vecfcn ufcn = nullptr;
     nlh_device_jacfcn ujac = nullptr;
     void *uctx = nullptr;
-    // a built-in curve model (nlh_curve_model_create): uctx is this context, which the model owns together with the device
-    // copies of t, y, w behind it (one allocation, curve_base, on curve_device)
+    // The four launcher-backed kinds the library makes itself: uctx is the kind's context below, which the model owns
+    // together with the device copy of the host arrays behind it -- one allocation, owned, on owned_device.
+    void *owned = nullptr;
+    int owned_device = 0;
+    // a built-in curve model (nlh_curve_model_create): t, y, w
     nlh_curve_ctx *curve = nullptr;
-    void *curve_base = nullptr;
-    int curve_device = 0;
-    // a formula model (nlh_expr_model_create): uctx is this context; the model owns it, the copy of the program behind it
-    // and the device copies of t, y, w (curve_base on curve_device, as the curve model's)
+    // a formula model (nlh_expr_model_create): t, y, w, and a copy of the program
     nlh_expr_ctx *expr = nullptr;
     nlh_expr *expr_prog = nullptr;
-    // a mapped model (nlh_pmap_model_create): uctx is this wrapping context around another model's launchers; the model owns
-    // it and the device copy of the full parameters behind it (curve_base on curve_device)
+    // a mapped model (nlh_pmap_model_create): the wrapping context around another model's launchers; the full parameters
     nlh_pmap_ctx *pmap = nullptr;
-    // a model with a loss (nlh_loss_model_create): uctx is this wrapping context around another model's launchers; the model
-    // owns it and the device copy of the scales behind it (curve_base on curve_device)
+    // a model with a loss (nlh_loss_model_create): the wrapping context around another model's launchers; the scales
     nlh_loss_ctx *loss = nullptr;
 };
+
+// Host arrays, one after the other, into one device allocation on the handle's device; synchronised (nlh_internal.h).
+int nlh_upload(nlh_handle *h, const char *what, std::initializer_list<HostPart> parts, void **base)
+{
+    *base = nullptr;
+    HIPCHK(h, hipSetDevice(h->device));
+    size_t bytes = 0;
+    for (const HostPart &p : parts) bytes += p.bytes;
+    char *d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) {
+        h->err = std::string("hipMalloc (") + what + ")";
+        return NLH_OUT_OF_MEMORY_ERROR;
+    }
+    hipError_t e = hipSuccess;
+    size_t at = 0;
+    for (const HostPart &p : parts) {
+        if (e == hipSuccess && p.bytes) e = hipMemcpyAsync(d + at, p.p, p.bytes, hipMemcpyHostToDevice, h->stream);
+        at += p.bytes;
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        hipFree(d);
+        h->err = std::string("hipMemcpy (") + what + "): " + hipGetErrorString(e);
+        return NLH_ERR_HIP;
+    }
+    *base = d;
+    return 0;
+}
 
 int nlh_device_fcn_model_create(int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn, nlh_device_jacfcn jacfcn, void *ctx,
                                 nlh_dq_model **out)
@@ -198,29 +224,17 @@ int nlh_curve_model_create(nlh_handle *h, int32_t kind, int32_t ncomp, int32_t n
     const int32_t n = nlh_curve_nparams(kind, ncomp, nbase);
     if (!out || n < 0 || nprob < 1 || m < 1 || !t || !y) return NLH_INVALID_INPUT_ERROR;
     if (m < n) return NLH_UNDERDEFINED_PROBLEM_ERROR;
-    HIPCHK(h, hipSetDevice(h->device));
     const size_t pm = (size_t)nprob * m, tm = shared_t ? (size_t)m : pm;
     double *base = nullptr;
-    if (hipMalloc(&base, sizeof(double) * (tm + pm * (w ? 2 : 1))) != hipSuccess) {
-        h->err = "hipMalloc (curve model)";
-        return NLH_OUT_OF_MEMORY_ERROR;
-    }
-    hipError_t e = hipMemcpyAsync(base, t, sizeof(double) * tm, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + tm, y, sizeof(double) * pm, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && w) e = hipMemcpyAsync(base + tm + pm, w, sizeof(double) * pm, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        hipFree(base);
-        h->err = std::string("hipMemcpy (curve model): ") + hipGetErrorString(e);
-        return NLH_ERR_HIP;
-    }
+    if (const int rc = nlh_upload(h, "curve model", {{t, sizeof(double) * tm}, {y, sizeof(double) * pm}, {w, w ? sizeof(double) * pm : 0}},
+                                  (void **)&base)) return rc;
     nlh_curve_ctx *c = new nlh_curve_ctx();
     c->kind = kind; c->ncomp = ncomp; c->nbase = nbase; c->shared_t = shared_t != 0; c->m = m;
     c->dt = base; c->dy = base + tm; c->dw = w ? base + tm + pm : nullptr;
     nlh_dq_model *md = new nlh_dq_model();
     md->nprob = nprob; md->m = m; md->n = n; md->gamma = 0.0;
     md->ufcn = nlh_curve_device_fcn; md->ujac = analytic ? nlh_curve_device_jac : nullptr; md->uctx = c;
-    md->curve = c; md->curve_base = base; md->curve_device = h->device;
+    md->curve = c; md->owned = base; md->owned_device = h->device;
     *out = md;
     return 0;
 }
@@ -234,22 +248,10 @@ int nlh_expr_model_create(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32
     if (!out || !e || nprob < 1 || m < 1 || !t || !y) return NLH_INVALID_INPUT_ERROR;
     const int32_t n = e->prog.nparams;
     if (m < n) return NLH_UNDERDEFINED_PROBLEM_ERROR;
-    HIPCHK(h, hipSetDevice(h->device));
     const size_t pm = (size_t)nprob * m, stride = shared_t ? (size_t)m : pm, tm = stride * e->prog.nvar;
     double *base = nullptr;
-    if (hipMalloc(&base, sizeof(double) * (tm + pm * (w ? 2 : 1))) != hipSuccess) {
-        h->err = "hipMalloc (formula model)";
-        return NLH_OUT_OF_MEMORY_ERROR;
-    }
-    hipError_t er = hipMemcpyAsync(base, t, sizeof(double) * tm, hipMemcpyHostToDevice, h->stream);
-    if (er == hipSuccess) er = hipMemcpyAsync(base + tm, y, sizeof(double) * pm, hipMemcpyHostToDevice, h->stream);
-    if (er == hipSuccess && w) er = hipMemcpyAsync(base + tm + pm, w, sizeof(double) * pm, hipMemcpyHostToDevice, h->stream);
-    if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
-    if (er != hipSuccess) {
-        hipFree(base);
-        h->err = std::string("hipMemcpy (formula model): ") + hipGetErrorString(er);
-        return NLH_ERR_HIP;
-    }
+    if (const int rc = nlh_upload(h, "formula model", {{t, sizeof(double) * tm}, {y, sizeof(double) * pm}, {w, w ? sizeof(double) * pm : 0}},
+                                  (void **)&base)) return rc;
     nlh_dq_model *md = new nlh_dq_model();
     md->expr_prog = new nlh_expr(*e);
     nlh_expr_ctx *c = new nlh_expr_ctx();
@@ -257,7 +259,7 @@ int nlh_expr_model_create(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32
     c->dt = base; c->dy = base + tm; c->dw = w ? base + tm + pm : nullptr;
     md->nprob = nprob; md->m = m; md->n = n; md->gamma = 0.0;
     md->ufcn = nlh_expr_device_fcn; md->ujac = analytic ? nlh_expr_device_jac : nullptr; md->uctx = c;
-    md->expr = c; md->curve_base = base; md->curve_device = h->device;
+    md->expr = c; md->owned = base; md->owned_device = h->device;
     *out = md;
     return 0;
 }
@@ -272,27 +274,16 @@ int nlh_pmap_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_pm
     int32_t N, n;
     nlh_pmap_shape(pm, &N, &n, nullptr);
     if (N != inner->n) return NLH_INVALID_INPUT_ERROR;
-    HIPCHK(h, hipSetDevice(h->device));
     const size_t cnt = (shared_full ? 1 : (size_t)inner->nprob) * N;
     double *base = nullptr;
-    if (hipMalloc(&base, sizeof(double) * cnt) != hipSuccess) {
-        h->err = "hipMalloc (mapped model)";
-        return NLH_OUT_OF_MEMORY_ERROR;
-    }
-    hipError_t e = hipMemcpyAsync(base, full, sizeof(double) * cnt, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        hipFree(base);
-        h->err = std::string("hipMemcpy (mapped model): ") + hipGetErrorString(e);
-        return NLH_ERR_HIP;
-    }
+    if (const int urc = nlh_upload(h, "mapped model", {{full, sizeof(double) * cnt}}, (void **)&base)) return urc;
     nlh_pmap_ctx *pc = nullptr;
     const int rc = nlh_pmap_wrap(h, pm, inner->ufcn, inner->ujac, inner->uctx, base, shared_full, &pc);
     if (rc) { hipFree(base); return rc; }
     nlh_dq_model *md = new nlh_dq_model();
     md->nprob = inner->nprob; md->m = inner->m; md->n = n; md->gamma = 0.0;
     md->ufcn = nlh_pmap_device_fcn; md->ujac = inner->ujac ? nlh_pmap_device_jac : nullptr; md->uctx = pc;
-    md->pmap = pc; md->curve_base = base; md->curve_device = h->device;
+    md->pmap = pc; md->owned = base; md->owned_device = h->device;
     *out = md;
     return 0;
 }
@@ -313,7 +304,7 @@ int nlh_loss_model_create(nlh_handle *h, const nlh_dq_model *inner, int32_t kind
     nlh_dq_model *md = new nlh_dq_model();
     md->nprob = inner->nprob; md->m = inner->m; md->n = inner->n; md->gamma = 0.0;
     md->ufcn = nlh_loss_device_fcn; md->ujac = inner->ujac ? nlh_loss_device_jac : nullptr; md->uctx = lc;
-    md->loss = lc; md->curve_base = base; md->curve_device = h->device;
+    md->loss = lc; md->owned = base; md->owned_device = h->device;
     *out = md;
     return 0;
 }
@@ -325,7 +316,7 @@ void nlh_dq_model_destroy(nlh_dq_model *md)
     nlh_loss_unwrap(md->loss);
     delete md->expr;
     delete md->expr_prog;
-    if (md->curve_base) { hipSetDevice(md->curve_device); hipFree(md->curve_base); }
+    if (md->owned) { hipSetDevice(md->owned_device); hipFree(md->owned); }
     delete md->curve;
     for (auto &pt : md->parts)
         if (pt.dA) { hipSetDevice(pt.device); hipFree(pt.dA); }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The ISA condition of the parameter-map kernels, checked by cross-compiling: for every instantiation of
-k_pmap_expand, k_pmap_gather, k_pmap_iota, k_pmap_jac and k_pmap_cov, no private segment, no spilled VGPR and no scratch
+k_pmap_expand, k_pmap_gather, k_pmap_jac and k_pmap_cov and of the shared k_wrap_iota, no private segment, no spilled VGPR and no scratch
 instruction; the vector stores to global memory (global_store, flat_store, buffer_store) are counted and printed beside
 them.  Compiles nonlin_amd/csrc/nlh_pmap.hip for gfx950 to assembly (needs hipcc, no GPU), prints the summary that is
 committed as profiles/pmap_isa.txt, and exits 1 when a kernel breaks the condition.
@@ -26,7 +26,7 @@ def main():
                                 "group_segment_fixed_size", "kernarg_segment_size")}
     bad = False
     print("parameter-map kernels, gfx950, flags: " + " ".join(FLAGS))
-    for name in sorted(n for n in meta if "k_pmap_" in n):
+    for name in sorted(n for n in meta if "k_pmap_" in n or "k_wrap_iota" in n):
         body = asm[asm.index(name + ":"):]
         body = body[:body.index(".Lfunc_end")]
         ins = [ln.split()[0] for ln in body.splitlines() if ln.startswith("\t") and ln.strip() and not ln.strip().startswith((".", ";"))]
