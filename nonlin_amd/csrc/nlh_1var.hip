@@ -108,9 +108,6 @@ static int r1_lockstep(nlh_handle *h, const nlh_options *o, int kind, bool user_
     return 0;
 }
 
-// Problems per lock-step run: at most two points per problem, and the point offsets are int32.
-static const int32_t R1_SLICE = 1 << 28;
-
 // One problem behind host callbacks (fcnnvar flattened to C, called with n = 1).
 static int r1_host(nlh_handle *h, const nlh_options *o, int kind, nlh_fcnnvar fcn, nlh_fcnnvar diff, void *ctx, double x1,
                    double x2, double *x, double *f, nlh_iteration_behavior *ib)
@@ -185,24 +182,20 @@ static int r1_batch_device(nlh_handle *h, const nlh_options *o, int kind, int32_
     if (!o || nprob < 0 || (nprob > 0 && (!dlim || !dx))) return NLH_INVALID_INPUT_ERROR;
     if (nprob == 0) return 0;
     HIPCHK(h, hipSetDevice(h->device));
-    for (int64_t p0 = 0; p0 < nprob; p0 += R1_SLICE) {               // (int64: p0 + R1_SLICE may pass INT32_MAX)
-        const int32_t cnt = (int32_t)std::min<int64_t>(R1_SLICE, nprob - p0);
-        R1Eval ev = [&](int32_t npoints, const int32_t *dprob, const double *dxs, double *dfs, double *dds, const int32_t *,
-                        bool diff_round) -> int {
-            int urc = fcn(ctx, (void *)h->stream, npoints, dprob, 1, dxs, 1, dfs);
-            if (urc) { h->err = "fcn1var: the user's launcher returned " + std::to_string(urc); return NLH_ERR_HIP; }
-            if (diff && diff_round) {
-                urc = diff(ctx, (void *)h->stream, npoints, dprob, 1, dxs, 1, dds);
-                if (urc) { h->err = "fcn1var: the user's derivative launcher returned " + std::to_string(urc); return NLH_ERR_HIP; }
-            }
-            return 0;
-        };
-        const int rc = r1_lockstep(h, o, kind, diff != nullptr, fout != nullptr, cnt, (int32_t)p0, ev, dlim + 2 * (size_t)p0,
-                                   dx + p0, false, false, fout ? fout + p0 : nullptr, ib ? ib + p0 : nullptr,
-                                   status ? status + p0 : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    R1Eval ev = [&](int32_t npoints, const int32_t *dprob, const double *dxs, double *dfs, double *dds, const int32_t *,
+                    bool diff_round) -> int {
+        int urc = fcn(ctx, (void *)h->stream, npoints, dprob, 1, dxs, 1, dfs);
+        if (urc) return launcher_failed(h, urc, "fcn1var");
+        if (diff && diff_round && (urc = diff(ctx, (void *)h->stream, npoints, dprob, 1, dxs, 1, dds)))
+            return launcher_failed(h, urc, "fcn1var", "derivative launcher");
+        return 0;
+    };
+    const BatchIO io = {dx, nullptr, fout, ib, status};
+    return lockstep_slices(nprob, slice_root1v(), [&](int32_t p0, int32_t cnt) {
+        const BatchIO q = io.at(p0, 1, 1);
+        return r1_lockstep(h, o, kind, diff != nullptr, fout != nullptr, cnt, p0, ev, dlim + 2 * (size_t)p0, q.x, false, false, q.fout, q.ib,
+                           q.status);
+    });
 }
 
 int nlh_brent_solve_batch_device(nlh_handle *h, const nlh_options *o, int32_t nprob, nlh_device_vecfcn fcn, void *ctx,
@@ -228,18 +221,11 @@ int nlh_root1v_solve_batch_device_h(nlh_handle *h, const nlh_options *o, int new
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;
     if (!o || nprob < 0 || (nprob > 0 && (!lim || !x))) return NLH_INVALID_INPUT_ERROR;
     if (nprob == 0) return 0;
-    int rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    if ((rc = ensure(h, h->xdev, sizeof(double) * 3 * (size_t)nprob))) return rc;
-    double *dlim = (double *)h->xdev.p, *dx = dlim + 2 * (size_t)nprob;
-    HIPCHK(h, hipMemcpyAsync(dlim, lim, sizeof(double) * 2 * (size_t)nprob, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(dx, x, sizeof(double) * (size_t)nprob, hipMemcpyHostToDevice, h->stream));
-    if ((rc = r1_batch_device(h, o, newton ? R1_NEWTON : R1_BRENT, nprob, fcn, newton ? diff : nullptr, ctx, dlim, dx, fout,
-                              ib, status)))
-        return rc;
-    HIPCHK(h, hipMemcpyAsync(x, dx, sizeof(double) * (size_t)nprob, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return staged_call(h, {{const_cast<double *>(lim), sizeof(double) * 2 * (size_t)nprob, true, false, &h->fdev},
+                           {x, sizeof(double) * (size_t)nprob, true, true, &h->xdev}}, [&](void *const *d) {
+        return r1_batch_device(h, o, newton ? R1_NEWTON : R1_BRENT, nprob, fcn, newton ? diff : nullptr, ctx, (const double *)d[0],
+                               (double *)d[1], fout, ib, status);
+    });
 }
 
 // fcn1var_helper%diff on the host: the user's derivative, or the forward difference of :189-198 (f at x + h first, then

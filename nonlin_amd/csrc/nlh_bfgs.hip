@@ -404,6 +404,15 @@ static int bfgs_lockstep(nlh_handle *h, const nlh_options *o, int32_t nprob, int
     return 0;
 }
 
+// The lock-step solver over a batch, in the slices its residual source holds (a user's objective is a scalar: m = 1).
+static int bfgs_batch_rs(nlh_handle *h, const nlh_options *o, int32_t nprob, int32_t m, int32_t n, const ResidualSource &rs, double *dx,
+                         double *hfout, nlh_iteration_behavior *ib, int32_t *status)
+{
+    return residual_slices(rs, nprob, m, n, {dx, nullptr, hfout, ib, status}, [&](int32_t cnt, const ResidualSource &r, const BatchIO &q) {
+        return bfgs_lockstep(h, o, cnt, m, n, r, rs.user(), q.x, q.fout, q.ib, q.status);
+    });
+}
+
 int nlh_dq_bfgs_solve_batch(nlh_handle *h, const nlh_options *o, int32_t nprob, int32_t m, int32_t n, const double *dA,
                             const double *db, double gamma, double *dx, double *hfout, nlh_iteration_behavior *ib,
                             int32_t *status)
@@ -412,14 +421,8 @@ int nlh_dq_bfgs_solve_batch(nlh_handle *h, const nlh_options *o, int32_t nprob, 
     if (!o || n < 1 || m < 1) return NLH_INVALID_INPUT_ERROR;
     HIPCHK(h, hipSetDevice(h->device));
     static const int bfgs_host = [] { const char *e = getenv("NLH_BFGS_HOSTLOOP"); return e ? atoi(e) : 0; }();
-    if (!bfgs_host) {
-        ResidualSource rs;
-        rs.dA = dA; rs.db = db; rs.gamma = gamma;
-        return lockstep_slices(nprob, [&](int32_t p0, int32_t cnt) {
-            return bfgs_lockstep(h, o, cnt, m, n, rs.shifted(p0, m, n), false, dx + (size_t)p0 * n,
-                                 hfout ? hfout + p0 : nullptr, ib ? ib + p0 : nullptr, status ? status + p0 : nullptr);
-        });
-    }
+    if (!bfgs_host)
+        return bfgs_batch_rs(h, o, nprob, m, n, ResidualSource::dense_quadratic(dA, db, gamma), dx, hfout, ib, status);
     // one problem per call; run_problems deals the problems to worker threads with private handles
     auto solve_one = [&](nlh_handle *h, int p) -> int {
         int rc;
@@ -482,19 +485,8 @@ int nlh_bfgs_solve_batch_device(nlh_handle *h, const nlh_options *o, int32_t npr
     if (!o || n < 1 || (nprob > 0 && !dx)) return NLH_INVALID_INPUT_ERROR;
     if (nprob <= 0) return 0;
     HIPCHK(h, hipSetDevice(h->device));
-    nlh_options oq = *o;
-    if (nprob > 1) oq.print_status = 0;
-    ResidualSource rs;
-    rs.fcn = fcn; rs.jac = gradfcn; rs.ctx = ctx;
-    // (a launcher is asked for nprob * n points at once)
-    const int32_t slice = (int32_t)std::max<int64_t>(1, std::min<int64_t>(NLH_MAX_LOCKSTEP, ((int64_t)1 << 30) / n));
-    for (int32_t p0 = 0; p0 < nprob; p0 += slice) {
-        const int32_t cnt = std::min<int32_t>(slice, nprob - p0);
-        const int rc = bfgs_lockstep(h, &oq, cnt, 1, n, rs.shifted(p0, 1, n), true, dx + (size_t)p0 * n, hfout ? hfout + p0 : nullptr,
-                                     ib ? ib + p0 : nullptr, status ? status + p0 : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    const nlh_options oq = silent_in_batch(*o, nprob);
+    return bfgs_batch_rs(h, &oq, nprob, 1, n, ResidualSource::launchers(fcn, gradfcn, ctx), dx, hfout, ib, status);
 }
 
 // The same behind a host array.
@@ -506,15 +498,9 @@ int nlh_bfgs_solve_batch_device_h(nlh_handle *h, const nlh_options *o, int32_t n
     if (nprob <= 0) return 0;
     if (!x || !o || n < 1) return NLH_INVALID_INPUT_ERROR;
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;
-    int rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    if ((rc = ensure(h, h->xdev, sizeof(double) * (size_t)nprob * n))) return rc;
-    double *dx = (double *)h->xdev.p;
-    HIPCHK(h, hipMemcpyAsync(dx, x, sizeof(double) * (size_t)nprob * n, hipMemcpyHostToDevice, h->stream));
-    if ((rc = nlh_bfgs_solve_batch_device(h, o, nprob, n, fcn, gradfcn, ctx, dx, fout, ib, status))) return rc;
-    HIPCHK(h, hipMemcpyAsync(x, dx, sizeof(double) * (size_t)nprob * n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return staged_call(h, {{x, sizeof(double) * (size_t)nprob * n, true, true, &h->xdev}}, [&](void *const *d) {
+        return nlh_bfgs_solve_batch_device(h, o, nprob, n, fcn, gradfcn, ctx, (double *)d[0], fout, ib, status);
+    });
 }
 
 // cholesky_rank1_update / cholesky_rank1_downdate stand-ins (call sites src/nonlin_optimize.f90:721-722): in place on the

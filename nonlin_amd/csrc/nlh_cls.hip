@@ -403,6 +403,16 @@ static int cls_lockstep(nlh_handle *h, const nlh_options *o, double delta0, doub
     return 0;
 }
 
+// The lock-step solver over a batch, in the slices its residual source holds.
+static int cls_batch_rs(nlh_handle *h, const nlh_options *o, double delta0, double stepscale0, const double *xl, const double *xu,
+                        int32_t nprob, int32_t m, int32_t n, const ResidualSource &rs, double *dx, double *dfvec,
+                        nlh_iteration_behavior *ib, int32_t *status)
+{
+    return residual_slices(rs, nprob, m, n, {dx, dfvec, nullptr, ib, status}, [&](int32_t cnt, const ResidualSource &r, const BatchIO &q) {
+        return cls_lockstep(h, o, delta0, stepscale0, xl, xu, cnt, m, n, r, q.x, q.fvec, q.ib, q.status);
+    });
+}
+
 int nlh_dq_cls_solve_batch(nlh_handle *h, const nlh_options *o, double delta0, double stepscale0, const double *xl,
                            const double *xu, int32_t nprob, int32_t m, int32_t n, const double *dA, const double *db,
                            double gamma, double *dx, double *dfvec, nlh_iteration_behavior *ib, int32_t *status)
@@ -412,14 +422,9 @@ int nlh_dq_cls_solve_batch(nlh_handle *h, const nlh_options *o, double delta0, d
     if (n > m) return NLH_UNDERDEFINED_PROBLEM_ERROR;
     HIPCHK(h, hipSetDevice(h->device));
     static const int cls_host = [] { const char *e = getenv("NLH_CLS_HOSTLOOP"); return e ? atoi(e) : 0; }();
-    if (!cls_host) {
-        ResidualSource rs;
-        rs.dA = dA; rs.db = db; rs.gamma = gamma;
-        return lockstep_slices(nprob, [&](int32_t p0, int32_t cnt) {
-            return cls_lockstep(h, o, delta0, stepscale0, xl, xu, cnt, m, n, rs.shifted(p0, m, n),
-                                dx + (size_t)p0 * n, dfvec + (size_t)p0 * m, ib ? ib + p0 : nullptr, status ? status + p0 : nullptr);
-        });
-    }
+    if (!cls_host)
+        return cls_batch_rs(h, o, delta0, stepscale0, xl, xu, nprob, m, n, ResidualSource::dense_quadratic(dA, db, gamma), dx, dfvec, ib,
+                            status);
     // one problem per call; run_problems deals the problems to worker threads with private handles
     auto solve_one = [&](nlh_handle *h, int p) -> int {
         int rc;
@@ -479,18 +484,8 @@ int nlh_cls_solve_batch_device(nlh_handle *h, const nlh_options *o, double delta
     if (!o || n < 1 || m < 1 || !dx || !dfvec) return NLH_INVALID_INPUT_ERROR;
     if (n > m) return NLH_UNDERDEFINED_PROBLEM_ERROR;           // :989
     HIPCHK(h, hipSetDevice(h->device));
-    ResidualSource rs;
-    rs.fcn = fcn; rs.jac = jacfcn; rs.ctx = ctx;
-    nlh_options oq = *o;
-    if (nprob > 1) oq.print_status = 0;
-    const int32_t slice = (int32_t)std::max<int64_t>(1, std::min<int64_t>(NLH_MAX_LOCKSTEP, ((int64_t)1 << 30) / n));
-    for (int32_t p0 = 0; p0 < nprob; p0 += slice) {
-        const int32_t cnt = std::min<int32_t>(slice, nprob - p0);
-        const int rc = cls_lockstep(h, &oq, delta0, stepscale0, xl, xu, cnt, m, n, rs.shifted(p0, m, n), dx + (size_t)p0 * n,
-                                    dfvec + (size_t)p0 * m, ib ? ib + p0 : nullptr, status ? status + p0 : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    const nlh_options oq = silent_in_batch(*o, nprob);
+    return cls_batch_rs(h, &oq, delta0, stepscale0, xl, xu, nprob, m, n, ResidualSource::launchers(fcn, jacfcn, ctx), dx, dfvec, ib, status);
 }
 
 int nlh_cls_solve_batch_device_h(nlh_handle *h, const nlh_options *o, double delta0, double stepscale0, const double *xl, const double *xu,
@@ -501,15 +496,10 @@ int nlh_cls_solve_batch_device_h(nlh_handle *h, const nlh_options *o, double del
     if (nprob <= 0) return 0;
     if (!o || !x || !fvec || n < 1 || m < 1) return NLH_INVALID_INPUT_ERROR;
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = ensure(h, h->xdev, sizeof(double) * (size_t)nprob * n))) return rc;
-    if ((rc = ensure(h, h->fdev, sizeof(double) * (size_t)nprob * m))) return rc;
-    double *dx = (double *)h->xdev.p, *df = (double *)h->fdev.p;
-    HIPCHK(h, hipMemcpyAsync(dx, x, sizeof(double) * (size_t)nprob * n, hipMemcpyHostToDevice, h->stream));
-    if ((rc = nlh_cls_solve_batch_device(h, o, delta0, stepscale0, xl, xu, nprob, m, n, fcn, jacfcn, ctx, dx, df, ib, status))) return rc;
-    HIPCHK(h, hipMemcpyAsync(x, dx, sizeof(double) * (size_t)nprob * n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(fvec, df, sizeof(double) * (size_t)nprob * m, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
+    const size_t xbytes = sizeof(double) * (size_t)nprob * n, fbytes = sizeof(double) * (size_t)nprob * m;
+    return staged_call(h, {{x, xbytes, true, true, &h->xdev}, {fvec, fbytes, false, true, &h->fdev}},
+                       [&](void *const *d) {
+                           return nlh_cls_solve_batch_device(h, o, delta0, stepscale0, xl, xu, nprob, m, n, fcn, jacfcn, ctx, (double *)d[0],
+                                                             (double *)d[1], ib, status);
+                       });
 }

@@ -260,8 +260,7 @@ void launch_dq_residual(nlh_handle *h, int nprob, int m, int n, const double *A,
     const int nblk = (m + RB - 1) / RB;
     // the problem index rides in gridDim.y (65535 at most): more problems than that go in slices (the lock-step drivers
     // slice their batches themselves; the stage-level and model entry points come here with whatever the caller has)
-    for (int p0 = 0; p0 < nprob; p0 += NLH_MAX_LOCKSTEP) {
-        const int cnt = std::min<int>(NLH_MAX_LOCKSTEP, nprob - p0);
+    lockstep_slices(nprob, [&](int32_t p0, int32_t cnt) {
         dim3 grid(nblk, cnt);
         const double *Ap = A + (size_t)p0 * m * n, *bp = b + (size_t)p0 * m, *xp = x + (size_t)p0 * n;
         double *fp = f + (size_t)p0 * m, *pp = part ? part + (size_t)p0 * nblk * 2 : nullptr;
@@ -270,7 +269,8 @@ void launch_dq_residual(nlh_handle *h, int nprob, int m, int n, const double *A,
             hipLaunchKernelGGL(k_dq_residual2<RB / 2>, grid, dim3(RB / 2), sh, h->stream, m, n, Ap, bp, gamma, xp, fp, pp, sp, want);
         else
             hipLaunchKernelGGL(k_dq_residual<RB>, grid, dim3(RB), sh, h->stream, m, n, Ap, bp, gamma, xp, fp, pp, sp, want);
-    }
+        return 0;
+    });
 }
 
 void launch_dq_panel(nlh_handle *h, int nprob, int m, int n, const double *A, const double *b,
@@ -349,12 +349,29 @@ int nlh_format_status(int32_t iter, int32_t nfeval, int32_t njaceval, double xno
     return snprintf(buf, len > 0 ? (size_t)len : 0, " \nIteration: %d\nFunction Evaluations: %d\n%sChange in Variable: %s\nResidual: %s\n",
                     iter, nfeval, jl, a, b);
 }
-int lockstep_slices(int32_t nprob, const std::function<int(int32_t, int32_t)> &run)         // run(first, count)
+
+// The shell of a batch entry point (nlh_internal.h): a batch through a lock-step driver, the host-array twin.
+int residual_slices(const ResidualSource &rs, int32_t nprob, int m, int n, const BatchIO &io,
+                    const std::function<int(int32_t, const ResidualSource &, const BatchIO &)> &run)
 {
-    for (int32_t p0 = 0; p0 < nprob; p0 += NLH_MAX_LOCKSTEP) {
-        const int rc = run(p0, std::min<int32_t>(NLH_MAX_LOCKSTEP, nprob - p0));
-        if (rc) return rc;
+    return lockstep_slices(nprob, rs.slice(n), [&](int32_t p0, int32_t cnt) { return run(cnt, rs.shifted(p0, m, n), io.at(p0, m, n)); });
+}
+
+int staged_call(nlh_handle *h, std::initializer_list<HostArray> arrays, const std::function<int(void *const *)> &call)
+{
+    HIPCHK(h, hipSetDevice(h->device));
+    std::vector<void *> dev;
+    int rc;
+    for (const HostArray &a : arrays) {
+        if ((rc = ensure(h, *a.buf, a.bytes))) return rc;
+        dev.push_back(a.buf->p);
     }
+    for (const HostArray &a : arrays)
+        if (a.in) HIPCHK(h, hipMemcpyAsync(a.buf->p, a.host, a.bytes, hipMemcpyHostToDevice, h->stream));
+    if ((rc = call(dev.data()))) return rc;
+    for (const HostArray &a : arrays)
+        if (a.out) HIPCHK(h, hipMemcpyAsync(a.host, a.buf->p, a.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
 }
 

@@ -166,24 +166,18 @@ int nlh_lm_covariance_batch_device(nlh_handle *h, int32_t nprob, int32_t m, int3
     int rc = cv_check(m, n, scaled);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
-    ResidualSource rs;
-    rs.fcn = fcn; rs.jac = jacfcn; rs.ctx = ctx;
-    // slices: the lock-step kernels carry the problem index in a grid dimension (NLH_MAX_LOCKSTEP), and the point count of
-    // one launcher call stays inside 31 bits (as nlh_fd_jacobian_device)
-    const int32_t per = (int32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)nprob, (size_t)NLH_MAX_LOCKSTEP),
-                                                                      ((size_t)1 << 30) / ((size_t)n * std::max(m, n))));
-    for (int32_t p0 = 0; p0 < nprob; p0 += per) {
-        const int32_t cnt = std::min(per, nprob - p0);
+    const ResidualSource rs = ResidualSource::launchers(fcn, jacfcn, ctx);
+    return lockstep_slices(nprob, slice_panel(m, n), [&](int32_t p0, int32_t cnt) {
+        int rcs;
         CvWs w;
-        if ((rc = cv_workspace(h, cnt, m, n, false, w))) return rc;
+        if ((rcs = cv_workspace(h, cnt, m, n, false, w))) return rcs;
         const ResidualSource r = rs.shifted(p0, m, n);
         const double *xs = dx + (size_t)p0 * n;
-        if ((rc = residual_eval(h, r, cnt, m, n, xs, w.f, nullptr, nullptr, -1))) return rc;
-        if ((rc = residual_jacobian(h, r, cnt, m, n, xs, w.f, w.J, nullptr, nullptr, -1, false, false, true))) return rc;
-        if ((rc = cv_tail(h, cnt, m, n, w, scaled, tol, dcov + (size_t)p0 * n * n, dsigma ? dsigma + (size_t)p0 * n : nullptr,
-                          drank ? drank + p0 : nullptr, dchi2 ? dchi2 + p0 : nullptr))) return rc;
-    }
-    return 0;
+        if ((rcs = residual_eval(h, r, cnt, m, n, xs, w.f, nullptr, nullptr, -1))) return rcs;
+        if ((rcs = residual_jacobian(h, r, cnt, m, n, xs, w.f, w.J, nullptr, nullptr, -1, false, false, true))) return rcs;
+        return cv_tail(h, cnt, m, n, w, scaled, tol, dcov + (size_t)p0 * n * n, dsigma ? dsigma + (size_t)p0 * n : nullptr,
+                       drank ? drank + p0 : nullptr, dchi2 ? dchi2 + p0 : nullptr);
+    });
 }
 
 // device staging of the host-array forms (h->cvH): x, cov, sigma, chi2, rank for nprob problems

@@ -196,9 +196,9 @@ static int dv_select(nlh_handle *h, int nprob, const LmState *st, int want, size
     return 0;
 }
 
-static int dv_fail(nlh_handle *h, int rc, const char *what)
+int launcher_failed(nlh_handle *h, int rc, const char *what, const char *which)
 {
-    h->err = std::string(what) + ": the user's launcher returned " + std::to_string(rc);
+    h->err = std::string(what) + ": the user's " + which + " returned " + std::to_string(rc);
     return NLH_ERR_HIP;
 }
 
@@ -230,7 +230,7 @@ int residual_eval(nlh_handle *h, const ResidualSource &rs, int nprob, int m, int
     {
         Timed t(h, NLH_K_DQ_RESIDUAL);
         const int urc = rs.fcn(rs.ctx, (void *)h->stream, cnt, dprob, n, X, m, F);
-        if (urc) return dv_fail(h, urc, "vecfcn");
+        if (urc) return launcher_failed(h, urc, "vecfcn");
     }
     if (!direct)
         hipLaunchKernelGGL(k_dv_scatter_f, dim3((m + 255) / 256, cnt), dim3(256), 0, h->stream, m, (const int32_t *)list, (const double *)F, f);
@@ -296,7 +296,7 @@ int residual_jacobian(nlh_handle *h, const ResidualSource &rs, int nprob, int m,
                 {
                     Timed t(h, NLH_K_DQ_JACOBIAN);
                     const int urc = rs.jac(rs.ctx, (void *)h->stream, kc, dprob + k0, n, X + (size_t)k0 * n, m, Pc);
-                    if (urc) return dv_fail(h, urc, "jacobianfcn");
+                    if (urc) return launcher_failed(h, urc, "jacobianfcn");
                 }
                 const dim3 grid((((m + 7) & ~7) + 255) / 256, n, kc);
                 if (to_qrx) hipLaunchKernelGGL(k_dv_place_jac<true>, grid, dim3(256), 0, h->stream, m, n, (const double *)Pc, out + pshift * tst, lq, ld, coff, tst);
@@ -307,7 +307,7 @@ int residual_jacobian(nlh_handle *h, const ResidualSource &rs, int nprob, int m,
                 Timed t(h, NLH_K_DQ_PANEL);                     // (a share of) the n perturbed evaluations of the problems that are due
                 const size_t q0 = (size_t)k0 * n + j0;
                 const int urc = rs.fcn(rs.ctx, (void *)h->stream, kc * jn, dprob + q0, n, (const double *)X + q0 * n, m, Pc);
-                if (urc) return dv_fail(h, urc, "vecfcn");
+                if (urc) return launcher_failed(h, urc, "vecfcn");
             }
             Timed t(h, NLH_K_FD_JACOBIAN);                      // :274
             // (a column group of one problem: the kernels see a problem of jn columns whose arrays start at column j0)
@@ -502,14 +502,8 @@ int nlh_fd_jacobian_device(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, n
     if (nprob <= 0) return 0;
     if (m < 1 || n < 1 || !dx || !dJ) return NLH_INVALID_INPUT_ERROR;
     HIPCHK(h, hipSetDevice(h->device));
-    ResidualSource rs;
-    rs.fcn = fcn; rs.jac = jacfcn; rs.ctx = ctx;
-    // slices keep the point count of one launcher call (nprob * n) and the panel inside 31 bits / a bounded workspace
-    // ... and the problem count inside what the kernels carry in gridDim.y / .z (NLH_MAX_LOCKSTEP, as every other *_device entry point)
-    const int32_t per = (int32_t)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)nprob, (size_t)NLH_MAX_LOCKSTEP),
-                                                                      ((size_t)1 << 30) / ((size_t)n * std::max(m, n))));
-    for (int32_t p0 = 0; p0 < nprob; p0 += per) {
-        const int32_t cnt = std::min(per, nprob - p0);
+    const ResidualSource rs = ResidualSource::launchers(fcn, jacfcn, ctx);
+    const int rcs = lockstep_slices(nprob, slice_panel(m, n), [&](int32_t p0, int32_t cnt) {
         int rc;
         const double *f0 = dfv ? dfv + (size_t)p0 * m : nullptr;
         ResidualSource r = rs.shifted(p0, m, n);
@@ -518,9 +512,9 @@ int nlh_fd_jacobian_device(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, n
             if ((rc = residual_eval(h, r, cnt, m, n, dx + (size_t)p0 * n, (double *)h->fdev.p, nullptr, nullptr, -1))) return rc;
             f0 = (const double *)h->fdev.p;
         }
-        if ((rc = residual_jacobian(h, r, cnt, m, n, dx + (size_t)p0 * n, f0, dJ + (size_t)p0 * m * n, nullptr, nullptr, -1, false,
-                                    false, true))) return rc;
-    }
+        return residual_jacobian(h, r, cnt, m, n, dx + (size_t)p0 * n, f0, dJ + (size_t)p0 * m * n, nullptr, nullptr, -1, false, false, true);
+    });
+    if (rcs) return rcs;
     HIPCHK(h, hipGetLastError());
     return 0;
 }

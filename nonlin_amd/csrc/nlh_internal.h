@@ -133,6 +133,40 @@ void launch_dq_panel(nlh_handle *h, int nprob, int m, int n, const double *A, co
                      double *P, const LmState *st, int want, const double *f0_fused = nullptr, bool to_qrx = false);
 void launch_fd(nlh_handle *h, int nprob, int m, int n, const double *P, const double *f0, const double *x, double *J,
                const LmState *st, int want);
+// ---------------------------------------------------------------------------
+// The shell of a batch entry point around its lock-step driver (nlh_core.hip): slices, host staging, a silent batch.
+// ---------------------------------------------------------------------------
+// Several kernels of the lock-step drivers carry the problem index in gridDim.y / .z (at most 65535): a larger batch is
+// solved in slices of NLH_MAX_LOCKSTEP problems, one after the other (independent problems: the same bits).
+static const int32_t NLH_MAX_LOCKSTEP = 65535;
+// The one slice loop: run(first, count) on consecutive runs of at most `slice` problems until one returns non-zero (a
+// 64-bit counter: first + slice may pass INT32_MAX).  A template, not a std::function: launch_dq_residual comes here once
+// per solver iteration, and its closure would not fit a std::function's own storage.
+template <class Run> static inline int lockstep_slices(int32_t nprob, int32_t slice, Run &&run)
+{
+    for (int64_t p0 = 0; p0 < nprob; p0 += slice) {
+        const int rc = run((int32_t)p0, (int32_t)std::min<int64_t>(slice, nprob - p0));
+        if (rc) return rc;
+    }
+    return 0;
+}
+template <class Run> static inline int lockstep_slices(int32_t nprob, Run &&run) { return lockstep_slices(nprob, NLH_MAX_LOCKSTEP, run); }
+// Slice lengths of a user's launcher (the lock-step ones also hold NLH_MAX_LOCKSTEP).
+// One Jacobian call asks the launcher for count * n points at once, and its panel is addressed with 31-bit point counts.
+static inline int32_t slice_points(int32_t n)
+{
+    return (int32_t)std::max<int64_t>(1, std::min<int64_t>(NLH_MAX_LOCKSTEP, ((int64_t)1 << 30) / n));
+}
+// A covariance or FD-Jacobian call keeps the whole panel: count * n points of max(m, n) doubles inside 31 bits.
+static inline int32_t slice_panel(int32_t m, int32_t n)
+{
+    return (int32_t)std::max<size_t>(1, std::min<size_t>((size_t)NLH_MAX_LOCKSTEP, ((size_t)1 << 30) / ((size_t)n * std::max(m, n))));
+}
+// Nelder-Mead's staging list holds count * (n + 1) points whose offsets are int32.
+static inline int32_t slice_simplex(int32_t n) { return (int32_t)std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)n + 1)); }
+// A scalar root has at most two points per problem in flight, and the point offsets are int32.
+static inline int32_t slice_root1v() { return 1 << 28; }
+
 // Which residual a lock-step driver evaluates (nlh_devfcn.hip): the built-in dense-quadratic family (dA, db, gamma), or a
 // user's launchers (include/nonlin_hip.h: nlh_device_vecfcn / nlh_device_jacfcn).  pbase: index, in the caller's batch,
 // of the first problem of the range the driver works on (slices, sub-batches) -- what the user's dprob entries count from.
@@ -143,7 +177,20 @@ struct ResidualSource {
     nlh_device_jacfcn jac = nullptr;
     void *ctx = nullptr;
     int32_t pbase = 0;
+    static ResidualSource dense_quadratic(const double *dA, const double *db, double gamma)
+    {
+        ResidualSource r;
+        r.dA = dA; r.db = db; r.gamma = gamma;
+        return r;
+    }
+    static ResidualSource launchers(nlh_device_vecfcn fcn, nlh_device_jacfcn jac, void *ctx)
+    {
+        ResidualSource r;
+        r.fcn = fcn; r.jac = jac; r.ctx = ctx;
+        return r;
+    }
     bool user() const { return fcn != nullptr; }
+    int32_t slice(int32_t n) const { return user() ? slice_points(n) : NLH_MAX_LOCKSTEP; }   // problems of one lock-step run
     ResidualSource shifted(int32_t p0, int m, int n) const
     {
         ResidualSource r = *this;
@@ -152,6 +199,36 @@ struct ResidualSource {
         return r;
     }
 };
+// What a lock-step driver reads and writes per problem: x [n] and fvec [m] on the device, fout, ib and status on the host;
+// any but x may be NULL.  at(p0): the same arrays from problem p0 on.
+struct BatchIO {
+    double *x, *fvec, *fout;
+    nlh_iteration_behavior *ib;
+    int32_t *status;
+    BatchIO at(int32_t p0, int m, int n) const
+    {
+        return {x + (size_t)p0 * n, fvec ? fvec + (size_t)p0 * m : nullptr, fout ? fout + p0 : nullptr, ib ? ib + p0 : nullptr,
+                status ? status + p0 : nullptr};
+    }
+};
+// A batch through a lock-step driver in slices of rs.slice(n): run(count, the slice's residual source, the slice's arrays).
+int residual_slices(const ResidualSource &rs, int32_t nprob, int m, int n, const BatchIO &io,
+                    const std::function<int(int32_t, const ResidualSource &, const BatchIO &)> &run);
+// The host-array twin of a device-pointer entry point: each host array gets a device copy in a buffer of the handle (in:
+// uploaded before the call), call(dev) runs the device form on dev[k], the copy of array k, and, when it returns 0, the out
+// arrays are downloaded and the stream is synchronised once.  A non-zero return of call copies nothing back.
+struct HostArray { void *host; size_t bytes; bool in, out; DevBuf *buf; };
+int staged_call(nlh_handle *h, std::initializer_list<HostArray> arrays, const std::function<int(void *const *)> &call);
+// A batch stays silent: the status block is a single solve's (the reference prints between the iterations of ONE solve), and a
+// slice, a sub-batch or a share of a dealt batch may hold a single problem.
+static inline nlh_options silent_in_batch(const nlh_options &o, int32_t nprob)
+{
+    nlh_options q = o;
+    if (nprob > 1) q.print_status = 0;
+    return q;
+}
+// h->err = "<what>: the user's <which> returned <rc>"; returns NLH_ERR_HIP (nlh_devfcn.hip)
+int launcher_failed(nlh_handle *h, int rc, const char *what, const char *which = "launcher");
 // F(x) for the problems at stage `want` (st == nullptr: every problem): x [nprob][n] -> f [nprob][m]; part (optional):
 // the per-block partial sums of squares k_dq_residual leaves (the non-exact policies' norms).
 int residual_eval(nlh_handle *h, const ResidualSource &rs, int nprob, int m, int n, const double *x, double *f, double *part,
@@ -310,11 +387,6 @@ static const int32_t NLH_DQ_MAX_N = 20000;
 static inline int factor_threads(int n) { return n >= 96 ? 1024 : 256; }
 void print_status(int iter, int nfeval, int njaceval, double xnorm, double fnorm);
 
-
-// Several kernels of the lock-step drivers carry the problem index in gridDim.y / .z (at most 65535): a larger batch is
-// solved in slices of NLH_MAX_LOCKSTEP problems, one after the other (independent problems: the same bits).
-static const int32_t NLH_MAX_LOCKSTEP = 65535;
-int lockstep_slices(int32_t nprob, const std::function<int(int32_t, int32_t)> &run);         // run(first, count)
 
 static const int QN_MAX_N = 8192;      // k_qn_retri / k_bf_chol_*: 8 columns per thread at most (4 up to n = 4096)
 // eight columns per thread: beyond 4096 columns -- or, NLH_QN_FORCE_NC8 (tests), wherever the four-column instance would run

@@ -536,23 +536,11 @@ static int lm_sub_batches(const nlh_options *o, int nprob, int m, int n)
     return S < 1 ? 1 : S;
 }
 
-static int lm_solve_batch_rs(nlh_handle *h, const nlh_options *o, int32_t nprob, int32_t m, int32_t n, const ResidualSource &rs,
-                             double *dx, double *dfvec, nlh_iteration_behavior *ib, int32_t *status)
+// One slice: dealt to sub-batches, or as one lock-step batch.
+static int lm_solve_slice(nlh_handle *h, const nlh_options *o, int32_t nprob, int32_t m, int32_t n, const ResidualSource &rs,
+                          double *dx, double *dfvec, nlh_iteration_behavior *ib, int32_t *status)
 {
-    if (!h) return NLH_ERR_BAD_HANDLE;
-    if (nprob <= 0) return 0;
-    int rc = check_opts_lm(o, m, n);
-    if (rc) return rc;
-    // a user's launcher is asked for nprob * n points at once and its panel is addressed with 31-bit point counts
-    const int32_t slice = rs.user() ? (int32_t)std::max<int64_t>(1, std::min<int64_t>(NLH_MAX_LOCKSTEP, ((int64_t)1 << 30) / n)) : NLH_MAX_LOCKSTEP;
-    if (nprob > slice) {
-        for (int32_t p0 = 0; p0 < nprob; p0 += slice) {
-            const int32_t cnt = std::min<int32_t>(slice, nprob - p0);
-            if ((rc = lm_solve_batch_rs(h, o, cnt, m, n, rs.shifted(p0, m, n), dx + (size_t)p0 * n, dfvec + (size_t)p0 * m, ib ? ib + p0 : nullptr,
-                                        status ? status + p0 : nullptr))) return rc;
-        }
-        return 0;
-    }
+    int rc;
     const int S = lm_sub_batches(o, nprob, m, n);
     if (S == 1) return lm_solve_range(h, o, nprob, m, n, rs, dx, dfvec, ib, status);
     if ((rc = ensure_workers(h, S))) return rc;
@@ -583,13 +571,23 @@ static int lm_solve_batch_rs(nlh_handle *h, const nlh_options *o, int32_t nprob,
     return 0;
 }
 
+static int lm_solve_batch_rs(nlh_handle *h, const nlh_options *o, int32_t nprob, int32_t m, int32_t n, const ResidualSource &rs,
+                             double *dx, double *dfvec, nlh_iteration_behavior *ib, int32_t *status)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (nprob <= 0) return 0;
+    const int rc = check_opts_lm(o, m, n);
+    if (rc) return rc;
+    return residual_slices(rs, nprob, m, n, {dx, dfvec, nullptr, ib, status}, [&](int32_t cnt, const ResidualSource &r, const BatchIO &q) {
+        return lm_solve_slice(h, o, cnt, m, n, r, q.x, q.fvec, q.ib, q.status);
+    });
+}
+
 int nlh_dq_lm_solve_batch(nlh_handle *h, const nlh_options *o, int32_t nprob, int32_t m, int32_t n,
                           const double *dA, const double *db, double gamma, double *dx, double *dfvec,
                           nlh_iteration_behavior *ib, int32_t *status)
 {
-    ResidualSource rs;
-    rs.dA = dA; rs.db = db; rs.gamma = gamma;
-    return lm_solve_batch_rs(h, o, nprob, m, n, rs, dx, dfvec, ib, status);
+    return lm_solve_batch_rs(h, o, nprob, m, n, ResidualSource::dense_quadratic(dA, db, gamma), dx, dfvec, ib, status);
 }
 
 // least_squares_solver%solve on a batch of problems whose residual is the USER'S device function (launchers,
@@ -602,11 +600,8 @@ int nlh_lm_solve_batch_device(nlh_handle *h, const nlh_options *o, int32_t nprob
     if (ib && nprob > 0) memset(ib, 0, sizeof(*ib) * (size_t)nprob);          // :177-185
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;              // :188
     if (!o || (nprob > 0 && (!dx || !dfvec))) return NLH_INVALID_INPUT_ERROR;
-    ResidualSource rs;
-    rs.fcn = fcn; rs.jac = jacfcn; rs.ctx = ctx;
-    nlh_options oq = *o;
-    if (nprob > 1) oq.print_status = 0;                         // the status block is a single solve's (:372-374)
-    return lm_solve_batch_rs(h, &oq, nprob, m, n, rs, dx, dfvec, ib, status);
+    const nlh_options oq = silent_in_batch(*o, nprob);          // (:372-374)
+    return lm_solve_batch_rs(h, &oq, nprob, m, n, ResidualSource::launchers(fcn, jacfcn, ctx), dx, dfvec, ib, status);
 }
 
 // The same behind host arrays (the Fortran shim's set_device_fcn + solve / solve_batch).
@@ -618,19 +613,13 @@ int nlh_lm_solve_batch_device_h(nlh_handle *h, const nlh_options *o, int32_t npr
     if (nprob <= 0) return 0;
     if (!x || !fvec || !o) return NLH_INVALID_INPUT_ERROR;
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;
-    int rc = check_opts_lm(o, m, n);
+    const int rc = check_opts_lm(o, m, n);
     if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    if ((rc = ensure(h, h->xdev, sizeof(double) * (size_t)nprob * n))) return rc;
-    if ((rc = ensure(h, h->fdev, sizeof(double) * (size_t)nprob * m))) return rc;
-    double *dx = (double *)h->xdev.p, *df = (double *)h->fdev.p;
-    HIPCHK(h, hipMemcpyAsync(dx, x, sizeof(double) * (size_t)nprob * n, hipMemcpyHostToDevice, h->stream));
-    rc = nlh_lm_solve_batch_device(h, o, nprob, m, n, fcn, jacfcn, ctx, dx, df, ib, status);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(x, dx, sizeof(double) * (size_t)nprob * n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(fvec, df, sizeof(double) * (size_t)nprob * m, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
+    const size_t xbytes = sizeof(double) * (size_t)nprob * n, fbytes = sizeof(double) * (size_t)nprob * m;
+    return staged_call(h, {{x, xbytes, true, true, &h->xdev}, {fvec, fbytes, false, true, &h->fdev}},
+                       [&](void *const *d) {
+                           return nlh_lm_solve_batch_device(h, o, nprob, m, n, fcn, jacfcn, ctx, (double *)d[0], (double *)d[1], ib, status);
+                       });
 }
 
 // ===========================================================================

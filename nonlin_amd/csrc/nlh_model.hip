@@ -410,18 +410,12 @@ int nlh_dq_model_eval(nlh_handle *h, const nlh_dq_model *md, const double *x, do
     if (md->ufcn) {                                              // a user's device function: one point per problem
         if (!h) return NLH_ERR_BAD_HANDLE;
         if (!x || !f) return NLH_INVALID_INPUT_ERROR;
-        HIPCHK(h, hipSetDevice(h->device));
-        int rc;
-        const size_t nx = (size_t)md->nprob * md->n, nf = (size_t)md->nprob * md->m;
-        if ((rc = ensure(h, h->xdev, sizeof(double) * nx))) return rc;
-        if ((rc = ensure(h, h->fdev, sizeof(double) * nf))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->xdev.p, x, sizeof(double) * nx, hipMemcpyHostToDevice, h->stream));
-        ResidualSource rs;
-        rs.fcn = md->ufcn; rs.jac = md->ujac; rs.ctx = md->uctx;
-        if ((rc = residual_eval(h, rs, md->nprob, md->m, md->n, (const double *)h->xdev.p, (double *)h->fdev.p, nullptr, nullptr, -1))) return rc;
-        HIPCHK(h, hipMemcpyAsync(f, h->fdev.p, sizeof(double) * nf, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return 0;
+        const size_t xbytes = sizeof(double) * (size_t)md->nprob * md->n, fbytes = sizeof(double) * (size_t)md->nprob * md->m;
+        return staged_call(h, {{const_cast<double *>(x), xbytes, true, false, &h->xdev}, {f, fbytes, false, true, &h->fdev}},
+                           [&](void *const *d) {
+                               return residual_eval(h, ResidualSource::launchers(md->ufcn, md->ujac, md->uctx), md->nprob, md->m, md->n,
+                                                    (const double *)d[0], (double *)d[1], nullptr, nullptr, -1);
+                           });
     }
     return model_run(h, md, const_cast<double *>(x), false, f, nullptr, nullptr,
                      [&](nlh_handle *ph, const DqPart &pt, nlh_iteration_behavior *, int32_t *) -> int {
@@ -436,10 +430,7 @@ int nlh_dq_model_lm_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_mode
                           nlh_iteration_behavior *ib, int32_t *status)
 {
     if (!md || !o) return NLH_INVALID_INPUT_ERROR;
-    // a batch stays silent (the reference prints between the iterations of ONE solve): a share of a dealt batch may hold a
-    // single problem and would otherwise print from its host thread
-    nlh_options oq = *o;
-    if (md->nprob > 1) oq.print_status = 0;
+    const nlh_options oq = silent_in_batch(*o, md->nprob);      // (a share of a dealt batch would print from its host thread)
     o = &oq;
     if (md->ufcn) return nlh_lm_solve_batch_device_h(h, o, md->nprob, md->m, md->n, md->ufcn, md->ujac, md->uctx, x, fvec, ib, status);
     return model_run(h, md, x, true, fvec, ib, status,
@@ -496,8 +487,7 @@ int nlh_dq_model_newton_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_
                               double *fvec, nlh_iteration_behavior *ib, int32_t *status)
 {
     if (!md || !o) return NLH_INVALID_INPUT_ERROR;
-    nlh_options oq = *o;
-    if (md->nprob > 1) oq.print_status = 0;               // (see nlh_dq_model_lm_solve)
+    const nlh_options oq = silent_in_batch(*o, md->nprob);
     o = &oq;
     if (md->m != md->n) return NLH_INVALID_INPUT_ERROR;         // src/nonlin_solve.f90:519
     if (md->ufcn)                                                // (analytic: whether to use the user's jacobianfcn launcher)
@@ -513,8 +503,7 @@ int nlh_dq_model_quasi_newton_solve(nlh_handle *h, const nlh_options *o, const n
                                     int32_t analytic, double *x, double *fvec, nlh_iteration_behavior *ib, int32_t *status)
 {
     if (!md || !o) return NLH_INVALID_INPUT_ERROR;
-    nlh_options oq = *o;
-    if (md->nprob > 1) oq.print_status = 0;               // (see nlh_dq_model_lm_solve)
+    const nlh_options oq = silent_in_batch(*o, md->nprob);
     o = &oq;
     if (md->m != md->n) return NLH_INVALID_INPUT_ERROR;         // src/nonlin_solve.f90:241
     if (md->ufcn)
@@ -533,8 +522,7 @@ int nlh_dq_model_cls_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_mod
                            int32_t *status)
 {
     if (!md || !o) return NLH_INVALID_INPUT_ERROR;
-    nlh_options oq = *o;
-    if (md->nprob > 1) oq.print_status = 0;               // (see nlh_dq_model_lm_solve)
+    const nlh_options oq = silent_in_batch(*o, md->nprob);
     o = &oq;
     if (md->ufcn) return nlh_cls_solve_batch_device_h(h, o, delta0, stepscale0, xl, xu, md->nprob, md->m, md->n, md->ufcn, md->ujac, md->uctx, x,
                                                       fvec, ib, status);
@@ -580,8 +568,7 @@ int nlh_dq_model_bfgs_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_mo
                             nlh_iteration_behavior *ib, int32_t *status)
 {
     if (!md || !o) return NLH_INVALID_INPUT_ERROR;
-    nlh_options oq = *o;
-    if (md->nprob > 1) oq.print_status = 0;               // (see nlh_dq_model_lm_solve)
+    const nlh_options oq = silent_in_batch(*o, md->nprob);
     o = &oq;
     if (md->ufcn) {
         // bfgs minimises a scalar fcnnvar: a user's model with ONE function is exactly that (its launcher is called with

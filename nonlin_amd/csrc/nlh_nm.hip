@@ -79,9 +79,6 @@ static int nm_lockstep(nlh_handle *h, const nlh_options *o, double init_size, in
     return 0;
 }
 
-// Problems per lock-step run: the staging list holds nprob (n + 1) points whose offsets are int32.
-static int32_t nm_slice(int32_t n) { return (int32_t)std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)n + 1)); }
-
 int nlh_nelder_mead_solve(nlh_handle *h, const nlh_options *o, double init_size, int32_t n, nlh_fcnnvar fcn, void *ctx,
                           double *x, double *simplex, int32_t use_simplex, double *fout, nlh_iteration_behavior *ib)
 {
@@ -130,7 +127,7 @@ int nlh_nelder_mead_solve_batch_device(nlh_handle *h, const nlh_options *o, doub
     if (!o || n < 1 || nprob < 0 || (nprob > 0 && !dx) || (use_simplex && !dsimplex)) return NLH_INVALID_INPUT_ERROR;
     if (nprob == 0) return 0;
     HIPCHK(h, hipSetDevice(h->device));
-    const int32_t slice = nm_slice(n);
+    const int32_t slice = slice_simplex(n);
     const size_t npts = (size_t)n + 1;
     int rc;
     double *dsim = dsimplex;
@@ -138,18 +135,16 @@ int nlh_nelder_mead_solve_batch_device(nlh_handle *h, const nlh_options *o, doub
         if ((rc = ensure(h, h->bfB, sizeof(double) * (size_t)std::min(slice, nprob) * npts * n))) return rc;
         dsim = (double *)h->bfB.p;
     }
-    for (int32_t p0 = 0; p0 < nprob; p0 += slice) {
-        const int32_t cnt = std::min<int32_t>(slice, nprob - p0);
-        NmEval ev = [&](int32_t npoints, const int32_t *dprob, const double *dxs, double *dfs) -> int {
-            const int urc = fcn(ctx, (void *)h->stream, npoints, dprob, n, dxs, 1, dfs);
-            if (urc) { h->err = "fcnnvar: the user's launcher returned " + std::to_string(urc); return NLH_ERR_HIP; }
-            return 0;
-        };
-        rc = nm_lockstep(h, o, init_size, cnt, n, p0, ev, dx + (size_t)p0 * n, dsimplex ? dsim + (size_t)p0 * npts * n : dsim,
-                         use_simplex != 0, false, fout ? fout + p0 : nullptr, ib ? ib + p0 : nullptr, status ? status + p0 : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    NmEval ev = [&](int32_t npoints, const int32_t *dprob, const double *dxs, double *dfs) -> int {
+        const int urc = fcn(ctx, (void *)h->stream, npoints, dprob, n, dxs, 1, dfs);
+        return urc ? launcher_failed(h, urc, "fcnnvar") : 0;
+    };
+    const BatchIO io = {dx, nullptr, fout, ib, status};
+    return lockstep_slices(nprob, slice, [&](int32_t p0, int32_t cnt) {
+        const BatchIO q = io.at(p0, 1, n);
+        return nm_lockstep(h, o, init_size, cnt, n, p0, ev, q.x, dsimplex ? dsim + (size_t)p0 * npts * n : dsim, use_simplex != 0, false,
+                           q.fout, q.ib, q.status);
+    });
 }
 
 // The same behind host arrays x [nprob][n] (what nlh_dq_model_nelder_mead_solve runs on a user's model).
@@ -162,13 +157,7 @@ int nlh_nm_solve_batch_device_h(nlh_handle *h, const nlh_options *o, double init
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;
     if (!o || n < 1 || nprob < 0 || (nprob > 0 && !x)) return NLH_INVALID_INPUT_ERROR;
     if (nprob == 0) return 0;
-    int rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    if ((rc = ensure(h, h->xdev, sizeof(double) * (size_t)nprob * n))) return rc;
-    double *dx = (double *)h->xdev.p;
-    HIPCHK(h, hipMemcpyAsync(dx, x, sizeof(double) * (size_t)nprob * n, hipMemcpyHostToDevice, h->stream));
-    if ((rc = nlh_nelder_mead_solve_batch_device(h, o, init_size, nprob, n, fcn, ctx, dx, nullptr, 0, fout, ib, status))) return rc;
-    HIPCHK(h, hipMemcpyAsync(x, dx, sizeof(double) * (size_t)nprob * n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
+    return staged_call(h, {{x, sizeof(double) * (size_t)nprob * n, true, true, &h->xdev}}, [&](void *const *d) {
+        return nlh_nelder_mead_solve_batch_device(h, o, init_size, nprob, n, fcn, ctx, (double *)d[0], nullptr, 0, fout, ib, status);
+    });
 }

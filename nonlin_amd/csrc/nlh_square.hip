@@ -776,23 +776,16 @@ static int square_batch_rs(nlh_handle *h, const nlh_options *o, bool broyden, in
 {
     if (!h) return NLH_ERR_BAD_HANDLE;
     if (!o || n < 1 || nprob < 1) return NLH_INVALID_INPUT_ERROR;
-    const int32_t slice = rs.user() ? (int32_t)std::max<int64_t>(1, std::min<int64_t>(NLH_MAX_LOCKSTEP, ((int64_t)1 << 30) / n)) : NLH_MAX_LOCKSTEP;
-    for (int32_t p0 = 0; p0 < nprob; p0 += slice) {
-        const int32_t cnt = std::min<int32_t>(slice, nprob - p0);
-        const int rc = square_lockstep(h, o, broyden, jdelta, cnt, n, rs.shifted(p0, n, n), analytic, dx + (size_t)p0 * n, dfvec + (size_t)p0 * n,
-                                       ib ? ib + p0 : nullptr, status ? status + p0 : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
+    return residual_slices(rs, nprob, n, n, {dx, dfvec, nullptr, ib, status}, [&](int32_t cnt, const ResidualSource &r, const BatchIO &q) {
+        return square_lockstep(h, o, broyden, jdelta, cnt, n, r, analytic, q.x, q.fvec, q.ib, q.status);
+    });
 }
 
 int nlh_dq_newton_solve_batch(nlh_handle *h, const nlh_options *o, int32_t nprob, int32_t n, const double *dA,
                               const double *db, double gamma, int32_t analytic, double *dx, double *dfvec,
                               nlh_iteration_behavior *ib, int32_t *status)
 {
-    ResidualSource rs;
-    rs.dA = dA; rs.db = db; rs.gamma = gamma;
-    return square_batch_rs(h, o, false, 0, nprob, n, rs, analytic, dx, dfvec, ib, status);
+    return square_batch_rs(h, o, false, 0, nprob, n, ResidualSource::dense_quadratic(dA, db, gamma), analytic, dx, dfvec, ib, status);
 }
 
 // newton_solver%solve / quasi_newton_solver%solve on a batch of square problems whose residual (and, optionally, Jacobian)
@@ -805,11 +798,8 @@ static int square_device(nlh_handle *h, const nlh_options *o, bool broyden, int 
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;              // src/nonlin_solve.f90:516 / :238
     if (nprob <= 0) return 0;
     if (!o || !dx || !dfvec) return NLH_INVALID_INPUT_ERROR;
-    ResidualSource rs;
-    rs.fcn = fcn; rs.jac = jacfcn; rs.ctx = ctx;
-    nlh_options oq = *o;
-    if (nprob > 1) oq.print_status = 0;                         // the status block is a single solve's (:611-613)
-    return square_batch_rs(h, &oq, broyden, jdelta, nprob, n, rs, 0, dx, dfvec, ib, status);
+    const nlh_options oq = silent_in_batch(*o, nprob);          // (:611-613)
+    return square_batch_rs(h, &oq, broyden, jdelta, nprob, n, ResidualSource::launchers(fcn, jacfcn, ctx), 0, dx, dfvec, ib, status);
 }
 
 static int square_device_h(nlh_handle *h, const nlh_options *o, bool broyden, int jdelta, int32_t nprob, int32_t n, nlh_device_vecfcn fcn,
@@ -819,18 +809,10 @@ static int square_device_h(nlh_handle *h, const nlh_options *o, bool broyden, in
     if (nprob <= 0) return 0;
     if (!o || !x || !fvec || n < 1) return NLH_INVALID_INPUT_ERROR;
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    const size_t cnt = (size_t)nprob * n;
-    if ((rc = ensure(h, h->xdev, sizeof(double) * cnt))) return rc;
-    if ((rc = ensure(h, h->fdev, sizeof(double) * cnt))) return rc;
-    double *dx = (double *)h->xdev.p, *df = (double *)h->fdev.p;
-    HIPCHK(h, hipMemcpyAsync(dx, x, sizeof(double) * cnt, hipMemcpyHostToDevice, h->stream));
-    if ((rc = square_device(h, o, broyden, jdelta, nprob, n, fcn, jacfcn, ctx, dx, df, ib, status))) return rc;
-    HIPCHK(h, hipMemcpyAsync(x, dx, sizeof(double) * cnt, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(fvec, df, sizeof(double) * cnt, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return 0;
+    const size_t bytes = sizeof(double) * (size_t)nprob * n;
+    return staged_call(h, {{x, bytes, true, true, &h->xdev}, {fvec, bytes, false, true, &h->fdev}}, [&](void *const *d) {
+        return square_device(h, o, broyden, jdelta, nprob, n, fcn, jacfcn, ctx, (double *)d[0], (double *)d[1], ib, status);
+    });
 }
 
 int nlh_newton_solve_batch_device(nlh_handle *h, const nlh_options *o, int32_t nprob, int32_t n, nlh_device_vecfcn fcn,
@@ -914,9 +896,8 @@ int nlh_dq_quasi_newton_solve_batch(nlh_handle *h, const nlh_options *o, int32_t
 {
     if (!h) return NLH_ERR_BAD_HANDLE;
     if (!o || n < 1 || nprob < 1) return NLH_INVALID_INPUT_ERROR;
-    ResidualSource rs;
-    rs.dA = dA; rs.db = db; rs.gamma = gamma;
-    return square_batch_rs(h, o, true, jdelta, nprob, n, rs, analytic, dx, dfvec, ib, status);   // the same state machine
+    return square_batch_rs(h, o, true, jdelta, nprob, n, ResidualSource::dense_quadratic(dA, db, gamma), analytic, dx, dfvec, ib,
+                           status);                              // the same state machine
 }
 
 int nlh_lu_factor(nlh_handle *h, int32_t nprob, int32_t n, double *dA, int32_t *dipvt, int32_t *dinfo)
