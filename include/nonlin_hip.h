@@ -1050,6 +1050,98 @@ int nlh_expr_fit_batch_loss_h(nlh_handle *h, const nlh_options *opts, const nlh_
 int nlh_loss_model_create(nlh_handle *h, const nlh_dq_model *inner, int32_t kind, const double *scale, int32_t shared_scale,
                           nlh_dq_model **model);
 
+/* ---- Poisson likelihood fits (no counterpart in nonlin v2.2.0): counting data for ANY device model.  For counts -- photon
+ * counting decays, histogrammed spectra, low-dose images -- least squares is the wrong estimator: weighting by 1/sqrt(y)
+ * biases a decay rate by several per cent at 50 counts, and the unweighted fit wastes information.  The Poisson deviance
+ *   sum_i D_i,  D_i = 2 [mu_i - y_i + y_i log(y_i / mu_i)]  ( = -2 log L up to a constant of the data)
+ * is a sum of squares of the DEVIANCE RESIDUALS d_i = sign(mu_i - y_i) * sqrt(D_i), so the unchanged LM and bounded solvers
+ * minimise -2 log L when they are handed d and its Jacobian.  Like a loss, this is a pair of wrapping launchers around any
+ * inner launcher pair (built-in curve, formula, a user's own), so everything that takes launchers works through it:
+ * nlh_lm_solve_batch_device, nlh_cls_solve_batch_device, nlh_lm_covariance_batch_device, nlh_fd_jacobian_device, the model
+ * objects and the maps (a map wraps the Poisson pair, not the other way round).
+ * The inner pair is an ordinary least-squares model bound WITHOUT weights, so that its residual is r = model - y.  The
+ * wrapper is given the same counts dy [nprob][m], an optional mask dw [nprob][m] of 0.0 / 1.0 (NULL: every row counts) and a
+ * floor mu_floor > 0, all on the DEVICE; point q reads row dprob[q] of dy and dw (a NULL dprob means q itself).
+ * THE ARITHMETIC IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation.  Per row, f = mu_floor:
+ *   f not finite or not positive          out = g = NaN, every row (the entry points that take a HOST floor refuse it)
+ *   masked: dw given and w == 0.0         out = +0.0, g = 0.0; the Jacobian row is STORED as +0.0, not multiplied.  (The mask is
+ *                                         the wrapper's, because a real row with y = 0 and mu -> 0 has inner residual 0 too.)
+ *   w neither 0.0 nor 1.0, y < 0.0 or y not finite            out = g = NaN
+ *   floor       mu = r + y; low = mu < f; rr = low ? f - y : r
+ *   y == 0.0    D = 2.0*rr; s = sqrt(D); d = s; g = 1.0/s
+ *   y >  0.0    e = rr/y; a = fabs(e); u = (rr + y)/y
+ *               a <= 2^-6   q = 1.0/13; q = 1.0/k - e*q for k = 12 .. 2 (the constants 1.0/k); h = (e*e)*q
+ *                           -- the series of e - log(1 + e), no library function
+ *               otherwise   l = (e < -0.5) ? log(u) : log1p(e); h = e - l
+ *               D = (2.0*y)*h; s = sqrt(D); d = copysign(s, e)
+ *               g = (e == 0.0) ? 1.0/sqrt(y) : a/(u*s)                     ( = (1 - y/mu) / d )
+ *   result      low: out = d + g*(mu - f);  otherwise out = d.             J'[i][j] = g_i * J[i][j]
+ * Below the floor out is the C1 linear extension of d: a clamp would leave the solver without a slope, NaN would kill the
+ * problem.  No sum crosses a row: a row's bits do not depend on the launch, the batch or the workgroup form.  Rows that reach
+ * no library function (masked, y = 0, the series, and floor rows whose base point is one of those) are reproducible bit for
+ * bit; the others carry the device library's log1p or log, and d and g stay within 2^-44 relative of the exact values over
+ * the documented domain: y in [0.01, 1e6], |e| in [1e-12, 1e6], e + 1 >= 1e-12 (DESIGN.md 4h derives the bound). ---- */
+typedef struct nlh_pois_ctx nlh_pois_ctx;
+/* The wrapping launchers.  nlh_pois_wrap makes their context on the handle's device; the inner pair (fcn, jac -- NULL: none
+ * --, inner_ctx), dy and dw stay the caller's and must outlive the context.  mu_floor is not checked here (the table's NaN).
+ *   nlh_pois_device_fcn  the inner fcn straight into the caller's dF; then the table's out, in place.
+ *   nlh_pois_device_jac  the inner fcn into scratch R [npoints][m]; the inner jac straight into the caller's dJ; then
+ *                        every row of dJ times its g, in place.  With a NULL inner jac it returns
+ *                        NLH_UNDEFINED_FUNCTION_ERROR: pass a NULL jacfcn to the solver instead (forward differences of
+ *                        the wrapped residual).
+ * Both enqueue only on the stream handed in, never synchronise and may be called from several host threads on different
+ * streams.  A malformed context, n < 1 or m < 1 returns non-zero before any launch.  An inner error comes back as it is,
+ * with no further launch.  When dprob is NULL the launchers build a problem list of their own, for the inner launcher and for
+ * the rows of dy and dw.  Scratch belongs to the context, exactly as a loss's: one buffer per stream, grown on demand, kept
+ * until nlh_pois_unwrap, at most 1 GiB per call; a call that needs more runs in slices of points -- the same bits.
+ * NLH_POIS_SCRATCH = bytes lowers the cap, NLH_POIS_FORM = row | flat forces a workgroup form for the sizes it can hold,
+ * NLH_POIS_SPLIT = number of column groups overrides the column split (environment, read at each call; tests). */
+int  nlh_pois_wrap(nlh_handle *h, const double *dy, const double *dw, double mu_floor, nlh_device_vecfcn fcn,
+                   nlh_device_jacfcn jac, void *inner_ctx, nlh_pois_ctx **out);
+void nlh_pois_unwrap(nlh_pois_ctx *c);
+int  nlh_pois_device_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dF);
+int  nlh_pois_device_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dJ);
+/* The table applied to raw residuals dr [nprob][m] = model - y on the DEVICE (the handle's stream): dout, dg and the row
+ * deviances ddev (the table's D: the deviance at max(mu, f); 0.0 on a masked row) [nprob][m], each may be NULL; dout may be
+ * dr itself. */
+int  nlh_pois_apply_batch(nlh_handle *h, int32_t nprob, int32_t m, const double *dy, const double *dw, double mu_floor,
+                          const double *dr, double *dout, double *dg, double *ddev);
+/* One-call Poisson fits: the _pmap entry points plus mu_floor after pm; dw (w) now means the 0 / 1 mask, and the model itself
+ * is bound without weights.  The composition is fixed: the Poisson pair wraps the model's launchers, and the map, if any,
+ * wraps the result.  What comes back: dfvec is the deviance residual d; dchi2 is the deviance / dof = (sum of d_i^2, i
+ * ascending, sequential) / dof with dof = unmasked rows - n (a problem with dof <= 0 gets NLH_INVALID_INPUT_ERROR in its
+ * status, as with zero weights); dsigma / dcov are UNSCALED, nlh_lm_covariance_batch_device with scaled = 0: (J'^T J')^-1 is the
+ * inverse Fisher information at the fit, and Poisson noise has no free variance.  Errors, in this order: the _pmap entry
+ * point's; then NLH_INVALID_INPUT_ERROR for a mu_floor that is not finite or not positive.  The _h forms also refuse, with
+ * NLH_INVALID_INPUT_ERROR, a w outside {0, 1} and, on a row the mask keeps, a y that is negative or not finite (a masked
+ * row may hold anything there too: NaN padding of ragged data is accepted). */
+int nlh_curve_fit_batch_pois(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                             int32_t m, const double *dt, int32_t shared_t, const double *dy, const double *dw, int32_t analytic,
+                             const double *xl, const double *xu, const nlh_pmap *pm, double mu_floor, double *dx,
+                             double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+                             nlh_iteration_behavior *ib, int32_t *status);
+int nlh_curve_fit_batch_pois_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                               int32_t m, const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic,
+                               const double *xl, const double *xu, const nlh_pmap *pm, double mu_floor, double *x,
+                               double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+                               nlh_iteration_behavior *ib, int32_t *status);
+int nlh_expr_fit_batch_pois(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+                            int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl,
+                            const double *xu, const nlh_pmap *pm, double mu_floor, double *dx, double *dfvec, double *dsigma,
+                            double *dcov, double *dchi2, int32_t *drank, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_expr_fit_batch_pois_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+                              int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl,
+                              const double *xu, const nlh_pmap *pm, double mu_floor, double *x, double *fvec, double *sigma,
+                              double *cov, double *chi2, int32_t *rank, nlh_iteration_behavior *ib, int32_t *status);
+/* A device-function MODEL minimising the Poisson deviance over a launcher-backed inner model (device-function, curve or
+ * formula, created WITHOUT weights; a dense-quadratic model: NLH_INVALID_INPUT_ERROR), which must outlive it.  y, w (NULL: no
+ * mask): HOST [nprob][m]; the model owns its device copies and its wrapping context.  Every nlh_dq_model_* solver and
+ * nlh_dq_model_lm_covariance (pass scaled = 0) then takes it; a mapped model may be made over it.  Errors: NLH_ERR_BAD_HANDLE,
+ * then NLH_INVALID_INPUT_ERROR (a NULL argument, a dense-quadratic inner model, a bad mu_floor, a w outside {0, 1}, a y that
+ * is negative or not finite on a row the mask keeps). */
+int nlh_pois_model_create(nlh_handle *h, const nlh_dq_model *inner, const double *y, const double *w, double mu_floor,
+                          nlh_dq_model **model);
+
 /* ---- per-kernel timing (HIP events on the handle's stream) ------------------ */
 #define NLH_K_DQ_RESIDUAL   0
 #define NLH_K_DQ_PANEL      1

@@ -4,6 +4,7 @@ The product path has no CPU fallback: if the shared library is missing, or no GP
 visible when a compute entry point is called, this module raises.
 """
 import ctypes as C
+import math
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -297,6 +298,29 @@ SYMBOLS = {
                                             c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
                                             C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_loss_model_create": (C.c_int, [_H, C.c_void_p, C.c_int32, c_double_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "nlh_pois_wrap": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "nlh_pois_unwrap": (None, [C.c_void_p]),
+    "nlh_pois_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_pois_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_pois_apply_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "nlh_curve_fit_batch_pois": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_double,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_curve_fit_batch_pois_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p,
+                                             C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_double,
+                                             c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
+                                             C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_fit_batch_pois": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_double,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_fit_batch_pois_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p,
+                                            c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_double,
+                                            c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
+                                            C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_pois_model_create": (C.c_int, [_H, C.c_void_p, c_double_p, c_double_p, C.c_double, C.POINTER(C.c_void_p)]),
     "nlh_timing_enable": (None, [_H, C.c_int32]),
     "nlh_timing_reset": (None, [_H]),
     "nlh_timing_get": (C.c_int, [_H, C.c_int32, c_double_p, C.POINTER(C.c_int64)]),
@@ -529,6 +553,26 @@ class Loss:
         if not self.shared and len(self.scale) != nprob:
             raise ValueError(f"Loss: {len(self.scale)} scales for {nprob} problems")
         return self.scale, int(self.shared)
+
+
+class Poisson:
+    """The Poisson likelihood as the statistic of a fit (include/nonlin_hip.h: nlh_pois_*; host data only, needs no GPU): the
+    fit minimises the Poisson deviance of the counts y instead of a sum of squares.  mu_floor: below this model value the
+    deviance residual is continued linearly (C1), so that a model that strays to zero or below keeps a slope.  The default,
+    2^-20, is far below one count, so no meaningful model touches it, and large enough that the extension's slope stays
+    finite; it is a default, not a measurement.  Raises ValueError for a floor that is not finite or not positive (what the
+    library's entry points refuse)."""
+
+    def __init__(self, mu_floor=2.0 ** -20):
+        if isinstance(mu_floor, (bool, str)) or not hasattr(mu_floor, "__float__"):
+            raise ValueError(f"Poisson: mu_floor must be a number, not {mu_floor!r}")
+        try:
+            f = float(mu_floor)
+        except (TypeError, ValueError):
+            raise ValueError(f"Poisson: mu_floor must be a number, not {mu_floor!r}") from None
+        if not (math.isfinite(f) and f > 0.0):
+            raise ValueError("Poisson: mu_floor must be finite and positive")
+        self.mu_floor = f
 
 
 class Handle:

@@ -2,7 +2,7 @@
 // (kernels and arithmetic: nlh_kernels_curve.h) as library-owned launchers of the open device-residual path, so that the
 // lock-step machines of least_squares_solver, constrained_least_squares_solver and the covariance chain fit them without
 // knowing them.  Here: the launchers and which workgroup form a call runs, model values at arbitrary abscissae
-// (nlh_curve_eval_batch), and the six one-call fits nlh_curve_fit_batch*: a curve model as the FitSource of the pipeline
+// (nlh_curve_eval_batch), and the eight one-call fits nlh_curve_fit_batch*: a curve model as the FitSource of the pipeline
 // (nlh_fit.hip).  The model object that owns its data is nlh_curve_model_create (nlh_model.hip).
 #include "nlh_internal.h"
 #include "nlh_launch.h"
@@ -170,4 +170,22 @@ int nlh_curve_fit_batch_loss_h(nlh_handle *h, const nlh_options *opts, int32_t k
 {
     return curve_fit(h, opts, kind, ncomp, nbase, analytic, {nprob, m, t, shared_t, y, w, xl, xu, pm, loss, scale, shared_scale, x, fvec, sigma,
                                                              cov, chi2, rank, ib, status}, true);
+}
+
+int nlh_curve_fit_batch_pois(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m, const double *dt,
+    int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl, const double *xu, const nlh_pmap *pm,
+    double mu_floor, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+    nlh_iteration_behavior *ib, int32_t *status)
+{
+    return curve_fit(h, opts, kind, ncomp, nbase, analytic, {nprob, m, dt, shared_t, dy, dw, xl, xu, pm, NLH_LOSS_LINEAR, nullptr, 0, dx, dfvec, dsigma,
+                                             dcov, dchi2, drank, ib, status, NLH_STAT_POISSON, mu_floor}, false);
+}
+
+int nlh_curve_fit_batch_pois_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m, const double *t,
+    int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl, const double *xu, const nlh_pmap *pm,
+    double mu_floor, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+    nlh_iteration_behavior *ib, int32_t *status)
+{
+    return curve_fit(h, opts, kind, ncomp, nbase, analytic, {nprob, m, t, shared_t, y, w, xl, xu, pm, NLH_LOSS_LINEAR, nullptr, 0, x, fvec, sigma,
+                                             cov, chi2, rank, ib, status, NLH_STAT_POISSON, mu_floor}, true);
 }

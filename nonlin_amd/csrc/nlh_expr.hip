@@ -3,7 +3,7 @@
 // postfix of the parse tree as it goes -- no folding, no reassociation, no sharing -- with, per instruction, the mask of
 // the parameters its subtree names and the instruction that produced its left operand.  Then the launchers of the open
 // device-residual path (kernels and arithmetic: nlh_kernels_expr.h), which form a call runs and how many Jacobian
-// columns a pass carries, model values (nlh_expr_eval_batch) and the six one-call fits nlh_expr_fit_batch*: a formula as
+// columns a pass carries, model values (nlh_expr_eval_batch) and the eight one-call fits nlh_expr_fit_batch*: a formula as
 // the FitSource of the pipeline (nlh_fit.hip).  The model object that owns its program and data is nlh_expr_model_create
 // (nlh_model.hip).
 #include "nlh_internal.h"
@@ -411,4 +411,22 @@ int nlh_expr_fit_batch_loss_h(nlh_handle *h, const nlh_options *opts, const nlh_
 {
     return expr_fit(h, opts, e, analytic, {nprob, m, t, shared_t, y, w, xl, xu, pm, loss, scale, shared_scale, x, fvec, sigma, cov, chi2, rank,
                                            ib, status}, true);
+}
+
+int nlh_expr_fit_batch_pois(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+    int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl, const double *xu, const nlh_pmap *pm,
+    double mu_floor, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+    nlh_iteration_behavior *ib, int32_t *status)
+{
+    return expr_fit(h, opts, e, analytic, {nprob, m, dt, shared_t, dy, dw, xl, xu, pm, NLH_LOSS_LINEAR, nullptr, 0, dx, dfvec, dsigma,
+                                             dcov, dchi2, drank, ib, status, NLH_STAT_POISSON, mu_floor}, false);
+}
+
+int nlh_expr_fit_batch_pois_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+    int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl, const double *xu, const nlh_pmap *pm,
+    double mu_floor, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+    nlh_iteration_behavior *ib, int32_t *status)
+{
+    return expr_fit(h, opts, e, analytic, {nprob, m, t, shared_t, y, w, xl, xu, pm, NLH_LOSS_LINEAR, nullptr, 0, x, fvec, sigma,
+                                             cov, chi2, rank, ib, status, NLH_STAT_POISSON, mu_floor}, true);
 }

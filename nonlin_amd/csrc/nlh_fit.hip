@@ -1,9 +1,11 @@
-// nlh_fit.hip -- the one-call fit + errors pipeline behind the twelve entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss}{,_h}
+// nlh_fit.hip -- the one-call fit + errors pipeline behind the entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois}{,_h}
 // (nlh_internal.h: nlh_fit_run).  A model kind hands it a FitSource -- its launchers, a context and how to point that context
 // at a run of problems -- and the rest of the entry point's arguments as a FitArgs; here are the documented ladder of checks,
 // the staging of host arrays, the composition (the loss wraps the model's launchers, the parameter map, if any, wraps the
 // result), the solve and covariance of every run of consecutive problems that have degrees of freedom, and the rule of
-// zero-weight padding.  Nothing here knows what a curve or a formula is.  Kernels: nlh_kernels_fit.h.
+// zero-weight padding.  A Poisson fit (FitArgs::stat) puts the Poisson wrapper where the loss sits, around a model bound
+// without weights: w is then the wrapper's 0 / 1 mask, the covariance is unscaled and chi2 is the deviance over the degrees
+// of freedom.  Nothing here knows what a curve or a formula is.  Kernels: nlh_kernels_fit.h.
 #include "nlh_internal.h"
 #include "nlh_kernels_fit.h"
 
@@ -20,18 +22,20 @@ struct FitRun {
     nlh_device_jacfcn jac;
     void *ctx;
     nlh_loss_ctx *lc = nullptr;
+    nlh_pois_ctx *qc = nullptr;
     nlh_pmap_ctx *pc = nullptr;
     const double *fullc = nullptr;     // the map's private copy of the full parameters
     void bind(int32_t p0) const
     {
-        src->bind(src->ctx, a->t, a->y, a->w, p0);
+        src->bind(src->ctx, a->t, a->y, qc ? nullptr : a->w, p0);
+        if (qc) pois_ctx_rebind(qc, a->y + (size_t)p0 * a->m, a->w ? a->w + (size_t)p0 * a->m : nullptr);
         if (lc) loss_ctx_rebind(lc, a->shared_scale ? a->scale : a->scale + p0);
         if (pc) pmap_ctx_rebind(pc, fullc + (size_t)p0 * N);
     }
 };
 }   // namespace
 
-// Solve (bounded when xl or xu is given), covariance with scaled = 1 when any of dsigma, dcov, the caller's chi2 is asked for,
+// Solve (bounded when xl or xu is given), covariance with scaled = 1 (a Poisson fit: 0) when any of dsigma, dcov, the caller's chi2 is asked for,
 // the degrees-of-freedom rule of zero weights, NaN and rank -1 for problems that did not solve: over n unknowns -- the
 // model's parameters, or the free ones of a map, whose arrays xl .. status these then are.
 static int fit_solve(const FitRun &r, int32_t n, const double *xl, const double *xu, double *dx, double *dsigma, double *dcov, int32_t *status)
@@ -45,6 +49,7 @@ static int fit_solve(const FitRun &r, int32_t n, const double *xl, const double 
     nlh_iteration_behavior *ib = a.ib;
     int rc;
     const bool errors = dsigma || dcov || dchi2;
+    const bool pois = a.stat == NLH_STAT_POISSON;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const size_t np = (size_t)nprob, nn = (size_t)n * n;
@@ -75,7 +80,7 @@ static int fit_solve(const FitRun &r, int32_t n, const double *xl, const double 
         else rc = nlh_lm_solve_batch_device(h, r.opts, cnt, m, n, r.fcn, r.jac, r.ctx, xs, fs, ibs, &st[p0]);
         if (rc) return rc;
         if (errors &&
-            (rc = nlh_lm_covariance_batch_device(h, cnt, m, n, r.fcn, r.jac, r.ctx, xs, 1, 0.0, cov + (size_t)p0 * nn,
+            (rc = nlh_lm_covariance_batch_device(h, cnt, m, n, r.fcn, r.jac, r.ctx, xs, pois ? 0 : 1, 0.0, cov + (size_t)p0 * nn,
                                                  dsigma ? dsigma + (size_t)p0 * n : nullptr, drank ? drank + p0 : nullptr,
                                                  dchi2 ? dchi2 + p0 : nullptr))) return rc;
         p0 = p1;
@@ -83,7 +88,7 @@ static int fit_solve(const FitRun &r, int32_t n, const double *xl, const double 
     if (errors) {
         HIPCHK(h, hipMemcpyAsync(dstat, st.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_fit_post, dim3((nprob + 63) / 64), dim3(64), 0, s, nprob, m, n, (const int32_t *)dstat,
-                           dw ? (const int32_t *)dnz : (const int32_t *)nullptr, (const double *)dfvec, cov, dsigma, dchi2, drank);
+                           dw ? (const int32_t *)dnz : (const int32_t *)nullptr, (const double *)dfvec, cov, dsigma, dchi2, drank, pois ? 1 : 0);
         HIPCHK(h, hipStreamSynchronize(s));                      // (st is a host vector)
     }
     if (status) memcpy(status, st.data(), sizeof(int32_t) * np);
@@ -156,11 +161,25 @@ static int fit_mapped(FitRun r, int32_t n)
 }
 
 // The composition on device pointers: the loss wraps the model's launchers (NLH_LOSS_LINEAR: no context, no kernel of the
-// loss), the map, if any, wraps the result.  n: the unknowns of the solve.
+// loss) -- in a Poisson fit the Poisson wrapper does, in the same place --, the map, if any, wraps the result.  n: the
+// unknowns of the solve.
 static int fit_device(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, int32_t n)
 {
     FitRun r{h, opts, &src, &a, src.N, src.fcn, src.jac, src.ctx};
     auto run = [&]() { return a.pm ? fit_mapped(r, n) : fit_solve(r, n, a.xl, a.xu, a.x, a.sigma, a.cov, a.status); };
+    if (a.stat == NLH_STAT_POISSON) {
+        int rc = nlh_pois_wrap(h, a.y, a.w, a.mu_floor, src.fcn, src.jac, src.ctx, &r.qc);
+        if (rc) return rc;
+        r.fcn = nlh_pois_device_fcn; r.jac = src.jac ? nlh_pois_device_jac : nullptr; r.ctx = r.qc;
+        rc = run();
+        const hipError_t e = hipStreamSynchronize(h->stream);     // (the context's scratch goes)
+        nlh_pois_unwrap(r.qc);
+        if (!rc && e != hipSuccess) {
+            h->err = std::string("Poisson fit: ") + hipGetErrorString(e);
+            return NLH_ERR_HIP;
+        }
+        return rc;
+    }
     if (a.loss == NLH_LOSS_LINEAR) return run();
     int rc = nlh_loss_wrap(h, a.loss, a.scale, a.shared_scale, src.fcn, src.jac, src.ctx, &r.lc);
     if (rc) return rc;
@@ -225,7 +244,7 @@ static int fit_staged(nlh_handle *h, const nlh_options *opts, const FitSource &s
     return rc;
 }
 
-// The checks of every one of the twelve entry points, in the documented order, and then the fit.
+// The checks of every one of the entry points, in the documented order, and then the fit.
 int nlh_fit_run(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, bool host)
 {
     if (!h) return NLH_ERR_BAD_HANDLE;
@@ -241,7 +260,9 @@ int nlh_fit_run(nlh_handle *h, const nlh_options *opts, const FitSource &src, co
     if (a.nprob == 0) return 0;
     if (!opts || !a.t || !a.y || !a.x || !a.fvec || (a.loss != NLH_LOSS_LINEAR && !a.scale)) return NLH_INVALID_INPUT_ERROR;
     if ((a.sigma || a.cov || a.chi2) && a.m <= n) return NLH_INVALID_INPUT_ERROR;   // no degree of freedom for errors
+    if (a.stat == NLH_STAT_POISSON && !nlh_pois_floor_ok(a.mu_floor)) return NLH_INVALID_INPUT_ERROR;
     if (!host) return fit_device(h, opts, src, a, n);
+    if (a.stat == NLH_STAT_POISSON && !nlh_pois_data_ok(a.y, a.w, (size_t)a.nprob * a.m)) return NLH_INVALID_INPUT_ERROR;
     double *dscale = nullptr;                                     // checks the host scales: finite, positive (LINEAR: none, NULL)
     int rc = nlh_loss_scale_upload(h, a.loss, a.scale, a.shared_scale ? 1 : (size_t)a.nprob, &dscale);
     if (rc) return rc;

@@ -12,15 +12,16 @@
 //   nlh_polyroots.hip  polynomial%roots, batched evaluate
 //   nlh_covar.hip      parameter covariance
 //   nlh_devfcn.hip     user device residuals: the open launcher path, the built-in family as launchers
-//   nlh_curve.hip      built-in curve models: launchers, values, the six nlh_curve_fit_batch* entry points
-//   nlh_expr.hip       formula models: compiler, launchers, values, the six nlh_expr_fit_batch* entry points
-//   nlh_fit.hip        the fit + errors pipeline behind those twelve (nlh_fit_run below)
+//   nlh_curve.hip      built-in curve models: launchers, values, the eight nlh_curve_fit_batch* entry points
+//   nlh_expr.hip       formula models: compiler, launchers, values, the eight nlh_expr_fit_batch* entry points
+//   nlh_fit.hip        the fit + errors pipeline behind those sixteen (nlh_fit_run below)
 //   nlh_pmap.hip       parameter maps: the map object, the wrapping launchers, gather / expand / covariance
 //   nlh_loss.hip       robust losses: the wrapping launchers, apply, the upload of host scales
+//   nlh_pois.hip       Poisson likelihood fits: the wrapping launchers, apply, the check of host counts and masks
 //   nlh_model.hip      device sets, device residual models behind host arrays
 //   nlh_qrx.hip        the exact lmfactor
 // Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it launches.  nlh_launch.h:
-// the host side of the (point, row) kernels' two workgroup forms and what the two pairs of wrapping launchers share.
+// the host side of the (point, row) kernels' two workgroup forms and what the pairs of wrapping launchers share.
 #pragma once
 #include "../../include/nonlin_hip.h"
 
@@ -330,7 +331,7 @@ struct nlh_expr {
     int32_t nconst;
 };
 
-// The one-call fit + errors of the twelve entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss}{,_h} (nlh_fit.hip).
+// The one-call fit + errors of the sixteen entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois}{,_h} (nlh_fit.hip).
 // FitSource: what a model kind hands the pipeline.  bind points the context's data at problem p0 of dt, dy, dw (the whole
 // batch's device arrays) before each run of consecutive problems; whatever else the context holds stays the whole batch's.
 struct FitSource {
@@ -343,7 +344,10 @@ struct FitSource {
     void (*bind)(void *ctx, const double *dt, const double *dy, const double *dw, int32_t p0);
 };
 // FitArgs: the rest of an entry point's arguments, as the header documents them, for the device-pointer form and the
-// host-array form alike.  A plain fit is pm = NULL, loss = NLH_LOSS_LINEAR (which reads no scale).
+// host-array form alike.  A plain fit is pm = NULL, loss = NLH_LOSS_LINEAR (which reads no scale).  stat: what is minimised
+// -- the sum of squares (the twelve least-squares entry points leave it and mu_floor at their defaults), or the Poisson
+// deviance of the counts y, w then being the 0 / 1 mask of the rows.
+enum { NLH_STAT_LSQ = 0, NLH_STAT_POISSON = 1 };
 struct FitArgs {
     int32_t nprob, m;
     const double *t;
@@ -357,15 +361,20 @@ struct FitArgs {
     int32_t *rank;
     nlh_iteration_behavior *ib;
     int32_t *status;
+    int32_t stat = NLH_STAT_LSQ;
+    double mu_floor = 0.0;
 };
 // The documented ladder of checks, then: solve (bounded when xl or xu is given), covariance with scaled = 1 when any of sigma,
 // cov, chi2 is asked for, the degrees-of-freedom rule of zero weights, NaN and rank -1 for problems that did not solve.  The
 // loss wraps the model's launchers; the map, if any, wraps the result.  host: the arrays are host arrays (the scales too).
+// NLH_STAT_POISSON: the model is bound without weights, the Poisson wrapper sits where the loss sits, the covariance is
+// unscaled, and chi2 = deviance / dof with dof = unmasked rows - n.
 int nlh_fit_run(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, bool host);
 // what the pipeline needs of a wrapping context besides the public nlh_*_wrap / _unwrap: where a run of problems starts in
 // the caller's arrays (nlh_loss.hip, nlh_pmap.hip), and the map's three small launches on the context's copy of the tables
 struct PmapTables;                     // nlh_kernels_pmap.h
 void loss_ctx_rebind(nlh_loss_ctx *c, const double *dscale);
+void pois_ctx_rebind(nlh_pois_ctx *c, const double *dy, const double *dw);
 void pmap_ctx_rebind(nlh_pmap_ctx *c, const double *dfull);
 const PmapTables *pmap_ctx_tables(const nlh_pmap_ctx *c);
 void pmap_gather(const PmapTables *T, hipStream_t s, int nprob, const double *full, double *x);
@@ -381,6 +390,10 @@ int nlh_upload(nlh_handle *h, const char *what, std::initializer_list<HostPart> 
 bool nlh_loss_kind_ok(int32_t kind);
 bool nlh_loss_scale_ok(int32_t kind, const double *scale, size_t cnt);
 int nlh_loss_scale_upload(nlh_handle *h, int32_t kind, const double *scale, size_t cnt, double **dscale);
+// Poisson fits (nlh_pois.hip): a floor finite and positive; a HOST mask (NULL: none) of 0.0 / 1.0, every one of cnt, and HOST
+// counts finite and not negative on every row the mask keeps
+bool nlh_pois_floor_ok(double mu_floor);
+bool nlh_pois_data_ok(const double *y, const double *w, size_t cnt);
 // columns the built-in dense-quadratic family's kernels accept (x in LDS, lds_max of nlh_create): beyond it NLH_ARRAY_SIZE_ERROR
 static const int32_t NLH_DQ_MAX_N = 20000;
 

@@ -16,10 +16,11 @@ k_fit_count(int nprob, int m, const double *__restrict__ w, int32_t *__restrict_
 
 // What a one-call fit does after the covariance chain: a problem that did not solve gets NaN and rank -1; with weights,
 // chi2 = (sum of f_i^2, i ascending, sequential) / dof and every entry of cov is multiplied once by (m - n) / dof before
-// sigma_i = sqrt(cov(i,i)) is taken.  Any of cov, sigma, chi2, rank may be null.
+// sigma_i = sqrt(cov(i,i)) is taken.  unscaled (a Poisson fit, whose covariance carries no chi2): chi2 as above, cov and sigma
+// as they are.  Any of cov, sigma, chi2, rank may be null.
 static __global__ void __launch_bounds__(64)
 k_fit_post(int nprob, int m, int n, const int32_t *__restrict__ status, const int32_t *__restrict__ nz, const double *__restrict__ f,
-           double *__restrict__ cov, double *__restrict__ sigma, double *__restrict__ chi2, int32_t *__restrict__ rank)
+           double *__restrict__ cov, double *__restrict__ sigma, double *__restrict__ chi2, int32_t *__restrict__ rank, int unscaled)
 {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= nprob) return;
@@ -40,6 +41,7 @@ k_fit_post(int nprob, int m, int n, const int32_t *__restrict__ status, const in
         for (int i = 0; i < m; ++i) s = s + fp[i] * fp[i];
         chi2[p] = s / dof;
     }
+    if (unscaled) return;
     const double scale = (double)(m - n) / dof;
     if (cov)
         for (size_t e = 0; e < nn; ++e) {

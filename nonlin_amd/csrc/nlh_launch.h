@@ -1,5 +1,5 @@
-// nlh_launch.h -- the host side of the (point, row) kernels' two workgroup forms (nlh_kernels_place.h), and what the two
-// pairs of wrapping launchers -- parameter maps (nlh_pmap.hip), robust losses (nlh_loss.hip) -- share: the per-stream
+// nlh_launch.h -- the host side of the (point, row) kernels' two workgroup forms (nlh_kernels_place.h), and what the
+// pairs of wrapping launchers -- parameter maps (nlh_pmap.hip), robust losses (nlh_loss.hip), Poisson fits (nlh_pois.hip) -- share: the per-stream
 // scratch of a context, its cap, the column groups and grid of a column-split Jacobian kernel, and the slice loop of a call.
 // Every environment variable is read at every call (tests set them between calls).
 #pragma once

@@ -97,6 +97,8 @@ struct nlh_dq_model {
     nlh_pmap_ctx *pmap = nullptr;
     // a model with a loss (nlh_loss_model_create): the wrapping context around another model's launchers; the scales
     nlh_loss_ctx *loss = nullptr;
+    // a Poisson model (nlh_pois_model_create): the wrapping context around another model's launchers; the counts and the mask
+    nlh_pois_ctx *pois = nullptr;
 };
 
 // Host arrays, one after the other, into one device allocation on the handle's device; synchronised (nlh_internal.h).
@@ -309,11 +311,33 @@ int nlh_loss_model_create(nlh_handle *h, const nlh_dq_model *inner, int32_t kind
     return 0;
 }
 
+// A Poisson model over a launcher-backed inner model created WITHOUT weights (nlh_pois.hip: the wrapping launchers).
+int nlh_pois_model_create(nlh_handle *h, const nlh_dq_model *inner, const double *y, const double *w, double mu_floor, nlh_dq_model **out)
+{
+    if (out) *out = nullptr;
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (!out || !inner || !inner->ufcn || !y || !nlh_pois_floor_ok(mu_floor)) return NLH_INVALID_INPUT_ERROR;
+    const size_t pm = (size_t)inner->nprob * inner->m;
+    if (!nlh_pois_data_ok(y, w, pm)) return NLH_INVALID_INPUT_ERROR;
+    double *base = nullptr;
+    if (const int urc = nlh_upload(h, "Poisson model", {{y, sizeof(double) * pm}, {w, w ? sizeof(double) * pm : 0}}, (void **)&base)) return urc;
+    nlh_pois_ctx *qc = nullptr;
+    const int rc = nlh_pois_wrap(h, base, w ? base + pm : nullptr, mu_floor, inner->ufcn, inner->ujac, inner->uctx, &qc);
+    if (rc) { hipFree(base); return rc; }
+    nlh_dq_model *md = new nlh_dq_model();
+    md->nprob = inner->nprob; md->m = inner->m; md->n = inner->n; md->gamma = 0.0;
+    md->ufcn = nlh_pois_device_fcn; md->ujac = inner->ujac ? nlh_pois_device_jac : nullptr; md->uctx = qc;
+    md->pois = qc; md->owned = base; md->owned_device = h->device;
+    *out = md;
+    return 0;
+}
+
 void nlh_dq_model_destroy(nlh_dq_model *md)
 {
     if (!md) return;
     nlh_pmap_unwrap(md->pmap);
     nlh_loss_unwrap(md->loss);
+    nlh_pois_unwrap(md->pois);
     delete md->expr;
     delete md->expr_prog;
     if (md->owned) { hipSetDevice(md->owned_device); hipFree(md->owned); }

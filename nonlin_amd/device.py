@@ -20,6 +20,7 @@ from ._lib import CURVE_GAUSS, CURVE_LORENTZ, CURVE_EXPDECAY, CURVE_KINDS, curve
 from ._lib import Expr  # noqa: E402,F401
 from ._lib import ParamMap  # noqa: E402,F401
 from ._lib import Loss  # noqa: E402,F401
+from ._lib import Poisson  # noqa: E402,F401
 
 
 def _chk(t, shape, name):
@@ -75,6 +76,15 @@ class _LossCtx(_PmapCtx):
     def close(self):
         if getattr(self, "ptr", None) is not None and self.ptr.value:
             self.lib.nlh_loss_unwrap(self.ptr)
+            self.ptr = C.c_void_p()
+
+
+class _PoisCtx(_PmapCtx):
+    """The context of the Poisson wrapping launchers (nlh_pois_ctx), with everything it points at kept alive."""
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.lib.nlh_pois_unwrap(self.ptr)
             self.ptr = C.c_void_p()
 
 
@@ -268,7 +278,7 @@ class DeviceSolver:
         return y
 
     def curve_fit_batch(self, kind, t, y, x0, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
-                        covariance=True, opts=None, pmap=None, loss=None):
+                        covariance=True, opts=None, pmap=None, loss=None, stat=None):
         """Fit + errors of y.shape[0] curves in one call (nlh_curve_fit_batch): least_squares_solver%solve -- or, with lower /
         upper ([n], one box for every problem), constrained_least_squares_solver%solve -- from x0 [nprob, n] (not modified),
         then the scaled parameter covariance at the solution.  Rows with weight 0 pad ragged data: they do not count as
@@ -279,7 +289,12 @@ class DeviceSolver:
         bound entries at fixed and tied positions are not read, and sigma / cov are those of the full parameters.
         loss (a Loss): a robust fit (nlh_curve_fit_batch_loss), with or without pmap.  fvec is then the transformed residual
         rho~, chi2 = sum rho~^2 / dof, and sigma / cov are those of the transformed problem; loss_apply on the raw residuals
-        gives the weights that flag outliers.  None calls exactly what is called without it."""
+        gives the weights that flag outliers.  None calls exactly what is called without it.
+        stat (a Poisson): y are counts and the fit minimises their Poisson deviance (nlh_curve_fit_batch_pois), with or without
+        pmap.  weights is then the 0 / 1 mask of the rows, fvec the deviance residual, chi2 the deviance / dof, and sigma / cov
+        are unscaled: the inverse Fisher information.  stat together with loss raises ValueError."""
+        if stat is not None and loss is not None:
+            raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
         k = curve_kind(kind)
         nprob, m, shared = self._curve_data(t, y, weights)
         n = curve_nparams(k, ncomp, baseline)
@@ -306,7 +321,12 @@ class DeviceSolver:
         ptr = lambda a: a.data_ptr() if a is not None else None
         plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
         phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
-        if loss is not None:
+        if stat is not None:
+            rc = self.lib.nlh_curve_fit_batch_pois(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
+                                                   y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
+                                                   pmap.ptr if pmap is not None else None, stat.mu_floor,
+                                                   x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
+        elif loss is not None:
             dscale, sh = self._loss_scale(loss, nprob, dev)
             rc = self.lib.nlh_curve_fit_batch_loss(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
                                                    y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
@@ -320,7 +340,7 @@ class DeviceSolver:
             rc = self.lib.nlh_curve_fit_batch_pmap(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
                                                    y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr,
                                                    x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        name = "nlh_curve_fit_batch_loss" if loss is not None else "nlh_curve_fit_batch" if pmap is None else "nlh_curve_fit_batch_pmap"
+        name = "nlh_curve_fit_batch_pois" if stat is not None else "nlh_curve_fit_batch_loss" if loss is not None else "nlh_curve_fit_batch" if pmap is None else "nlh_curve_fit_batch_pmap"
         self.h.check(rc, name)
         if rc:
             raise RuntimeError(f"{name} returned {rc}")
@@ -379,10 +399,12 @@ class DeviceSolver:
         return y
 
     def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None,
-                       pmap=None, loss=None):
+                       pmap=None, loss=None, stat=None):
         """Fit + errors of y.shape[0] data sets to a formula in one call (nlh_expr_fit_batch): curve_fit_batch with an Expr in
-        the place of (kind, ncomp, baseline), pmap (e.g. ParamMap.for_expr(expr, ...)) and loss (a Loss) included.  Returns
-        (x, fvec, sigma, cov, chi2, rank, ibs, status)."""
+        the place of (kind, ncomp, baseline), pmap (e.g. ParamMap.for_expr(expr, ...)), loss (a Loss) and stat (a Poisson)
+        included.  Returns (x, fvec, sigma, cov, chi2, rank, ibs, status)."""
+        if stat is not None and loss is not None:
+            raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
         nprob, m, shared = self._expr_data(expr, t, y, weights)
         n = expr.nparams
         _chk(x0, (nprob, n), "x0")
@@ -408,7 +430,12 @@ class DeviceSolver:
         ptr = lambda a: a.data_ptr() if a is not None else None
         plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
         phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
-        if loss is not None:
+        if stat is not None:
+            rc = self.lib.nlh_expr_fit_batch_pois(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(),
+                                                  ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr if pmap is not None else None,
+                                                  stat.mu_floor,
+                                                  x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
+        elif loss is not None:
             dscale, sh = self._loss_scale(loss, nprob, dev)
             rc = self.lib.nlh_expr_fit_batch_loss(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(),
                                                   ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr if pmap is not None else None,
@@ -422,7 +449,7 @@ class DeviceSolver:
             rc = self.lib.nlh_expr_fit_batch_pmap(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(),
                                                   ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr,
                                                   x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        name = "nlh_expr_fit_batch_loss" if loss is not None else "nlh_expr_fit_batch" if pmap is None else "nlh_expr_fit_batch_pmap"
+        name = "nlh_expr_fit_batch_pois" if stat is not None else "nlh_expr_fit_batch_loss" if loss is not None else "nlh_expr_fit_batch" if pmap is None else "nlh_expr_fit_batch_pmap"
         self.h.check(rc, name)
         if rc:
             raise RuntimeError(f"{name} returned {rc}")
@@ -526,6 +553,44 @@ class DeviceSolver:
         if rc:
             raise RuntimeError(f"nlh_loss_apply_batch returned {rc}")
         return out, g, wgt
+
+    # -- Poisson likelihood fits ---------------------------------------------------
+    def pois_launchers(self, stat, fcn, jac, ctx, y, weights=None):
+        """The Poisson deviance for any launcher pair: wraps (fcn, jac, ctx) -- of curve_launchers or expr_launchers made
+        WITHOUT weights on the same counts y [nprob, m], or a user's own whose residual is model - y -- in the Poisson
+        launchers (nlh_pois_wrap) and returns (fcn, jac, ctx) for lm_solve_batch_device, cls_solve_batch_device,
+        lm_covariance_batch_device (scaled=False: the inverse Fisher information), fd_jacobian_device and pmap_launchers.
+        weights: the 0 / 1 mask [nprob, m] of the rows, or None.  jac is None without an inner Jacobian launcher (pass jac=None
+        to the solver: forward differences of the wrapped residual).  Keep the returned ctx alive while solving; ctx.close()
+        frees it (so does garbage collection)."""
+        nprob, m = y.shape
+        _chk(y, (nprob, m), "y")
+        if weights is not None:
+            _chk(weights, (nprob, m), "weights")
+        out = C.c_void_p()
+        rc = self.lib.nlh_pois_wrap(self.h.ptr, y.data_ptr(), weights.data_ptr() if weights is not None else None, stat.mu_floor,
+                                    self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), C.byref(out))
+        self.h.check(rc, "nlh_pois_wrap")
+        if rc:
+            raise RuntimeError(f"nlh_pois_wrap returned {rc}")
+        wrapped = _PoisCtx(self.lib, out, (stat, fcn, jac, ctx, y, weights))
+        return (C.cast(self.lib.nlh_pois_device_fcn, _lib.DEVFCN),
+                C.cast(self.lib.nlh_pois_device_jac, _lib.DEVFCN) if jac is not None else None, wrapped)
+
+    def pois_apply(self, stat, r, y, weights=None):
+        """(out, g, dev) of raw residuals r = model - y [nprob, m] for counts y under a Poisson (nlh_pois_apply_batch): the
+        deviance residual, the row factor of the Jacobian, and the row's deviance (0.0 on a masked row)."""
+        nprob, m = r.shape
+        _chk(r, (nprob, m), "r"); _chk(y, (nprob, m), "y")
+        if weights is not None:
+            _chk(weights, (nprob, m), "weights")
+        out, g, dev = (torch.empty_like(r) for _ in range(3))
+        rc = self.lib.nlh_pois_apply_batch(self.h.ptr, nprob, m, y.data_ptr(), weights.data_ptr() if weights is not None else None,
+                                           stat.mu_floor, r.data_ptr(), out.data_ptr(), g.data_ptr(), dev.data_ptr())
+        self.h.check(rc, "nlh_pois_apply_batch")
+        if rc:
+            raise RuntimeError(f"nlh_pois_apply_batch returned {rc}")
+        return out, g, dev
 
     def _ctxp(self, ctx):
         if isinstance(ctx, _PmapCtx):

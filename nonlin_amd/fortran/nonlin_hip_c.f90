@@ -237,6 +237,16 @@ module nonlin_hip_c
             type(c_ptr), intent(out) :: model
             integer(c_int) :: rc
         end function
+        ! Poisson likelihood fits (include/nonlin_hip.h: nlh_pois_*): a model minimising the deviance of counts over an unweighted model
+        function nlh_pois_model_create(h, inner, y, w, mu_floor, model) bind(C, name="nlh_pois_model_create") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h, inner
+            real(c_double), intent(in) :: y(*)
+            type(c_ptr), value :: w
+            real(c_double), value :: mu_floor
+            type(c_ptr), intent(out) :: model
+            integer(c_int) :: rc
+        end function
         function nlh_curve_nparams(kind, ncomp, nbase) bind(C, name="nlh_curve_nparams") result(n)
             import :: c_int32_t
             integer(c_int32_t), value :: kind, ncomp, nbase

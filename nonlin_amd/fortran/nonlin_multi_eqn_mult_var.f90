@@ -62,6 +62,7 @@ module nonlin_multi_eqn_mult_var
         procedure, public :: create_expr => dmb_create_expr
         procedure, public :: create_mapped => dmb_create_mapped
         procedure, public :: create_robust => dmb_create_robust
+        procedure, public :: create_poisson => dmb_create_poisson
         procedure, public :: destroy => dmb_destroy
         procedure, public :: is_defined => dmb_defined
         procedure, public :: get_problem_count => dmb_nprob
@@ -476,6 +477,44 @@ contains
         sc = scale
         call this%destroy()
         rc = nlh_loss_model_create(nlh_default_handle(), inner%model_, kind, sc, shared, this%model_)
+        if (rc /= 0) error stop rc
+        this%neqn_ = inner%neqn_
+        this%nvar_ = inner%nvar_
+        this%nprob_ = inner%nprob_
+        this%analytic_ = inner%analytic_
+    end subroutine
+
+    !> The Poisson likelihood for a launcher-backed model created WITHOUT weights (create_curve, create_expr,
+    !> create_from_device_fcn) on the same counts y(m, nprob): a model of the same unknowns over inner, which must outlive it,
+    !> whose residuals are the deviance residuals, so that the unchanged solvers minimise -2 log L (INTEGRATION.md 6k).  w(m,
+    !> nprob), optional, is the mask of the rows: 1 counts, 0 does not.  mu_floor, optional (default 2**(-20)): below this model
+    !> value the residual is continued linearly.  solve_batch then returns the deviance residuals; call covariance_batch with
+    !> scaled = .false.: the inverse Fisher information.  Counts that are negative or not finite on a row the mask keeps (a
+    !> masked row may hold anything), a mask entry that is neither 0 nor 1 or a floor that is not finite or not positive stop
+    !> the program with NL_INVALID_INPUT_ERROR.
+    subroutine dmb_create_poisson(this, inner, y, w, mu_floor)
+        class(device_model_batch), intent(inout) :: this
+        class(device_model_batch), intent(in) :: inner
+        real(real64), intent(in), dimension(:,:) :: y
+        real(real64), intent(in), dimension(:,:), optional :: w
+        real(real64), intent(in), optional :: mu_floor
+        integer(c_int) :: rc
+        real(c_double) :: floor_
+        real(c_double), allocatable, target :: yc(:,:), wc(:,:)
+        type(c_ptr) :: wp
+        if (.not.inner%is_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR
+        if (any(shape(y) /= [inner%neqn_, inner%nprob_])) error stop NL_ARRAY_SIZE_ERROR
+        floor_ = 2.0d0**(-20)
+        if (present(mu_floor)) floor_ = mu_floor
+        yc = y
+        wp = c_null_ptr
+        if (present(w)) then
+            if (any(shape(w) /= [inner%neqn_, inner%nprob_])) error stop NL_ARRAY_SIZE_ERROR
+            wc = w
+            wp = c_loc(wc)
+        end if
+        call this%destroy()
+        rc = nlh_pois_model_create(nlh_default_handle(), inner%model_, yc, wp, floor_, this%model_)
         if (rc /= 0) error stop rc
         this%neqn_ = inner%neqn_
         this%nvar_ = inner%nvar_
