@@ -1142,6 +1142,110 @@ int nlh_expr_fit_batch_pois_h(nlh_handle *h, const nlh_options *opts, const nlh_
 int nlh_pois_model_create(nlh_handle *h, const nlh_dq_model *inner, const double *y, const double *w, double mu_floor,
                           nlh_dq_model **model);
 
+/* ---- global fits: parameters shared across the data sets of a group, for any device model -------------------------------
+ * A GROUP is G = nsets data sets of one inner model with N = nfull parameters, S = nshared of which have one value for the
+ * whole group; the other L = N - S are free per data set.  A tie (nlh_pmap) links parameters inside one problem; a group
+ * links them across problems.  G consecutive inner problems p G + g of m rows are, as they lie in memory, ONE outer problem
+ * p of M = G m rows: y, weights and fvec [ngroup G][m] are [ngroup][M] as they stand.
+ * THE ORDER OF THE OUTER UNKNOWNS IS PART OF THE INTERFACE: n = S + G L of them,
+ *   the shared parameters first, in ascending inner index;
+ *   then, for data set g = 0 .. G - 1, its local parameters in ascending inner index.
+ * nlh_group_index(g, set, k) is the outer unknown of inner parameter k of data set `set` (the same for every set when k is
+ * shared; -1 out of range).  S may be 0 (nothing shared: a block-diagonal problem) or N (everything shared).
+ * The group object is host code and needs no GPU (nlh_group_gather_batch, _expand_batch and _sigma_batch keep a device copy of
+ * its tables in it from their first use, which nlh_group_destroy frees).  shared [nshared]: distinct inner indices, in any
+ * order.  Refused with NLH_INVALID_INPUT_ERROR, *g left NULL: a NULL argument (shared may be NULL when nshared = 0), nfull
+ * < 1 or > NLH_PMAP_MAX_N, nshared outside 0 .. nfull, an index out of range or repeated, nsets < 1, n beyond int32.
+ * A group's Jacobian is DENSE to the solver, [n][M], though the local columns of a data set are zero in every other data
+ * set's rows: its size and the solve's cost grow as G^2 and G^3.  The practical range is G of tens, not thousands. */
+typedef struct nlh_group nlh_group;
+int  nlh_group_create(int32_t nfull, int32_t nshared, const int32_t *shared, int32_t nsets, nlh_group **g);
+void nlh_group_destroy(nlh_group *g);
+void nlh_group_shape(const nlh_group *g, int32_t *nfull, int32_t *nshared, int32_t *nsets,
+                     int32_t *nouter);                                                       /* any output may be NULL */
+int32_t nlh_group_index(const nlh_group *g, int32_t set, int32_t k);
+/* The wrapping launchers.  nlh_group_wrap makes their context on the handle's device around ANY inner launcher pair (a
+ * curve's, a formula's, a loss's, a Poisson pair's, a map's, a user's own) whose context indexes its data by inner problem;
+ * jac may be NULL.  nlh_group_device_fcn / _jac are then launchers of the outer problem with `out` as their context: outer
+ * point q of outer problem p (dprob ? dprob[q] : q) stands for the G inner points q G + g of inner problems p G + g.
+ *   nlh_group_device_fcn  expand into scratch P [npoints G][N] and the inner problem list; the inner fcn with npoints G
+ *                         points, n = N and m = M / G STRAIGHT INTO the caller's dF (no copy)
+ *   nlh_group_device_jac  expand; the inner jac into scratch Jf [npoints G][N][m]; scatter into dJ [npoints][n][M]
+ *                         (column-major, ld = M): a shared column takes rows g m + i from every data set, the local column
+ *                         (g, l) from its own and is +0.0 in every other row.  Every entry of dJ is written.  With a NULL
+ *                         inner jac pass NULL for the outer jac: the solver then takes forward differences over the n
+ *                         OUTER unknowns, (n + 1) G inner evaluations per Jacobian where a structured difference would
+ *                         need (N + 1) G -- correct, but wasteful at large G.
+ * Nothing is computed: values are copied, so the bits are the inner launchers'.  Both return NLH_INVALID_INPUT_ERROR when M
+ * is not a multiple of G or n != S + G L, NLH_UNDEFINED_FUNCTION_ERROR for a Jacobian call without an inner jac, and
+ * otherwise what the inner launcher returns.  They do not synchronise.
+ * Scratch belongs to the context, exactly as a map's: one buffer per stream, grown on demand, kept until
+ * nlh_group_unwrap, at most 1 GiB per call; a call that needs more runs in slices of outer points -- the same bits.
+ * NLH_GROUP_SCRATCH = bytes lowers the cap, NLH_GROUP_FORM = row | flat forces a workgroup form of the scatter for the sizes it
+ * can hold (flat: m <= 256), NLH_GROUP_SPLIT = number of column groups overrides its column split (environment, read at each
+ * call; tests).  The scatter moves 8 G m N bytes in and 8 G m (S + G L) out per outer point; it is store-bound and at large G
+ * mostly writes zeros, which is what a dense solver costs. */
+typedef struct nlh_group_ctx nlh_group_ctx;
+int  nlh_group_wrap(nlh_handle *h, const nlh_group *g, nlh_device_vecfcn fcn, nlh_device_jacfcn jac, void *inner_ctx,
+                    nlh_group_ctx **out);
+void nlh_group_unwrap(nlh_group_ctx *c);
+int  nlh_group_device_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t M, double *dF);
+int  nlh_group_device_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t M, double *dJ);
+/* The batch steps on the DEVICE (the handle's stream; copies, no arithmetic):
+ *   gather  dfull [ngroup G][N] -> dx [ngroup][n]; a shared parameter takes the value of the group's data set 0
+ *   expand  dx [ngroup][n] -> dfull [ngroup G][N]
+ *   sigma   dsigma [ngroup][n] -> dsigma_full [ngroup G][N]; NaN for every data set of a group whose dfail [ngroup] entry is
+ *           non-zero (dfail may be NULL) */
+int  nlh_group_gather_batch(nlh_handle *h, const nlh_group *g, int32_t ngroup, const double *dfull, double *dx);
+int  nlh_group_expand_batch(nlh_handle *h, const nlh_group *g, int32_t ngroup, const double *dx, double *dfull);
+int  nlh_group_sigma_batch(nlh_handle *h, const nlh_group *g, int32_t ngroup, const double *dsigma, const int32_t *dfail,
+                           double *dsigma_full);
+/* One-call global fits: the arguments of nlh_curve_fit_batch / nlh_expr_fit_batch plus, after xu, the group, a loss
+ * (loss, dscale [nprob] per DATA SET or one shared; NLH_LOSS_LINEAR: none, dscale not read) and a statistic (stat: 0 least
+ * squares, 1 Poisson deviance with mu_floor, dw then the 0 / 1 mask; the loss must then be NLH_LOSS_LINEAR).  They take no
+ * parameter map: a map inside a group works through the launchers by hand.  nprob counts DATA SETS and must be a multiple
+ * of G; ngroup = nprob / G.  The composition is fixed: the loss (or the Poisson pair) wraps the model's launchers per data
+ * set, the group wraps the result.  The caller sees per-data-set arrays:
+ *   dx [nprob][N] in and out: on entry a shared parameter starts from the value of the group's data set 0; on exit it is
+ *   equal across the group.  dfvec [nprob][m], dsigma [nprob][N] (a shared parameter's sigma repeated per data set).
+ *   xl, xu: HOST [N] or NULL, expanded to the n outer unknowns.
+ * and per GROUP: dcov [ngroup][n][n] in the outer order (nlh_group_index locates entries), dchi2, drank, ib, status [ngroup].
+ * Every rule of the unsuffixed entry point that names m or n holds with M = G m and n = S + G L: M >= n, M > n for errors, and
+ * the zero-weight degrees of freedom, counted over the group's G m rows (a group is refused on its own count alone: a data
+ * set whose rows all weigh 0 does not refuse its group, but its local columns are then zero and drank reports the
+ * shortfall).  Errors, in this order:
+ * NLH_ERR_BAD_HANDLE; NLH_INVALID_INPUT_ERROR (a model that is refused, nprob < 0, m < 1, a NULL group, a group of another
+ * parameter count, nprob not a multiple of G); NLH_UNDERDEFINED_PROBLEM_ERROR (M < n); NLH_INVALID_INPUT_ERROR (a loss
+ * outside 0 .. 3, a stat outside 0 .. 1, Poisson with a loss); then, unless nprob = 0, NLH_INVALID_INPUT_ERROR for a NULL
+ * array, errors asked for with M <= n, a bad mu_floor; the _h forms check scales, masks and counts as the _loss and _pois
+ * entry points do. */
+int nlh_curve_fit_batch_group(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                              int32_t m, const double *dt, int32_t shared_t, const double *dy, const double *dw, int32_t analytic,
+                              const double *xl, const double *xu, const nlh_group *g, int32_t loss, const double *dscale,
+                              int32_t shared_scale, int32_t stat, double mu_floor, double *dx, double *dfvec, double *dsigma,
+                              double *dcov, double *dchi2, int32_t *drank, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_curve_fit_batch_group_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                                int32_t m, const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic,
+                                const double *xl, const double *xu, const nlh_group *g, int32_t loss, const double *scale,
+                                int32_t shared_scale, int32_t stat, double mu_floor, double *x, double *fvec, double *sigma,
+                                double *cov, double *chi2, int32_t *rank, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_expr_fit_batch_group(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+                             int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl,
+                             const double *xu, const nlh_group *g, int32_t loss, const double *dscale, int32_t shared_scale,
+                             int32_t stat, double mu_floor, double *dx, double *dfvec, double *dsigma, double *dcov,
+                             double *dchi2, int32_t *drank, nlh_iteration_behavior *ib, int32_t *status);
+int nlh_expr_fit_batch_group_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+                               int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl,
+                               const double *xu, const nlh_group *g, int32_t loss, const double *scale, int32_t shared_scale,
+                               int32_t stat, double mu_floor, double *x, double *fvec, double *sigma, double *cov,
+                               double *chi2, int32_t *rank, nlh_iteration_behavior *ib, int32_t *status);
+/* A device-function MODEL of the outer unknowns of a group over a launcher-backed inner model (device-function, curve,
+ * formula, loss, Poisson or mapped; a dense-quadratic model: NLH_INVALID_INPUT_ERROR), which must outlive it: nprob / G
+ * problems of G m rows and n unknowns.  The same contract as nlh_pmap_model_create.  Errors: NLH_ERR_BAD_HANDLE, then
+ * NLH_INVALID_INPUT_ERROR (a NULL argument, a dense-quadratic inner model, a group of another parameter count, an inner nprob
+ * that is no multiple of G). */
+int nlh_group_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_group *g, nlh_dq_model **model);
+
 /* ---- per-kernel timing (HIP events on the handle's stream) ------------------ */
 #define NLH_K_DQ_RESIDUAL   0
 #define NLH_K_DQ_PANEL      1

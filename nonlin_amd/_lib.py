@@ -321,6 +321,34 @@ SYMBOLS = {
                                             c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
                                             C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_pois_model_create": (C.c_int, [_H, C.c_void_p, c_double_p, c_double_p, C.c_double, C.POINTER(C.c_void_p)]),
+    "nlh_group_create": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "nlh_group_destroy": (None, [C.c_void_p]),
+    "nlh_group_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
+    "nlh_group_index": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
+    "nlh_group_wrap": (C.c_int, [_H, C.c_void_p, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "nlh_group_unwrap": (None, [C.c_void_p]),
+    "nlh_group_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_group_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_group_gather_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_group_expand_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_group_sigma_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_curve_fit_batch_group": (C.c_int, [
+        _H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+        C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_curve_fit_batch_group_h": (C.c_int, [
+        _H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+        c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, c_double_p, C.c_int32,
+        C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_fit_batch_group": (C.c_int, [
+        _H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32,
+        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+        C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_fit_batch_group_h": (C.c_int, [
+        _H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32,
+        c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, c_double_p, C.c_int32,
+        C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_group_model_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "nlh_timing_enable": (None, [_H, C.c_int32]),
     "nlh_timing_reset": (None, [_H]),
     "nlh_timing_get": (C.c_int, [_H, C.c_int32, c_double_p, C.POINTER(C.c_int64)]),
@@ -507,6 +535,58 @@ class ParamMap:
     def close(self):
         if getattr(self, "ptr", None) is not None and self.ptr.value:
             self.lib.nlh_pmap_destroy(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Group:
+    """A group of data sets for a global fit (nlh_group_create: host code, needs no GPU): nsets data sets of one model with
+    nparams parameters, of which the ones listed in shared have one value for the whole group and the others are free per data
+    set.  E.g. Group(3, shared=(1,), nsets=8): eight decays a*exp(-k*t)+c with one k.  The outer unknowns are nouter =
+    S + nsets * (nparams - S): the shared parameters first, in ascending index, then the local ones of data set 0, 1, ...,
+    each in ascending index; index(set, k) is the outer unknown of parameter k of data set `set`.  Raises ValueError for what
+    the library refuses (an index out of range or repeated, nsets < 1).  A group's Jacobian is dense to the solver: nsets of
+    tens, not thousands.  close() frees it (so does garbage collection)."""
+
+    def __init__(self, nparams, shared=(), nsets=1):
+        import numpy as np
+        self.lib = load()
+        self.ptr = C.c_void_p()
+        sh = np.ascontiguousarray([int(k) for k in shared], dtype=np.int32)
+        rc = self.lib.nlh_group_create(int(nparams), len(sh), sh.ctypes.data_as(c_int32_p), int(nsets), C.byref(self.ptr))
+        if rc:
+            self.ptr = C.c_void_p()
+            raise ValueError(f"Group: the library refuses this group (nlh_group_create returned {rc}): nparams must be 1 .. 8192, "
+                             "shared must hold distinct indices in 0 .. nparams - 1, nsets must be at least 1, and the outer "
+                             "unknowns S + nsets * (nparams - S) must fit 31 bits")
+        s = [C.c_int32() for _ in range(4)]
+        self.lib.nlh_group_shape(self.ptr, *[C.byref(v) for v in s])
+        self.nparams, self.nshared, self.nsets, self.nouter = (v.value for v in s)
+
+    @classmethod
+    def for_expr(cls, expr, shared=(), nsets=1):
+        """The same by the parameter names of an Expr: Group.for_expr(e, shared=("k",), nsets=8)."""
+        names = [v.strip() for v in expr.params.split(",")]
+        for name in shared:
+            if name not in names:
+                raise ValueError(f"Group: {name!r} is not a parameter of the formula ({', '.join(names)})")
+        return cls(len(names), shared=[names.index(k) for k in shared], nsets=nsets)
+
+    def index(self, set, k):
+        """The outer unknown of parameter k of data set `set` (nlh_group_index)."""
+        j = self.lib.nlh_group_index(self.ptr, int(set), int(k))
+        if j < 0:
+            raise IndexError(f"Group.index({set}, {k}): outside {self.nsets} data sets of {self.nparams} parameters")
+        return j
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.lib.nlh_group_destroy(self.ptr)
             self.ptr = C.c_void_p()
 
     def __del__(self):

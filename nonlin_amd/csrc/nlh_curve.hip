@@ -189,3 +189,26 @@ int nlh_curve_fit_batch_pois_h(nlh_handle *h, const nlh_options *opts, int32_t k
     return curve_fit(h, opts, kind, ncomp, nbase, analytic, {nprob, m, t, shared_t, y, w, xl, xu, pm, NLH_LOSS_LINEAR, nullptr, 0, x, fvec, sigma,
                                              cov, chi2, rank, ib, status, NLH_STAT_POISSON, mu_floor}, true);
 }
+
+// The global fits: the loss (or the Poisson pair) wraps the curve per data set, the group wraps the result (nlh_fit.hip).
+int nlh_curve_fit_batch_group(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m,
+                              const double *dt, int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl,
+                              const double *xu, const nlh_group *g, int32_t loss, const double *dscale, int32_t shared_scale, int32_t stat,
+                              double mu_floor, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+                              nlh_iteration_behavior *ib, int32_t *status)
+{
+    if (h && !g) return NLH_INVALID_INPUT_ERROR;
+    return curve_fit(h, opts, kind, ncomp, nbase, analytic, {nprob, m, dt, shared_t, dy, dw, xl, xu, nullptr, loss, dscale, shared_scale, dx,
+                                                             dfvec, dsigma, dcov, dchi2, drank, ib, status, stat, mu_floor, g}, false);
+}
+
+int nlh_curve_fit_batch_group_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m,
+                                const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl,
+                                const double *xu, const nlh_group *g, int32_t loss, const double *scale, int32_t shared_scale, int32_t stat,
+                                double mu_floor, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+                                nlh_iteration_behavior *ib, int32_t *status)
+{
+    if (h && !g) return NLH_INVALID_INPUT_ERROR;
+    return curve_fit(h, opts, kind, ncomp, nbase, analytic, {nprob, m, t, shared_t, y, w, xl, xu, nullptr, loss, scale, shared_scale, x, fvec,
+                                                             sigma, cov, chi2, rank, ib, status, stat, mu_floor, g}, true);
+}

@@ -1,4 +1,4 @@
-// nlh_fit.hip -- the one-call fit + errors pipeline behind the entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois}{,_h}
+// nlh_fit.hip -- the one-call fit + errors pipeline behind the entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois,_group}{,_h}
 // (nlh_internal.h: nlh_fit_run).  A model kind hands it a FitSource -- its launchers, a context and how to point that context
 // at a run of problems -- and the rest of the entry point's arguments as a FitArgs; here are the documented ladder of checks,
 // the staging of host arrays, the composition (the loss wraps the model's launchers, the parameter map, if any, wraps the
@@ -25,11 +25,12 @@ struct FitRun {
     nlh_pois_ctx *qc = nullptr;
     nlh_pmap_ctx *pc = nullptr;
     const double *fullc = nullptr;     // the map's private copy of the full parameters
+    int32_t G = 1;                     // a global fit: a problem of the solve is G of the model's, a->m its G m rows
     void bind(int32_t p0) const
     {
-        src->bind(src->ctx, a->t, a->y, qc ? nullptr : a->w, p0);
+        src->bind(src->ctx, a->t, a->y, qc ? nullptr : a->w, p0 * G);
         if (qc) pois_ctx_rebind(qc, a->y + (size_t)p0 * a->m, a->w ? a->w + (size_t)p0 * a->m : nullptr);
-        if (lc) loss_ctx_rebind(lc, a->shared_scale ? a->scale : a->scale + p0);
+        if (lc) loss_ctx_rebind(lc, a->shared_scale ? a->scale : a->scale + (size_t)p0 * G);
         if (pc) pmap_ctx_rebind(pc, fullc + (size_t)p0 * N);
     }
 };
@@ -160,13 +161,76 @@ static int fit_mapped(FitRun r, int32_t n)
     return rc;
 }
 
+// ... of groups: fit_solve over the n outer unknowns of ngroup problems of M = G m rows with the group's launchers around r's,
+// between a gather and an expansion.  y, w and fvec are the caller's as they stand; x and sigma are per data set on the
+// caller's side and per group in between; cov, chi2, rank, ib and status are per group on both.
+static int fit_grouped(FitRun r, int32_t n)
+{
+    nlh_handle *h = r.h;
+    const FitArgs &a = *r.a;
+    int32_t G;
+    nlh_group_shape(a.grp, nullptr, nullptr, &G, nullptr);
+    const int32_t ngroup = a.nprob / G;
+    const size_t N = (size_t)r.N, nf = (size_t)n, ng = (size_t)ngroup;
+    if ((ng * std::max(nf, (size_t)G * N) + 255) / 256 > 0x7fffffffu) return NLH_ARRAY_SIZE_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    int rc = 0;
+    const size_t doubles = ng * nf + (a.sigma ? ng * nf : 0);    // the outer unknowns, their sigma; the failure flags
+    double *base = nullptr;
+    if (hipMalloc(&base, sizeof(double) * doubles + sizeof(int32_t) * ng) != hipSuccess) {
+        h->err = "hipMalloc (global fit)";
+        return NLH_OUT_OF_MEMORY_ERROR;
+    }
+    double *xo = base, *so = a.sigma ? base + ng * nf : nullptr;
+    int32_t *dfail = (int32_t *)(base + doubles);
+    std::vector<double> lo, hi;                                   // the bounds of parameter k at every outer unknown of k
+    for (int32_t g = 0; g < G; ++g)
+        for (int32_t k = 0; k < (int32_t)N; ++k) {
+            const int32_t j = nlh_group_index(a.grp, g, k);
+            if (a.xl) { lo.resize(nf); lo[j] = a.xl[k]; }
+            if (a.xu) { hi.resize(nf); hi[j] = a.xu[k]; }
+        }
+    FitArgs ga = a;                                               // what the solve sees: ngroup problems of G m rows
+    ga.nprob = ngroup; ga.m = G * a.m;
+    std::vector<int32_t> st(ng, 0);
+    nlh_group_ctx *gc = nullptr;                                  // its copy of the tables serves the steps here too
+    hipError_t e = hipSuccess;
+    rc = nlh_group_wrap(h, a.grp, r.fcn, r.jac, r.ctx, &gc);
+    if (!rc) {
+        group_gather(group_ctx_tables(gc), s, ngroup, a.x, xo);
+        r.fcn = nlh_group_device_fcn; r.jac = r.jac ? nlh_group_device_jac : nullptr; r.ctx = gc;
+        r.a = &ga; r.G = G;
+        rc = fit_solve(r, n, a.xl ? lo.data() : nullptr, a.xu ? hi.data() : nullptr, xo, so, a.cov, st.data());
+    }
+    if (!rc) {
+        // every group, also one that was refused on its degrees of freedom: on exit a shared parameter is equal across it
+        group_expand(group_ctx_tables(gc), s, ngroup, xo, nullptr, a.x);
+        if (a.sigma) {
+            e = hipMemcpyAsync(dfail, st.data(), sizeof(int32_t) * ng, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) group_expand(group_ctx_tables(gc), s, ngroup, so, dfail, a.sigma);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(s);                // (st is a host vector; the buffers go)
+    nlh_group_unwrap(gc);
+    (void)hipFree(base);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) {
+        h->err = std::string("global fit: ") + hipGetErrorString(e);
+        return NLH_ERR_HIP;
+    }
+    if (!rc && a.status) memcpy(a.status, st.data(), sizeof(int32_t) * ng);
+    return rc;
+}
+
 // The composition on device pointers: the loss wraps the model's launchers (NLH_LOSS_LINEAR: no context, no kernel of the
 // loss) -- in a Poisson fit the Poisson wrapper does, in the same place --, the map, if any, wraps the result.  n: the
 // unknowns of the solve.
 static int fit_device(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, int32_t n)
 {
     FitRun r{h, opts, &src, &a, src.N, src.fcn, src.jac, src.ctx};
-    auto run = [&]() { return a.pm ? fit_mapped(r, n) : fit_solve(r, n, a.xl, a.xu, a.x, a.sigma, a.cov, a.status); };
+    auto run = [&]() { return a.grp ? fit_grouped(r, n) : a.pm ? fit_mapped(r, n) : fit_solve(r, n, a.xl, a.xu, a.x, a.sigma, a.cov, a.status); };
     if (a.stat == NLH_STAT_POISSON) {
         int rc = nlh_pois_wrap(h, a.y, a.w, a.mu_floor, src.fcn, src.jac, src.ctx, &r.qc);
         if (rc) return rc;
@@ -200,11 +264,17 @@ static int fit_staged(nlh_handle *h, const nlh_options *opts, const FitSource &s
 {
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    const size_t N = (size_t)src.N, np = (size_t)a.nprob, pm = np * a.m, nn = N * N;
+    const size_t N = (size_t)src.N, np = (size_t)a.nprob, pm = np * a.m;
+    size_t nq = np, nn = N * N;                                   // problems of the solve and the doubles of one's cov: a global fit's
+    if (a.grp) {                                                  // are per group and over the outer unknowns
+        int32_t G;
+        nlh_group_shape(a.grp, nullptr, nullptr, &G, nullptr);
+        nq = np / G; nn = (size_t)n * n;
+    }
     const size_t tm = src.tdoubles * (a.shared_t ? (size_t)a.m : pm);
-    const size_t doubles = tm + pm * (a.w ? 3 : 2) + np * N + (a.sigma ? np * N : 0) + (a.cov ? np * nn : 0) + (a.chi2 ? np : 0);
+    const size_t doubles = tm + pm * (a.w ? 3 : 2) + np * N + (a.sigma ? np * N : 0) + (a.cov ? nq * nn : 0) + (a.chi2 ? nq : 0);
     double *base = nullptr;
-    if (hipMalloc(&base, sizeof(double) * doubles + sizeof(int32_t) * np) != hipSuccess) {
+    if (hipMalloc(&base, sizeof(double) * doubles + sizeof(int32_t) * nq) != hipSuccess) {
         h->err = std::string("hipMalloc (") + src.what + ")";
         return NLH_OUT_OF_MEMORY_ERROR;
     }
@@ -216,8 +286,8 @@ static int fit_staged(nlh_handle *h, const nlh_options *opts, const FitSource &s
     d.fvec = q; q += pm;
     d.x = q; q += np * N;
     d.sigma = a.sigma ? q : nullptr; q += a.sigma ? np * N : 0;
-    d.cov = a.cov ? q : nullptr; q += a.cov ? np * nn : 0;
-    d.chi2 = a.chi2 ? q : nullptr; q += a.chi2 ? np : 0;
+    d.cov = a.cov ? q : nullptr; q += a.cov ? nq * nn : 0;
+    d.chi2 = a.chi2 ? q : nullptr; q += a.chi2 ? nq : 0;
     d.rank = a.rank ? (int32_t *)q : nullptr;
     d.t = dt; d.y = dy; d.w = dw; d.scale = dscale;
     hipError_t e = hipMemcpyAsync(dt, a.t, sizeof(double) * tm, hipMemcpyHostToDevice, s);
@@ -230,9 +300,9 @@ static int fit_staged(nlh_handle *h, const nlh_options *opts, const FitSource &s
         e = hipMemcpyAsync(a.x, d.x, sizeof(double) * np * N, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(a.fvec, d.fvec, sizeof(double) * pm, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess && a.sigma) e = hipMemcpyAsync(a.sigma, d.sigma, sizeof(double) * np * N, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && a.cov) e = hipMemcpyAsync(a.cov, d.cov, sizeof(double) * np * nn, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && a.chi2) e = hipMemcpyAsync(a.chi2, d.chi2, sizeof(double) * np, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && a.rank) e = hipMemcpyAsync(a.rank, d.rank, sizeof(int32_t) * np, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && a.cov) e = hipMemcpyAsync(a.cov, d.cov, sizeof(double) * nq * nn, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && a.chi2) e = hipMemcpyAsync(a.chi2, d.chi2, sizeof(double) * nq, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && a.rank) e = hipMemcpyAsync(a.rank, d.rank, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s);
     }
     const hipError_t e2 = hipStreamSynchronize(s);
     (void)hipFree(base);
@@ -255,11 +325,22 @@ int nlh_fit_run(nlh_handle *h, const nlh_options *opts, const FitSource &src, co
         nlh_pmap_shape(a.pm, &nfull, &n, nullptr);
         if (nfull != src.N) return NLH_INVALID_INPUT_ERROR;
     }
-    if (a.m < n) return NLH_UNDERDEFINED_PROBLEM_ERROR;
+    int64_t M = a.m;                                              // the rows of a problem of the solve: a group's G m
+    if (a.grp) {
+        int32_t nfull, G;
+        if (a.pm) return NLH_INVALID_INPUT_ERROR;
+        nlh_group_shape(a.grp, &nfull, nullptr, &G, &n);
+        if (nfull != src.N || a.nprob % G != 0) return NLH_INVALID_INPUT_ERROR;
+        M = (int64_t)G * a.m;
+        if (M > 0x7fffffff) return NLH_ARRAY_SIZE_ERROR;
+    }
+    if (M < n) return NLH_UNDERDEFINED_PROBLEM_ERROR;
     if (!nlh_loss_kind_ok(a.loss)) return NLH_INVALID_INPUT_ERROR;
+    if (a.stat != NLH_STAT_LSQ && a.stat != NLH_STAT_POISSON) return NLH_INVALID_INPUT_ERROR;
+    if (a.stat == NLH_STAT_POISSON && a.loss != NLH_LOSS_LINEAR) return NLH_INVALID_INPUT_ERROR;
     if (a.nprob == 0) return 0;
     if (!opts || !a.t || !a.y || !a.x || !a.fvec || (a.loss != NLH_LOSS_LINEAR && !a.scale)) return NLH_INVALID_INPUT_ERROR;
-    if ((a.sigma || a.cov || a.chi2) && a.m <= n) return NLH_INVALID_INPUT_ERROR;   // no degree of freedom for errors
+    if ((a.sigma || a.cov || a.chi2) && M <= n) return NLH_INVALID_INPUT_ERROR;     // no degree of freedom for errors
     if (a.stat == NLH_STAT_POISSON && !nlh_pois_floor_ok(a.mu_floor)) return NLH_INVALID_INPUT_ERROR;
     if (!host) return fit_device(h, opts, src, a, n);
     if (a.stat == NLH_STAT_POISSON && !nlh_pois_data_ok(a.y, a.w, (size_t)a.nprob * a.m)) return NLH_INVALID_INPUT_ERROR;

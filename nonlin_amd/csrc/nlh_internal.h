@@ -18,6 +18,7 @@
 //   nlh_pmap.hip       parameter maps: the map object, the wrapping launchers, gather / expand / covariance
 //   nlh_loss.hip       robust losses: the wrapping launchers, apply, the upload of host scales
 //   nlh_pois.hip       Poisson likelihood fits: the wrapping launchers, apply, the check of host counts and masks
+//   nlh_group.hip      global fits: the group object, the wrapping launchers, gather / expand / sigma
 //   nlh_model.hip      device sets, device residual models behind host arrays
 //   nlh_qrx.hip        the exact lmfactor
 // Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it launches.  nlh_launch.h:
@@ -331,7 +332,7 @@ struct nlh_expr {
     int32_t nconst;
 };
 
-// The one-call fit + errors of the sixteen entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois}{,_h} (nlh_fit.hip).
+// The one-call fit + errors of the twenty entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois,_group}{,_h} (nlh_fit.hip).
 // FitSource: what a model kind hands the pipeline.  bind points the context's data at problem p0 of dt, dy, dw (the whole
 // batch's device arrays) before each run of consecutive problems; whatever else the context holds stays the whole batch's.
 struct FitSource {
@@ -363,6 +364,7 @@ struct FitArgs {
     int32_t *status;
     int32_t stat = NLH_STAT_LSQ;
     double mu_floor = 0.0;
+    const nlh_group *grp = nullptr;    // a global fit: nprob data sets in groups; cov, chi2, rank, ib, status per group
 };
 // The documented ladder of checks, then: solve (bounded when xl or xu is given), covariance with scaled = 1 when any of sigma,
 // cov, chi2 is asked for, the degrees-of-freedom rule of zero weights, NaN and rank -1 for problems that did not solve.  The
@@ -381,6 +383,10 @@ void pmap_gather(const PmapTables *T, hipStream_t s, int nprob, const double *fu
 void pmap_expand(const PmapTables *T, hipStream_t s, int nprob, const double *x, const double *full, int shared_full, double *p);
 void pmap_cov(const PmapTables *T, hipStream_t s, int nprob, const double *cov, const double *sigma, const int32_t *fail, double *covf,
               double *sigf);
+struct GroupTables;                    // nlh_kernels_group.h: the same of a group's context (nlh_group.hip)
+const GroupTables *group_ctx_tables(const nlh_group_ctx *c);
+void group_gather(const GroupTables *T, hipStream_t s, int ngroup, const double *full, double *x);
+void group_expand(const GroupTables *T, hipStream_t s, int ngroup, const double *x, const int32_t *fail, double *p);
 // Host arrays, one after the other, into ONE device allocation on the handle's device, the caller's to hipFree; synchronised.
 // Errors name `what` in h->err: "hipMalloc (what)", "hipMemcpy (what): ...".  A part of 0 bytes is skipped.  (nlh_model.hip)
 struct HostPart { const void *p; size_t bytes; };

@@ -99,6 +99,8 @@ struct nlh_dq_model {
     nlh_loss_ctx *loss = nullptr;
     // a Poisson model (nlh_pois_model_create): the wrapping context around another model's launchers; the counts and the mask
     nlh_pois_ctx *pois = nullptr;
+    // a global model (nlh_group_model_create): the wrapping context around another model's launchers; nothing else
+    nlh_group_ctx *group = nullptr;
 };
 
 // Host arrays, one after the other, into one device allocation on the handle's device; synchronised (nlh_internal.h).
@@ -332,9 +334,31 @@ int nlh_pois_model_create(nlh_handle *h, const nlh_dq_model *inner, const double
     return 0;
 }
 
+// A model of the outer unknowns of a group over a launcher-backed inner model (nlh_group.hip: the wrapping launchers): every
+// G consecutive problems of the inner model are one problem of G m rows.
+int nlh_group_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_group *g, nlh_dq_model **out)
+{
+    if (out) *out = nullptr;
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (!out || !inner || !g || !inner->ufcn) return NLH_INVALID_INPUT_ERROR;
+    int32_t N, G, n;
+    nlh_group_shape(g, &N, nullptr, &G, &n);
+    if (N != inner->n || inner->nprob % G != 0 || (int64_t)G * inner->m > 0x7fffffff) return NLH_INVALID_INPUT_ERROR;
+    nlh_group_ctx *gc = nullptr;
+    const int rc = nlh_group_wrap(h, g, inner->ufcn, inner->ujac, inner->uctx, &gc);
+    if (rc) return rc;
+    nlh_dq_model *md = new nlh_dq_model();
+    md->nprob = inner->nprob / G; md->m = G * inner->m; md->n = n; md->gamma = 0.0;
+    md->ufcn = nlh_group_device_fcn; md->ujac = inner->ujac ? nlh_group_device_jac : nullptr; md->uctx = gc;
+    md->group = gc;
+    *out = md;
+    return 0;
+}
+
 void nlh_dq_model_destroy(nlh_dq_model *md)
 {
     if (!md) return;
+    nlh_group_unwrap(md->group);
     nlh_pmap_unwrap(md->pmap);
     nlh_loss_unwrap(md->loss);
     nlh_pois_unwrap(md->pois);

@@ -88,6 +88,15 @@ class _PoisCtx(_PmapCtx):
             self.ptr = C.c_void_p()
 
 
+class _GroupCtx(_PmapCtx):
+    """The context of a group's wrapping launchers (nlh_group_ctx), with everything it points at kept alive."""
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.lib.nlh_group_unwrap(self.ptr)
+            self.ptr = C.c_void_p()
+
+
 class DeviceSolver:
     """Owns an nlh handle bound to torch's current stream on `device`."""
 
@@ -277,8 +286,36 @@ class DeviceSolver:
             raise RuntimeError(f"nlh_curve_eval_batch returned {rc}")
         return y
 
+    @staticmethod
+    def _fit_outputs(x0, m, covariance, nsolve, nunk):
+        """What a one-call fit writes: x (a copy of x0 [nprob, n]), fvec [nprob, m], sigma [nprob, n] and, per problem of the
+        solve -- nsolve of them over nunk unknowns: the data sets themselves, or the groups of a global fit --, cov, chi2, rank
+        (None with covariance=False), the iteration records and the status array."""
+        nprob, n = x0.shape
+        dev = x0.device
+        x = x0.clone()
+        fvec = torch.empty((nprob, m), dtype=torch.float64, device=dev)
+        sigma = cov = chi2 = rank = None
+        if covariance:
+            sigma = torch.empty((nprob, n), dtype=torch.float64, device=dev)
+            cov = torch.empty((nsolve, nunk, nunk), dtype=torch.float64, device=dev)
+            chi2 = torch.empty((nsolve,), dtype=torch.float64, device=dev)
+            rank = torch.empty((nsolve,), dtype=torch.int32, device=dev)
+        return x, fvec, sigma, cov, chi2, rank, (_lib.IterationBehavior * nsolve)(), (C.c_int32 * nsolve)()
+
+    @staticmethod
+    def _fit_bounds(lower, upper, n):
+        """(lo, hi, plo, phi): the box of a one-call fit as host arrays [n] (None: no bound) and the pointers to them."""
+        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64)
+        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
+        for b in (lo, hi):
+            if b is not None and b.shape != (n,):
+                raise ValueError(f"bounds: expected {n} entries")
+        return (lo, hi, None if lo is None else lo.ctypes.data_as(_lib.c_double_p),
+                None if hi is None else hi.ctypes.data_as(_lib.c_double_p))
+
     def curve_fit_batch(self, kind, t, y, x0, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
-                        covariance=True, opts=None, pmap=None, loss=None, stat=None):
+                        covariance=True, opts=None, pmap=None, loss=None, stat=None, group=None):
         """Fit + errors of y.shape[0] curves in one call (nlh_curve_fit_batch): least_squares_solver%solve -- or, with lower /
         upper ([n], one box for every problem), constrained_least_squares_solver%solve -- from x0 [nprob, n] (not modified),
         then the scaled parameter covariance at the solution.  Rows with weight 0 pad ragged data: they do not count as
@@ -292,35 +329,29 @@ class DeviceSolver:
         gives the weights that flag outliers.  None calls exactly what is called without it.
         stat (a Poisson): y are counts and the fit minimises their Poisson deviance (nlh_curve_fit_batch_pois), with or without
         pmap.  weights is then the 0 / 1 mask of the rows, fvec the deviance residual, chi2 the deviance / dof, and sigma / cov
-        are unscaled: the inverse Fisher information.  stat together with loss raises ValueError."""
+        are unscaled: the inverse Fisher information.  stat together with loss raises ValueError.
+        group (a Group over the model's n parameters): a global fit (nlh_curve_fit_batch_group), with or without loss or stat:
+        every group.nsets consecutive rows of y are one group, whose shared parameters have one value.  x0, x, fvec and sigma
+        stay per data set (a shared parameter starts from the value of the group's first data set and comes back equal across
+        the group); cov [ngroup, nouter, nouter] (group.index locates entries), chi2, rank, ibs and status are per group.
+        group together with pmap raises ValueError.  None calls exactly what is called without it."""
         if stat is not None and loss is not None:
             raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
         k = curve_kind(kind)
         nprob, m, shared = self._curve_data(t, y, weights)
         n = curve_nparams(k, ncomp, baseline)
         _chk(x0, (nprob, n), "x0")
+        if group is not None:
+            call = lambda *rest: self.lib.nlh_curve_fit_batch_group(self.h.ptr, rest[0], k, int(ncomp), int(baseline), *rest[1:])
+            return self._group_fit("nlh_curve_fit_batch_group", call, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
+                                   lower, upper, analytic, covariance, opts)
         if pmap is not None and pmap.nfull != n:
             raise ValueError(f"pmap maps {pmap.nfull} parameters, the model has {n}")
         dev = y.device
-        x = x0.clone()
-        fvec = torch.empty((nprob, m), dtype=torch.float64, device=dev)
-        sigma = cov = chi2 = rank = None
-        if covariance:
-            sigma = torch.empty((nprob, n), dtype=torch.float64, device=dev)
-            cov = torch.empty((nprob, n, n), dtype=torch.float64, device=dev)
-            chi2 = torch.empty((nprob,), dtype=torch.float64, device=dev)
-            rank = torch.empty((nprob,), dtype=torch.int32, device=dev)
-        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64)
-        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
-        for b in (lo, hi):
-            if b is not None and b.shape != (n,):
-                raise ValueError(f"bounds: expected {n} entries")
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, nprob, n)
+        lo, hi, plo, phi = self._fit_bounds(lower, upper, n)
         o = opts or self.options()
         ptr = lambda a: a.data_ptr() if a is not None else None
-        plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
-        phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
         if stat is not None:
             rc = self.lib.nlh_curve_fit_batch_pois(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
                                                    y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
@@ -399,37 +430,27 @@ class DeviceSolver:
         return y
 
     def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None,
-                       pmap=None, loss=None, stat=None):
+                       pmap=None, loss=None, stat=None, group=None):
         """Fit + errors of y.shape[0] data sets to a formula in one call (nlh_expr_fit_batch): curve_fit_batch with an Expr in
-        the place of (kind, ncomp, baseline), pmap (e.g. ParamMap.for_expr(expr, ...)), loss (a Loss) and stat (a Poisson)
-        included.  Returns (x, fvec, sigma, cov, chi2, rank, ibs, status)."""
+        the place of (kind, ncomp, baseline), pmap (e.g. ParamMap.for_expr(expr, ...)), loss (a Loss), stat (a Poisson) and
+        group (e.g. Group.for_expr(expr, shared=("k",), nsets=8): nlh_expr_fit_batch_group) included.  Returns (x, fvec, sigma,
+        cov, chi2, rank, ibs, status)."""
         if stat is not None and loss is not None:
             raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
         nprob, m, shared = self._expr_data(expr, t, y, weights)
         n = expr.nparams
         _chk(x0, (nprob, n), "x0")
+        if group is not None:
+            call = lambda *rest: self.lib.nlh_expr_fit_batch_group(self.h.ptr, rest[0], expr.ptr, *rest[1:])
+            return self._group_fit("nlh_expr_fit_batch_group", call, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
+                                   lower, upper, analytic, covariance, opts)
         if pmap is not None and pmap.nfull != n:
             raise ValueError(f"pmap maps {pmap.nfull} parameters, the formula has {n}")
         dev = y.device
-        x = x0.clone()
-        fvec = torch.empty((nprob, m), dtype=torch.float64, device=dev)
-        sigma = cov = chi2 = rank = None
-        if covariance:
-            sigma = torch.empty((nprob, n), dtype=torch.float64, device=dev)
-            cov = torch.empty((nprob, n, n), dtype=torch.float64, device=dev)
-            chi2 = torch.empty((nprob,), dtype=torch.float64, device=dev)
-            rank = torch.empty((nprob,), dtype=torch.int32, device=dev)
-        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64)
-        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
-        for b in (lo, hi):
-            if b is not None and b.shape != (n,):
-                raise ValueError(f"bounds: expected {n} entries")
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, nprob, n)
+        lo, hi, plo, phi = self._fit_bounds(lower, upper, n)
         o = opts or self.options()
         ptr = lambda a: a.data_ptr() if a is not None else None
-        plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
-        phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
         if stat is not None:
             rc = self.lib.nlh_expr_fit_batch_pois(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(),
                                                   ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr if pmap is not None else None,
@@ -514,6 +535,89 @@ class DeviceSolver:
         if rc:
             raise RuntimeError(f"nlh_pmap_cov_batch returned {rc}")
         return cf, sf
+
+    # -- global fits ---------------------------------------------------------------
+    def group_launchers(self, group, fcn, jac, ctx):
+        """Parameters shared across data sets for any launcher pair: wraps (fcn, jac, ctx) -- of curve_launchers,
+        expr_launchers, loss_launchers, pois_launchers, pmap_launchers or a user's own, over nprob = ngroup * group.nsets
+        problems of m rows -- in the group's launchers (nlh_group_wrap) and returns (fcn, jac, ctx) for lm_solve_batch_device,
+        cls_solve_batch_device, lm_covariance_batch_device and fd_jacobian_device, which then work on x [ngroup, group.nouter]
+        with m = group.nsets * m rows: y, weights and fvec [nprob, m] are [ngroup, nsets * m] as they stand.  jac is None
+        without an inner Jacobian launcher (pass jac=None to the solver: forward differences over the outer unknowns).  Keep
+        the returned ctx alive while solving; ctx.close() frees it (so does garbage collection)."""
+        out = C.c_void_p()
+        rc = self.lib.nlh_group_wrap(self.h.ptr, group.ptr, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), C.byref(out))
+        self.h.check(rc, "nlh_group_wrap")
+        if rc:
+            raise RuntimeError(f"nlh_group_wrap returned {rc}")
+        wrapped = _GroupCtx(self.lib, out, (group, fcn, jac, ctx))
+        return (C.cast(self.lib.nlh_group_device_fcn, _lib.DEVFCN),
+                C.cast(self.lib.nlh_group_device_jac, _lib.DEVFCN) if jac is not None else None, wrapped)
+
+    def group_gather(self, group, full):
+        """The outer unknowns x [ngroup, nouter] of per-data-set parameters [ngroup * nsets, nparams] (nlh_group_gather_batch):
+        a shared parameter takes the value of the group's data set 0."""
+        nprob = full.shape[0]
+        _chk(full, (nprob, group.nparams), "full")
+        if nprob % group.nsets:
+            raise ValueError(f"full has {nprob} rows: no multiple of the group's {group.nsets} data sets")
+        ngroup = nprob // group.nsets
+        x = torch.empty((ngroup, group.nouter), dtype=torch.float64, device=full.device)
+        rc = self.lib.nlh_group_gather_batch(self.h.ptr, group.ptr, ngroup, full.data_ptr(), x.data_ptr())
+        self.h.check(rc, "nlh_group_gather_batch")
+        if rc:
+            raise RuntimeError(f"nlh_group_gather_batch returned {rc}")
+        return x
+
+    def group_expand(self, group, x):
+        """The per-data-set parameters [ngroup * nsets, nparams] of the outer unknowns x [ngroup, nouter] (nlh_group_expand_batch)."""
+        ngroup = x.shape[0]
+        _chk(x, (ngroup, group.nouter), "x")
+        p = torch.empty((ngroup * group.nsets, group.nparams), dtype=torch.float64, device=x.device)
+        rc = self.lib.nlh_group_expand_batch(self.h.ptr, group.ptr, ngroup, x.data_ptr(), p.data_ptr())
+        self.h.check(rc, "nlh_group_expand_batch")
+        if rc:
+            raise RuntimeError(f"nlh_group_expand_batch returned {rc}")
+        return p
+
+    def group_sigma(self, group, sigma, fail=None):
+        """The per-data-set standard errors [ngroup * nsets, nparams] of those of the outer unknowns [ngroup, nouter]
+        (nlh_group_sigma_batch); fail: int32 [ngroup], non-zero for a group that did not solve (NaN everywhere)."""
+        ngroup = sigma.shape[0]
+        _chk(sigma, (ngroup, group.nouter), "sigma")
+        sf = torch.empty((ngroup * group.nsets, group.nparams), dtype=torch.float64, device=sigma.device)
+        rc = self.lib.nlh_group_sigma_batch(self.h.ptr, group.ptr, ngroup, sigma.data_ptr(), fail.data_ptr() if fail is not None else None,
+                                            sf.data_ptr())
+        self.h.check(rc, "nlh_group_sigma_batch")
+        if rc:
+            raise RuntimeError(f"nlh_group_sigma_batch returned {rc}")
+        return sf
+
+    def _group_fit(self, name, call, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0, lower, upper, analytic,
+                   covariance, opts):
+        """The one-call global fit behind curve_fit_batch / expr_fit_batch with group=; call(opts, nprob, m, ...) is the entry
+        point with the model's own arguments bound."""
+        if pmap is not None:
+            raise ValueError("group and pmap exclude each other: a map inside a group works through pmap_launchers and group_launchers")
+        if group.nparams != n:
+            raise ValueError(f"group is over {group.nparams} parameters, the model has {n}")
+        if nprob % group.nsets:
+            raise ValueError(f"{nprob} data sets: no multiple of the group's {group.nsets}")
+        ngroup, no = nprob // group.nsets, group.nouter
+        dev = y.device
+        x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, ngroup, no)
+        lo, hi, plo, phi = self._fit_bounds(lower, upper, n)
+        o = opts or self.options()
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        dscale, sh = self._loss_scale(loss, nprob, dev) if loss is not None else (None, 0)
+        rc = call(C.byref(o), nprob, m, t.data_ptr(), shared, y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi, group.ptr,
+                  loss.kind if loss is not None else 0, ptr(dscale), sh, 1 if stat is not None else 0,
+                  stat.mu_floor if stat is not None else 0.0, x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank),
+                  ib, status)
+        self.h.check(rc, name)
+        if rc:
+            raise RuntimeError(f"{name} returned {rc}")
+        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(ngroup)], [int(status[p]) for p in range(ngroup)])
 
     # -- robust losses -------------------------------------------------------------
     def _loss_scale(self, loss, nprob, dev=None):

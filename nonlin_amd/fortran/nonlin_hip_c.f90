@@ -227,6 +227,30 @@ module nonlin_hip_c
             type(c_ptr), intent(out) :: model
             integer(c_int) :: rc
         end function
+        ! global fits (include/nonlin_hip.h: nlh_group_*): the group object (host code), and a model of its outer unknowns
+        ! over a launcher-backed model (shared is 0-based here)
+        function nlh_group_create(nfull, nshared, shared, nsets, g) bind(C, name="nlh_group_create") result(rc)
+            import :: c_ptr, c_int, c_int32_t
+            integer(c_int32_t), value :: nfull, nshared, nsets
+            integer(c_int32_t), intent(in) :: shared(*)
+            type(c_ptr), intent(out) :: g
+            integer(c_int) :: rc
+        end function
+        subroutine nlh_group_destroy(g) bind(C, name="nlh_group_destroy")
+            import :: c_ptr
+            type(c_ptr), value :: g
+        end subroutine
+        subroutine nlh_group_shape(g, nfull, nshared, nsets, nouter) bind(C, name="nlh_group_shape")
+            import :: c_ptr, c_int32_t
+            type(c_ptr), value :: g
+            integer(c_int32_t), intent(out) :: nfull, nshared, nsets, nouter
+        end subroutine
+        function nlh_group_model_create(h, inner, g, model) bind(C, name="nlh_group_model_create") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: h, inner, g
+            type(c_ptr), intent(out) :: model
+            integer(c_int) :: rc
+        end function
         ! robust losses (include/nonlin_hip.h: nlh_loss_*): a model with a loss over a launcher-backed model
         function nlh_loss_model_create(h, inner, kind, scale, shared_scale, model) bind(C, name="nlh_loss_model_create") result(rc)
             import :: c_ptr, c_int, c_int32_t, c_double

@@ -61,6 +61,7 @@ module nonlin_multi_eqn_mult_var
         procedure, public :: create_curve => dmb_create_curve
         procedure, public :: create_expr => dmb_create_expr
         procedure, public :: create_mapped => dmb_create_mapped
+        procedure, public :: create_global => dmb_create_global
         procedure, public :: create_robust => dmb_create_robust
         procedure, public :: create_poisson => dmb_create_poisson
         procedure, public :: destroy => dmb_destroy
@@ -453,6 +454,42 @@ contains
         this%neqn_ = inner%neqn_
         this%nvar_ = nfree
         this%nprob_ = inner%nprob_
+        this%analytic_ = inner%analytic_
+    end subroutine
+
+    !> A global fit over a launcher-backed model (create_curve, create_expr, create_from_device_fcn, create_mapped,
+    !> create_robust, create_poisson): a model of the OUTER unknowns of groups of nsets consecutive problems of inner, which
+    !> must outlive it.  shared(:): the 1-based parameters of inner that have one value for a whole group (distinct, in any
+    !> order; size 0: nothing shared); the others are free per data set.  The model has nprob / nsets problems of nsets * m
+    !> equations and S + nsets * (N - S) unknowns: the shared parameters first, in ascending index, then per data set its local
+    !> ones, in ascending index (INTEGRATION.md 6l).  solve_batch, covariance_batch and evaluate take x(nouter, nprob / nsets)
+    !> and fvec(nsets * m, nprob / nsets).  A group the library refuses, or an inner problem count that is no multiple of
+    !> nsets, stops the program with NL_INVALID_INPUT_ERROR.
+    subroutine dmb_create_global(this, inner, shared, nsets)
+        class(device_model_batch), intent(inout) :: this
+        class(device_model_batch), intent(in) :: inner
+        integer(int32), intent(in), dimension(:) :: shared
+        integer(int32), intent(in) :: nsets
+        integer(c_int) :: rc
+        integer(c_int32_t) :: nfull, nshared, g, nouter
+        integer(c_int32_t), allocatable :: sc(:)
+        type(c_ptr) :: grp
+        if (.not.inner%is_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR
+        if (nsets < 1) error stop NL_INVALID_INPUT_ERROR
+        if (mod(inner%nprob_, nsets) /= 0) error stop NL_INVALID_INPUT_ERROR
+        allocate(sc(max(size(shared), 1)))
+        sc = 0
+        sc(1:size(shared)) = shared - 1
+        rc = nlh_group_create(int(inner%nvar_, c_int32_t), int(size(shared), c_int32_t), sc, nsets, grp)
+        if (rc /= 0) error stop NL_INVALID_INPUT_ERROR
+        call nlh_group_shape(grp, nfull, nshared, g, nouter)
+        call this%destroy()
+        rc = nlh_group_model_create(nlh_default_handle(), inner%model_, grp, this%model_)
+        call nlh_group_destroy(grp)                          ! (the model keeps its own copies of the tables)
+        if (rc /= 0) error stop rc
+        this%neqn_ = inner%neqn_ * nsets
+        this%nvar_ = nouter
+        this%nprob_ = inner%nprob_ / nsets
         this%analytic_ = inner%analytic_
     end subroutine
 
