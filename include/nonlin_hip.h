@@ -1142,6 +1142,72 @@ int nlh_expr_fit_batch_pois_h(nlh_handle *h, const nlh_options *opts, const nlh_
 int nlh_pois_model_create(nlh_handle *h, const nlh_dq_model *inner, const double *y, const double *w, double mu_floor,
                           nlh_dq_model **model);
 
+/* ---- instrument-response fits (no counterpart in nonlin v2.2.0): ANY device model convolved with a kernel along its rows.
+ * A detector does not record the model: it records the model convolved with the instrument's response -- the IRF of a
+ * photon-counting set-up for a decay, the line shape of a spectrometer for a spectrum.  Fitting the convolved model
+ * ("reconvolution") uses every bin; the alternative, fitting only the tail the response does not touch, is biased or has
+ * nothing left to fit when the lifetime is comparable to the response (README, the study table).  Like a loss, this is a
+ * pair of wrapping launchers around any inner launcher pair, so everything that takes launchers works through it; a loss, the
+ * Poisson pair, a map or a group wrap the convolved pair, not the other way round.
+ * The inner pair follows the Poisson convention: an ordinary least-squares model bound WITHOUT weights to the same y, so that
+ * its residual is r = model - y.  The wrapper is given dy [nprob][m], optional weights dw [nprob][m] (NULL: none) and the
+ * kernel, all on the DEVICE; point q belongs to problem p = dprob ? dprob[q] : q and reads row p of dy and dw and the taps
+ * kp = shared_k ? k : k + p L.
+ * THE ARITHMETIC IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation.  The convolution c of one column
+ * v [0 .. m-1] (the model values, or one column of the inner Jacobian), row i:
+ *   acc = +0.0
+ *   for j = 0 .. L-1 ascending:   s = i + origin - j
+ *       NLH_CONV_ZERO: s outside 0 .. m-1 -> the tap is SKIPPED (nothing multiplied, nothing added)
+ *       NLH_CONV_HOLD: s = min(max(s, 0), m-1)
+ *       t = kp[j] * v[s];  acc = acc + t
+ *   c_i = acc
+ *   residual    mu_s = r_s + y_s (one add); c over mu; out_i = c_i - y_i; with weights out_i = w_i * out_i
+ *   Jacobian    J'[i][j] = c_i over column j of the inner Jacobian; with weights w_i * c_i
+ *   weights     a row with w_i == 0.0 is STORED as +0.0 in dF and in every column of dJ, not multiplied
+ * No sum crosses threads: every output is one sequential chain, so its bits do not depend on the batch, the workgroup form,
+ * the row tile or the slice, and a numpy restatement reproduces them bit for bit.  Two consequences:
+ *   - the model is convolved over ALL m rows, whatever their weights: the rows must lie on one uniform grid, and y must be
+ *     finite on EVERY row, padded rows included -- a NaN in y_s reaches every row that reads s;
+ *   - with NLH_CONV_ZERO a constant baseline ramps up over the first taps of a causal kernel: mask the pre-pulse bins with
+ *     w = 0, or use NLH_CONV_HOLD when the window starts on a flat part.
+ * The kernel is used as given, not normalised. ---- */
+#define NLH_CONV_MAX_L   1024
+#define NLH_CONV_ZERO    0      /* rows outside 0 .. m-1 contribute nothing */
+#define NLH_CONV_HOLD    1      /* rows outside take the nearest edge row's value */
+typedef struct nlh_conv {
+    int32_t L;            /* taps, 1 .. NLH_CONV_MAX_L (L > m is allowed) */
+    int32_t origin;       /* 0 .. L-1: tap `origin` sits on the output row.  0 = causal (IRF), (L-1)/2 = centred (line shape) */
+    int32_t ext;          /* NLH_CONV_ZERO | NLH_CONV_HOLD */
+    int32_t shared_k;     /* k is [L], one kernel for every problem; otherwise [nprob][L] */
+    const double *k;      /* device pointer; used as given, not normalised */
+} nlh_conv;
+typedef struct nlh_conv_ctx nlh_conv_ctx;
+/* The wrapping launchers.  nlh_conv_wrap makes their context on the handle's device; *cv is copied, while its k, the inner
+ * pair (fcn, jac -- NULL: none --, inner_ctx), dy and dw stay the caller's and must outlive the context.
+ *   nlh_conv_device_fcn  the inner fcn into scratch R [npoints][m]; then the table's residual into the caller's dF.
+ *   nlh_conv_device_jac  the inner jac into scratch Jf [npoints][n][m]; then the table's Jacobian into dJ [npoints][n][m],
+ *                        out of place; every entry is written.  With a NULL inner jac it returns
+ *                        NLH_UNDEFINED_FUNCTION_ERROR: pass a NULL jacfcn to the solver instead (forward differences of
+ *                        the wrapped residual).
+ * Both enqueue only on the stream handed in, never synchronise and may be called from several host threads on different
+ * streams.  A malformed context, n < 1, m < 1 or a bad L / origin / ext returns non-zero before any launch.  An inner error
+ * comes back as it is, with no further launch.  When dprob is NULL the launchers build a problem list of their own.  Scratch
+ * belongs to the context, exactly as a loss's: one buffer per stream, grown on demand, kept until nlh_conv_unwrap, at most
+ * 1 GiB per call; a call that needs more runs in slices of points -- the same bits.  NLH_CONV_SCRATCH = bytes lowers the cap,
+ * NLH_CONV_FORM = row | flat forces a workgroup form for the sizes it can hold (flat: m <= 256), NLH_CONV_SPLIT = number of
+ * column groups overrides the column split (environment, read at each call; tests).
+ * Errors of nlh_conv_wrap: NLH_ERR_BAD_HANDLE; NLH_INVALID_INPUT_ERROR (a NULL out, dy, cv or cv->k, L outside 1 ..
+ * NLH_CONV_MAX_L, origin outside 0 .. L-1, ext outside 0 .. 1); NLH_UNDEFINED_FUNCTION_ERROR (a NULL fcn). */
+int  nlh_conv_wrap(nlh_handle *h, const nlh_conv *cv, const double *dy, const double *dw, nlh_device_vecfcn fcn,
+                   nlh_device_jacfcn jac, void *inner_ctx, nlh_conv_ctx **out);
+void nlh_conv_unwrap(nlh_conv_ctx *c);
+int  nlh_conv_device_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dF);
+int  nlh_conv_device_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dJ);
+/* The bare convolution c of arbitrary columns dv [nprob][ncol][m] on the DEVICE (the handle's stream) into dout of the same
+ * shape, dout != dv; problem p uses the taps of p.  The convolved model for plotting is nlh_curve_eval_batch (or the
+ * formula's) followed by this with ncol = 1. */
+int  nlh_conv_apply_batch(nlh_handle *h, const nlh_conv *cv, int32_t nprob, int32_t m, int32_t ncol, const double *dv, double *dout);
+
 /* ---- global fits: parameters shared across the data sets of a group, for any device model -------------------------------
  * A GROUP is G = nsets data sets of one inner model with N = nfull parameters, S = nshared of which have one value for the
  * whole group; the other L = N - S are free per data set.  A tie (nlh_pmap) links parameters inside one problem; a group
@@ -1245,6 +1311,51 @@ int nlh_expr_fit_batch_group_h(nlh_handle *h, const nlh_options *opts, const nlh
  * NLH_INVALID_INPUT_ERROR (a NULL argument, a dense-quadratic inner model, a group of another parameter count, an inner nprob
  * that is no multiple of G). */
 int nlh_group_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_group *g, nlh_dq_model **model);
+
+/* A device-function MODEL of a launcher-backed inner model (device-function, curve or formula, created WITHOUT weights; a
+ * dense-quadratic model: NLH_INVALID_INPUT_ERROR) convolved with an instrument response; the inner model must outlive it.
+ * cv->k, y, w (NULL: no weights): HOST arrays, [L] or [nprob][L], [nprob][m]; the model owns its device copies and its
+ * wrapping context.  Every nlh_dq_model_* solver and nlh_dq_model_lm_covariance then takes it; a loss, Poisson, mapped or
+ * global model may be made over it.  Errors: NLH_ERR_BAD_HANDLE, then NLH_INVALID_INPUT_ERROR (a NULL argument, a
+ * dense-quadratic inner model, a bad L / origin / ext, a tap or a y that is not finite). */
+int nlh_conv_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_conv *cv, const double *y, const double *w,
+                          nlh_dq_model **model);
+/* One-call fits with an instrument response: the arguments of the _group entry points plus, after the group, a parameter map
+ * and the transform.  g may be NULL (no group), pm may be NULL (no map); both together: NLH_INVALID_INPUT_ERROR.  cv is
+ * required; its k is a DEVICE pointer here and a HOST pointer in the _h forms, which stage it with the other arrays.  The
+ * composition is fixed: the convolving pair wraps the model's launchers FIRST, the model bound without weights and dw
+ * becoming the convolving pair's weights; the loss or the Poisson pair wraps the result -- under the Poisson pair the
+ * convolving pair gets no weights and the Poisson pair keeps dw as its 0 / 1 mask (masked rows are +0.0) --; the map or the
+ * group goes outside.  dfvec is the residual of the convolved model; everything else is what the _group (with a group), the
+ * _pmap, _loss or _pois entry point of the same arguments returns.  Errors, in this order: the _group entry point's (without
+ * its refusal of a NULL group; through its "unless nprob = 0" step); then NLH_INVALID_INPUT_ERROR for a NULL cv or cv->k, L
+ * outside 1 .. NLH_CONV_MAX_L, origin outside 0 .. L-1, ext outside 0 .. 1; the _h forms also refuse, with
+ * NLH_INVALID_INPUT_ERROR, a tap that is not finite and a y that is not finite on ANY row, whatever its weight; then they
+ * check scales, masks and counts as the _loss and _pois entry points do. */
+int nlh_curve_fit_batch_conv(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                             int32_t m, const double *dt, int32_t shared_t, const double *dy, const double *dw, int32_t analytic,
+                             const double *xl, const double *xu, const nlh_group *g, const nlh_pmap *pm, const nlh_conv *cv,
+                             int32_t loss, const double *dscale, int32_t shared_scale, int32_t stat, double mu_floor, double *dx,
+                             double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+                             nlh_iteration_behavior *ib, int32_t *status);
+int nlh_curve_fit_batch_conv_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                               int32_t m, const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic,
+                               const double *xl, const double *xu, const nlh_group *g, const nlh_pmap *pm, const nlh_conv *cv,
+                               int32_t loss, const double *scale, int32_t shared_scale, int32_t stat, double mu_floor, double *x,
+                               double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+                               nlh_iteration_behavior *ib, int32_t *status);
+int nlh_expr_fit_batch_conv(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+                            int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl,
+                            const double *xu, const nlh_group *g, const nlh_pmap *pm, const nlh_conv *cv, int32_t loss,
+                            const double *dscale, int32_t shared_scale, int32_t stat, double mu_floor, double *dx, double *dfvec,
+                            double *dsigma, double *dcov, double *dchi2, int32_t *drank, nlh_iteration_behavior *ib,
+                            int32_t *status);
+int nlh_expr_fit_batch_conv_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+                              int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl,
+                              const double *xu, const nlh_group *g, const nlh_pmap *pm, const nlh_conv *cv, int32_t loss,
+                              const double *scale, int32_t shared_scale, int32_t stat, double mu_floor, double *x, double *fvec,
+                              double *sigma, double *cov, double *chi2, int32_t *rank, nlh_iteration_behavior *ib,
+                              int32_t *status);
 
 /* ---- per-kernel timing (HIP events on the handle's stream) ------------------ */
 #define NLH_K_DQ_RESIDUAL   0

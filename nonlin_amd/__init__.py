@@ -13,6 +13,7 @@ from .api import (  # noqa: F401
     ParamMap, PMAP_FREE, PMAP_FIXED, PMAP_TIED,
     Loss, LOSS_LINEAR, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY, LOSS_KINDS,
     Poisson,
+    Convolve, CONV_ZERO, CONV_HOLD,
     Group,
     NL_NO_ERROR, NL_INVALID_INPUT_ERROR, NL_ARRAY_SIZE_ERROR, NL_OUT_OF_MEMORY_ERROR,
     NL_INVALID_OPERATION_ERROR, NL_CONVERGENCE_ERROR, NL_DIVERGENT_BEHAVIOR_ERROR,

@@ -321,6 +321,11 @@ SYMBOLS = {
                                             c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
                                             C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_pois_model_create": (C.c_int, [_H, C.c_void_p, c_double_p, c_double_p, C.c_double, C.POINTER(C.c_void_p)]),
+    "nlh_conv_wrap": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "nlh_conv_unwrap": (None, [C.c_void_p]),
+    "nlh_conv_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_conv_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_conv_apply_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "nlh_group_create": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "nlh_group_destroy": (None, [C.c_void_p]),
     "nlh_group_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
@@ -348,6 +353,27 @@ SYMBOLS = {
         _H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32,
         c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, c_double_p, C.c_int32,
         C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_curve_fit_batch_conv": (C.c_int, [
+        _H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+        C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+        C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_curve_fit_batch_conv_h": (C.c_int, [
+        _H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+        c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+        c_double_p, C.c_int32, C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
+        C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_fit_batch_conv": (C.c_int, [
+        _H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32,
+        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+        C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+        C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_fit_batch_conv_h": (C.c_int, [
+        _H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32,
+        c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+        c_double_p, C.c_int32, C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
+        C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_conv_model_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, c_double_p, c_double_p, C.POINTER(C.c_void_p)]),
     "nlh_group_model_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "nlh_timing_enable": (None, [_H, C.c_int32]),
     "nlh_timing_reset": (None, [_H]),
@@ -653,6 +679,70 @@ class Poisson:
         if not (math.isfinite(f) and f > 0.0):
             raise ValueError("Poisson: mu_floor must be finite and positive")
         self.mu_floor = f
+
+
+# extensions of an instrument response beyond the rows of the data (include/nonlin_hip.h: NLH_CONV_*)
+CONV_ZERO, CONV_HOLD = 0, 1
+CONV_EXTENDS = {"zero": CONV_ZERO, "hold": CONV_HOLD}
+CONV_MAX_L = 1024
+
+
+class ConvStruct(C.Structure):
+    """nlh_conv."""
+    _fields_ = [("L", C.c_int32), ("origin", C.c_int32), ("ext", C.c_int32), ("shared_k", C.c_int32), ("k", C.c_void_p)]
+
+
+class Convolve:
+    """An instrument response as the transform of a fit (include/nonlin_hip.h: nlh_conv_*; host data only, needs no GPU): the
+    model is convolved along its rows with `kernel` before it is compared with the data.  kernel: 1-D, one for every problem,
+    or 2-D [nprob, L], one per problem; L = 1 .. 1024 taps.  origin: the tap that sits on the output row -- 0 a causal
+    response (an IRF), (L - 1) // 2 a centred one (a line shape).  extend: "zero" (rows outside the data contribute nothing)
+    or "hold" (they take the nearest edge row's value).  The kernel is used as given; normalize=True divides each kernel by
+    the sequential sum of its taps first.  Raises ValueError for what the library refuses: no taps or too many, an origin
+    outside 0 .. L - 1, an unknown extension, a tap that is not finite (a sum that is zero or not finite, with normalize)."""
+
+    def __init__(self, kernel, origin=0, extend="zero", normalize=False):
+        import numpy as np
+        try:
+            k = np.array(kernel, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"Convolve: the kernel must be a sequence of numbers, not {kernel!r}") from None
+        if k.ndim not in (1, 2) or k.shape[-1] < 1 or k.shape[0] < 1:
+            raise ValueError("Convolve: the kernel is 1-D [L], or 2-D [nprob, L], with at least one tap")
+        if k.shape[-1] > CONV_MAX_L:
+            raise ValueError(f"Convolve: {k.shape[-1]} taps, at most {CONV_MAX_L}")
+        if not np.isfinite(k).all():
+            raise ValueError("Convolve: every tap must be finite")
+        if isinstance(origin, bool) or not isinstance(origin, (int, np.integer)) or not 0 <= int(origin) < k.shape[-1]:
+            raise ValueError(f"Convolve: origin must be an integer in 0 .. {k.shape[-1] - 1}, not {origin!r}")
+        if isinstance(extend, str) and extend.lower() in CONV_EXTENDS:
+            ext = CONV_EXTENDS[extend.lower()]
+        elif not isinstance(extend, (bool, str)) and isinstance(extend, (int, np.integer)) and int(extend) in (CONV_ZERO, CONV_HOLD):
+            ext = int(extend)
+        else:
+            raise ValueError(f"Convolve: unknown extension {extend!r} (one of {', '.join(CONV_EXTENDS)})")
+        self.shared = k.ndim == 1
+        k = np.ascontiguousarray(k.reshape(-1, k.shape[-1]))
+        if normalize:
+            tot = np.zeros(len(k))
+            with np.errstate(over="ignore"):
+                for j in range(k.shape[1]):                          # the sequential sum, tap by tap
+                    tot = tot + k[:, j]
+            if not (np.isfinite(tot).all() and (tot != 0.0).all()):
+                raise ValueError("Convolve: normalize needs taps whose sum is finite and not zero")
+            k = k / tot[:, None]
+        self.kernel = k                                              # [1, L] or [nprob, L]
+        self.L, self.origin, self.ext = int(k.shape[1]), int(origin), ext
+
+    def kernel_for(self, nprob):
+        """The host taps a call on nprob problems passes: ([L], shared = 1) or ([nprob, L], shared = 0)."""
+        if not self.shared and len(self.kernel) != nprob:
+            raise ValueError(f"Convolve: kernels for {len(self.kernel)} problems, the call has {nprob}")
+        return (self.kernel[0] if self.shared else self.kernel), int(self.shared)
+
+    def struct(self, kptr):
+        """nlh_conv with the taps at kptr (a device or host address, as the entry point wants them)."""
+        return ConvStruct(self.L, self.origin, self.ext, int(self.shared), kptr)
 
 
 class Handle:

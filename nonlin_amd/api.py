@@ -21,6 +21,7 @@ from ._lib import ParamMap, PMAP_FREE, PMAP_FIXED, PMAP_TIED  # noqa: F401  (par
 from ._lib import Group  # noqa: F401  (global fits)
 from ._lib import Loss, LOSS_LINEAR, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY, LOSS_KINDS  # noqa: F401  (robust losses)
 from ._lib import Poisson  # noqa: F401  (Poisson likelihood fits)
+from ._lib import Convolve, CONV_ZERO, CONV_HOLD  # noqa: F401  (instrument-response fits)
 
 # src/nonlin_error_handling.f90:10-38
 NL_NO_ERROR = 0

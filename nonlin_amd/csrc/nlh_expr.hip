@@ -453,3 +453,27 @@ int nlh_expr_fit_batch_group_h(nlh_handle *h, const nlh_options *opts, const nlh
     return expr_fit(h, opts, e, analytic, {nprob, m, t, shared_t, y, w, xl, xu, nullptr, loss, scale, shared_scale, x, fvec, sigma, cov, chi2,
                                            rank, ib, status, stat, mu_floor, g}, true);
 }
+
+// The fits with an instrument response: the convolving pair wraps the model's launchers, then the loss or the Poisson pair, then
+// the map or the group (nlh_fit.hip).
+int nlh_expr_fit_batch_conv(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+                             int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl, const double *xu,
+                             const nlh_group *g, const nlh_pmap *pm, const nlh_conv *cv, int32_t loss, const double *dscale, int32_t shared_scale,
+                             int32_t stat, double mu_floor, double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2,
+                             int32_t *drank, nlh_iteration_behavior *ib, int32_t *status)
+{
+    static const nlh_conv none{};                                 // (a NULL cv: refused where the ladder checks the transform)
+    return expr_fit(h, opts, e, analytic, {nprob, m, dt, shared_t, dy, dw, xl, xu, pm, loss, dscale, shared_scale, dx, dfvec, dsigma, dcov, dchi2, drank,
+            ib, status, stat, mu_floor, g, cv ? cv : &none}, false);
+}
+
+int nlh_expr_fit_batch_conv_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+                             int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl, const double *xu,
+                             const nlh_group *g, const nlh_pmap *pm, const nlh_conv *cv, int32_t loss, const double *scale, int32_t shared_scale,
+                             int32_t stat, double mu_floor, double *x, double *fvec, double *sigma, double *cov, double *chi2,
+                             int32_t *rank, nlh_iteration_behavior *ib, int32_t *status)
+{
+    static const nlh_conv none{};                                 // (a NULL cv: refused where the ladder checks the transform)
+    return expr_fit(h, opts, e, analytic, {nprob, m, t, shared_t, y, w, xl, xu, pm, loss, scale, shared_scale, x, fvec, sigma, cov, chi2, rank,
+            ib, status, stat, mu_floor, g, cv ? cv : &none}, true);
+}

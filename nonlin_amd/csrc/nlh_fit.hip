@@ -1,11 +1,12 @@
-// nlh_fit.hip -- the one-call fit + errors pipeline behind the entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois,_group}{,_h}
-// (nlh_internal.h: nlh_fit_run).  A model kind hands it a FitSource -- its launchers, a context and how to point that context
-// at a run of problems -- and the rest of the entry point's arguments as a FitArgs; here are the documented ladder of checks,
+// nlh_fit.hip -- the one-call fit + errors pipeline behind the entry points
+// nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois,_group,_conv}{,_h} (nlh_internal.h: nlh_fit_run).  A model kind hands it a
+// FitSource -- its launchers, a context and how to point that context at a run of problems -- and the rest of the entry point's arguments as a FitArgs; here are the documented ladder of checks,
 // the staging of host arrays, the composition (the loss wraps the model's launchers, the parameter map, if any, wraps the
 // result), the solve and covariance of every run of consecutive problems that have degrees of freedom, and the rule of
 // zero-weight padding.  A Poisson fit (FitArgs::stat) puts the Poisson wrapper where the loss sits, around a model bound
 // without weights: w is then the wrapper's 0 / 1 mask, the covariance is unscaled and chi2 is the deviance over the degrees
-// of freedom.  Nothing here knows what a curve or a formula is.  Kernels: nlh_kernels_fit.h.
+// of freedom.  An instrument response (FitArgs::cv) puts the convolving pair innermost, around a model bound without weights.
+// Nothing here knows what a curve or a formula is.  Kernels: nlh_kernels_fit.h.
 #include "nlh_internal.h"
 #include "nlh_kernels_fit.h"
 
@@ -24,11 +25,17 @@ struct FitRun {
     nlh_loss_ctx *lc = nullptr;
     nlh_pois_ctx *qc = nullptr;
     nlh_pmap_ctx *pc = nullptr;
+    nlh_conv_ctx *cc = nullptr;        // an instrument response: innermost, around the model's launchers
     const double *fullc = nullptr;     // the map's private copy of the full parameters
     int32_t G = 1;                     // a global fit: a problem of the solve is G of the model's, a->m its G m rows
     void bind(int32_t p0) const
     {
-        src->bind(src->ctx, a->t, a->y, qc ? nullptr : a->w, p0 * G);
+        src->bind(src->ctx, a->t, a->y, qc || cc ? nullptr : a->w, p0 * G);
+        if (cc) {                                                 // (its weights: none under the Poisson pair, which keeps the mask)
+            const size_t at = (size_t)p0 * a->m;
+            conv_ctx_rebind(cc, a->y + at, a->w && !qc ? a->w + at : nullptr,
+                            a->cv->shared_k ? a->cv->k : a->cv->k + (size_t)p0 * G * a->cv->L);
+        }
         if (qc) pois_ctx_rebind(qc, a->y + (size_t)p0 * a->m, a->w ? a->w + (size_t)p0 * a->m : nullptr);
         if (lc) loss_ctx_rebind(lc, a->shared_scale ? a->scale : a->scale + (size_t)p0 * G);
         if (pc) pmap_ctx_rebind(pc, fullc + (size_t)p0 * N);
@@ -224,17 +231,19 @@ static int fit_grouped(FitRun r, int32_t n)
     return rc;
 }
 
-// The composition on device pointers: the loss wraps the model's launchers (NLH_LOSS_LINEAR: no context, no kernel of the
-// loss) -- in a Poisson fit the Poisson wrapper does, in the same place --, the map, if any, wraps the result.  n: the
-// unknowns of the solve.
-static int fit_device(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, int32_t n)
+// The composition on device pointers: the loss wraps r's launchers -- the model's, or the convolved model's -- (NLH_LOSS_LINEAR:
+// no context, no kernel of the loss) -- in a Poisson fit the Poisson wrapper does, in the same place --, the map or the group,
+// if any, wraps the result.  n: the unknowns of the solve.
+static int fit_composed(nlh_handle *h, FitRun &r, const FitArgs &a, int32_t n)
 {
-    FitRun r{h, opts, &src, &a, src.N, src.fcn, src.jac, src.ctx};
+    const nlh_device_vecfcn fcn = r.fcn;
+    const nlh_device_jacfcn jac = r.jac;
+    void *const ctx = r.ctx;
     auto run = [&]() { return a.grp ? fit_grouped(r, n) : a.pm ? fit_mapped(r, n) : fit_solve(r, n, a.xl, a.xu, a.x, a.sigma, a.cov, a.status); };
     if (a.stat == NLH_STAT_POISSON) {
-        int rc = nlh_pois_wrap(h, a.y, a.w, a.mu_floor, src.fcn, src.jac, src.ctx, &r.qc);
+        int rc = nlh_pois_wrap(h, a.y, a.w, a.mu_floor, fcn, jac, ctx, &r.qc);
         if (rc) return rc;
-        r.fcn = nlh_pois_device_fcn; r.jac = src.jac ? nlh_pois_device_jac : nullptr; r.ctx = r.qc;
+        r.fcn = nlh_pois_device_fcn; r.jac = jac ? nlh_pois_device_jac : nullptr; r.ctx = r.qc;
         rc = run();
         const hipError_t e = hipStreamSynchronize(h->stream);     // (the context's scratch goes)
         nlh_pois_unwrap(r.qc);
@@ -245,14 +254,33 @@ static int fit_device(nlh_handle *h, const nlh_options *opts, const FitSource &s
         return rc;
     }
     if (a.loss == NLH_LOSS_LINEAR) return run();
-    int rc = nlh_loss_wrap(h, a.loss, a.scale, a.shared_scale, src.fcn, src.jac, src.ctx, &r.lc);
+    int rc = nlh_loss_wrap(h, a.loss, a.scale, a.shared_scale, fcn, jac, ctx, &r.lc);
     if (rc) return rc;
-    r.fcn = nlh_loss_device_fcn; r.jac = src.jac ? nlh_loss_device_jac : nullptr; r.ctx = r.lc;
+    r.fcn = nlh_loss_device_fcn; r.jac = jac ? nlh_loss_device_jac : nullptr; r.ctx = r.lc;
     rc = run();
     const hipError_t e = hipStreamSynchronize(h->stream);         // (the context's scratch goes)
     nlh_loss_unwrap(r.lc);
     if (!rc && e != hipSuccess) {
         h->err = std::string("fit with a loss: ") + hipGetErrorString(e);
+        return NLH_ERR_HIP;
+    }
+    return rc;
+}
+
+// ... with an instrument response (FitArgs::cv) first: the convolving pair wraps the model's launchers, the model bound
+// without weights; w is the convolving pair's, unless a Poisson pair follows, which keeps it as its mask.
+static int fit_device(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, int32_t n)
+{
+    FitRun r{h, opts, &src, &a, src.N, src.fcn, src.jac, src.ctx};
+    if (!a.cv) return fit_composed(h, r, a, n);
+    int rc = nlh_conv_wrap(h, a.cv, a.y, a.stat == NLH_STAT_POISSON ? nullptr : a.w, src.fcn, src.jac, src.ctx, &r.cc);
+    if (rc) return rc;
+    r.fcn = nlh_conv_device_fcn; r.jac = src.jac ? nlh_conv_device_jac : nullptr; r.ctx = r.cc;
+    rc = fit_composed(h, r, a, n);
+    const hipError_t e = hipStreamSynchronize(h->stream);         // (the context's scratch goes)
+    nlh_conv_unwrap(r.cc);
+    if (!rc && e != hipSuccess) {
+        h->err = std::string("fit with an instrument response: ") + hipGetErrorString(e);
         return NLH_ERR_HIP;
     }
     return rc;
@@ -272,7 +300,8 @@ static int fit_staged(nlh_handle *h, const nlh_options *opts, const FitSource &s
         nq = np / G; nn = (size_t)n * n;
     }
     const size_t tm = src.tdoubles * (a.shared_t ? (size_t)a.m : pm);
-    const size_t doubles = tm + pm * (a.w ? 3 : 2) + np * N + (a.sigma ? np * N : 0) + (a.cov ? nq * nn : 0) + (a.chi2 ? nq : 0);
+    const size_t kd = a.cv ? (size_t)a.cv->L * (a.cv->shared_k ? 1 : np) : 0;      // the taps of an instrument response
+    const size_t doubles = tm + pm * (a.w ? 3 : 2) + np * N + (a.sigma ? np * N : 0) + (a.cov ? nq * nn : 0) + (a.chi2 ? nq : 0) + kd;
     double *base = nullptr;
     if (hipMalloc(&base, sizeof(double) * doubles + sizeof(int32_t) * nq) != hipSuccess) {
         h->err = std::string("hipMalloc (") + src.what + ")";
@@ -288,12 +317,16 @@ static int fit_staged(nlh_handle *h, const nlh_options *opts, const FitSource &s
     d.sigma = a.sigma ? q : nullptr; q += a.sigma ? np * N : 0;
     d.cov = a.cov ? q : nullptr; q += a.cov ? nq * nn : 0;
     d.chi2 = a.chi2 ? q : nullptr; q += a.chi2 ? nq : 0;
+    double *dk = q; q += kd;
     d.rank = a.rank ? (int32_t *)q : nullptr;
     d.t = dt; d.y = dy; d.w = dw; d.scale = dscale;
+    nlh_conv dcv{};
+    if (a.cv) { dcv = *a.cv; dcv.k = dk; d.cv = &dcv; }
     hipError_t e = hipMemcpyAsync(dt, a.t, sizeof(double) * tm, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(dy, a.y, sizeof(double) * pm, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && a.w) e = hipMemcpyAsync(dw, a.w, sizeof(double) * pm, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d.x, a.x, sizeof(double) * np * N, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && a.cv) e = hipMemcpyAsync(dk, a.cv->k, sizeof(double) * kd, hipMemcpyHostToDevice, s);
     int rc = 0;
     if (e == hipSuccess) rc = fit_device(h, opts, src, d, n);
     if (e == hipSuccess && !rc) {
@@ -342,7 +375,9 @@ int nlh_fit_run(nlh_handle *h, const nlh_options *opts, const FitSource &src, co
     if (!opts || !a.t || !a.y || !a.x || !a.fvec || (a.loss != NLH_LOSS_LINEAR && !a.scale)) return NLH_INVALID_INPUT_ERROR;
     if ((a.sigma || a.cov || a.chi2) && M <= n) return NLH_INVALID_INPUT_ERROR;     // no degree of freedom for errors
     if (a.stat == NLH_STAT_POISSON && !nlh_pois_floor_ok(a.mu_floor)) return NLH_INVALID_INPUT_ERROR;
+    if (a.cv && !nlh_conv_ok(a.cv)) return NLH_INVALID_INPUT_ERROR;
     if (!host) return fit_device(h, opts, src, a, n);
+    if (a.cv && !nlh_conv_data_ok(a.cv, a.y, (size_t)a.nprob, (size_t)a.m)) return NLH_INVALID_INPUT_ERROR;
     if (a.stat == NLH_STAT_POISSON && !nlh_pois_data_ok(a.y, a.w, (size_t)a.nprob * a.m)) return NLH_INVALID_INPUT_ERROR;
     double *dscale = nullptr;                                     // checks the host scales: finite, positive (LINEAR: none, NULL)
     int rc = nlh_loss_scale_upload(h, a.loss, a.scale, a.shared_scale ? 1 : (size_t)a.nprob, &dscale);

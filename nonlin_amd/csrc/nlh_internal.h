@@ -18,6 +18,7 @@
 //   nlh_pmap.hip       parameter maps: the map object, the wrapping launchers, gather / expand / covariance
 //   nlh_loss.hip       robust losses: the wrapping launchers, apply, the upload of host scales
 //   nlh_pois.hip       Poisson likelihood fits: the wrapping launchers, apply, the check of host counts and masks
+//   nlh_conv.hip       instrument-response fits: the wrapping launchers, apply, the check of a transform
 //   nlh_group.hip      global fits: the group object, the wrapping launchers, gather / expand / sigma
 //   nlh_model.hip      device sets, device residual models behind host arrays
 //   nlh_qrx.hip        the exact lmfactor
@@ -332,7 +333,7 @@ struct nlh_expr {
     int32_t nconst;
 };
 
-// The one-call fit + errors of the twenty entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois,_group}{,_h} (nlh_fit.hip).
+// The one-call fit + errors of the twenty-four entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois,_group,_conv}{,_h} (nlh_fit.hip).
 // FitSource: what a model kind hands the pipeline.  bind points the context's data at problem p0 of dt, dy, dw (the whole
 // batch's device arrays) before each run of consecutive problems; whatever else the context holds stays the whole batch's.
 struct FitSource {
@@ -365,6 +366,7 @@ struct FitArgs {
     int32_t stat = NLH_STAT_LSQ;
     double mu_floor = 0.0;
     const nlh_group *grp = nullptr;    // a global fit: nprob data sets in groups; cov, chi2, rank, ib, status per group
+    const nlh_conv *cv = nullptr;      // an instrument response: the model is convolved with it (k: as the other arrays, device or host)
 };
 // The documented ladder of checks, then: solve (bounded when xl or xu is given), covariance with scaled = 1 when any of sigma,
 // cov, chi2 is asked for, the degrees-of-freedom rule of zero weights, NaN and rank -1 for problems that did not solve.  The
@@ -400,6 +402,12 @@ int nlh_loss_scale_upload(nlh_handle *h, int32_t kind, const double *scale, size
 // counts finite and not negative on every row the mask keeps
 bool nlh_pois_floor_ok(double mu_floor);
 bool nlh_pois_data_ok(const double *y, const double *w, size_t cnt);
+// instrument-response fits (nlh_conv.hip): a transform the header accepts (k not NULL, L, origin and ext in range); where a
+// run of problems starts in the caller's arrays
+bool nlh_conv_ok(const nlh_conv *cv);
+// ... with HOST taps and HOST data of nprob problems of m rows: every tap and every y finite (every row is convolved)
+bool nlh_conv_data_ok(const nlh_conv *cv, const double *y, size_t nprob, size_t m);
+void conv_ctx_rebind(nlh_conv_ctx *c, const double *dy, const double *dw, const double *dk);
 // columns the built-in dense-quadratic family's kernels accept (x in LDS, lds_max of nlh_create): beyond it NLH_ARRAY_SIZE_ERROR
 static const int32_t NLH_DQ_MAX_N = 20000;
 

@@ -99,6 +99,8 @@ struct nlh_dq_model {
     nlh_loss_ctx *loss = nullptr;
     // a Poisson model (nlh_pois_model_create): the wrapping context around another model's launchers; the counts and the mask
     nlh_pois_ctx *pois = nullptr;
+    // a convolved model (nlh_conv_model_create): the wrapping context around another model's launchers; the data, weights and taps
+    nlh_conv_ctx *conv = nullptr;
     // a global model (nlh_group_model_create): the wrapping context around another model's launchers; nothing else
     nlh_group_ctx *group = nullptr;
 };
@@ -313,6 +315,30 @@ int nlh_loss_model_create(nlh_handle *h, const nlh_dq_model *inner, int32_t kind
     return 0;
 }
 
+// A convolved model over a launcher-backed inner model created WITHOUT weights (nlh_conv.hip: the wrapping launchers).
+int nlh_conv_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_conv *cv, const double *y, const double *w, nlh_dq_model **out)
+{
+    if (out) *out = nullptr;
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (!out || !inner || !inner->ufcn || !y || !nlh_conv_ok(cv)) return NLH_INVALID_INPUT_ERROR;
+    const size_t pm = (size_t)inner->nprob * inner->m, kd = (size_t)cv->L * (cv->shared_k ? 1 : (size_t)inner->nprob);
+    if (!nlh_conv_data_ok(cv, y, (size_t)inner->nprob, (size_t)inner->m)) return NLH_INVALID_INPUT_ERROR;
+    double *base = nullptr;
+    if (const int urc = nlh_upload(h, "convolved model", {{y, sizeof(double) * pm}, {cv->k, sizeof(double) * kd}, {w, w ? sizeof(double) * pm : 0}},
+                                   (void **)&base)) return urc;
+    nlh_conv dcv = *cv;
+    dcv.k = base + pm;
+    nlh_conv_ctx *cc = nullptr;
+    const int rc = nlh_conv_wrap(h, &dcv, base, w ? base + pm + kd : nullptr, inner->ufcn, inner->ujac, inner->uctx, &cc);
+    if (rc) { hipFree(base); return rc; }
+    nlh_dq_model *md = new nlh_dq_model();
+    md->nprob = inner->nprob; md->m = inner->m; md->n = inner->n; md->gamma = 0.0;
+    md->ufcn = nlh_conv_device_fcn; md->ujac = inner->ujac ? nlh_conv_device_jac : nullptr; md->uctx = cc;
+    md->conv = cc; md->owned = base; md->owned_device = h->device;
+    *out = md;
+    return 0;
+}
+
 // A Poisson model over a launcher-backed inner model created WITHOUT weights (nlh_pois.hip: the wrapping launchers).
 int nlh_pois_model_create(nlh_handle *h, const nlh_dq_model *inner, const double *y, const double *w, double mu_floor, nlh_dq_model **out)
 {
@@ -362,6 +388,7 @@ void nlh_dq_model_destroy(nlh_dq_model *md)
     nlh_pmap_unwrap(md->pmap);
     nlh_loss_unwrap(md->loss);
     nlh_pois_unwrap(md->pois);
+    nlh_conv_unwrap(md->conv);
     delete md->expr;
     delete md->expr_prog;
     if (md->owned) { hipSetDevice(md->owned_device); hipFree(md->owned); }

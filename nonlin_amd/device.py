@@ -21,6 +21,7 @@ from ._lib import Expr  # noqa: E402,F401
 from ._lib import ParamMap  # noqa: E402,F401
 from ._lib import Loss  # noqa: E402,F401
 from ._lib import Poisson  # noqa: E402,F401
+from ._lib import Convolve  # noqa: E402,F401
 
 
 def _chk(t, shape, name):
@@ -85,6 +86,15 @@ class _PoisCtx(_PmapCtx):
     def close(self):
         if getattr(self, "ptr", None) is not None and self.ptr.value:
             self.lib.nlh_pois_unwrap(self.ptr)
+            self.ptr = C.c_void_p()
+
+
+class _ConvCtx(_PmapCtx):
+    """The context of the convolving launchers (nlh_conv_ctx), with everything it points at kept alive."""
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.lib.nlh_conv_unwrap(self.ptr)
             self.ptr = C.c_void_p()
 
 
@@ -315,7 +325,7 @@ class DeviceSolver:
                 None if hi is None else hi.ctypes.data_as(_lib.c_double_p))
 
     def curve_fit_batch(self, kind, t, y, x0, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
-                        covariance=True, opts=None, pmap=None, loss=None, stat=None, group=None):
+                        covariance=True, opts=None, pmap=None, loss=None, stat=None, group=None, conv=None):
         """Fit + errors of y.shape[0] curves in one call (nlh_curve_fit_batch): least_squares_solver%solve -- or, with lower /
         upper ([n], one box for every problem), constrained_least_squares_solver%solve -- from x0 [nprob, n] (not modified),
         then the scaled parameter covariance at the solution.  Rows with weight 0 pad ragged data: they do not count as
@@ -334,13 +344,21 @@ class DeviceSolver:
         every group.nsets consecutive rows of y are one group, whose shared parameters have one value.  x0, x, fvec and sigma
         stay per data set (a shared parameter starts from the value of the group's first data set and comes back equal across
         the group); cov [ngroup, nouter, nouter] (group.index locates entries), chi2, rank, ibs and status are per group.
-        group together with pmap raises ValueError.  None calls exactly what is called without it."""
+        group together with pmap raises ValueError.  None calls exactly what is called without it.
+        conv (a Convolve): the model is convolved with an instrument response before it is compared with y
+        (nlh_curve_fit_batch_conv), with or without pmap, loss, stat or group: t must be a uniform grid and y finite on every
+        row, padded ones included.  fvec is the residual of the convolved model; conv_apply on curve_eval's values gives the
+        convolved model itself.  None calls exactly what is called without it."""
         if stat is not None and loss is not None:
             raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
         k = curve_kind(kind)
         nprob, m, shared = self._curve_data(t, y, weights)
         n = curve_nparams(k, ncomp, baseline)
         _chk(x0, (nprob, n), "x0")
+        if conv is not None:
+            call = lambda *rest: self.lib.nlh_curve_fit_batch_conv(self.h.ptr, rest[0], k, int(ncomp), int(baseline), *rest[1:])
+            return self._conv_fit("nlh_curve_fit_batch_conv", call, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
+                                  lower, upper, analytic, covariance, opts)
         if group is not None:
             call = lambda *rest: self.lib.nlh_curve_fit_batch_group(self.h.ptr, rest[0], k, int(ncomp), int(baseline), *rest[1:])
             return self._group_fit("nlh_curve_fit_batch_group", call, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
@@ -430,7 +448,7 @@ class DeviceSolver:
         return y
 
     def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None,
-                       pmap=None, loss=None, stat=None, group=None):
+                       pmap=None, loss=None, stat=None, group=None, conv=None):
         """Fit + errors of y.shape[0] data sets to a formula in one call (nlh_expr_fit_batch): curve_fit_batch with an Expr in
         the place of (kind, ncomp, baseline), pmap (e.g. ParamMap.for_expr(expr, ...)), loss (a Loss), stat (a Poisson) and
         group (e.g. Group.for_expr(expr, shared=("k",), nsets=8): nlh_expr_fit_batch_group) included.  Returns (x, fvec, sigma,
@@ -440,6 +458,10 @@ class DeviceSolver:
         nprob, m, shared = self._expr_data(expr, t, y, weights)
         n = expr.nparams
         _chk(x0, (nprob, n), "x0")
+        if conv is not None:                                          # (a Convolve: as in curve_fit_batch)
+            call = lambda *rest: self.lib.nlh_expr_fit_batch_conv(self.h.ptr, rest[0], expr.ptr, *rest[1:])
+            return self._conv_fit("nlh_expr_fit_batch_conv", call, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
+                                  lower, upper, analytic, covariance, opts)
         if group is not None:
             call = lambda *rest: self.lib.nlh_expr_fit_batch_group(self.h.ptr, rest[0], expr.ptr, *rest[1:])
             return self._group_fit("nlh_expr_fit_batch_group", call, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
@@ -619,6 +641,37 @@ class DeviceSolver:
             raise RuntimeError(f"{name} returned {rc}")
         return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(ngroup)], [int(status[p]) for p in range(ngroup)])
 
+    def _conv_fit(self, name, call, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0, lower, upper, analytic,
+                  covariance, opts):
+        """The one-call fit with an instrument response behind curve_fit_batch / expr_fit_batch with conv=; call(opts, nprob, m,
+        ...) is the entry point with the model's own arguments bound.  What comes back is per group with a group, per data set
+        without."""
+        if group is not None and pmap is not None:
+            raise ValueError("group and pmap exclude each other: a map inside a group works through pmap_launchers and group_launchers")
+        if group is not None and group.nparams != n:
+            raise ValueError(f"group is over {group.nparams} parameters, the model has {n}")
+        if group is not None and nprob % group.nsets:
+            raise ValueError(f"{nprob} data sets: no multiple of the group's {group.nsets}")
+        if pmap is not None and pmap.nfull != n:
+            raise ValueError(f"pmap maps {pmap.nfull} parameters, the model has {n}")
+        nsolve, nunk = (nprob // group.nsets, group.nouter) if group is not None else (nprob, n)
+        dev = y.device
+        x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, nsolve, nunk)
+        lo, hi, plo, phi = self._fit_bounds(lower, upper, n)
+        o = opts or self.options()
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        dscale, sh = self._loss_scale(loss, nprob, dev) if loss is not None else (None, 0)
+        cv, dk = self._conv_struct(conv, nprob, dev)
+        rc = call(C.byref(o), nprob, m, t.data_ptr(), shared, y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
+                  group.ptr if group is not None else None, pmap.ptr if pmap is not None else None, C.byref(cv),
+                  loss.kind if loss is not None else 0, ptr(dscale), sh, 1 if stat is not None else 0,
+                  stat.mu_floor if stat is not None else 0.0, x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank),
+                  ib, status)
+        self.h.check(rc, name)
+        if rc:
+            raise RuntimeError(f"{name} returned {rc}")
+        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nsolve)], [int(status[p]) for p in range(nsolve)])
+
     # -- robust losses -------------------------------------------------------------
     def _loss_scale(self, loss, nprob, dev=None):
         """(device tensor of the scales of a Loss for nprob problems, shared flag)."""
@@ -695,6 +748,53 @@ class DeviceSolver:
         if rc:
             raise RuntimeError(f"nlh_pois_apply_batch returned {rc}")
         return out, g, dev
+
+    # -- instrument-response fits ---------------------------------------------------
+    def _conv_struct(self, conv, nprob, dev=None):
+        """(nlh_conv of a Convolve for nprob problems, the device tensor of its taps: keep it alive)."""
+        k, _ = conv.kernel_for(nprob)
+        dk = torch.from_numpy(np.ascontiguousarray(k)).to(dev if dev is not None else self.device)
+        return conv.struct(dk.data_ptr()), dk
+
+    def conv_launchers(self, conv, fcn, jac, ctx, y, weights=None):
+        """An instrument response for any launcher pair: wraps (fcn, jac, ctx) -- of curve_launchers or expr_launchers made
+        WITHOUT weights on the same data y [nprob, m], or a user's own whose residual is model - y -- in the convolving
+        launchers (nlh_conv_wrap) and returns (fcn, jac, ctx) for lm_solve_batch_device, cls_solve_batch_device,
+        lm_covariance_batch_device, fd_jacobian_device, loss_launchers, pois_launchers, pmap_launchers and group_launchers:
+        the residual is conv(model) - y, times weights [nprob, m] when given.  jac is None without an inner Jacobian launcher
+        (pass jac=None to the solver: forward differences of the wrapped residual).  Keep the returned ctx alive while
+        solving; ctx.close() frees it (so does garbage collection)."""
+        nprob, m = y.shape
+        _chk(y, (nprob, m), "y")
+        if weights is not None:
+            _chk(weights, (nprob, m), "weights")
+        cv, dk = self._conv_struct(conv, nprob, y.device)
+        out = C.c_void_p()
+        rc = self.lib.nlh_conv_wrap(self.h.ptr, C.byref(cv), y.data_ptr(), weights.data_ptr() if weights is not None else None,
+                                    self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), C.byref(out))
+        self.h.check(rc, "nlh_conv_wrap")
+        if rc:
+            raise RuntimeError(f"nlh_conv_wrap returned {rc}")
+        wrapped = _ConvCtx(self.lib, out, (conv, dk, fcn, jac, ctx, y, weights))
+        return (C.cast(self.lib.nlh_conv_device_fcn, _lib.DEVFCN),
+                C.cast(self.lib.nlh_conv_device_jac, _lib.DEVFCN) if jac is not None else None, wrapped)
+
+    def conv_apply(self, conv, v):
+        """The bare convolution of columns v [nprob, m] or [nprob, ncol, m] under a Convolve (nlh_conv_apply_batch), e.g. of
+        curve_eval's model values for plotting the convolved model.  Returns a new tensor of v's shape."""
+        if v.dim() not in (2, 3):
+            raise ValueError("v: expected [nprob, m] or [nprob, ncol, m]")
+        nprob, m = v.shape[0], v.shape[-1]
+        ncol = v.shape[1] if v.dim() == 3 else 1
+        _chk(v, v.shape, "v")
+        cv, dk = self._conv_struct(conv, nprob, v.device)
+        out = torch.empty_like(v)
+        rc = self.lib.nlh_conv_apply_batch(self.h.ptr, C.byref(cv), nprob, m, ncol, v.data_ptr(), out.data_ptr())
+        self.h.check(rc, "nlh_conv_apply_batch")
+        if rc:
+            raise RuntimeError(f"nlh_conv_apply_batch returned {rc}")
+        torch.cuda.current_stream(v.device).synchronize()             # (dk goes with this frame)
+        return out
 
     def _ctxp(self, ctx):
         if isinstance(ctx, _PmapCtx):

@@ -30,6 +30,15 @@ module nonlin_hip_c
     integer(c_int32_t), parameter :: NLH_PMAP_FREE = 0, NLH_PMAP_FIXED = 1, NLH_PMAP_TIED = 2
     ! kinds of a robust loss (include/nonlin_hip.h: NLH_LOSS_*)
     integer(c_int32_t), parameter :: NLH_LOSS_LINEAR = 0, NLH_LOSS_HUBER = 1, NLH_LOSS_SOFT_L1 = 2, NLH_LOSS_CAUCHY = 3
+    ! extensions of an instrument response beyond the rows of the data, and the transform itself (include/nonlin_hip.h: nlh_conv)
+    integer(c_int32_t), parameter :: NLH_CONV_ZERO = 0, NLH_CONV_HOLD = 1
+    type, bind(C) :: nlh_conv
+        integer(c_int32_t) :: L
+        integer(c_int32_t) :: origin
+        integer(c_int32_t) :: ext
+        integer(c_int32_t) :: shared_k
+        type(c_ptr) :: k
+    end type
 
     interface
         subroutine nlh_default_options(opts) bind(C, name="nlh_default_options")
@@ -268,6 +277,16 @@ module nonlin_hip_c
             real(c_double), intent(in) :: y(*)
             type(c_ptr), value :: w
             real(c_double), value :: mu_floor
+            type(c_ptr), intent(out) :: model
+            integer(c_int) :: rc
+        end function
+        ! instrument-response fits (include/nonlin_hip.h: nlh_conv_*): an unweighted model convolved with a kernel along its rows
+        function nlh_conv_model_create(h, inner, cv, y, w, model) bind(C, name="nlh_conv_model_create") result(rc)
+            import :: c_ptr, c_int, c_double, nlh_conv
+            type(c_ptr), value :: h, inner
+            type(nlh_conv), intent(in) :: cv
+            real(c_double), intent(in) :: y(*)
+            type(c_ptr), value :: w
             type(c_ptr), intent(out) :: model
             integer(c_int) :: rc
         end function

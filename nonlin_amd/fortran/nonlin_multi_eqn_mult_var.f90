@@ -21,6 +21,7 @@ module nonlin_multi_eqn_mult_var
     public :: NLH_CURVE_GAUSS, NLH_CURVE_LORENTZ, NLH_CURVE_EXPDECAY   ! kinds of device_model_batch%create_curve (from nonlin_hip_c)
     public :: NLH_PMAP_FREE, NLH_PMAP_FIXED, NLH_PMAP_TIED             ! kinds of a parameter, device_model_batch%create_mapped
     public :: NLH_LOSS_LINEAR, NLH_LOSS_HUBER, NLH_LOSS_SOFT_L1, NLH_LOSS_CAUCHY   ! kinds of device_model_batch%create_robust
+    public :: NLH_CONV_ZERO, NLH_CONV_HOLD                             ! extensions of device_model_batch%create_convolved
     public :: NLH_FACTOR_AUTO, NLH_FACTOR_QR, NLH_FACTOR_EXACT     ! values of equation_solver%factor_policy (from nonlin_hip_c)
     public :: nlh_use_devices
     public :: nlh_vecfcn_trampoline
@@ -64,6 +65,7 @@ module nonlin_multi_eqn_mult_var
         procedure, public :: create_global => dmb_create_global
         procedure, public :: create_robust => dmb_create_robust
         procedure, public :: create_poisson => dmb_create_poisson
+        procedure, public :: create_convolved => dmb_create_convolved
         procedure, public :: destroy => dmb_destroy
         procedure, public :: is_defined => dmb_defined
         procedure, public :: get_problem_count => dmb_nprob
@@ -552,6 +554,50 @@ contains
         end if
         call this%destroy()
         rc = nlh_pois_model_create(nlh_default_handle(), inner%model_, yc, wp, floor_, this%model_)
+        if (rc /= 0) error stop rc
+        this%neqn_ = inner%neqn_
+        this%nvar_ = inner%nvar_
+        this%nprob_ = inner%nprob_
+        this%analytic_ = inner%analytic_
+    end subroutine
+
+    !> An instrument response for a launcher-backed model created WITHOUT weights (create_curve, create_expr,
+    !> create_from_device_fcn) on the same data y(m, nprob): a model of the same unknowns over inner, which must outlive it,
+    !> whose residuals are conv(model) - y, times w(m, nprob) when given (INTEGRATION.md 6m).  k(L, 1) is one kernel for every
+    !> problem, k(L, nprob) one per problem, L = 1 .. 1024, used as given; origin = 0 .. L - 1 is the tap that sits on the output
+    !> row, counted from 0 as in nonlin_hip.h (0: a causal response, (L - 1) / 2: a centred one); ext is NLH_CONV_ZERO (rows
+    !> outside the data contribute nothing) or NLH_CONV_HOLD (they take the nearest edge row's value).  The rows must lie on one
+    !> uniform grid and y must be finite on every row.  create_robust, create_poisson, create_mapped and create_global take
+    !> the result.  What the library refuses stops the program with NL_INVALID_INPUT_ERROR.
+    subroutine dmb_create_convolved(this, inner, k, origin, ext, y, w)
+        class(device_model_batch), intent(inout) :: this
+        class(device_model_batch), intent(in) :: inner
+        real(real64), intent(in), dimension(:,:) :: k
+        integer(int32), intent(in) :: origin, ext
+        real(real64), intent(in), dimension(:,:) :: y
+        real(real64), intent(in), dimension(:,:), optional :: w
+        integer(c_int) :: rc
+        real(c_double), allocatable, target :: kc(:,:), yc(:,:), wc(:,:)
+        type(c_ptr) :: wp
+        type(nlh_conv) :: cv
+        if (.not.inner%is_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR
+        if (any(shape(y) /= [inner%neqn_, inner%nprob_])) error stop NL_ARRAY_SIZE_ERROR
+        if (size(k, 2) /= 1 .and. size(k, 2) /= inner%nprob_) error stop NL_ARRAY_SIZE_ERROR
+        kc = k
+        yc = y
+        wp = c_null_ptr
+        if (present(w)) then
+            if (any(shape(w) /= [inner%neqn_, inner%nprob_])) error stop NL_ARRAY_SIZE_ERROR
+            wc = w
+            wp = c_loc(wc)
+        end if
+        cv%L = size(k, 1)
+        cv%origin = origin
+        cv%ext = ext
+        cv%shared_k = merge(1, 0, size(k, 2) == 1)
+        cv%k = c_loc(kc)
+        call this%destroy()
+        rc = nlh_conv_model_create(nlh_default_handle(), inner%model_, cv, yc, wp, this%model_)
         if (rc /= 0) error stop rc
         this%neqn_ = inner%neqn_
         this%nvar_ = inner%nvar_
