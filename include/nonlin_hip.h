@@ -479,6 +479,17 @@ int nlh_dq_jacobian(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, const do
 /* J^T J (fp64 MFMA, deterministic split-K) and J^T f.  dG [nprob][n][n], dg [nprob][n]. */
 int nlh_gram(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, const double *dJ,
              const double *df, double *dG, double *dg);
+/* Which kernel form nlh_gram (and the normal-equations policy) takes for an m-by-n problem, and its K-split count:
+ * host code only -- no handle, no device -- the very function the launch dispatches through, under the process's
+ * NLH_GRAM512 / NLH_GRAM_TRI environment as it is at the call.  Form and split count depend on the
+ * shape only, never on the batch; forms never change a bit of G.  Returns the form; *nsplit (may be NULL) = K-splits;
+ * *direct (may be NULL) = 1 when the kernel writes G and g in place and no reduce is launched (a triangle form with one
+ * split).  -NLH_INVALID_INPUT_ERROR for m < 1 or n < 1. */
+enum { NLH_GRAM_FORM_BLOCK = 0,    /* k_gram_mfma: a workgroup per 64 x 64 block of the lower block triangle */
+       NLH_GRAM_FORM_TRI8 = 1,     /* k_gram_tri<8>: 96 < n <= 128, the whole lower triangle in one workgroup */
+       NLH_GRAM_FORM_TRI16 = 2,    /* k_gram_tri<16>: 224 < n <= 256 */
+       NLH_GRAM_FORM_512 = 3 };    /* k_gram_512: 256 < n <= 512, four workgroups per (problem, K-split) */
+int32_t nlh_gram_plan(int32_t m, int32_t n, int32_t *nsplit, int32_t *direct);
 /* lmfactor replacement on the Gram matrix: pivoted Cholesky P^T G P = R^T R with
  * MINPACK's pivot rule, acnorm = sqrt(diag G), qtf = R^-T P^T g.  dG is overwritten
  * by R (upper triangle).  ipvt is 0-based.  info[k] != 0 => ill-conditioned/rank-deficient. */

@@ -708,30 +708,8 @@ k_gram_reduce(int n, int nsplit, const double *__restrict__ Gpart, double *__res
     if (r != c) G[(size_t)p * nn + (size_t)c * n + r] = s;      // ... and its mirror G(r, c)
 }
 
-// g = J^T f: one wave per column, lanes stride the rows (coalesced), shuffle reduction.
-static __global__ void __launch_bounds__(256)
-k_jtf(int m, int n, const double *__restrict__ J, const double *__restrict__ f,
-      double *__restrict__ g, const LmState *__restrict__ st, int want_stage)
-{
-    const int p = blockIdx.y;
-    if (st && st[p].stage != want_stage) return;
-    const int lane = threadIdx.x & 63;
-    const int j = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (j >= n) return;
-    const double *col = J + (size_t)p * m * n + (size_t)j * m;
-    const double *fp = f + (size_t)p * m;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int i = lane;
-    for (; i + 192 < m; i += 256) {
-        s0 = s0 + col[i] * fp[i];
-        s1 = s1 + col[i + 64] * fp[i + 64];
-        s2 = s2 + col[i + 128] * fp[i + 128];
-        s3 = s3 + col[i + 192] * fp[i + 192];
-    }
-    for (; i < m; i += 64) s0 = s0 + col[i] * fp[i];
-    double s = wave_reduce_sum((s0 + s1) + (s2 + s3));
-    if (lane == 0) g[(size_t)p * n + j] = s;
-}
+// (g = J^T f on the normal-equations path rides along in the Gram kernels above.  The stand-alone kernel that once formed
+// it, k_jtf, was launched nowhere and is gone; its timing slot NLH_K_JTF now times k_jtf_exact below.)
 
 // grad(i) = dot(jac(:,i), fvec) in the reference's order (src/nonlin_solve.f90:565-567): one thread per column,
 // rows ascending, separate multiply and add.  The Newton line search feeds dot(grad, dir) into the backtracking

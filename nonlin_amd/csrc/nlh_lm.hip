@@ -143,13 +143,37 @@ static int gram_splits(int m)
 }
 
 static bool gram512_on() { const char *e = getenv("NLH_GRAM512"); return !e || atoi(e) != 0; }   // (0: k_gram_mfma for 256 < n <= 512, for comparison)
+static bool gram_tri_on() { const char *e = getenv("NLH_GRAM_TRI"); return !e || atoi(e) != 0; }  // (0: k_gram_mfma for 96 < n <= 128 and 224 < n <= 256)
+
+// Which kernel form forms G for an m-by-n problem (NLH_GRAM_FORM_*) and in how many K-splits, under the environment
+// as it is now (read per call: tests compare the forms bit for bit in one process).  launch_gram dispatches through
+// this, nlh_gram_plan reports it.
+static int gram_form(int m, int n, int *nsplit)
+{
+    *nsplit = gram_splits(m);
+    if (n > 224 && n <= 256 && gram_tri_on()) return NLH_GRAM_FORM_TRI16;
+    if (n > 96 && n <= 128 && gram_tri_on()) return NLH_GRAM_FORM_TRI8;
+    if (n > 256 && n <= 512 && gram512_on()) return NLH_GRAM_FORM_512;
+    return NLH_GRAM_FORM_BLOCK;
+}
+
+int32_t nlh_gram_plan(int32_t m, int32_t n, int32_t *nsplit, int32_t *direct)
+{
+    if (m < 1 || n < 1) return -NLH_INVALID_INPUT_ERROR;
+    int ns;
+    const int form = gram_form(m, n, &ns);
+    if (nsplit) *nsplit = ns;
+    if (direct) *direct = (form == NLH_GRAM_FORM_TRI16 || form == NLH_GRAM_FORM_TRI8) && ns == 1;
+    return form;
+}
 
 static int launch_gram(nlh_handle *h, int nprob, int m, int n, const double *J, const double *f,
                        double *G, double *g, const LmState *st, int want)
 {
     const int nb = (n + GRAM_BT - 1) / GRAM_BT;
     const int nblk = nb * (nb + 1) / 2;
-    const int ns = gram_splits(m);
+    int ns;
+    const int form = gram_form(m, n, &ns);
     int rps = (m + ns - 1) / ns;
     rps = ((rps + GRAM_KT - 1) / GRAM_KT) * GRAM_KT;
     int rc = ensure(h, h->Gpart, sizeof(double) * ((size_t)nprob * ns * n * n + (size_t)nprob * ns * n));
@@ -159,8 +183,8 @@ static int launch_gram(nlh_handle *h, int nprob, int m, int n, const double *J, 
     {
         Timed t(h, NLH_K_GRAM);
         const long items = (long)ns * nprob;
-        const bool tri16 = n > 224 && n <= 256;
-        const bool tri8 = n > 96 && n <= 128;
+        const bool tri16 = form == NLH_GRAM_FORM_TRI16;
+        const bool tri8 = form == NLH_GRAM_FORM_TRI8;
         if (tri16 || tri8) {
             // whole lower triangle per workgroup, J staged once
             const int nt = tri16 ? 16 : 8;
@@ -175,7 +199,7 @@ static int launch_gram(nlh_handle *h, int nprob, int m, int n, const double *J, 
                                    g ? f : (const double *)nullptr, gp, st, want, ns, direct ? G : (double *)nullptr,
                                    direct ? g : (double *)nullptr);
             if (direct) return 0;          // one split: G and g are final, nothing to reduce
-        } else if (n > 256 && n <= 512 && gram512_on()) {
+        } else if (form == NLH_GRAM_FORM_512) {
             // four workgroups per item: the two diagonal 256-column blocks and the two halves of the square between them
             const long groups = (items + 7) / 8;
             const size_t sh = sizeof(double) * (size_t)(2 * 384 * GRAM_LD2 + 2 * GRAM_KT2 + 1024);   // two 16-row tile buffers

@@ -53,6 +53,21 @@ def qrx_plan(nprob, m, n, nact=0, have_stages=False):
     return rec(head), [rec(steps[i]) for i in range(n)]
 
 
+# names of the NLH_GRAM_FORM_* values of include/nonlin_hip.h, in order
+GRAM_FORMS = ("block", "tri8", "tri16", "512")
+
+
+def gram_plan(m, n):
+    """The kernel form and K-split count of G = J^T J for an m-by-n problem (nlh_gram_plan: host code, needs no GPU; the
+    function the launch itself dispatches through), under this process's NLH_GRAM512 / NLH_GRAM_TRI environment as it is
+    now.  Returns {"form": one of GRAM_FORMS, "nsplit": K-splits, "direct": no reduce launch}."""
+    ns, direct = C.c_int32(), C.c_int32()
+    rc = _lib.load().nlh_gram_plan(m, n, C.byref(ns), C.byref(direct))
+    if rc < 0:
+        raise ValueError(f"nlh_gram_plan({m}, {n}): error {rc}")
+    return {"form": GRAM_FORMS[rc], "nsplit": int(ns.value), "direct": bool(direct.value)}
+
+
 class _PmapCtx:
     """The context of a map's wrapping launchers (nlh_pmap_ctx), with everything it points at kept alive."""
 

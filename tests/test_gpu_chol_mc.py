@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import gram_cases as GC
+
 pytestmark = pytest.mark.gpu
 
 
@@ -80,8 +82,13 @@ def test_gram_512_same_bits_as_block_kernel(ds, nb, m, n):
     # g = J^T f: k_gram_512 adds sixteen partial sums per column and split (out of its loader's registers), the block kernel
     # four: the same vector to rounding, not to the bit
     assert float((g0 - g1).abs().max()) <= 1e-14 * float(g0.abs().max()) * np.sqrt(m)
+    Jc, fc = J.cpu(), f.cpu()                    # ... and entry by entry within the bound either must meet (tests/gram_cases.py)
+    for p in range(nb):
+        assert ((g0[p] - g1[p]).abs().cpu().numpy() <= (m + GC.nsplit_of(m) + 2) * GC.U * GC.abs_jtf(Jc[p], fc[p])).all(), p
     Gref = torch.matmul(J, J.transpose(1, 2))
     gref = torch.matmul(J, f.unsqueeze(-1)).squeeze(-1)
     assert float((G1 - Gref).abs().max()) <= 1e-13 * float(Gref.abs().max()) * np.sqrt(m)
     assert float((g1 - gref).abs().max()) <= 1e-13 * float(gref.abs().max()) * np.sqrt(m)
     assert torch.equal(G1, G1.transpose(1, 2))
+    GC.assert_bound(G1, g1, Jc, fc, GC.route(full=False))     # |G - Gref| <= (m + nsplit + 2) 2^-53 |J|^T |J|, entry by entry
+    GC.assert_bound(G0, g0, Jc, fc, GC.route(full=False))

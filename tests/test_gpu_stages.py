@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import gram_cases as GC
+
 pytestmark = pytest.mark.gpu
 
 
@@ -74,6 +76,8 @@ def test_gram_mfma(ds, m, n):
     assert float((gv - gref).abs().max()) <= 1e-13 * float(gref.abs().max()) * np.sqrt(m)
     assert torch.equal(G, G.transpose(1, 2))
     assert torch.equal(G, G2) and torch.equal(gv, gv2)
+    # and entry by entry, each against its own size: |G - Gref| <= (m + nsplit + 2) 2^-53 |J|^T |J| (tests/gram_cases.py)
+    GC.assert_bound(G, gv, J.cpu(), f.cpu(), GC.route(full=False))
 
 
 @pytest.mark.parametrize("m,n", [(21, 4), (512, 64), (300, 37), (2048, 128)])
