@@ -1368,6 +1368,127 @@ int nlh_expr_fit_batch_conv_h(nlh_handle *h, const nlh_options *opts, const nlh_
                               double *sigma, double *cov, double *chi2, int32_t *rank, nlh_iteration_behavior *ib,
                               int32_t *status);
 
+/* ---- separable fits (no counterpart in nonlin v2.2.0): variable projection for ANY device model.  Most fit models are linear
+ * in many of their parameters -- a curve kind in its amplitudes and baseline coefficients, a formula like vmax*s/(km+s) in one
+ * or two.  Variable projection (Golub & Pereyra; Kaufman's Jacobian) solves for those exactly at every trial point, so the
+ * solver iterates over the nonlinear ones only and the caller gives no starting values for the linear ones.  Like a parameter
+ * map it is a pair of wrapping launchers around any inner launcher pair, so everything that takes launchers works through it.
+ * "Linear" is the caller's declaration: the inner model must be affine in those parameters at fixed nonlinear ones.
+ * The nonlinear unknowns are the other full parameters in ascending full index: n = N - L.
+ * THE ARITHMETIC IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation.  Per point, alpha the n
+ * nonlinear values handed in:
+ *   basis     p0 = (c = +0.0, alpha);  the inner jac at p0: its L linear columns are Phi (m x L);  the inner fcn at p0: f0
+ *             (residuals are model - y here, so the residual at (c, alpha) is Phi c + f0)
+ *   sum       EVERY sum over rows below has one order: 256 partials; partial j starts at +0.0 and takes the rows i = j (mod
+ *             256) in ascending i as s = s + a*b; the partials combine as a 256-thread block sum does: inside each run of 64
+ *             the tree  p[l] = p[l] + p[l + off], l < off, for off = 32, 16, 8, 4, 2, 1;  then t = +0.0 and t = t + (the
+ *             result of run w) for w = 0, 1, 2, 3
+ *   QR        unpivoted Householder on [Phi | f0].  norm0_l = sqrt(sum over all rows of w_i*w_i) of column l before any
+ *             reflector.  Column l = 0 .. L-1 in turn, w its current values, r = the live columns so far:
+ *               sigma = sum_{i>r} w_i*w_i;  norm = sqrt(w_r*w_r + sigma)
+ *               DEAD when norm <= 2^-40 * norm0_l: the column is skipped, makes no reflector and gets c_l = +0.0
+ *               else beta = -copysign(norm, w_r);  v_i = w_i / (w_r - beta) for i > r;  tau = (beta - w_r) / beta;  R_rr = beta;
+ *               the reflector is applied to every later column of Phi and to f0, and r becomes r + 1
+ *   apply     a reflector (v, tau) at position r to a column x:  s = x_r + sum_{i>r} v_i*x_i;  s = tau*s;  x_r = x_r - s;
+ *             x_i = x_i - s*v_i for i > r.  R_rk is x_r of column k after the reflector at position r
+ *   solve     z_j = -(Q^T f0)_j, the entry of f0 at column j's position.  j descending over the live columns:  s = z_j;  then
+ *             s = s - R_jk*c_k for the live k > j in ascending k;  c_j = s / R_jj.  rank = the live columns
+ *   fcn       p^ = (c, alpha); the inner fcn at p^ straight into the caller's dF: the residual the solver sees is, bit for
+ *             bit, the inner model's residual at the full parameters nlh_sep_solve_batch returns
+ *   jac       basis, QR and solve as above; the inner jac at p^; each of its n nonlinear columns d is projected,
+ *             d - Q1 Q1^T d, as: the live reflectors in order; the leading rank entries to +0.0; the live reflectors in
+ *             reverse order.  This is Kaufman's approximation; its J^T r is the exact gradient, because r is orthogonal to
+ *             span Phi.
+ * A point's bits do not depend on the launch shape, the slice, the batch or the workgroup form. ---- */
+#define NLH_SEP_MAX_L 32
+typedef struct nlh_sep nlh_sep;
+/* The object (host code, needs no GPU).  lin [nlin]: the full indices of the linear parameters, ascending.  Refused with
+ * NLH_INVALID_INPUT_ERROR, *sp left NULL: nlin < 1 or > NLH_SEP_MAX_L; no nonlinear parameter left (nfull - nlin < 1);
+ * nfull > NLH_PMAP_MAX_N; a NULL lin; an index out of range, repeated or not ascending. */
+int  nlh_sep_create(int32_t nfull, int32_t nlin, const int32_t *lin, nlh_sep **sp);
+void nlh_sep_destroy(nlh_sep *sp);
+void nlh_sep_shape(const nlh_sep *sp, int32_t *nfull, int32_t *nlin, int32_t *nnonlin);      /* any output may be NULL */
+/* Read-back, for restatements (either output may be NULL): lin [nlin], nonlin [nfull - nlin] = the full index of each
+ * nonlinear unknown. */
+int  nlh_sep_tables(const nlh_sep *sp, int32_t *lin, int32_t *nonlin);
+/* The wrapping launchers.  nlh_sep_wrap makes their context on the handle's device: a copy of the tables, scratch, the inner
+ * pair (fcn, jac, inner_ctx; all stay the caller's and must outlive the context).  The inner jac is REQUIRED -- its linear
+ * columns are the basis --: a NULL fcn or jac is NLH_UNDEFINED_FUNCTION_ERROR (after NLH_ERR_BAD_HANDLE for a NULL handle and
+ * NLH_INVALID_INPUT_ERROR for a NULL sp or out).  The outer Jacobian may still be left to forward differences: pass a NULL
+ * jacfcn to the solver.
+ *   nlh_sep_device_fcn  three inner calls (jac and fcn at p0, fcn at p^) and the QR-and-solve kernel
+ *   nlh_sep_device_jac  three inner calls (jac and fcn at p0, jac at p^), the QR-and-solve kernel and the projection kernel
+ * Both enqueue only on the stream handed in, never synchronise and may be called from several host threads on different
+ * streams.  A malformed context, n != N - L or m < N returns non-zero before any launch.  An inner error comes back as it is,
+ * with no further launch; by then only the context's own scratch has been written, nothing of the caller's.
+ * Scratch belongs to the context: one buffer per stream, grown on demand, reused, kept until nlh_sep_unwrap, at most 1 GiB
+ * per call and so per stream.  A call that needs more runs in slices of points -- the same bits.  NLH_SEP_SCRATCH = bytes
+ * (environment, read at each call; tests) lowers the cap.
+ * One workgroup of 256 threads works on a point, in one of two forms with the same bits: lds -- the panel [Phi | f0], and then
+ * the reflectors and the columns of D (32 per workgroup at most), live in LDS, while m (L + 1 + n) doubles fit a workgroup's
+ * LDS --, global -- the panel stays in the context's scratch and is re-read through the cache.  NLH_SEP_FORM = lds | global
+ * (environment, read at each call; tests) forces one where it fits (lds is what runs where it fits). */
+typedef struct nlh_sep_ctx nlh_sep_ctx;
+int  nlh_sep_wrap(nlh_handle *h, const nlh_sep *sp, nlh_device_vecfcn fcn, nlh_device_jacfcn jac, void *inner_ctx, nlh_sep_ctx **out);
+void nlh_sep_unwrap(nlh_sep_ctx *c);
+int  nlh_sep_device_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dF);
+int  nlh_sep_device_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dJ);
+/* The two steps around a solve made through the launchers by hand, on DEVICE arrays (the handle's stream):
+ *   gather   dfull [nprob][N] -> dx [nprob][n], the nonlinear values
+ *   solve    dalpha [nprob][n] -> dfull [nprob][N] = (c(alpha), alpha), drank [nprob] (may be NULL) = the live columns; basis,
+ *            QR and solve of the context's inner pair on problems 0 .. nprob-1 of m rows each (the context does not know m)
+ * There is no covariance step: the covariance of a separable fit is the existing chain on the INNER pair at the full
+ * solution, N x N with m - N degrees of freedom. */
+int  nlh_sep_gather_batch(nlh_handle *h, const nlh_sep *sp, int32_t nprob, const double *dfull, double *dx);
+int  nlh_sep_solve_batch(nlh_handle *h, nlh_sep_ctx *c, int32_t nprob, int32_t m, const double *dalpha, double *dfull, int32_t *drank);
+
+/* A device-function MODEL of the n = N - L nonlinear unknowns over a launcher-backed inner model (device-function, curve,
+ * formula, convolved; a dense-quadratic model: NLH_INVALID_INPUT_ERROR), which must outlive it; the model owns its projecting
+ * context.  The same contract as nlh_pmap_model_create: every nlh_dq_model_* solver then takes it (x [nprob][n]);
+ * nlh_dq_model_lm_covariance on it is the covariance of the PROJECTED problem -- for the errors of a separable fit call it on
+ * the inner model at the full solution.  Errors: NLH_ERR_BAD_HANDLE, then NLH_INVALID_INPUT_ERROR (a NULL argument, a
+ * dense-quadratic inner model, an sp whose N is not the inner model's n), NLH_UNDEFINED_FUNCTION_ERROR (an inner model
+ * created without its analytic Jacobian). */
+int  nlh_sep_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_sep *sp, nlh_dq_model **model);
+/* One-call separable fits: nlh_curve_fit_batch / nlh_expr_fit_batch plus, after xu, a group (may be NULL), an instrument response (may be NULL; its k a
+ * DEVICE pointer here, a HOST pointer in the _h forms) and the separable object (required).  They take no map, no loss and
+ * no statistic: both are nonlinear in c and do not belong inside the projection.  The composition: the convolving pair, if
+ * any, wraps the model's launchers first, the model bound without weights; the projecting pair wraps that; the group goes
+ * outside: it is declared over the model's N parameters, its shared ones must all be nonlinear, and the solve runs through the
+ * group of the same shared parameters over the n nonlinear ones (shared lifetimes, the amplitudes projected out per data set).
+ * With a group dx, dfvec and dsigma stay per data set and dcov, dchi2, drank, ib, status are per group, and the errors are
+ * what the _group entry point reports for the unprojected model at dx.
+ * What the caller sees is FULL, exactly as from the _conv entry point: dx [nprob][N] -- on entry the linear positions are
+ * ignored, on exit it is the full solution (c(alpha), alpha) of every problem that was solved (one that is refused on its
+ * degrees of freedom keeps its x) --, dfvec the inner residual at dx, and dsigma, dcov, dchi2, drank what
+ * nlh_lm_covariance_batch_device gives for the UNPROJECTED pair at dx: N x N, m - N degrees of freedom, the zero-weight rule
+ * with N.  m >= N (NLH_UNDERDEFINED_PROBLEM_ERROR otherwise), m > N for errors.  analytic chooses the outer Jacobian --
+ * Kaufman's projected one, or forward differences over the nonlinear unknowns -- and the Jacobian of the errors; the model's
+ * analytic Jacobian is used for the basis either way.  xl / xu [N] (host): entries at linear positions must be infinite (or
+ * the array NULL): a bound on a projected parameter cannot be honoured.  Errors, in this order: the _conv entry point's
+ * (without its refusal of a NULL cv); then NLH_INVALID_INPUT_ERROR for a NULL sp, an sp of another N, a shared linear
+ * parameter, a finite bound at a linear position. */
+int nlh_curve_fit_batch_sep(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                            int32_t m, const double *dt, int32_t shared_t, const double *dy, const double *dw, int32_t analytic,
+                            const double *xl, const double *xu, const nlh_group *g, const nlh_conv *cv, const nlh_sep *sp,
+                            double *dx, double *dfvec, double *dsigma, double *dcov, double *dchi2, int32_t *drank,
+                            nlh_iteration_behavior *ib, int32_t *status);
+int nlh_curve_fit_batch_sep_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob,
+                              int32_t m, const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic,
+                              const double *xl, const double *xu, const nlh_group *g, const nlh_conv *cv, const nlh_sep *sp,
+                              double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
+                              nlh_iteration_behavior *ib, int32_t *status);
+int nlh_expr_fit_batch_sep(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *dt,
+                           int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl,
+                           const double *xu, const nlh_group *g, const nlh_conv *cv, const nlh_sep *sp, double *dx, double *dfvec,
+                           double *dsigma, double *dcov, double *dchi2, int32_t *drank, nlh_iteration_behavior *ib,
+                           int32_t *status);
+int nlh_expr_fit_batch_sep_h(nlh_handle *h, const nlh_options *opts, const nlh_expr *e, int32_t nprob, int32_t m, const double *t,
+                             int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl,
+                             const double *xu, const nlh_group *g, const nlh_conv *cv, const nlh_sep *sp, double *x, double *fvec,
+                             double *sigma, double *cov, double *chi2, int32_t *rank, nlh_iteration_behavior *ib,
+                             int32_t *status);
+
 /* ---- per-kernel timing (HIP events on the handle's stream) ------------------ */
 #define NLH_K_DQ_RESIDUAL   0
 #define NLH_K_DQ_PANEL      1

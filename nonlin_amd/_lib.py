@@ -276,6 +276,33 @@ SYMBOLS = {
                                             c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p,
                                             c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_pmap_model_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, c_double_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "nlh_curve_fit_batch_sep": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_curve_fit_batch_sep_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p,
+                                            C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
+                                            C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_expr_fit_batch_sep": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior),
+                                         c_int32_p]),
+    "nlh_expr_fit_batch_sep_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p,
+                                           c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p,
+                                           c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior),
+                                           c_int32_p]),
+    "nlh_sep_model_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "nlh_sep_create": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, C.POINTER(C.c_void_p)]),
+    "nlh_sep_destroy": (None, [C.c_void_p]),
+    "nlh_sep_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p]),
+    "nlh_sep_tables": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p]),
+    "nlh_sep_wrap": (C.c_int, [_H, C.c_void_p, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "nlh_sep_unwrap": (None, [C.c_void_p]),
+    "nlh_sep_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_sep_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_sep_gather_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_sep_solve_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_loss_wrap": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
     "nlh_loss_unwrap": (None, [C.c_void_p]),
     "nlh_loss_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -614,6 +641,71 @@ class Group:
     def close(self):
         if getattr(self, "ptr", None) is not None and self.ptr.value:
             self.lib.nlh_group_destroy(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+SEP_MAX_L = 32
+
+
+class Separable:
+    """Which of a model's nparams parameters are linear (nlh_sep_create: host code, needs no GPU), for a separable fit:
+    variable projection solves for them exactly at every trial point, the solver iterates over the others.  linear: their
+    indices, in any order.  E.g. Separable(5, linear=(0, 2, 4)) for a1*exp(-k1*t) + a2*exp(-k2*t) + c.  The nonlinear unknowns
+    are the other parameters in ascending index.  "Linear" is a declaration: the model must be affine in those parameters at
+    fixed nonlinear ones (DeviceSolver.sep_check measures it).  Raises ValueError for what the library refuses (no or more than
+    32 linear parameters, none left nonlinear, an index out of range or repeated).  close() frees it (so does garbage
+    collection)."""
+
+    def __init__(self, nparams, linear=()):
+        import numpy as np
+        self.lib = load()
+        self.ptr = C.c_void_p()
+        idx = [int(k) for k in linear]
+        lin = np.ascontiguousarray(sorted(idx), dtype=np.int32)
+        rc = self.lib.nlh_sep_create(int(nparams), len(lin), lin.ctypes.data_as(c_int32_p), C.byref(self.ptr))
+        if rc:
+            self.ptr = C.c_void_p()
+            raise ValueError(f"Separable: the library refuses this declaration (nlh_sep_create returned {rc}): linear must hold "
+                             f"1 .. {SEP_MAX_L} distinct indices in 0 .. nparams - 1 and leave at least one parameter nonlinear")
+        s = [C.c_int32() for _ in range(3)]
+        self.lib.nlh_sep_shape(self.ptr, *[C.byref(v) for v in s])
+        self.nparams, self.nlin, self.nnonlin = (v.value for v in s)
+
+    @classmethod
+    def for_curve(cls, kind, ncomp=1, baseline=-1):
+        """The amplitudes and the baseline coefficients of a built-in curve model."""
+        k = curve_kind(kind)
+        n = curve_nparams(k, ncomp, baseline)
+        per = 2 if k == CURVE_EXPDECAY else 3
+        return cls(n, linear=[per * c for c in range(int(ncomp))] + list(range(per * int(ncomp), n)))
+
+    @classmethod
+    def for_expr(cls, expr, linear=()):
+        """The same by the parameter names of an Expr: Separable.for_expr(e, linear=("a", "c"))."""
+        names = [v.strip() for v in expr.params.split(",")]
+        for name in linear:
+            if name not in names:
+                raise ValueError(f"Separable: {name!r} is not a parameter of the formula ({', '.join(names)})")
+        return cls(len(names), linear=[names.index(k) for k in linear])
+
+    def tables(self):
+        """(linear, nonlinear): the full indices of the linear parameters and of the nonlinear unknowns (nlh_sep_tables)."""
+        import numpy as np
+        lin, nl = np.zeros(self.nlin, dtype=np.int32), np.zeros(self.nnonlin, dtype=np.int32)
+        rc = self.lib.nlh_sep_tables(self.ptr, lin.ctypes.data_as(c_int32_p), nl.ctypes.data_as(c_int32_p))
+        if rc:
+            raise RuntimeError(f"nlh_sep_tables returned {rc}")
+        return lin, nl
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.lib.nlh_sep_destroy(self.ptr)
             self.ptr = C.c_void_p()
 
     def __del__(self):

@@ -22,6 +22,7 @@ from ._lib import Group  # noqa: F401  (global fits)
 from ._lib import Loss, LOSS_LINEAR, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY, LOSS_KINDS  # noqa: F401  (robust losses)
 from ._lib import Poisson  # noqa: F401  (Poisson likelihood fits)
 from ._lib import Convolve, CONV_ZERO, CONV_HOLD  # noqa: F401  (instrument-response fits)
+from ._lib import Separable  # noqa: F401  (separable fits)
 
 # src/nonlin_error_handling.f90:10-38
 NL_NO_ERROR = 0

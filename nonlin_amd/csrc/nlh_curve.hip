@@ -236,3 +236,24 @@ int nlh_curve_fit_batch_conv_h(nlh_handle *h, const nlh_options *opts, int32_t k
     return curve_fit(h, opts, kind, ncomp, nbase, analytic, {nprob, m, t, shared_t, y, w, xl, xu, pm, loss, scale, shared_scale, x, fvec, sigma, cov, chi2, rank,
             ib, status, stat, mu_floor, g, cv ? cv : &none}, true);
 }
+
+// The separable fits: the convolving pair, if any, wraps the model's launchers, the projecting pair wraps that (nlh_fit.hip).
+int nlh_curve_fit_batch_sep(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m,
+                            const double *dt, int32_t shared_t, const double *dy, const double *dw, int32_t analytic, const double *xl,
+                            const double *xu, const nlh_group *g, const nlh_conv *cv, const nlh_sep *sp, double *dx, double *dfvec,
+                            double *dsigma, double *dcov, double *dchi2, int32_t *drank, nlh_iteration_behavior *ib, int32_t *status)
+{
+    return curve_fit(h, opts, kind, ncomp, nbase, analytic, {nprob, m, dt, shared_t, dy, dw, xl, xu, nullptr, NLH_LOSS_LINEAR, nullptr, 0, dx,
+                                                             dfvec, dsigma, dcov, dchi2, drank, ib, status, NLH_STAT_LSQ, 0.0, g, cv, true, sp,
+                                                             nlh_curve_device_jac}, false);
+}
+
+int nlh_curve_fit_batch_sep_h(nlh_handle *h, const nlh_options *opts, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t m,
+                              const double *t, int32_t shared_t, const double *y, const double *w, int32_t analytic, const double *xl,
+                              const double *xu, const nlh_group *g, const nlh_conv *cv, const nlh_sep *sp, double *x, double *fvec,
+                              double *sigma, double *cov, double *chi2, int32_t *rank, nlh_iteration_behavior *ib, int32_t *status)
+{
+    return curve_fit(h, opts, kind, ncomp, nbase, analytic, {nprob, m, t, shared_t, y, w, xl, xu, nullptr, NLH_LOSS_LINEAR, nullptr, 0, x, fvec,
+                                                             sigma, cov, chi2, rank, ib, status, NLH_STAT_LSQ, 0.0, g, cv, true, sp,
+                                                             nlh_curve_device_jac}, true);
+}

@@ -1,5 +1,5 @@
 // nlh_fit.hip -- the one-call fit + errors pipeline behind the entry points
-// nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois,_group,_conv}{,_h} (nlh_internal.h: nlh_fit_run).  A model kind hands it a
+// nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois,_group,_conv,_sep}{,_h} (nlh_internal.h: nlh_fit_run).  A model kind hands it a
 // FitSource -- its launchers, a context and how to point that context at a run of problems -- and the rest of the entry point's arguments as a FitArgs; here are the documented ladder of checks,
 // the staging of host arrays, the composition (the loss wraps the model's launchers, the parameter map, if any, wraps the
 // result), the solve and covariance of every run of consecutive problems that have degrees of freedom, and the rule of
@@ -27,6 +27,15 @@ struct FitRun {
     nlh_pmap_ctx *pc = nullptr;
     nlh_conv_ctx *cc = nullptr;        // an instrument response: innermost, around the model's launchers
     const double *fullc = nullptr;     // the map's private copy of the full parameters
+    // a separable fit: the solve runs over the nonlinear unknowns (of a group: the outer ones of the reduced group) through the
+    // projecting pair; after each run `full` turns the solved unknowns into the caller's full parameters and hands back where
+    // the unknowns of the errors lie; the errors and the degrees of freedom are those of the unprojected pair (ifcn, ijac, ictx)
+    // over its ne unknowns
+    std::function<int(int32_t p0, int32_t cnt, const double *solved, double **xerr)> full;
+    nlh_device_vecfcn ifcn = nullptr;
+    nlh_device_jacfcn ijac = nullptr;
+    void *ictx = nullptr;
+    int32_t ne = 0;
     int32_t G = 1;                     // a global fit: a problem of the solve is G of the model's, a->m its G m rows
     void bind(int32_t p0) const
     {
@@ -60,7 +69,8 @@ static int fit_solve(const FitRun &r, int32_t n, const double *xl, const double 
     const bool pois = a.stat == NLH_STAT_POISSON;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    const size_t np = (size_t)nprob, nn = (size_t)n * n;
+    const int32_t ne = r.full ? r.ne : n;                        // the unknowns of the errors and of the degrees of freedom
+    const size_t np = (size_t)nprob, nn = (size_t)ne * ne;
     // the handle's own buffer for this entry point: status and non-zero-weight counts, a cov when the caller wants none
     const size_t ints = 2 * np + 2;
     if ((rc = ensure(h, h->crv, sizeof(int32_t) * ints + sizeof(double) * (errors && !dcov ? np * nn : 0) + 64))) return rc;
@@ -73,7 +83,7 @@ static int fit_solve(const FitRun &r, int32_t n, const double *xl, const double 
         HIPCHK(h, hipMemcpyAsync(nz.data(), dnz, sizeof(int32_t) * np, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipStreamSynchronize(s));
         for (size_t p = 0; p < np; ++p)
-            if (nz[p] - n <= 0) st[p] = NLH_INVALID_INPUT_ERROR;
+            if (nz[p] - ne <= 0) st[p] = NLH_INVALID_INPUT_ERROR;
     }
     // runs of consecutive problems that have degrees of freedom (all of them, as a rule): exactly the calls a user makes
     for (int32_t p0 = 0; p0 < nprob;) {
@@ -87,22 +97,23 @@ static int fit_solve(const FitRun &r, int32_t n, const double *xl, const double 
         if (xl || xu) rc = nlh_cls_solve_batch_device(h, r.opts, 1.0, 1.0, xl, xu, cnt, m, n, r.fcn, r.jac, r.ctx, xs, fs, ibs, &st[p0]);
         else rc = nlh_lm_solve_batch_device(h, r.opts, cnt, m, n, r.fcn, r.jac, r.ctx, xs, fs, ibs, &st[p0]);
         if (rc) return rc;
+        if (r.full && (rc = r.full(p0, cnt, xs, &xs))) return rc;  // the full parameters of the solution, for the caller and the errors
         if (errors &&
-            (rc = nlh_lm_covariance_batch_device(h, cnt, m, n, r.fcn, r.jac, r.ctx, xs, pois ? 0 : 1, 0.0, cov + (size_t)p0 * nn,
-                                                 dsigma ? dsigma + (size_t)p0 * n : nullptr, drank ? drank + p0 : nullptr,
-                                                 dchi2 ? dchi2 + p0 : nullptr))) return rc;
+            (rc = nlh_lm_covariance_batch_device(h, cnt, m, ne, r.full ? r.ifcn : r.fcn, r.full ? r.ijac : r.jac, r.full ? r.ictx : r.ctx, xs,
+                                                 pois ? 0 : 1, 0.0, cov + (size_t)p0 * nn, dsigma ? dsigma + (size_t)p0 * ne : nullptr,
+                                                 drank ? drank + p0 : nullptr, dchi2 ? dchi2 + p0 : nullptr))) return rc;
         p0 = p1;
     }
     if (errors) {
         HIPCHK(h, hipMemcpyAsync(dstat, st.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_fit_post, dim3((nprob + 63) / 64), dim3(64), 0, s, nprob, m, n, (const int32_t *)dstat,
+        hipLaunchKernelGGL(k_fit_post, dim3((nprob + 63) / 64), dim3(64), 0, s, nprob, m, ne, (const int32_t *)dstat,
                            dw ? (const int32_t *)dnz : (const int32_t *)nullptr, (const double *)dfvec, cov, dsigma, dchi2, drank, pois ? 1 : 0);
         HIPCHK(h, hipStreamSynchronize(s));                      // (st is a host vector)
     }
     if (status) memcpy(status, st.data(), sizeof(int32_t) * np);
     if (ib)
         for (size_t p = 0; p < np; ++p)
-            if (st[p] == NLH_INVALID_INPUT_ERROR && nz.size() && nz[p] - n <= 0) ib[p] = nlh_iteration_behavior{};
+            if (st[p] == NLH_INVALID_INPUT_ERROR && nz.size() && nz[p] - ne <= 0) ib[p] = nlh_iteration_behavior{};
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -231,6 +242,105 @@ static int fit_grouped(FitRun r, int32_t n)
     return rc;
 }
 
+// ... of a separable model: fit_solve over the n = N - L nonlinear unknowns with the projecting launchers around r's pair,
+// whose Jacobian launcher is given whatever `analytic` says -- its linear columns are the basis --; analytic chooses the outer
+// Jacobian (the projected one, or forward differences over the nonlinear unknowns) and the Jacobian of the errors.  The
+// caller's arrays are the model's: x is gathered on entry and solved for on exit, problem by problem as they are solved (one
+// that is refused on its degrees of freedom keeps its x); sigma, cov, chi2 and rank are the inner pair's at the full solution.
+// With a group -- declared over the model's N parameters, its shared ones all nonlinear -- the group of the same shared
+// parameters over the n nonlinear ones wraps the projecting pair, and the errors are those of the caller's group around the
+// unprojected pair at the full solution: what the _group entry point reports there.
+static int fit_separated(FitRun r, bool analytic)
+{
+    nlh_handle *h = r.h;
+    const FitArgs &a = *r.a;
+    int32_t n;
+    nlh_sep_shape(a.sp, nullptr, nullptr, &n);
+    const int32_t N = r.N, m = a.m;
+    const size_t np = (size_t)a.nprob;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    std::vector<int32_t> nl(n);
+    nlh_sep_tables(a.sp, nullptr, nl.data());
+    int32_t G = 1, S = 0, no = n, nof = N;                        // a group: its sets, shared parameters, outer unknowns reduced and full
+    nlh_group *gred = nullptr;
+    if (a.grp) {
+        nlh_group_shape(a.grp, nullptr, &S, &G, &nof);
+        std::vector<int32_t> sh;
+        for (int32_t j = 0; j < n; ++j)
+            if (nlh_group_index(a.grp, 0, nl[j]) < S) sh.push_back(j);
+        if (const int rc = nlh_group_create(n, (int32_t)sh.size(), sh.data(), G, &gred)) return rc;
+        nlh_group_shape(gred, nullptr, nullptr, nullptr, &no);
+    }
+    const int32_t nsolve = a.nprob / G;
+    const size_t ns = (size_t)nsolve;
+    std::vector<double> lo, hi;                                   // the bounds of the nonlinear parameters at the unknowns of the solve
+    for (int32_t g = 0; g < G; ++g)
+        for (int32_t j = 0; j < n; ++j) {
+            const int32_t u = gred ? nlh_group_index(gred, g, j) : j;
+            if (a.xl) { lo.resize(no); lo[u] = a.xl[nl[j]]; }
+            if (a.xu) { hi.resize(no); hi[u] = a.xu[nl[j]]; }
+        }
+    // the handle's buffer: alpha [nprob][n], and of a group the unknowns of the solve, those of the errors, their sigma, the flags
+    const size_t doubles = np * n + (gred ? ns * no + ns * nof + (a.sigma ? ns * nof : 0) : 0);
+    int rc = ensure(h, h->sepx, sizeof(double) * doubles + sizeof(int32_t) * ns + 64);
+    if (rc) { nlh_group_destroy(gred); return rc; }
+    double *alpha = (double *)h->sepx.p, *xo = alpha + np * n, *xof = xo + (gred ? ns * no : 0), *so = xof + (gred ? ns * nof : 0);
+    int32_t *dfail = (int32_t *)(alpha + doubles);
+    nlh_sep_ctx *sc = nullptr;
+    nlh_group_ctx *gc = nullptr, *gcf = nullptr;                  // the reduced group around the projecting pair; the caller's around r's
+    FitArgs ga = a;                                               // what the solve sees: nsolve problems of G m rows
+    ga.nprob = nsolve; ga.m = G * m;
+    std::vector<int32_t> st(ns, 0);
+    const nlh_device_vecfcn fcn = r.fcn;
+    const nlh_device_jacfcn jac = r.jac;
+    void *const ctx = r.ctx;
+    rc = nlh_sep_wrap(h, a.sp, fcn, jac, ctx, &sc);
+    if (!rc) rc = nlh_sep_gather_batch(h, a.sp, a.nprob, a.x, alpha);
+    if (!rc && gred) rc = nlh_group_wrap(h, gred, nlh_sep_device_fcn, analytic ? nlh_sep_device_jac : nullptr, sc, &gc);
+    if (!rc && gred) rc = nlh_group_wrap(h, a.grp, fcn, analytic ? jac : nullptr, ctx, &gcf);
+    if (!rc && gred) rc = nlh_group_gather_batch(h, gred, nsolve, alpha, xo);
+    if (!rc) {
+        r.ifcn = gred ? nlh_group_device_fcn : fcn;
+        r.ijac = !analytic ? nullptr : gred ? nlh_group_device_jac : jac;
+        r.ictx = gred ? (void *)gcf : ctx;
+        r.ne = nof;
+        r.fcn = gred ? nlh_group_device_fcn : nlh_sep_device_fcn;
+        r.jac = !analytic ? nullptr : gred ? nlh_group_device_jac : nlh_sep_device_jac;
+        r.ctx = gred ? (void *)gc : (void *)sc;
+        r.a = &ga; r.G = G;
+        r.full = [&](int32_t p0, int32_t cnt, const double *solved, double **xerr) -> int {
+            double *al = alpha + (size_t)p0 * G * n, *xf = a.x + (size_t)p0 * G * N;
+            int e = 0;
+            if (gred && (e = nlh_group_expand_batch(h, gred, cnt, solved, al))) return e;
+            if ((e = nlh_sep_solve_batch(h, sc, cnt * G, m, gred ? al : solved, xf, nullptr))) return e;
+            *xerr = xf;
+            if (!gred) return 0;
+            *xerr = xof + (size_t)p0 * nof;
+            return nlh_group_gather_batch(h, a.grp, cnt, xf, *xerr);
+        };
+        rc = fit_solve(r, no, a.xl ? lo.data() : nullptr, a.xu ? hi.data() : nullptr, gred ? xo : alpha, gred ? (a.sigma ? so : nullptr) : a.sigma,
+                       a.cov, st.data());
+    }
+    hipError_t e = hipSuccess;
+    if (!rc && gred && a.sigma) {                                 // sigma per data set, NaN for a group that did not solve
+        e = hipMemcpyAsync(dfail, st.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) rc = nlh_group_sigma_batch(h, a.grp, nsolve, so, dfail, a.sigma);
+    }
+    const hipError_t e2 = hipStreamSynchronize(s);                // (st is a host vector; the contexts' scratch goes)
+    nlh_group_unwrap(gc);
+    nlh_group_unwrap(gcf);
+    nlh_sep_unwrap(sc);
+    nlh_group_destroy(gred);
+    if (e == hipSuccess) e = e2;
+    if (!rc && e != hipSuccess) {
+        h->err = std::string("separable fit: ") + hipGetErrorString(e);
+        return NLH_ERR_HIP;
+    }
+    if (!rc && a.status) memcpy(a.status, st.data(), sizeof(int32_t) * ns);
+    return rc;
+}
+
 // The composition on device pointers: the loss wraps r's launchers -- the model's, or the convolved model's -- (NLH_LOSS_LINEAR:
 // no context, no kernel of the loss) -- in a Poisson fit the Poisson wrapper does, in the same place --, the map or the group,
 // if any, wraps the result.  n: the unknowns of the solve.
@@ -239,7 +349,10 @@ static int fit_composed(nlh_handle *h, FitRun &r, const FitArgs &a, int32_t n)
     const nlh_device_vecfcn fcn = r.fcn;
     const nlh_device_jacfcn jac = r.jac;
     void *const ctx = r.ctx;
-    auto run = [&]() { return a.grp ? fit_grouped(r, n) : a.pm ? fit_mapped(r, n) : fit_solve(r, n, a.xl, a.xu, a.x, a.sigma, a.cov, a.status); };
+    auto run = [&]() {
+        return a.sp ? fit_separated(r, r.src->jac != nullptr) : a.grp ? fit_grouped(r, n) : a.pm ? fit_mapped(r, n)
+                                                                          : fit_solve(r, n, a.xl, a.xu, a.x, a.sigma, a.cov, a.status);
+    };
     if (a.stat == NLH_STAT_POISSON) {
         int rc = nlh_pois_wrap(h, a.y, a.w, a.mu_floor, fcn, jac, ctx, &r.qc);
         if (rc) return rc;
@@ -271,11 +384,13 @@ static int fit_composed(nlh_handle *h, FitRun &r, const FitArgs &a, int32_t n)
 // without weights; w is the convolving pair's, unless a Poisson pair follows, which keeps it as its mask.
 static int fit_device(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, int32_t n)
 {
-    FitRun r{h, opts, &src, &a, src.N, src.fcn, src.jac, src.ctx};
+    // (a separable fit needs the model's Jacobian launcher whatever `analytic` says: a.sp_jac; src.jac keeps saying which)
+    const nlh_device_jacfcn mjac = a.sp ? a.sp_jac : src.jac;
+    FitRun r{h, opts, &src, &a, src.N, src.fcn, mjac, src.ctx};
     if (!a.cv) return fit_composed(h, r, a, n);
-    int rc = nlh_conv_wrap(h, a.cv, a.y, a.stat == NLH_STAT_POISSON ? nullptr : a.w, src.fcn, src.jac, src.ctx, &r.cc);
+    int rc = nlh_conv_wrap(h, a.cv, a.y, a.stat == NLH_STAT_POISSON ? nullptr : a.w, src.fcn, mjac, src.ctx, &r.cc);
     if (rc) return rc;
-    r.fcn = nlh_conv_device_fcn; r.jac = src.jac ? nlh_conv_device_jac : nullptr; r.ctx = r.cc;
+    r.fcn = nlh_conv_device_fcn; r.jac = mjac ? nlh_conv_device_jac : nullptr; r.ctx = r.cc;
     rc = fit_composed(h, r, a, n);
     const hipError_t e = hipStreamSynchronize(h->stream);         // (the context's scratch goes)
     nlh_conv_unwrap(r.cc);
@@ -376,9 +491,23 @@ int nlh_fit_run(nlh_handle *h, const nlh_options *opts, const FitSource &src, co
     if ((a.sigma || a.cov || a.chi2) && M <= n) return NLH_INVALID_INPUT_ERROR;     // no degree of freedom for errors
     if (a.stat == NLH_STAT_POISSON && !nlh_pois_floor_ok(a.mu_floor)) return NLH_INVALID_INPUT_ERROR;
     if (a.cv && !nlh_conv_ok(a.cv)) return NLH_INVALID_INPUT_ERROR;
+    if (host && a.cv && !nlh_conv_data_ok(a.cv, a.y, (size_t)a.nprob, (size_t)a.m)) return NLH_INVALID_INPUT_ERROR;
+    if (host && a.stat == NLH_STAT_POISSON && !nlh_pois_data_ok(a.y, a.w, (size_t)a.nprob * a.m)) return NLH_INVALID_INPUT_ERROR;
+    if (a.want_sp) {            // a separable fit, after every check of the _conv entry point: the object, its N, no shared or bounded projected parameter
+        int32_t nfull, L, S = 0;
+        if (!a.sp || !a.sp_jac) return NLH_INVALID_INPUT_ERROR;
+        nlh_sep_shape(a.sp, &nfull, &L, nullptr);
+        if (nfull != src.N) return NLH_INVALID_INPUT_ERROR;
+        if (a.pm || a.loss != NLH_LOSS_LINEAR || a.stat != NLH_STAT_LSQ) return NLH_INVALID_INPUT_ERROR;
+        std::vector<int32_t> lin(L);
+        nlh_sep_tables(a.sp, lin.data(), nullptr);
+        if (a.grp) nlh_group_shape(a.grp, nullptr, &S, nullptr, nullptr);
+        for (int32_t k : lin)
+            if (a.grp && nlh_group_index(a.grp, 0, k) < S) return NLH_INVALID_INPUT_ERROR;     // a shared linear parameter
+        for (int32_t k : lin)
+            if ((a.xl && std::isfinite(a.xl[k])) || (a.xu && std::isfinite(a.xu[k]))) return NLH_INVALID_INPUT_ERROR;
+    }
     if (!host) return fit_device(h, opts, src, a, n);
-    if (a.cv && !nlh_conv_data_ok(a.cv, a.y, (size_t)a.nprob, (size_t)a.m)) return NLH_INVALID_INPUT_ERROR;
-    if (a.stat == NLH_STAT_POISSON && !nlh_pois_data_ok(a.y, a.w, (size_t)a.nprob * a.m)) return NLH_INVALID_INPUT_ERROR;
     double *dscale = nullptr;                                     // checks the host scales: finite, positive (LINEAR: none, NULL)
     int rc = nlh_loss_scale_upload(h, a.loss, a.scale, a.shared_scale ? 1 : (size_t)a.nprob, &dscale);
     if (rc) return rc;

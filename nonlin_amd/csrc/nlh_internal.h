@@ -20,6 +20,7 @@
 //   nlh_pois.hip       Poisson likelihood fits: the wrapping launchers, apply, the check of host counts and masks
 //   nlh_conv.hip       instrument-response fits: the wrapping launchers, apply, the check of a transform
 //   nlh_group.hip      global fits: the group object, the wrapping launchers, gather / expand / sigma
+//   nlh_sep.hip        separable fits: the object, the wrapping launchers (variable projection), gather / solve
 //   nlh_model.hip      device sets, device residual models behind host arrays
 //   nlh_qrx.hip        the exact lmfactor
 // Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it launches.  nlh_launch.h:
@@ -74,7 +75,8 @@ struct nlh_handle {
            qnQ, qnR, qnV, bfB, bfR, bfV, qxV, lumv, lus,
            dvX, dvF, dvIdx, dvP,          // user device residuals: points, compact residuals, problem lists, panel chunk (nlh_devfcn.hip)
            cvW, cvT, cvH,                 // covariance (nlh_covar.hip): the chain's arrays, the global-memory window, host-array staging
-           crv;                           // one-call fits (nlh_fit.hip): status, non-zero-weight counts, a covariance nobody asked to keep
+           crv,                           // one-call fits (nlh_fit.hip): status, non-zero-weight counts, a covariance nobody asked to keep
+           sepx;                          // one-call separable fits (nlh_fit.hip): the nonlinear unknowns and, of a group, the outer ones
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     DevBuf cholmc;                     // side buffer of the multi-CU Cholesky (solved panels, bad-pivot flags)
@@ -317,6 +319,7 @@ void nlh_polyroots_init_device(int lds_max);    // nlh_polyroots.hip (polynomial
 void nlh_covar_init_device(int lds_max);        // nlh_covar.hip (covar, nlh_lm_covariance*)
 void nlh_devfcn_init_device(int lds_max);        // nlh_devfcn.hip: the built-in family's launcher kernels keep x in LDS
 void nlh_expr_init_device(int lds_max);          // nlh_expr.hip: the formula interpreter keeps its stacks in LDS
+void nlh_sep_init_device(int lds_max);           // nlh_sep.hip: the separable fits' kernels keep a point's panel in LDS
 
 // A compiled formula (nlh_expr.hip; include/nonlin_hip.h: nlh_expr_*).  ExprProg is what the kernels read, passed by value in
 // the kernel arguments: code[i] = op | (arg & 0xff) << 8 | aroot << 16, aroot the instruction that produced the operand a
@@ -333,7 +336,7 @@ struct nlh_expr {
     int32_t nconst;
 };
 
-// The one-call fit + errors of the twenty-four entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois,_group,_conv}{,_h} (nlh_fit.hip).
+// The one-call fit + errors of the twenty-eight entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois,_group,_conv,_sep}{,_h} (nlh_fit.hip).
 // FitSource: what a model kind hands the pipeline.  bind points the context's data at problem p0 of dt, dy, dw (the whole
 // batch's device arrays) before each run of consecutive problems; whatever else the context holds stays the whole batch's.
 struct FitSource {
@@ -367,6 +370,11 @@ struct FitArgs {
     double mu_floor = 0.0;
     const nlh_group *grp = nullptr;    // a global fit: nprob data sets in groups; cov, chi2, rank, ib, status per group
     const nlh_conv *cv = nullptr;      // an instrument response: the model is convolved with it (k: as the other arrays, device or host)
+    // a separable fit (the _sep entry points set want_sp; sp itself may then not be NULL): the linear parameters are projected
+    // out; sp_jac: the model's Jacobian launcher, needed whatever `analytic` says (the source's jac follows analytic)
+    bool want_sp = false;
+    const nlh_sep *sp = nullptr;
+    nlh_device_jacfcn sp_jac = nullptr;
 };
 // The documented ladder of checks, then: solve (bounded when xl or xu is given), covariance with scaled = 1 when any of sigma,
 // cov, chi2 is asked for, the degrees-of-freedom rule of zero weights, NaN and rank -1 for problems that did not solve.  The

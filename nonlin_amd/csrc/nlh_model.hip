@@ -103,6 +103,8 @@ struct nlh_dq_model {
     nlh_conv_ctx *conv = nullptr;
     // a global model (nlh_group_model_create): the wrapping context around another model's launchers; nothing else
     nlh_group_ctx *group = nullptr;
+    // a separable model (nlh_sep_model_create): the projecting context around another model's launchers; nothing else
+    nlh_sep_ctx *sep = nullptr;
 };
 
 // Host arrays, one after the other, into one device allocation on the handle's device; synchronised (nlh_internal.h).
@@ -381,9 +383,31 @@ int nlh_group_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_g
     return 0;
 }
 
+// A model of the nonlinear unknowns of a separable object over a launcher-backed inner model that has a Jacobian launcher
+// (nlh_sep.hip: the projecting launchers).
+int nlh_sep_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_sep *sp, nlh_dq_model **out)
+{
+    if (out) *out = nullptr;
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (!out || !inner || !sp || !inner->ufcn) return NLH_INVALID_INPUT_ERROR;
+    int32_t N, n;
+    nlh_sep_shape(sp, &N, nullptr, &n);
+    if (N != inner->n) return NLH_INVALID_INPUT_ERROR;
+    nlh_sep_ctx *sc = nullptr;
+    const int rc = nlh_sep_wrap(h, sp, inner->ufcn, inner->ujac, inner->uctx, &sc);
+    if (rc) return rc;
+    nlh_dq_model *md = new nlh_dq_model();
+    md->nprob = inner->nprob; md->m = inner->m; md->n = n; md->gamma = 0.0;
+    md->ufcn = nlh_sep_device_fcn; md->ujac = nlh_sep_device_jac; md->uctx = sc;
+    md->sep = sc;
+    *out = md;
+    return 0;
+}
+
 void nlh_dq_model_destroy(nlh_dq_model *md)
 {
     if (!md) return;
+    nlh_sep_unwrap(md->sep);
     nlh_group_unwrap(md->group);
     nlh_pmap_unwrap(md->pmap);
     nlh_loss_unwrap(md->loss);

@@ -122,6 +122,15 @@ class _GroupCtx(_PmapCtx):
             self.ptr = C.c_void_p()
 
 
+class _SepCtx(_PmapCtx):
+    """The context of a separable fit's wrapping launchers (nlh_sep_ctx), with everything it points at kept alive."""
+
+    def close(self):
+        if getattr(self, "ptr", None) is not None and self.ptr.value:
+            self.lib.nlh_sep_unwrap(self.ptr)
+            self.ptr = C.c_void_p()
+
+
 class DeviceSolver:
     """Owns an nlh handle bound to torch's current stream on `device`."""
 
@@ -340,7 +349,7 @@ class DeviceSolver:
                 None if hi is None else hi.ctypes.data_as(_lib.c_double_p))
 
     def curve_fit_batch(self, kind, t, y, x0, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
-                        covariance=True, opts=None, pmap=None, loss=None, stat=None, group=None, conv=None):
+                        covariance=True, opts=None, pmap=None, loss=None, stat=None, group=None, conv=None, sep=None):
         """Fit + errors of y.shape[0] curves in one call (nlh_curve_fit_batch): least_squares_solver%solve -- or, with lower /
         upper ([n], one box for every problem), constrained_least_squares_solver%solve -- from x0 [nprob, n] (not modified),
         then the scaled parameter covariance at the solution.  Rows with weight 0 pad ragged data: they do not count as
@@ -363,13 +372,24 @@ class DeviceSolver:
         conv (a Convolve): the model is convolved with an instrument response before it is compared with y
         (nlh_curve_fit_batch_conv), with or without pmap, loss, stat or group: t must be a uniform grid and y finite on every
         row, padded ones included.  fvec is the residual of the convolved model; conv_apply on curve_eval's values gives the
-        convolved model itself.  None calls exactly what is called without it."""
+        convolved model itself.  None calls exactly what is called without it.
+        sep (a Separable, e.g. Separable.for_curve(kind, ncomp, baseline)): a separable fit (nlh_curve_fit_batch_sep), with or
+        without conv: the linear parameters are solved for exactly at every trial point (variable projection) and the solver
+        iterates over the others, so x0 needs no values at the linear positions.  Everything that comes back is full -- x the
+        solution with its linear parameters, fvec the model's residual there, sigma / cov / chi2 / rank those of the full
+        model at x.  Bounds at linear positions must be infinite.  With group the shared parameters must all be nonlinear
+        (shared lifetimes, amplitudes projected out per data set) and cov, chi2, rank, ibs, status are per group, as from
+        group= alone.  sep together with pmap, loss or stat raises ValueError: those are nonlinear in the projected parameters."""
         if stat is not None and loss is not None:
             raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
         k = curve_kind(kind)
         nprob, m, shared = self._curve_data(t, y, weights)
         n = curve_nparams(k, ncomp, baseline)
         _chk(x0, (nprob, n), "x0")
+        if sep is not None:
+            call = lambda *rest: self.lib.nlh_curve_fit_batch_sep(self.h.ptr, rest[0], k, int(ncomp), int(baseline), *rest[1:])
+            return self._sep_fit("nlh_curve_fit_batch_sep", call, sep, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights,
+                                 x0, lower, upper, analytic, covariance, opts)
         if conv is not None:
             call = lambda *rest: self.lib.nlh_curve_fit_batch_conv(self.h.ptr, rest[0], k, int(ncomp), int(baseline), *rest[1:])
             return self._conv_fit("nlh_curve_fit_batch_conv", call, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
@@ -463,7 +483,7 @@ class DeviceSolver:
         return y
 
     def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None,
-                       pmap=None, loss=None, stat=None, group=None, conv=None):
+                       pmap=None, loss=None, stat=None, group=None, conv=None, sep=None):
         """Fit + errors of y.shape[0] data sets to a formula in one call (nlh_expr_fit_batch): curve_fit_batch with an Expr in
         the place of (kind, ncomp, baseline), pmap (e.g. ParamMap.for_expr(expr, ...)), loss (a Loss), stat (a Poisson) and
         group (e.g. Group.for_expr(expr, shared=("k",), nsets=8): nlh_expr_fit_batch_group) included.  Returns (x, fvec, sigma,
@@ -473,6 +493,10 @@ class DeviceSolver:
         nprob, m, shared = self._expr_data(expr, t, y, weights)
         n = expr.nparams
         _chk(x0, (nprob, n), "x0")
+        if sep is not None:                                           # (a Separable, e.g. Separable.for_expr(expr, linear=("a", "c")): as in curve_fit_batch)
+            call = lambda *rest: self.lib.nlh_expr_fit_batch_sep(self.h.ptr, rest[0], expr.ptr, *rest[1:])
+            return self._sep_fit("nlh_expr_fit_batch_sep", call, sep, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights,
+                                 x0, lower, upper, analytic, covariance, opts)
         if conv is not None:                                          # (a Convolve: as in curve_fit_batch)
             call = lambda *rest: self.lib.nlh_expr_fit_batch_conv(self.h.ptr, rest[0], expr.ptr, *rest[1:])
             return self._conv_fit("nlh_expr_fit_batch_conv", call, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
@@ -687,6 +711,33 @@ class DeviceSolver:
             raise RuntimeError(f"{name} returned {rc}")
         return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nsolve)], [int(status[p]) for p in range(nsolve)])
 
+    def _sep_fit(self, name, call, sep, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0, lower, upper, analytic,
+                 covariance, opts):
+        """The one-call separable fit behind curve_fit_batch / expr_fit_batch with sep=; call(opts, nprob, m, ...) is the entry
+        point with the model's own arguments bound."""
+        if pmap is not None or loss is not None or stat is not None:
+            raise ValueError("sep excludes pmap, loss and stat: a map, a loss and a statistic are nonlinear in the projected parameters")
+        if sep.nparams != n:
+            raise ValueError(f"sep is over {sep.nparams} parameters, the model has {n}")
+        if group is not None and group.nparams != n:
+            raise ValueError(f"group is over {group.nparams} parameters, the model has {n}")
+        if group is not None and nprob % group.nsets:
+            raise ValueError(f"{nprob} data sets: no multiple of the group's {group.nsets}")
+        nsolve, nunk = (nprob // group.nsets, group.nouter) if group is not None else (nprob, n)
+        dev = y.device
+        x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, nsolve, nunk)
+        lo, hi, plo, phi = self._fit_bounds(lower, upper, n)
+        o = opts or self.options()
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        cv, dk = self._conv_struct(conv, nprob, dev) if conv is not None else (None, None)
+        rc = call(C.byref(o), nprob, m, t.data_ptr(), shared, y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
+                  group.ptr if group is not None else None, C.cast(C.byref(cv), C.c_void_p) if cv is not None else None, sep.ptr, x.data_ptr(), fvec.data_ptr(), ptr(sigma),
+                  ptr(cov), ptr(chi2), ptr(rank), ib, status)
+        self.h.check(rc, name)
+        if rc:
+            raise RuntimeError(f"{name} returned {rc}")
+        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nsolve)], [int(status[p]) for p in range(nsolve)])
+
     # -- robust losses -------------------------------------------------------------
     def _loss_scale(self, loss, nprob, dev=None):
         """(device tensor of the scales of a Loss for nprob problems, shared flag)."""
@@ -810,6 +861,63 @@ class DeviceSolver:
             raise RuntimeError(f"nlh_conv_apply_batch returned {rc}")
         torch.cuda.current_stream(v.device).synchronize()             # (dk goes with this frame)
         return out
+
+    # -- separable fits (variable projection) --------------------------------------
+    def sep_launchers(self, sep, fcn, jac, ctx):
+        """Wraps any inner launcher pair (fcn, jac, ctx) -- curve_launchers, expr_launchers, conv_launchers or a user's own,
+        over sep.nparams parameters -- in the projecting launchers (nlh_sep_wrap) and returns (fcn, jac, ctx) for
+        lm_solve_batch_device, cls_solve_batch_device, fd_jacobian_device and group_launchers over the sep.nnonlin nonlinear
+        unknowns; the linear parameters are solved for at every point.  The inner jac is required (its linear columns are the
+        basis); pass jac=None to the solver for a forward-difference outer Jacobian.  Keep the returned ctx alive while
+        solving; ctx.close() frees its scratch."""
+        if jac is None:
+            raise ValueError("sep_launchers: the inner Jacobian launcher is required (its linear columns are the basis)")
+        out = C.c_void_p()
+        rc = self.lib.nlh_sep_wrap(self.h.ptr, sep.ptr, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), C.byref(out))
+        self.h.check(rc, "nlh_sep_wrap")
+        if rc:
+            raise RuntimeError(f"nlh_sep_wrap returned {rc}")
+        wrapped = _SepCtx(self.lib, out, (sep, fcn, jac, ctx))
+        return (C.cast(self.lib.nlh_sep_device_fcn, _lib.DEVFCN), C.cast(self.lib.nlh_sep_device_jac, _lib.DEVFCN), wrapped)
+
+    def sep_gather(self, sep, full):
+        """The nonlinear unknowns alpha [nprob, nnonlin] of full parameters [nprob, nparams] (nlh_sep_gather_batch)."""
+        nprob = full.shape[0]
+        _chk(full, (nprob, sep.nparams), "full")
+        x = torch.empty((nprob, sep.nnonlin), dtype=torch.float64, device=full.device)
+        rc = self.lib.nlh_sep_gather_batch(self.h.ptr, sep.ptr, nprob, full.data_ptr(), x.data_ptr())
+        self.h.check(rc, "nlh_sep_gather_batch")
+        if rc:
+            raise RuntimeError(f"nlh_sep_gather_batch returned {rc}")
+        return x
+
+    def sep_solve(self, sep_ctx, m, alpha):
+        """(full, rank): the full parameters (c(alpha), alpha) [nprob, nparams] of the nonlinear unknowns alpha [nprob, nnonlin]
+        of problems 0 .. nprob-1 of m rows, and the live columns of each basis (nlh_sep_solve_batch).  sep_ctx: the context
+        sep_launchers returned."""
+        sep = sep_ctx._keep[0]
+        nprob = alpha.shape[0]
+        _chk(alpha, (nprob, sep.nnonlin), "alpha")
+        full = torch.empty((nprob, sep.nparams), dtype=torch.float64, device=alpha.device)
+        rank = torch.empty((nprob,), dtype=torch.int32, device=alpha.device)
+        rc = self.lib.nlh_sep_solve_batch(self.h.ptr, sep_ctx.ptr, nprob, int(m), alpha.data_ptr(), full.data_ptr(), rank.data_ptr())
+        self.h.check(rc, "nlh_sep_solve_batch")
+        if rc:
+            raise RuntimeError(f"nlh_sep_solve_batch returned {rc}")
+        return full, rank
+
+    def sep_check(self, sep, fcn, jac, ctx, m, full):
+        """How far the inner model is from affine in the parameters sep declares linear, at the full parameters
+        full [nprob, nparams]: the inner Jacobian is evaluated there and with every linear parameter c replaced by 2 c + 1;
+        returns the largest difference of a linear column between the two, relative to the largest entry of the linear
+        columns.  0.0: the declaration holds at these points."""
+        lin = torch.from_numpy(sep.tables()[0].astype("int64")).to(full.device)
+        other = full.clone()
+        other[:, lin] = 2.0 * full[:, lin] + 1.0
+        J1 = self.fd_jacobian_device(fcn, ctx, m, full, jac=jac)[:, lin]
+        J2 = self.fd_jacobian_device(fcn, ctx, m, other, jac=jac)[:, lin]
+        scale = float(torch.max(torch.abs(J1)))
+        return float(torch.max(torch.abs(J1 - J2))) / scale if scale > 0.0 else float(torch.max(torch.abs(J2)))
 
     def _ctxp(self, ctx):
         if isinstance(ctx, _PmapCtx):

@@ -260,6 +260,49 @@ module nonlin_hip_c
             type(c_ptr), intent(out) :: model
             integer(c_int) :: rc
         end function
+        ! separable fits (include/nonlin_hip.h: nlh_sep_*): the object, a model of the nonlinear unknowns over a launcher-backed
+        ! model, and the one-call fits behind host arrays (every array argument a C address: c_loc, or c_null_ptr where the
+        ! header allows NULL)
+        function nlh_sep_create(nfull, nlin, lin, sp) bind(C, name="nlh_sep_create") result(rc)
+            import :: c_ptr, c_int, c_int32_t
+            integer(c_int32_t), value :: nfull, nlin
+            integer(c_int32_t), intent(in) :: lin(*)
+            type(c_ptr), intent(out) :: sp
+            integer(c_int) :: rc
+        end function
+        subroutine nlh_sep_destroy(sp) bind(C, name="nlh_sep_destroy")
+            import :: c_ptr
+            type(c_ptr), value :: sp
+        end subroutine
+        subroutine nlh_sep_shape(sp, nfull, nlin, nnonlin) bind(C, name="nlh_sep_shape")
+            import :: c_ptr, c_int32_t
+            type(c_ptr), value :: sp
+            integer(c_int32_t), intent(out) :: nfull, nlin, nnonlin
+        end subroutine
+        function nlh_sep_model_create(h, inner, sp, model) bind(C, name="nlh_sep_model_create") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: h, inner, sp
+            type(c_ptr), intent(out) :: model
+            integer(c_int) :: rc
+        end function
+        function nlh_curve_fit_batch_sep_h(h, opts, kind, ncomp, nbase, nprob, m, t, shared_t, y, w, analytic, xl, xu, g, cv, sp, x, fvec, &
+                sigma, cov, chi2, rank, ib, status) bind(C, name="nlh_curve_fit_batch_sep_h") result(rc)
+            import :: c_ptr, c_int, c_int32_t, nlh_options
+            type(c_ptr), value :: h
+            type(nlh_options), intent(in) :: opts
+            integer(c_int32_t), value :: kind, ncomp, nbase, nprob, m, shared_t, analytic
+            type(c_ptr), value :: t, y, w, xl, xu, g, cv, sp, x, fvec, sigma, cov, chi2, rank, ib, status
+            integer(c_int) :: rc
+        end function
+        function nlh_expr_fit_batch_sep_h(h, opts, e, nprob, m, t, shared_t, y, w, analytic, xl, xu, g, cv, sp, x, fvec, sigma, cov, chi2, &
+                rank, ib, status) bind(C, name="nlh_expr_fit_batch_sep_h") result(rc)
+            import :: c_ptr, c_int, c_int32_t, nlh_options
+            type(c_ptr), value :: h, e
+            type(nlh_options), intent(in) :: opts
+            integer(c_int32_t), value :: nprob, m, shared_t, analytic
+            type(c_ptr), value :: t, y, w, xl, xu, g, cv, sp, x, fvec, sigma, cov, chi2, rank, ib, status
+            integer(c_int) :: rc
+        end function
         ! robust losses (include/nonlin_hip.h: nlh_loss_*): a model with a loss over a launcher-backed model
         function nlh_loss_model_create(h, inner, kind, scale, shared_scale, model) bind(C, name="nlh_loss_model_create") result(rc)
             import :: c_ptr, c_int, c_int32_t, c_double

@@ -63,6 +63,7 @@ module nonlin_multi_eqn_mult_var
         procedure, public :: create_expr => dmb_create_expr
         procedure, public :: create_mapped => dmb_create_mapped
         procedure, public :: create_global => dmb_create_global
+        procedure, public :: create_separable => dmb_create_separable
         procedure, public :: create_robust => dmb_create_robust
         procedure, public :: create_poisson => dmb_create_poisson
         procedure, public :: create_convolved => dmb_create_convolved
@@ -493,6 +494,48 @@ contains
         this%nvar_ = nouter
         this%nprob_ = inner%nprob_ / nsets
         this%analytic_ = inner%analytic_
+    end subroutine
+
+    !> A separable fit over a launcher-backed model that has its analytic Jacobian (create_curve, create_expr, create_convolved,
+    !> create_from_device_fcn with a Jacobian launcher): a model of the NONLINEAR unknowns of inner, which must outlive it.
+    !> linear(:): the 1-based parameters of inner the model is linear in (distinct, in any order; 1 .. 32 of them, at least one
+    !> parameter left); they are solved for exactly at every trial point (variable projection, INTEGRATION.md 6n) and the
+    !> solvers iterate over the others, in ascending index: solve_batch and evaluate take x(N - size(linear), nprob).  A
+    !> declaration the library refuses stops the program with NL_INVALID_INPUT_ERROR.
+    subroutine dmb_create_separable(this, inner, linear)
+        class(device_model_batch), intent(inout) :: this
+        class(device_model_batch), intent(in) :: inner
+        integer(int32), intent(in), dimension(:) :: linear
+        integer(c_int) :: rc
+        integer(c_int32_t) :: nfull, nlin, nnl, v
+        integer(c_int32_t), allocatable :: lc(:)
+        integer :: i, j
+        type(c_ptr) :: sp
+        if (.not.inner%is_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR
+        if (size(linear) < 1) error stop NL_INVALID_INPUT_ERROR
+        allocate(lc(size(linear)))
+        lc = linear - 1
+        do i = 2, size(lc)                                   ! ascending, as the library wants them
+            v = lc(i)
+            j = i - 1
+            do while (j >= 1)
+                if (lc(j) <= v) exit
+                lc(j + 1) = lc(j)
+                j = j - 1
+            end do
+            lc(j + 1) = v
+        end do
+        rc = nlh_sep_create(int(inner%nvar_, c_int32_t), int(size(lc), c_int32_t), lc, sp)
+        if (rc /= 0) error stop NL_INVALID_INPUT_ERROR
+        call nlh_sep_shape(sp, nfull, nlin, nnl)
+        call this%destroy()
+        rc = nlh_sep_model_create(nlh_default_handle(), inner%model_, sp, this%model_)
+        call nlh_sep_destroy(sp)                             ! (the model keeps its own copy of the tables)
+        if (rc /= 0) error stop rc
+        this%neqn_ = inner%neqn_
+        this%nvar_ = nnl
+        this%nprob_ = inner%nprob_
+        this%analytic_ = .true.
     end subroutine
 
     !> A robust loss for a launcher-backed model (create_curve, create_expr, create_from_device_fcn, create_mapped): a model
