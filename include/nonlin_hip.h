@@ -568,6 +568,31 @@ int nlh_qr_factor_full(nlh_handle *h, int32_t nprob, int32_t n, const double *dB
 int nlh_qr_rank1_update(nlh_handle *h, int32_t nprob, int32_t n, double *dQ, double *dRt,
                         const double *du, const double *dv);
 int nlh_solve_upper(nlh_handle *h, int32_t nprob, int32_t n, const double *dRt, double *dx);
+/* Sizes: nlh_qr_factor_full and nlh_qr_rank1_update return NLH_ARRAY_SIZE_ERROR beyond n = 8192 (the largest system the
+ * quasi-Newton solver takes), nlh_solve_upper where x (8 n bytes) and the kernel's own 4 KiB no longer fit the 158 KiB of
+ * LDS a workgroup may have (n = 19711 is the last that fits; 8192 works) -- each before anything is launched or written. */
+/* The Householder steps behind all of the above -- nlh_qr_factor_full, every constrained least-squares iteration, every
+ * polynomial fit -- as a stage of their own, for nprob work arrays [A | E]: dA [nprob][rows][ncA] and dE [nprob][rows][ncE],
+ * both ROW-major, transformed in place on the handle's stream.  On return A holds R in its upper triangle (exact zeros
+ * below the diagonal) and E = Q^T E: E = I (ncE = rows) gives Q^T, E = a right-hand side f gives Q^T f.  min(ncA, rows - 1)
+ * steps; a step whose squares below the diagonal sum to exactly zero is skipped (H = I) -- zeros, or entries below
+ * 1.5e-162, whose squares underflow -- and leaves (its diagonal entry, zeros).  Every sum runs in ascending row order, so
+ * A and E are bit-identical to the CPU restatement (nlo_qr_factor_cols) in every kernel form.  ncE = 0 is allowed (dE may
+ * then be NULL).  NLH_INVALID_INPUT_ERROR for nprob < 1, rows < 1, ncA < 1, ncE < 0, ncA > rows or a NULL array;
+ * NLH_ARRAY_SIZE_ERROR beyond 65535 problems, 1,048,560 rows or 2^20 columns (the kernels' grids); either way nothing is
+ * touched.  Scratch: nprob (2 rows + 2 (ncA + ncE) + 8) doubles of the handle's workspace. */
+int nlh_house_steps(nlh_handle *h, int32_t nprob, int32_t rows, int32_t ncA, int32_t ncE, double *dA, double *dE);
+/* Which kernel form those steps take for a shape: host code only -- no handle, no device -- the very function the launch
+ * dispatches through.  The shape and the batch size decide, never the data; forms never change a bit of the result.
+ * Returns the form; *tiles (may be NULL) = product tiles the form keeps in LDS (what distinguishes the two variants of
+ * NLH_HOUSE_FORM_FUSED16).  -NLH_INVALID_INPUT_ERROR / -NLH_ARRAY_SIZE_ERROR as nlh_house_steps.  nc = ncA + ncE: */
+enum { NLH_HOUSE_FORM_FUSED4 = 0,      /* k_qn_house_fused<4>: rows <= 4096 and nc nprob < 1536; 4 columns a workgroup, 2 tiles */
+       NLH_HOUSE_FORM_FUSED16 = 1,     /* k_qn_house_fused<16>: rows <= 4096 otherwise; 16 columns a workgroup; 2 tiles while
+                                          ceil(nc / 16) nprob <= 256, 1 beyond (two workgroups share a compute unit) */
+       NLH_HOUSE_FORM_DOT2 = 2,        /* k_qn_house_dot2: 4096 < rows <= 8192; 16 columns a workgroup, 2 tiles */
+       NLH_HOUSE_FORM_DOT_LDS = 3,     /* k_qn_house_dot<false>: 8192 < rows <= 18000; a thread per column, reflector in LDS, 0 tiles */
+       NLH_HOUSE_FORM_DOT_GLOBAL = 4 };/* k_qn_house_dot<true>: rows > 18000; the reflector stays in global memory */
+int32_t nlh_house_plan(int32_t nprob, int32_t rows, int32_t ncA, int32_t ncE, int32_t *tiles);
 /* cholesky_rank1_update (downdate = 0) / cholesky_rank1_downdate (1) stand-ins (call sites
  * src/nonlin_optimize.f90:721-722): R1^T R1 = R^T R +- u u^T in place on the ROW-major upper factor dRt;
  * du is consumed; *hinfo = 1 if the downdate would lose positive definiteness. */

@@ -131,6 +131,8 @@ SYMBOLS = {
     "nlh_qr_factor_full": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_qr_rank1_update": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_solve_upper": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_house_steps": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_house_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p]),
     "nlh_chol_rank1": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, c_int32_p]),
     "nlh_bf_chol_factor": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, c_int32_p]),
     "nlh_bf_solve_cholesky": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -431,3 +431,6 @@ static inline bool qn_nc8(int n)
     return n > 4096 || force;
 }
 static const int QN_LDS_ROWS = 18000;  // up to here k_qn_house_dot keeps the reflector (rows doubles) in LDS; beyond: in global memory
+// nlh_house_steps / nlh_house_plan: what the grids of the Householder kernels hold (problems on y or z, 16-row groups of
+// k_qn_house_apply on y: 65535 each) and a column count whose groups and products with nprob stay far inside int
+static const int QN_HOUSE_MAX_NPROB = 65535, QN_HOUSE_MAX_ROWS = 65535 * 16, QN_HOUSE_MAX_NC = 1 << 20;

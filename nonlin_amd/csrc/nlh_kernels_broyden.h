@@ -485,7 +485,7 @@ k_qn_house_fused(int rows, int ncA, int ncE, int j, double *__restrict__ Aall, d
 }
 
 // Second half: T(j,k) -= w_k, T(i,k) -= v_i w_k (elementwise, one thread per column and QN_RC rows),
-// column j becomes (beta, 0, ..., 0), and the updated column j+1 is copied to the other vbuf slot.
+// column j becomes (beta, 0, ..., 0) -- after a skipped step (tau = 0) (its diagonal, 0, ..., 0) --, and the updated column j+1 is copied to the other vbuf slot.
 #define QN_RC 16
 static __global__ void __launch_bounds__(256)
 k_qn_house_apply(int rows, int ncA, int ncE, int j, double *__restrict__ Aall, double *__restrict__ Eall,
@@ -509,9 +509,16 @@ k_qn_house_apply(int rows, int ncA, int ncE, int j, double *__restrict__ Aall, d
     if (tau == 0.0) {
         if (next_owner)
             for (int i = max(i0, j + 2); i < i1; ++i) vnext[i] = T[(size_t)i * ld];
-        if (fixcol && k == j && k < ncA) {                  // H = I: (diagonal value, zeros below)
-            const double alpha = st[(size_t)p * sps + 3];
-            for (int i = i0; i < i1; ++i) T[(size_t)i * ld] = (i == j) ? alpha : 0.0;
+        // H = I: column j becomes (diagonal value, zeros below).  The step is skipped when the SQUARES below the diagonal
+        // sum to zero, which entries below 1.5e-162 do as well as zeros: they are set to zero here, in every form (the
+        // fused form never stored the column, so it writes the diagonal too; the others leave the diagonal where it is).
+        if (k == j && k < ncA) {
+            if (fixcol) {
+                const double alpha = st[(size_t)p * sps + 3];
+                for (int i = i0; i < i1; ++i) T[(size_t)i * ld] = (i == j) ? alpha : 0.0;
+            } else {
+                for (int i = max(i0, j + 1); i < i1; ++i) T[(size_t)i * ld] = 0.0;
+            }
         }
         return;
     }

@@ -369,6 +369,35 @@ static int newton_core(nlh_handle *h, const nlh_options *o, int n, NewtonEval &e
 // ===========================================================================
 
 // B (column-major) -> Q, R: Householder QR with Q formed (qr_factor(b, q = q, r = r), :289)
+// Which kernel form the Householder steps of nprob work arrays [A | E] (rows x ncA | rows x ncE) take, and how many product
+// tiles it keeps in LDS: the shape decides, never the data.  launch_house_steps dispatches through this, nlh_house_plan
+// reports it.
+static int house_form(int nprob, int rows, int ncA, int ncE, int *tiles)
+{
+    const long nc = (long)ncA + ncE;
+    if (rows <= QN_FUSED_MAXROWS) {
+        // few columns in total: 4 per workgroup so that the chip has work (this form always has two tiles: its summing
+        // waves run a tile behind its producing waves)
+        if (nc * nprob < 1536) { *tiles = 2; return NLH_HOUSE_FORM_FUSED4; }
+        // more workgroups than CUs: one product tile each, so that two workgroups share a CU (their chains overlap)
+        *tiles = ((nc + 15) / 16) * nprob > 256 ? 1 : 2;
+        return NLH_HOUSE_FORM_FUSED16;
+    }
+    if (rows <= QN_DOT2_MAXROWS) { *tiles = 2; return NLH_HOUSE_FORM_DOT2; }    // workgroup-wide loads (reflector + two product tiles in LDS)
+    *tiles = 0;
+    return rows <= QN_LDS_ROWS ? NLH_HOUSE_FORM_DOT_LDS : NLH_HOUSE_FORM_DOT_GLOBAL;   // beyond: the reflector does not fit LDS
+}
+
+int32_t nlh_house_plan(int32_t nprob, int32_t rows, int32_t ncA, int32_t ncE, int32_t *tiles)
+{
+    if (nprob < 1 || rows < 1 || ncA < 1 || ncE < 0 || ncA > rows) return -NLH_INVALID_INPUT_ERROR;
+    if (nprob > QN_HOUSE_MAX_NPROB || rows > QN_HOUSE_MAX_ROWS || (long)ncA + ncE > QN_HOUSE_MAX_NC) return -NLH_ARRAY_SIZE_ERROR;
+    int t;
+    const int form = house_form(nprob, rows, ncA, ncE, &t);
+    if (tiles) *tiles = t;
+    return form;
+}
+
 // Householder steps on the row-major work array [A | E] (rows x ncA | rows x ncE); vbuf slot 0 must hold column 0 of A.
 void launch_house_steps(nlh_handle *h, int nprob, int rows, int ncA, int ncE, double *dA, double *dE,
                                double *vbuf, double *wbuf, double *st, const LmState *gst, int gwant)
@@ -377,15 +406,14 @@ void launch_house_steps(nlh_handle *h, int nprob, int rows, int ncA, int ncE, do
     hipStream_t s = h->stream;
     const int steps = std::min(ncA, rows - 1), nc = ncA + ncE;
     if (steps < 1) return;
-    if (rows <= QN_FUSED_MAXROWS) {
+    int tiles;
+    const int form = house_form(nprob, rows, ncA, ncE, &tiles);
+    if (form == NLH_HOUSE_FORM_FUSED4 || form == NLH_HOUSE_FORM_FUSED16) {
         // one pass per step: the update of step j-1 rides along with the sums of step j
-        const bool skinny = (long)nc * nprob < 1536;     // few columns in total: 4 per workgroup so that the chip has work
-        // more workgroups than CUs: one product tile each, so that two workgroups share a CU (their chains overlap)
-        // (the four-column form always has two tiles: its summing waves run a tile behind its producing waves)
-        const int dbuf = skinny ? 1 : ((long)((nc + 15) / 16) * nprob > 256 ? 0 : 1);
+        const int dbuf = tiles == 2;
         const size_t sh3 = qn_fused_lds(rows, dbuf);
         for (int j = 0; j < steps; ++j) {
-            if (skinny)
+            if (form == NLH_HOUSE_FORM_FUSED4)
                 hipLaunchKernelGGL(k_qn_house_fused<4>, dim3((nc + 3) / 4, nprob), dim3(512), sh3, s,
                                    rows, ncA, ncE, j, dA, dE, vbuf, wbuf, st, gst, gwant, dbuf);
             else
@@ -397,16 +425,15 @@ void launch_house_steps(nlh_handle *h, int nprob, int rows, int ncA, int ncE, do
                            rows, ncA, ncE, jl, dA, dE, vbuf, wbuf + (size_t)slot * nc, st + (size_t)slot * 4, 2 * nc, 8, 1, gst, gwant);
         return;
     }
-    const bool wide = rows <= QN_DOT2_MAXROWS;          // workgroup-wide loads (reflector + two product tiles in LDS)
     const size_t sh2 = sizeof(double) * ((size_t)rows + 2 * QN_DOT2_TR * QN_DOT2_CG);
     for (int j = 0; j < steps; ++j) {
-        if (wide)
+        if (form == NLH_HOUSE_FORM_DOT2)
             hipLaunchKernelGGL(k_qn_house_dot2, dim3((nc + QN_DOT2_CG - 1) / QN_DOT2_CG, nprob), dim3(256), sh2, s,
                                rows, ncA, ncE, j, dA, dE, vbuf, wbuf, st, gst, gwant);
-        else if (rows <= QN_LDS_ROWS)
+        else if (form == NLH_HOUSE_FORM_DOT_LDS)
             hipLaunchKernelGGL(k_qn_house_dot<false>, dim3((nc + QN_DOT_BS - 1) / QN_DOT_BS, nprob), dim3(QN_DOT_BS),
                                sizeof(double) * rows, s, rows, ncA, ncE, j, dA, dE, vbuf, wbuf, st, gst, gwant);
-        else                                                // the reflector does not fit LDS: it stays in global memory
+        else                                                // the reflector stays in global memory
             hipLaunchKernelGGL(k_qn_house_dot<true>, dim3((nc + QN_DOT_BS - 1) / QN_DOT_BS, nprob), dim3(QN_DOT_BS),
                                0, s, rows, ncA, ncE, j, dA, dE, vbuf, wbuf, st, gst, gwant);
         hipLaunchKernelGGL(k_qn_house_apply, dim3((nc + 255) / 256, (rows - j + QN_RC - 1) / QN_RC, nprob), dim3(256), 0, s,
@@ -424,7 +451,7 @@ static void launch_qn_qr(nlh_handle *h, int nprob, int n, const double *dB, doub
         dim3 grid((n + 31) / 32, (n + 31) / 32, nprob);
         hipLaunchKernelGGL(k_transpose, grid, dim3(256), 0, s, n, n, dB, dRt, n, gst, gwant);
     }
-    hipLaunchKernelGGL(k_qn_qr_init, dim3(std::min(1024, (n * n + 255) / 256), nprob), dim3(256), 0, s, n, dRt, dQ, vbuf, gst, gwant);
+    hipLaunchKernelGGL(k_qn_qr_init, dim3((unsigned)std::min<size_t>(1024, ((size_t)n * n + 255) / 256), nprob), dim3(256), 0, s, n, dRt, dQ, vbuf, gst, gwant);
     launch_house_steps(h, nprob, n, n, n, dRt, dQ, vbuf, wbuf, st, gst, gwant);
 }
 
@@ -925,10 +952,30 @@ int nlh_qr_factor_full(nlh_handle *h, int32_t nprob, int32_t n, const double *dB
 {
     if (!h) return NLH_ERR_BAD_HANDLE;
     if (n < 1 || nprob < 1) return NLH_INVALID_INPUT_ERROR;
+    if (n > QN_MAX_N) return NLH_ARRAY_SIZE_ERROR;      // as every caller of launch_qn_qr (whose grids are sized in int)
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     if ((rc = ensure(h, h->qnV, sizeof(double) * ((size_t)nprob * (16 * (size_t)n + 8))))) return rc;
     launch_qn_qr(h, nprob, n, dB, dQ, dRt, (double *)h->qnV.p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// The Householder steps as a stage of their own: [A | E] row-major in place (include/nonlin_hip.h).
+int nlh_house_steps(nlh_handle *h, int32_t nprob, int32_t rows, int32_t ncA, int32_t ncE, double *dA, double *dE)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    const int32_t form = nlh_house_plan(nprob, rows, ncA, ncE, nullptr);
+    if (form < 0) return -form;
+    if (!dA || (ncE > 0 && !dE)) return NLH_INVALID_INPUT_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    const size_t nc = (size_t)ncA + ncE;
+    // per problem: the reflector column (two slots of rows), w (two slots of nc), {tau, scal, beta, alpha} (two slots)
+    if ((rc = ensure(h, h->qnV, sizeof(double) * ((size_t)nprob * (2 * (size_t)rows + 2 * nc + 8))))) return rc;
+    double *vbuf = (double *)h->qnV.p, *wbuf = vbuf + (size_t)nprob * 2 * rows, *st = wbuf + (size_t)nprob * 2 * nc;
+    hipLaunchKernelGGL(k_qn_col0, dim3((rows + 255) / 256, nprob), dim3(256), 0, h->stream, rows, ncA, (const double *)dA, vbuf);
+    launch_house_steps(h, nprob, rows, ncA, ncE, dA, dE, vbuf, wbuf, st);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -952,6 +999,8 @@ int nlh_solve_upper(nlh_handle *h, int32_t nprob, int32_t n, const double *dRt, 
     if (!h) return NLH_ERR_BAD_HANDLE;
     if (n < 1 || nprob < 1) return NLH_INVALID_INPUT_ERROR;
     HIPCHK(h, hipSetDevice(h->device));
+    // x lives in dynamic LDS (8 n bytes): a launch the runtime refuses would leave x where it is behind some HIP error
+    if (!lds_fits((const void *)k_qn_solve_upper, sizeof(double) * (size_t)n)) return NLH_ARRAY_SIZE_ERROR;
     hipLaunchKernelGGL(k_qn_solve_upper, dim3(nprob), dim3(std::min(1024, ((n + 63) / 64) * 64)), sizeof(double) * n,
                        h->stream, n, dRt, dx, (size_t)n * n, (size_t)n, (const LmState *)nullptr, -1);
     HIPCHK(h, hipGetLastError());

@@ -68,6 +68,21 @@ def gram_plan(m, n):
     return {"form": GRAM_FORMS[rc], "nsplit": int(ns.value), "direct": bool(direct.value)}
 
 
+# names of the NLH_HOUSE_FORM_* values of include/nonlin_hip.h, in order
+HOUSE_FORMS = ("fused4", "fused16", "dot2", "dot_lds", "dot_global")
+
+
+def house_plan(nprob, rows, ncA, ncE):
+    """The kernel form of the Householder steps (DeviceSolver.house_steps, and every QR built on them) for nprob work
+    arrays [A | E] of rows x ncA | rows x ncE (nlh_house_plan: host code, needs no GPU; the function the launch itself
+    dispatches through).  Returns {"form": one of HOUSE_FORMS, "tiles": product tiles the form keeps in LDS}."""
+    tiles = C.c_int32()
+    rc = _lib.load().nlh_house_plan(nprob, rows, ncA, ncE, C.byref(tiles))
+    if rc < 0:
+        raise ValueError(f"nlh_house_plan({nprob}, {rows}, {ncA}, {ncE}): error {rc}")
+    return {"form": HOUSE_FORMS[rc], "tiles": int(tiles.value)}
+
+
 class _PmapCtx:
     """The context of a map's wrapping launchers (nlh_pmap_ctx), with everything it points at kept alive."""
 
@@ -1172,22 +1187,41 @@ class DeviceSolver:
         _chk(B, (nprob, n, n), "B")
         Q = torch.empty_like(B)
         Rt = torch.empty_like(B)
-        self.h.check(self.lib.nlh_qr_factor_full(self.h.ptr, nprob, n, B.data_ptr(), Q.data_ptr(), Rt.data_ptr()),
-                     "nlh_qr_factor_full")
+        rc = self.h.check(self.lib.nlh_qr_factor_full(self.h.ptr, nprob, n, B.data_ptr(), Q.data_ptr(), Rt.data_ptr()),
+                          "nlh_qr_factor_full")
+        if rc:
+            raise RuntimeError(f"nlh_qr_factor_full returned {rc}")
         return Q, Rt
+
+    def house_steps(self, A, E):
+        """The Householder steps of every QR here, in place: A [nprob, rows, ncA] and E [nprob, rows, ncE] (ncE may be 0)
+        are the ROW-major work arrays, i.e. A[p] and E[p] ARE the matrices.  On return A[p] holds R (exact zeros below
+        the diagonal) and E[p] = Q^T E[p].  Returns (A, E)."""
+        nprob, rows, ncA = A.shape
+        ncE = E.shape[2]
+        _chk(A, (nprob, rows, ncA), "A"); _chk(E, (nprob, rows, ncE), "E")
+        rc = self.h.check(self.lib.nlh_house_steps(self.h.ptr, nprob, rows, ncA, ncE, A.data_ptr(),
+                                                   E.data_ptr() if ncE else None), "nlh_house_steps")
+        if rc:
+            raise ValueError(f"nlh_house_steps({nprob}, {rows}, {ncA}, {ncE}) returned {rc}")
+        return A, E
 
     def qr_rank1_update(self, Q, Rt, u, v):
         """In place: Q1 R1 = Q R + u v^T."""
         nprob, n, _ = Q.shape
         _chk(Q, (nprob, n, n), "Q"); _chk(Rt, (nprob, n, n), "Rt"); _chk(u, (nprob, n), "u"); _chk(v, (nprob, n), "v")
-        self.h.check(self.lib.nlh_qr_rank1_update(self.h.ptr, nprob, n, Q.data_ptr(), Rt.data_ptr(), u.data_ptr(),
-                                                  v.data_ptr()), "nlh_qr_rank1_update")
+        rc = self.h.check(self.lib.nlh_qr_rank1_update(self.h.ptr, nprob, n, Q.data_ptr(), Rt.data_ptr(), u.data_ptr(),
+                                                       v.data_ptr()), "nlh_qr_rank1_update")
+        if rc:
+            raise RuntimeError(f"nlh_qr_rank1_update returned {rc}")
         return Q, Rt
 
     def solve_upper(self, Rt, x):
         nprob, n, _ = Rt.shape
         _chk(Rt, (nprob, n, n), "Rt"); _chk(x, (nprob, n), "x")
-        self.h.check(self.lib.nlh_solve_upper(self.h.ptr, nprob, n, Rt.data_ptr(), x.data_ptr()), "nlh_solve_upper")
+        rc = self.h.check(self.lib.nlh_solve_upper(self.h.ptr, nprob, n, Rt.data_ptr(), x.data_ptr()), "nlh_solve_upper")
+        if rc:
+            raise RuntimeError(f"nlh_solve_upper returned {rc}")
         return x
 
     def poly_fit_batch(self, x, y, order, thru_zero=False):

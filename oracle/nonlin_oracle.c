@@ -920,7 +920,10 @@ void nlo_qr_factor_full(int32_t n, const double *a_in, double *q, double *r)
         const double alpha = A_(a, n, j, j);
         double ssq = 0.0;
         for (int32_t i = j + 1; i < n; ++i) ssq = ssq + A_(a, n, i, j) * A_(a, n, i, j);
-        if (ssq == 0.0) continue;                                /* H = I (DLARFG with xnorm == 0) */
+        if (ssq == 0.0) {                                        /* H = I (DLARFG with xnorm == 0); entries whose squares */
+            for (int32_t i = j + 1; i < n; ++i) A_(a, n, i, j) = 0.0;     /* underflow count as the zeros they sum to */
+            continue;
+        }
         const double beta = -copysign(sqrt(alpha * alpha + ssq), alpha);
         const double tau = (beta - alpha) / beta;
         const double scal = 1.0 / (alpha - beta);
@@ -1168,7 +1171,10 @@ void nlo_qr_factor_rhs(int32_t m, int32_t n, double *a, double *f)
         const double alpha = A_(a, m, j, j);
         double ssq = 0.0;
         for (int32_t i = j + 1; i < m; ++i) ssq = ssq + A_(a, m, i, j) * A_(a, m, i, j);
-        if (ssq == 0.0) continue;
+        if (ssq == 0.0) {                                        /* H = I; what is below the diagonal (zeros, or entries whose */
+            for (int32_t i = j + 1; i < m; ++i) A_(a, m, i, j) = 0.0;     /* squares underflow) is set to zero: R has zeros there */
+            continue;
+        }
         const double beta = -copysign(sqrt(alpha * alpha + ssq), alpha);
         const double tau = (beta - alpha) / beta;
         const double scal = 1.0 / (alpha - beta);
@@ -1177,6 +1183,41 @@ void nlo_qr_factor_rhs(int32_t m, int32_t n, double *a, double *f)
         for (int32_t i = j + 1; i < m; ++i) A_(a, m, i, j) = 0.0;
         for (int32_t k = j + 1; k <= n; ++k) {                    /* k == n: the right-hand side */
             double *t = (k < n) ? &A_(a, m, 0, k) : f;
+            double w = t[j];
+            for (int32_t i = j + 1; i < m; ++i) w = w + v[i] * t[i];
+            w = tau * w;
+            t[j] = t[j] - w;
+            for (int32_t i = j + 1; i < m; ++i) t[i] = t[i] - v[i] * w;
+        }
+    }
+    free(v);
+}
+
+/* The same loop with ne extra columns instead of one right-hand side: Householder QR of the m-by-n column-major a
+ * (m >= n) with every reflector applied to the m-by-ne column-major e as well.  min(n, m - 1) steps, every sum in ascending
+ * row order, a step whose squares below the diagonal sum to zero skipped (H = I; what is below the diagonal set to zero).
+ * On exit a holds R in its upper triangle (zeros below), e = Q^T e.  ne = 1 is nlo_qr_factor_rhs; ne = m = n with e = I
+ * is nlo_qr_factor_full (q = e^T). */
+void nlo_qr_factor_cols(int32_t m, int32_t n, int32_t ne, double *a, double *e)
+{
+    double *v = (double *)malloc(sizeof(double) * (size_t)(m > 0 ? m : 1));
+    const int32_t steps = (n < m - 1) ? n : m - 1;
+    for (int32_t j = 0; j < steps; ++j) {
+        const double alpha = A_(a, m, j, j);
+        double ssq = 0.0;
+        for (int32_t i = j + 1; i < m; ++i) ssq = ssq + A_(a, m, i, j) * A_(a, m, i, j);
+        if (ssq == 0.0) {                                        /* H = I; what is below the diagonal (zeros, or entries whose */
+            for (int32_t i = j + 1; i < m; ++i) A_(a, m, i, j) = 0.0;     /* squares underflow) is set to zero: R has zeros there */
+            continue;
+        }
+        const double beta = -copysign(sqrt(alpha * alpha + ssq), alpha);
+        const double tau = (beta - alpha) / beta;
+        const double scal = 1.0 / (alpha - beta);
+        for (int32_t i = j + 1; i < m; ++i) v[i] = A_(a, m, i, j) * scal;
+        A_(a, m, j, j) = beta;
+        for (int32_t i = j + 1; i < m; ++i) A_(a, m, i, j) = 0.0;
+        for (int32_t k = j + 1; k < n + ne; ++k) {                /* k >= n: the extra columns */
+            double *t = (k < n) ? &A_(a, m, 0, k) : &A_(e, m, 0, k - n);
             double w = t[j];
             for (int32_t i = j + 1; i < m; ++i) w = w + v[i] * t[i];
             w = tau * w;

@@ -163,6 +163,8 @@ int nlo_quasi_newton_solve(const nlo_options *opt, int32_t jdelta, nlo_vecfcn fc
 
 /* constrained_least_squares_solver (src/nonlin_least_squares.f90:33-74, 793-1403). */
 void nlo_qr_factor_rhs(int32_t m, int32_t n, double *a, double *f);
+/* ... with ne extra columns e (m-by-ne, column-major) in place of f: e = Q^T e.  The restatement of nlh_house_steps. */
+void nlo_qr_factor_cols(int32_t m, int32_t n, int32_t ne, double *a, double *e);
 double nlo_alpha_box(int32_t n, const double *x, const double *p, const double *xl, const double *xu);
 void nlo_coleman_li_scaling(int32_t n, const double *x, const double *xl, const double *xu, double *s);
 void nlo_dogleg(int32_t m, int32_t n, double delta, const double *x, const double *f, const double *jac,

@@ -106,6 +106,8 @@ def lib():
         L.nlo_dq_cls_solve.argtypes = [C.POINTER(Options), C.c_double, C.c_double, dp, dp, C.POINTER(DqProblem), dp, dp,
                                        C.POINTER(IterationBehavior)]
         L.nlo_qr_factor_rhs.argtypes = [C.c_int32, C.c_int32, dp, dp]
+        L.nlo_qr_factor_cols.argtypes = [C.c_int32, C.c_int32, C.c_int32, dp, dp]
+        L.nlo_qr_factor_cols.restype = None
         L.nlo_bfgs_solve.argtypes = [C.POINTER(Options), FCNNVAR, GRADFCN, C.c_void_p, C.c_int32, dp, dp,
                                      C.POINTER(IterationBehavior)]
         L.nlo_bfgs_refactor_count.argtypes = [C.c_int]
@@ -352,6 +354,16 @@ def qr_factor_rhs(a, f):
     f = np.array(f, dtype=np.float64)
     lib().nlo_qr_factor_rhs(a.shape[0], a.shape[1], _dp(a), _dp(f))
     return a, f
+
+
+def qr_factor_cols(a, e):
+    """Householder QR of a tall matrix a (m x n) with the reflectors applied to the columns of e (m x ne, ne >= 0).
+    Returns (r_full, qte), both Fortran-order."""
+    a = np.array(a, dtype=np.float64, order="F")
+    e = np.array(e, dtype=np.float64, order="F")
+    assert a.ndim == 2 and e.ndim == 2 and e.shape[0] == a.shape[0] and a.shape[1] <= a.shape[0]
+    lib().nlo_qr_factor_cols(a.shape[0], a.shape[1], e.shape[1], _dp(a), _dp(e))
+    return a, e
 
 
 def qr_factor_full(a):

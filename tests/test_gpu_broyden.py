@@ -68,6 +68,199 @@ def test_solve_upper_bitwise(ds, oracle, n):
     assert np.array_equal(x[0].cpu().numpy(), oracle.solve_upper(R, b))
 
 
+# ---- the size edges of the two neighbours of the Householder steps (tests/test_gpu_house.py has those) ----
+NLH_ARRAY_SIZE_ERROR = 202
+
+
+def _rand(rng, shape):
+    """Generic float64 values, uniform in [-1/2, 1/2) (a fraction of the time a normal draw takes at 8192 x 8192; the
+    comparisons below are operation for operation, so any generic value serves)."""
+    return rng.random(shape) - 0.5
+
+
+def _upper_t(rng, n, zero_rows=()):
+    """L = R^T (C order, so that L.T is R in Fortran order without a copy) of a well-conditioned upper triangular R:
+    off-diagonal entries of size 1 / sqrt(n), diagonal near 3, a few exact zeros above the diagonal, and the rows of
+    zero_rows zero to the right of their diagonal."""
+    L = np.tril(_rand(rng, (n, n)))
+    L *= 1.0 / np.sqrt(n)
+    L[np.arange(n), np.arange(n)] += 3.0
+    for i, j in zip(rng.integers(0, n, 8), rng.integers(0, n, 8)):
+        if i < j:
+            L[j, i] = 0.0
+    for i in zero_rows:
+        L[i + 1:, i] = 0.0
+    return L
+
+
+def _solve_upper_ref(oracle, Rf, b):
+    """nlo_solve_upper on a Fortran-order R that is passed as it is (oracle.solve_upper copies R on every call)."""
+    import ctypes
+    assert Rf.flags.f_contiguous and Rf.dtype == np.float64
+    x = np.array(b, dtype=np.float64)
+    dp = ctypes.POINTER(ctypes.c_double)
+    oracle.lib().nlo_solve_upper(Rf.shape[0], Rf.ctypes.data_as(dp), x.ctypes.data_as(dp))
+    return x
+
+
+@pytest.mark.parametrize("n", [1, 2, 15, 16, 17, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2049, 4097, 8192])
+def test_solve_upper_bitwise_at_the_edges(ds, oracle, n):
+    """k_qn_solve_upper at one, two and several 16-column blocks, a partial last block, one and several rows a thread
+    (n > 1024: the rows a thread did not prefetch), with right-hand sides that make it skip columns: an x(j) that is
+    exactly zero WHEN ITS TURN COMES -- not merely on entry -- which needs the row of R zero to the right of the diagonal.
+    Five right-hand sides per R: dense; zeros scattered over such rows; one whole aligned block of sixteen of them (the
+    block's skip); the last entry; all zero.  Two problems with their own R below n = 4097, one from there."""
+    rng = np.random.default_rng(9000 + n)
+    nprob = 2 if n < 4097 else 1
+    nblk = (n + 15) // 16
+    blk = np.arange(16 * (nblk // 2), min(n, 16 * (nblk // 2) + 16))     # an aligned block (n < 16: all there is)
+    scat = np.unique(np.concatenate([rng.integers(0, n, max(1, n // 7)), [0, n - 1, min(n - 1, 1030)]]))
+    Ls = [_upper_t(rng, n, zero_rows=np.union1d(blk, scat)) for _ in range(nprob)]
+    Rfs = [L.T for L in Ls]
+    Rt = torch.stack([torch.from_numpy(L) for L in Ls]).to(ds.device).transpose(1, 2).contiguous()     # row-major R
+    for pattern in ("dense", "scattered", "block", "last", "allzero"):
+        b = _rand(rng, (nprob, n))
+        b[b == 0.0] = 1.0
+        if pattern == "scattered":
+            b[:, scat] = 0.0
+        elif pattern == "block":
+            b[:, blk] = 0.0
+        elif pattern == "last":
+            b[:, n - 1] = 0.0
+        elif pattern == "allzero":
+            b[:] = 0.0
+        x = torch.from_numpy(b.copy()).to(ds.device)
+        ds.solve_upper(Rt, x)
+        xg = x.cpu().numpy()
+        for p in range(nprob):
+            xo = _solve_upper_ref(oracle, Rfs[p], b[p])
+            assert np.isfinite(xo).all()
+            assert np.array_equal(xg[p], xo), (pattern, p, int(np.argmax(xg[p] != xo)))
+            if pattern == "scattered":
+                assert not xo[scat].any()
+            elif pattern == "block":
+                assert not xo[blk].any() and (n <= 16 or np.count_nonzero(xo) == n - len(blk))
+
+
+def test_solve_upper_refuses_what_lds_cannot_hold(ds):
+    """x lives in LDS: n = 20225 is beyond any workgroup's share and is refused with NLH_ARRAY_SIZE_ERROR before the
+    launch, x untouched (the tensors are of the full size, on the device only)."""
+    n = 20225
+    Rt = torch.zeros((1, n, n), dtype=torch.float64, device=ds.device)
+    x = torch.full((1, n), 7.0, dtype=torch.float64, device=ds.device)
+    assert ds.lib.nlh_solve_upper(ds.h.ptr, 1, n, Rt.data_ptr(), x.data_ptr()) == NLH_ARRAY_SIZE_ERROR
+    torch.cuda.synchronize()
+    assert bool((x == 7.0).all())
+    with pytest.raises(RuntimeError):
+        ds.solve_upper(Rt, x)
+
+
+def _arrow_solve_ref(d, c, f, b):
+    """x = R^-1 b in nlo_solve_upper's order of operations for R = diag(d) with a dense last column c (c[n-1] = d[n-1])
+    and a dense first row f (f[0] = d[0], f[n-1] = c[0]), every other entry zero: columns from the last to the first,
+    x(j) = x(j) / r(j,j), then x(i) = x(i) - x(j) r(i,j) for the rows above -- which leaves x(i) as it is wherever r(i,j) = 0."""
+    n = len(d)
+    x = np.array(b, dtype=np.float64)
+    if n > 1:
+        x[n - 1] = x[n - 1] / d[n - 1]
+        x[:n - 1] = x[:n - 1] - x[n - 1] * c[:n - 1]
+        x[1:n - 1] = x[1:n - 1] / d[1:n - 1]
+        x0 = float(x[0])
+        for xj, fj in zip(x[n - 2:0:-1].tolist(), f[n - 2:0:-1].tolist()):
+            x0 = x0 - xj * fj
+        x[0] = x0
+    x[0] = x[0] / d[0]
+    return x
+
+
+def test_solve_upper_at_the_lds_edge(ds, oracle):
+    """x (8 n bytes) and the kernel's own 4,104 bytes of LDS fill the 161,792 bytes a workgroup may have exactly at
+    n = 19711: that size is solved, to the bit, and n = 19712 is refused with x untouched.  A dense R of this size would
+    be 3 GB on the host, so R is built on the device -- a diagonal, a dense last column and a dense first row -- and the
+    reference is the restatement's operations written out for that pattern (_arrow_solve_ref), itself held to
+    nlo_solve_upper at a small size here."""
+    def parts(n, seed):
+        rng = np.random.default_rng(seed)
+        d, c, f, b = 3.0 + _rand(rng, n), _rand(rng, n), _rand(rng, n), _rand(rng, n) + 2.0
+        c[n - 1], f[0], f[n - 1] = d[n - 1], d[0], c[0]
+        return d, c, f, b
+
+    d, c, f, b = parts(40, 1)
+    R = np.diag(d)
+    R[:, 39], R[0, :] = c, f
+    assert np.array_equal(_arrow_solve_ref(d, c, f, b), oracle.solve_upper(R, b))
+
+    n = 19711
+    buf = torch.zeros((n + 1) * (n + 1), dtype=torch.float64, device=ds.device)
+    d, c, f, b = parts(n, 2)
+    Rt = buf[:n * n].view(1, n, n)
+    Rt[0].diagonal().copy_(torch.from_numpy(d))
+    Rt[0][:, n - 1] = torch.from_numpy(c).to(ds.device)
+    Rt[0][0, :] = torch.from_numpy(f).to(ds.device)
+    x = torch.from_numpy(b.copy()).to(ds.device)[None]
+    ds.solve_upper(Rt, x)
+    xo = _arrow_solve_ref(d, c, f, b)
+    assert np.isfinite(xo).all() and np.array_equal(x[0].cpu().numpy(), xo)
+
+    n = 19712
+    buf.zero_()
+    x = torch.full((1, n), 7.0, dtype=torch.float64, device=ds.device)
+    assert ds.lib.nlh_solve_upper(ds.h.ptr, 1, n, buf.data_ptr(), x.data_ptr()) == NLH_ARRAY_SIZE_ERROR
+    torch.cuda.synchronize()
+    assert bool((x == 7.0).all())
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 9, 10, 255, 256, 257, 1024, 1025, 4096, 4097, 8192])
+def test_qr_rank1_update_bitwise_at_the_edges(ds, oracle, n):
+    """The switches of k_qn_retri (one, four, eight columns a thread: 1024 / 1025, 4096 / 4097) and the tile edges of the
+    kernels around it.  The comparison is operation for operation, so Q need not be orthogonal: Q is random dense, scaled
+    by 1 / sqrt(n), R random upper triangular, and the oracle stays O(n^2).  Problem 0 (below n = 4096, where there are
+    two) is dense: every rotation takes the general branch of the Givens routine.  The last problem reaches both early
+    ones: some columns of its Q are unit vectors e_k with u_k = 0, so Q^T u is exactly zero there -- a run at the end
+    (g = 0) and one in the middle (f = 0) -- and its v has zeros."""
+    rng = np.random.default_rng(9100 + n)
+    nprob = 2 if n < 4096 else 1
+    Qt = _rand(rng, (nprob, n, n)) / np.sqrt(n)                 # Qt[p][j, i] = Q_p(i, j): the device layout
+    Lt = np.stack([np.tril(_rand(rng, (n, n))) for _ in range(nprob)])      # Lt[p] = R_p^T, so Lt[p].T is R_p in Fortran order
+    u, v = _rand(rng, (nprob, n)), _rand(rng, (nprob, n))
+    p = nprob - 1
+    cols = list(range(n - max(1, n // 4), n)) + ([n // 3] if n >= 9 else [])
+    if n >= 2:
+        ks = rng.choice(n, size=len(cols), replace=False)
+        Qt[p][cols, :] = 0.0
+        Qt[p][cols, ks] = 1.0
+        u[p][ks] = 0.0
+        v[p][rng.integers(0, n, max(1, n // 5))] = 0.0
+        w = Qt[p] @ u[p]
+        assert not w[cols].any() and np.count_nonzero(w) == n - len(cols)
+    Qd = torch.from_numpy(Qt).to(ds.device)
+    Rd = torch.from_numpy(Lt).to(ds.device).transpose(1, 2).contiguous()                # row-major R
+    ds.qr_rank1_update(Qd, Rd, torch.from_numpy(u.copy()).to(ds.device), torch.from_numpy(v.copy()).to(ds.device))
+    for p in range(nprob):
+        q1, r1 = oracle.qr_rank1_update(Qt[p].T, Lt[p].T, u[p], v[p])
+        assert np.isfinite(r1).all() and np.isfinite(q1).all()
+        # compared on the device, in the layouts the arrays have (q1.T and r1.T are C-contiguous views)
+        assert torch.equal(Rd[p].t(), torch.from_numpy(r1.T).to(ds.device)), (p, "R")
+        assert torch.equal(Qd[p], torch.from_numpy(q1.T).to(ds.device)), (p, "Q")
+        assert not bool(torch.tril(Rd[p], -1).any())
+
+
+def test_qr_entry_points_refuse_beyond_8192(ds):
+    """n = 8193: nlh_qr_rank1_update and nlh_qr_factor_full return NLH_ARRAY_SIZE_ERROR (the quasi-Newton solver's own
+    bound; the factorisation's launch arithmetic is sized for it) and leave Q and R untouched."""
+    n = 8193
+    Q = torch.full((1, n, n), 3.0, dtype=torch.float64, device=ds.device)
+    Rt = torch.full((1, n, n), 4.0, dtype=torch.float64, device=ds.device)
+    u = torch.ones((1, n), dtype=torch.float64, device=ds.device)
+    assert ds.lib.nlh_qr_rank1_update(ds.h.ptr, 1, n, Q.data_ptr(), Rt.data_ptr(), u.data_ptr(), u.data_ptr()) == NLH_ARRAY_SIZE_ERROR
+    B = torch.zeros((1, n, n), dtype=torch.float64, device=ds.device)
+    assert ds.lib.nlh_qr_factor_full(ds.h.ptr, 1, n, B.data_ptr(), Q.data_ptr(), Rt.data_ptr()) == NLH_ARRAY_SIZE_ERROR
+    torch.cuda.synchronize()
+    assert bool((Q == 3.0).all()) and bool((Rt == 4.0).all())
+    with pytest.raises(RuntimeError):
+        ds.qr_rank1_update(Q, Rt, u, u)
+
+
 def _solve_host(fcn, n, x0, jac=None, use_ls=True, args=None, jdelta=None):
     import nonlin_amd as nl
     obj = nl.vecfcn_helper()

@@ -11,6 +11,7 @@ import struct
 import numpy as np
 import pytest
 
+import house_cases as HC
 import problems_ref as P
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -330,6 +331,72 @@ def test_qr_factor_rhs_identities(oracle):
     x = oracle.solve_upper(R, qtf[:7])
     assert np.abs(x - np.linalg.lstsq(A, f, rcond=None)[0]).max() <= 1e-12
     assert abs(np.linalg.norm(qtf) - np.linalg.norm(f)) <= 1e-12
+
+
+# ---- nlo_qr_factor_cols: the general restatement of the Householder steps (tests/house_cases.py) ----
+@pytest.mark.parametrize("m,n", [(2, 1), (3, 3), (40, 7), (40, 40), (41, 40), (300, 13)])
+def test_qr_factor_cols_reproduces_qr_factor_rhs_bitwise(oracle, m, n):
+    """ne = 1 is nlo_qr_factor_rhs, bit for bit -- a column exactly zero below its diagonal (an H = I step), a column of
+    size 1e-170 (its squares underflow: skipped as well, and what was below its diagonal set to zero) and a NaN included."""
+    rng = np.random.default_rng([5, m, n])
+    for variant in ("dense", "skip", "tiny", "nan"):
+        A, f = rng.standard_normal((m, n)), rng.standard_normal(m)
+        if variant == "skip":
+            A[1:, 0] = 0.0
+        if variant == "tiny":
+            A[:, n // 2] *= 1e-170
+        if variant == "nan":
+            A[m // 2, n // 2] = np.nan
+        r0, qtf0 = oracle.qr_factor_rhs(A, f)
+        r1, e1 = oracle.qr_factor_cols(A, f[:, None])
+        if variant == "tiny":
+            assert not np.tril(r1, -1).any() and (m - 1 <= n // 2 or 0.0 < abs(r1[n // 2, n // 2]) < 1e-160)
+        assert np.array_equal(r1, r0, equal_nan=True) and np.array_equal(e1[:, 0], qtf0, equal_nan=True), variant
+
+
+@pytest.mark.parametrize("n", [1, 2, 9, 40, 130])
+def test_qr_factor_cols_reproduces_qr_factor_full_bitwise(oracle, n):
+    """ne = m = n with E = I is nlo_qr_factor_full, bit for bit: R = A on exit, Q = E^T."""
+    rng = np.random.default_rng([6, n])
+    A = rng.standard_normal((n, n))
+    if n >= 9:
+        A[3:, :3] = 0.0                            # column 2 is exactly zero below its diagonal when step 2 comes: H = I
+    if n >= 40:
+        A[:, 20] *= 1e-170                         # squares underflow: skipped too, zeros below the diagonal
+    q0, r0 = oracle.qr_factor_full(A)
+    r1, e1 = oracle.qr_factor_cols(A, np.eye(n))
+    assert np.array_equal(r1, r0) and np.array_equal(e1.T, q0) and not np.tril(r1, -1).any()
+    if n >= 9:
+        assert np.array_equal(r1[:3, :3], np.triu(r1[:3, :3])) and np.array_equal(e1[2, 3:], np.zeros(n - 3))
+
+
+def test_qr_factor_cols_without_extra_columns_and_in_pieces(oracle):
+    """ne = 0 leaves R alone, and the extra columns do not interact: each column of E alone gives the same bits."""
+    rng = np.random.default_rng(8)
+    A, E = rng.standard_normal((50, 9)), rng.standard_normal((50, 5))
+    r, e = oracle.qr_factor_cols(A, E)
+    r0, e0 = oracle.qr_factor_cols(A, np.zeros((50, 0)))
+    assert np.array_equal(r0, r) and e0.shape == (50, 0)
+    for k in range(5):
+        assert np.array_equal(oracle.qr_factor_cols(A, E[:, k:k + 1])[1][:, 0], e[:, k])
+
+
+@pytest.mark.parametrize("m,n", HC.STUDY_SHAPES)
+def test_qr_factor_cols_residuals_against_lapack(oracle, m, n):
+    """Correctness against something that is not this code: with E = I, the column-wise residuals of A - Q R and of
+    Q^T Q - I are at most four times the largest quotient tests/golden/house_study.json records (written by
+    tests/golden/make_house_study.py) over what numpy.linalg.qr (LAPACK) leaves on the same matrix -- both sides recomputed
+    here.  Four times: LAPACK's blocked sums and these ascending sums differ by the order of reduction only, which moves a
+    residual by small factors, not by orders."""
+    study = json.load(open(os.path.join(GOLDEN, "house_study.json")))
+    assert [m, n] in [[s["m"], s["n"]] for s in study["shapes"]]
+    assert study["worst_ratio"] == max(max(s["ratio"]) for s in study["shapes"]) and 1.0 <= study["worst_ratio"] <= 8.0
+    a = HC.study_matrix(m, n)
+    ours, lap = HC.oracle_residuals(oracle, a), HC.lapack_residuals(a)
+    print("fac, orth: ours %r LAPACK %r, allowed %.3g x" % (ours, lap, 4.0 * study["worst_ratio"]))
+    for o, l in zip(ours, lap):
+        assert l <= 100 * m * 2.0 ** -53            # LAPACK's own residual is a rounding-level figure
+        assert o <= 4.0 * study["worst_ratio"] * l
 
 
 @pytest.mark.parametrize("ic", [(0.5, 0.5), (1.0, 1.0)])
