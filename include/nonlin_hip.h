@@ -542,11 +542,19 @@ typedef struct nlh_qrx_plan_step {
     int32_t gwin;             /* what the pass's grid is built from, per problem: 64-column windows (wide_half: 32-column
                                  half windows, column: trailing columns) */
     int32_t lds, lds_max;     /* dynamic LDS bytes of the pass launch, and what its kernel is allowed */
+    int32_t tcur, oop;        /* the copy of the working matrix (0 / 1) the step's kernels read; 1: the flush writes the OTHER
+                                 copy, which the next step reads (wave / wave_shared under NLH_QRX_OOP != 0; a factorisation
+                                 whose second copy could not be allocated flushes in place instead, same results) */
 } nlh_qrx_plan_step;
 /* Fills *head and steps[0 .. min(n, cap)) (either may be NULL); returns n, -NLH_INVALID_INPUT_ERROR for nprob < 1,
  * n < 1 or m < n, -NLH_INVALID_OPERATION_ERROR for a plan no kernel instance exists for (a defect of the library). */
 int32_t nlh_qrx_plan(int32_t nprob, int32_t m, int32_t n, int32_t nact, int32_t have_stages,
                      nlh_qrx_plan_head *head, nlh_qrx_plan_step *steps, int32_t cap);
+/* The exact factorisation keeps its working matrix (8 bytes per element of the padded Jacobians) and, for batches large
+ * enough to take the lane-per-column passes, a SECOND copy that their flush writes instead of rewriting the first in place
+ * (memory of the exact policy, NLH_QRX_OOP).  Bytes the handle and its sub-batch workers hold for second
+ * copies right now: 0 until a factorisation asked for one, and when the device had no room for it. */
+int64_t nlh_qrx_second_matrix_bytes(nlh_handle *h);
 /* lmpar (:394-566, including its two deviations from MINPACK) on an n-by-n R
  * (leading dimension ldr) for every problem.  dtailsq[k] = sum of squares of the
  * caller's wa4(n+1:m).  Outputs: dpar (in/out), dxstep [nprob][n], dsdiag [nprob][n]. */

@@ -65,7 +65,8 @@ class QrxPlanHead(C.Structure):
 
 class QrxPlanStep(C.Structure):
     """nlh_qrx_plan_step."""
-    _fields_ = [(k, C.c_int32) for k in ("j", "cur", "np", "lo", "flush", "pf", "pivot", "pass", "gwin", "lds", "lds_max")]
+    _fields_ = [(k, C.c_int32) for k in ("j", "cur", "np", "lo", "flush", "pf", "pivot", "pass", "gwin", "lds", "lds_max",
+                                             "tcur", "oop")]
 
 
 # every symbol include/nonlin_hip.h declares: name -> (restype, argtypes)
@@ -122,6 +123,7 @@ SYMBOLS = {
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_lmfactor_exact": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_qrx_second_matrix_bytes": (C.c_int64, [_H]),
     "nlh_qrx_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(QrxPlanHead),
                                  C.POINTER(QrxPlanStep), C.c_int32]),
     "nlh_lmpar": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

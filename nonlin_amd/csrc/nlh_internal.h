@@ -73,6 +73,7 @@ struct nlh_handle {
     // named workspace buffers (grown on demand, reused across calls)
     DevBuf J, P, wa4, scratch, G, Gpart, vecs, ipvt, gvec, part, state, info, misc, lu, xdev, fdev, Adev, bdev, W2, R,
            qnQ, qnR, qnV, bfB, bfR, bfV, qxV, lumv, lus,
+           P2,                            // second copy of the exact factorisation's working matrix (lazy: qrx_second_matrix)
            dvX, dvF, dvIdx, dvP,          // user device residuals: points, compact residuals, problem lists, panel chunk (nlh_devfcn.hip)
            cvW, cvT, cvH,                 // covariance (nlh_covar.hip): the chain's arrays, the global-memory window, host-array staging
            crv,                           // one-call fits (nlh_fit.hip): status, non-zero-weight counts, a covariance nobody asked to keep

@@ -278,6 +278,31 @@ static int lm_workspace(nlh_handle *h, int nprob, int m, int n, LmWs &w, bool ne
     return 0;
 }
 
+// The second copy of the exact factorisation's working matrix, for the out-of-place flush of its lane forms (nlh_qrx.hip):
+// allocated per handle (so per sub-batch) the first time a factorisation's plan has such a flush, as large as the first
+// copy (21 GB more at 2048 x 4096x256, over all sub-batches).  Optional by construction: when it does not fit what the
+// device has free (less a reserve for the allocations a solve still makes), when hipMalloc refuses it, or under
+// NLH_QRX_OOP=2 (the tests' way into this branch), the answer is nullptr and every flush stays in place -- same bits.
+static double *qrx_second_matrix(nlh_handle *h, int nprob, int m, int n, int nact, bool have_stages)
+{
+    if (!qrx_wants_second_matrix(nprob, m, n, nact, have_stages) || qrx_oop_mode() == 2) return nullptr;
+    const size_t bytes = sizeof(double) * qrx_matrix_doubles(nprob, m, n), reserve = (size_t)256 << 20;
+    if (h->P2.p && h->P2.bytes >= bytes) return (double *)h->P2.p;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (free_b + h->P2.bytes < bytes + reserve) return nullptr;          // (ensure frees a smaller P2 before it allocates)
+    if (ensure(h, h->P2, bytes)) { (void)hipGetLastError(); h->err.clear(); return nullptr; }
+    return (double *)h->P2.p;
+}
+
+int64_t nlh_qrx_second_matrix_bytes(nlh_handle *h)
+{
+    if (!h) return 0;
+    size_t b = h->P2.p ? h->P2.bytes : 0;
+    for (const nlh_handle *wk : h->workers) b += wk && wk->P2.p ? wk->P2.bytes : 0;
+    return (int64_t)b;
+}
+
 // One pass over the factorisation + lmpar stages for every problem whose Jacobian is in
 // w.J (stage ST_HAVE_JAC or ST_NEED_QR) or whose factors are ready (inner-loop repeat).
 static int lm_factor_and_step(nlh_handle *h, const nlh_options *o, int nprob, int m, int n, LmWs &w,
@@ -293,7 +318,8 @@ static int lm_factor_and_step(nlh_handle *h, const nlh_options *o, int nprob, in
             if ((rc = ensure(h, h->qxV, qrx_workspace_bytes(nprob, m, n)))) return rc;
             QrxTimer tm{h, [](void *c, int which, hipStream_t s) { qrx_time_begin((nlh_handle *)c, which, s); },
                         [](void *c, int which, hipStream_t s) { qrx_time_end((nlh_handle *)c, which, s); }};
-            if (qrx_factor(h->stream, nprob, m, n, jac_in_qrx_layout ? (const double *)nullptr : w.J, w.P, dfvec, w.R, w.v, w.wa4,
+            if (qrx_factor(h->stream, nprob, m, n, jac_in_qrx_layout ? (const double *)nullptr : w.J, w.P,
+                           qrx_second_matrix(h, nprob, m, n, nact, true), dfvec, w.R, w.v, w.wa4,
                            w.scratch, dx, w.st, o->factor, o->gtol, h->qxV.p, &tm, nact))
                 return qrx_no_launch(h);
         }
@@ -844,7 +870,8 @@ int nlh_lmfactor_exact(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, const
     LmVecs v;
     memset(&v, 0, sizeof v);
     v.ipvt = dipvt; v.acnorm = dacnorm; v.qtf = dqtf; v.rdiag = drdiag;
-    if (qrx_factor(h->stream, nprob, m, n, dJ, (double *)h->P.p, df, dR, v, dwa4, dwa4, (const double *)nullptr, (LmState *)nullptr,
+    if (qrx_factor(h->stream, nprob, m, n, dJ, (double *)h->P.p, qrx_second_matrix(h, nprob, m, n, nprob, false), df, dR, v, dwa4, dwa4,
+                   (const double *)nullptr, (LmState *)nullptr,
                    100.0, 0.0, h->qxV.p, (const QrxTimer *)nullptr, nprob))
         return qrx_no_launch(h);
     HIPCHK(h, hipGetLastError());

@@ -27,12 +27,18 @@
 //   * column updates are DEFERRED: after step j a trailing column is not rewritten; its multiplier
 //     t_k = s_k / a_jj is kept and later passes apply the pending updates on the fly, oldest first --
 //     e = ((a - t_0 v_0) - t_1 v_1) ... -- the very roundings of the eager update (:655).  Every 7th step
-//     the pass stores e back (flush, whole 64-byte sectors): 8 B read + 8/7 B written per element and step instead of 24.
+//     the pass stores e back (flush): 8 B read + 8/7 B written per element and step instead of 24.  The flush of the
+//     lane forms (k_qrx_pass) writes OUT OF PLACE, into a second copy of T, 1 KB contiguous per store instruction (a wave's
+//     8-row x 64-column block turned through LDS); the factorisation tracks which copy is current and hands it to every
+//     kernel of a step (QrxPlanner::tcur).  Without a second copy (not enough memory, NLH_QRX_OOP=0) it writes T itself.
 //     (Measured: 12 or 16 slots per bank are slower -- the extra multiply / subtract pairs cost more than the
-//     flushes they save; a flushing pass runs at 4.8 TB/s, a plain one at 5.7-6.0 TB/s of the 6.3 achievable.)
+//     flushes they save; a flushing pass runs at 4.9 TB/s out of place, 4.5 in place, a plain one at 5.7-6.0 TB/s of the
+//     6.3 achievable.)
 //   * the column interchange (:626-637) never moves data: slot k of the permuted matrix carries a source
 //     column index src[k]; the pivot column is consumed into the reflector and slot kmax simply inherits
-//     slot j's source and pending multipliers.  The flush writes every slot to its own position.
+//     slot j's source and pending multipliers.  The flush writes every slot to its own position (of the copy it writes:
+//     after it that copy holds every live element -- rows >= j of every live slot, the residual included -- and nothing
+//     is written for dead rows or consumed columns).
 //   * RULE: no workgroup of a pass writes anything another workgroup of the same launch reads.  Workgroups of one
 //     launch need not run at the same time (more of them than the chip holds, or rows so few that one ends before a
 //     later one starts).  The slot maps in particular are written only by the pivot kernel (one workgroup per
@@ -72,7 +78,12 @@
 // flush's shape (16 bytes per lane at a 64-byte stride) runs at 3.7 TB/s, line-contiguous stores at 5.5 TB/s -- but a
 // kernel that reads AND writes in place reaches 4.8-5.0 TB/s of combined traffic whichever shape its stores have
 // (read-only: 6.1 TB/s), and the flush with its sectors transposed through LDS into 1 KB-contiguous stores took the
-// same 8.7 ms.  What a flush costs is set by mixed read/write traffic; the lever is fewer flushes (QRX_C).
+// same 8.7 ms.  What a flush costs is set by mixed read/write traffic; one lever is fewer flushes (QRX_C), the other is
+// not to read and write the same buffer: profiles/ubench/flush_store_shapes.hip, the same traffic at the headline's occupancy
+// (two waves per SIMD, windows as the waves of one workgroup), GB/s read + written: stores as above in place 4,842, into a
+// second buffer 5,322; whole sectors per lane quad (DPP exchange) 5,011 / 5,360; 1 KB contiguous through LDS 5,051 / 5,469.
+// In the kernel: full width 7.57 -> 6.99 ms out of place with 1 KB stores, 7.62 with the same stores in place
+// (profiles/flush_out_of_place.txt).
 // NORM2 of the pivot kernel: elements per lane of the serial phase = chunk / 64.  64 (chunks of 4096) when columns are
 // longer than 2048, 32 otherwise: half the LDS and 64 registers less, four workgroups per CU instead of two.
 
@@ -803,7 +814,7 @@ qrx_pass_tail(int p, int j, int k, int col, int wcol, int m, int n, int ld, int 
 template <int NP, bool FLUSH, bool SHARE>
 __global__ void __launch_bounds__(SHARE ? 64 * QRX_SHARE_MAXWIN : 64) __attribute__((amdgpu_waves_per_eu(1, (FLUSH && NP >= 4) ? 2 : 4)))
 k_qrx_pass(int p0, int nprob, int nwin, int lo, int m, int n, int ld, int coff, size_t tst, size_t vst, int j, int cur,
-           double *__restrict__ T, const double *__restrict__ Vall, double *__restrict__ tpall,
+           double *T, double *Tout, const double *__restrict__ Vall, double *__restrict__ tpall,
            int32_t *__restrict__ srcall, int32_t *__restrict__ slotall, double *__restrict__ rdall,
            double *__restrict__ waall, const QrxStep *__restrict__ stepall, double *__restrict__ Rall,
            double *__restrict__ qtfall, const LmState *__restrict__ st)
@@ -814,6 +825,8 @@ k_qrx_pass(int p0, int nprob, int nwin, int lo, int m, int n, int ld, int coff, 
     constexpr int LP = QRX_C;              // LDS row: the pending entries and the new one (NP + 1 <= QRX_C doubles)
     constexpr int NPI = NP < QRX_C ? NP : 0;
     __shared__ double vt[2][TR * LP];
+    // the flush turns each wave's 8-row x 64-column block (64 sectors of 64 bytes, one per lane) into 1 KB-contiguous stores
+    __shared__ __attribute__((aligned(16))) qrx_u32x4 xst[FLUSH ? (SHARE ? QRX_SHARE_MAXWIN : 1) : 1][FLUSH ? 256 : 1];
     // Workgroup -> (problem, window): consecutive workgroup ids go to consecutive XCDs, so the windows of one problem
     // are given ids that agree modulo 8: they share an L2 (reflector tiles, multipliers are fetched from the fabric once).
     const int b_ = blockIdx.x, grp = b_ / (8 * nwin), r_ = b_ % (8 * nwin);
@@ -829,6 +842,7 @@ k_qrx_pass(int p0, int nprob, int nwin, int lo, int m, int n, int ld, int coff, 
     int32_t *slotp = slotall + (size_t)p * ld;
     double *tpc = tpall + ((size_t)p * 2 + cur) * QRX_C * ldp;
     double *Tp = T + (size_t)p * tst;
+    double *Tq = (FLUSH ? Tout : T) + (size_t)p * tst;                  // where a flush writes: the OTHER copy of T, or T itself
     // tile barrier: with one wave per workgroup the compiler's __syncthreads (no s_barrier, counted waits) is what the
     // loops below were tuned with; shared tiles need a real barrier, ordering LDS traffic only (never the matrix loads)
     auto tile_barrier = [&]() __attribute__((always_inline)) {
@@ -894,6 +908,20 @@ k_qrx_pass(int p0, int nprob, int nwin, int lo, int m, int n, int ld, int coff, 
     const unsigned so = act ? (unsigned)col * 64u : 0x80000000u;
     const unsigned ko = act ? (unsigned)(coff + k) * 64u : 0x80000000u;  // where a flush puts the column (idle lanes: nowhere)
     const unsigned ldb = (unsigned)ld * 64u;                            // bytes per row block
+    // The flush stores through a descriptor of its own, on the copy of T it writes.  Whole tiles go out 1 KB-contiguous per
+    // instruction: the lanes park their sectors in LDS (piece q of lane c at xs[4 c + (q ^ ((c >> 2) & 3))]: no bank
+    // conflict on either side) and store instruction q writes the sectors of lanes 16 q .. 16 q + 15, lane l the piece l & 3
+    // of lane 16 q + (l >> 2) -- to where THAT lane's column goes (kq: its ko, fetched once).
+    const __amdgpu_buffer_rsrc_t rdst =
+        __builtin_amdgcn_make_buffer_rsrc(Tq + (size_t)(jb >> 3) * ld * 8, 0, (int)((size_t)nblk * ld * 64), 0x00020000);
+    qrx_u32x4 *xs = xst[FLUSH && SHARE ? win : 0];
+    unsigned kq[4];
+    if (FLUSH) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            kq[q] = (unsigned)__builtin_amdgcn_ds_bpermute(4 * (q * 16 + (lane >> 2)), (int)ko) + (unsigned)(lane & 3) * 16u;
+    }
+    const int xw = lane * 4, xsw = (lane >> 2) & 3, xr = (lane >> 2) * 4 + ((lane & 3) ^ ((lane >> 4) & 3));
     double a0[U], a1[U];
     auto load = [&](double (&buf)[U], int rbase) __attribute__((always_inline)) {                      // rbase: rel row, a multiple of 8
 #pragma unroll
@@ -953,15 +981,18 @@ k_qrx_pass(int p0, int nprob, int nwin, int lo, int m, int n, int ld, int coff, 
                             qrx_u32x4 w;
                             w.x = (unsigned)__double2loint(est[2 * q2]); w.y = (unsigned)__double2hiint(est[2 * q2]);
                             w.z = (unsigned)__double2loint(est[2 * q2 + 1]); w.w = (unsigned)__double2hiint(est[2 * q2 + 1]);
-                            __builtin_amdgcn_raw_buffer_store_b128(w, rsrc, ko + 16u * q2, boff, QRX_AUX_STORE);
+                            xs[xw + (q2 ^ xsw)] = w;
                         }
+#pragma unroll
+                        for (int q2 = 0; q2 < 4; ++q2)
+                            __builtin_amdgcn_raw_buffer_store_b128(xs[q2 * 64 + xr], rdst, kq[q2], boff, QRX_AUX_STORE);
                     }
                 } else {                                                // first / last tile: row by row
                     qrx_u32x2 w;
                     w.x = (unsigned)__double2loint(e0); w.y = (unsigned)__double2hiint(e0);
-                    if (ok0) __builtin_amdgcn_raw_buffer_store_b64(w, rsrc, ko + ioff, boff, QRX_AUX_STORE);
+                    if (ok0) __builtin_amdgcn_raw_buffer_store_b64(w, rdst, ko + ioff, boff, QRX_AUX_STORE);
                     w.x = (unsigned)__double2loint(e1); w.y = (unsigned)__double2hiint(e1);
-                    if (ok1) __builtin_amdgcn_raw_buffer_store_b64(w, rsrc, ko + ioff + 8u, boff, QRX_AUX_STORE);
+                    if (ok1) __builtin_amdgcn_raw_buffer_store_b64(w, rdst, ko + ioff + 8u, boff, QRX_AUX_STORE);
                 }
             }
             // keep a pair's work together: with many pending updates the scheduler otherwise hoists the LDS reads of
@@ -1018,7 +1049,7 @@ k_qrx_pass(int p0, int nprob, int nwin, int lo, int m, int n, int ld, int coff, 
     for (; t < ntile; ++t) tile_guard(t);
 
     if (!act) return;
-    qrx_pass_tail<NP, FLUSH>(p, j, k, col, coff + k, m, n, ld, cur, vst, s, rowj, rk0, wa0, refl, ajj, tq, Tp, vc, vo, tpall,
+    qrx_pass_tail<NP, FLUSH>(p, j, k, col, coff + k, m, n, ld, cur, vst, s, rowj, rk0, wa0, refl, ajj, tq, Tq, vc, vo, tpall,
                              rdall, waall, Rall, qtfall);
 }
 
@@ -1944,6 +1975,18 @@ struct QrxKnobs {
 };
 static const QrxKnobs &qrx_knobs() { static const QrxKnobs k; return k; }
 
+// NLH_QRX_OOP, read per call (tests and A/B runs compare the settings in one process): where the flush of the lane forms
+// (k_qrx_pass) writes.  1 (default): to the second copy of T, when the caller has one; 0: in place; 2: as 1, but the caller
+// treats the second copy's allocation as denied (the fall-back to the in-place flush, nlh_lm.hip).  No result bit changes.
+int qrx_oop_mode()
+{
+    const char *e = getenv("NLH_QRX_OOP");
+    if (!e) return 1;
+    if ((e[0] == '0' || e[0] == '1' || e[0] == '2') && !e[1]) return e[0] - '0';
+    fprintf(stderr, "nonlin_hip: NLH_QRX_OOP=%s ignored (not 0, 1 or 2)\n", e);
+    return 1;
+}
+
 // A plan no kernel instance exists for is a defect of this file: -DNLH_DEBUG builds stop there, others report it.
 static int qrx_plan_bug(const nlh_qrx_plan_step &s)
 {
@@ -1959,9 +2002,11 @@ struct QrxPlanner {
     const int m, n;
     nlh_qrx_plan_head head;
     int j = 0, cur = 0, np = 0, lo = 1;      // lo: first slot position that can still hold live data (step 0 moves physically)
+    int tcur = 0;                            // the copy of T that holds the live matrix: 0 is where the Jacobian is written
+    const bool oop_ok;                       // the lane forms' flush may write the other copy
     bool prev_flushed = false;
 
-    QrxPlanner(int nprob, int m_, int n_, int nact, bool have_stages, const QrxKnobs &k_) : k(k_), m(m_), n(n_)
+    QrxPlanner(int nprob, int m_, int n_, int nact, bool have_stages, const QrxKnobs &k_, bool oop_ok_) : k(k_), m(m_), n(n_), oop_ok(oop_ok_)
     {
         if (nact <= 0 || nact > nprob) nact = nprob;
         const bool percol = (long)nact * n <= k.initn;
@@ -2014,7 +2059,7 @@ struct QrxPlanner {
     int next(nlh_qrx_plan_step &s)
     {
         if (j >= n) return 0;
-        s.j = j; s.cur = cur;
+        s.j = j; s.cur = cur; s.tcur = tcur; s.oop = 0;
         s.pivot = pivot_form();
         if (head.sweep == NLH_QRX_SWEEP_COLUMN) {
             // a workgroup per trailing column, the update one step behind (k_qrx_pass_col): one pending reflector from
@@ -2033,6 +2078,9 @@ struct QrxPlanner {
             if (!(s.flush ? qrx_can_flush(np) : np <= QRX_C - 2) || (wide && np > QRX_RPW_MAXNP) || (s.pass == NLH_QRX_PASS_FOUR_WAVE && np >= 8))
                 return qrx_plan_bug(s);
             prev_flushed = s.flush;
+            // only k_qrx_pass flushes out of place; every other form rewrites the copy it reads
+            s.oop = s.flush && oop_ok && (s.pass == NLH_QRX_PASS_WAVE || s.pass == NLH_QRX_PASS_WAVE_SHARED);
+            if (s.oop) tcur ^= 1;
             if (s.flush) { np = 1; lo = j + 1; } else np += 1;
         }
         if (s.flush) cur ^= 1;
@@ -2045,7 +2093,7 @@ extern "C" int32_t nlh_qrx_plan(int32_t nprob, int32_t m, int32_t n, int32_t nac
                                 nlh_qrx_plan_step *steps, int32_t cap)
 {
     if (nprob < 1 || n < 1 || m < n) return -NLH_INVALID_INPUT_ERROR;
-    QrxPlanner plan(nprob, m, n, nact, have_stages != 0, qrx_knobs());
+    QrxPlanner plan(nprob, m, n, nact, have_stages != 0, qrx_knobs(), qrx_oop_mode() != 0);
     if (head) *head = plan.head;
     nlh_qrx_plan_step s;
     int more;
@@ -2054,12 +2102,23 @@ extern "C" int32_t nlh_qrx_plan(int32_t nprob, int32_t m, int32_t n, int32_t nac
     return more < 0 ? -NLH_INVALID_OPERATION_ERROR : n;
 }
 
+// Does the factorisation of this batch flush out of place anywhere, i.e. is a second copy of T worth allocating?
+bool qrx_wants_second_matrix(int nprob, int m, int n, int nact, bool have_stages)
+{
+    if (qrx_oop_mode() == 0) return false;
+    QrxPlanner plan(nprob, m, n, nact, have_stages, qrx_knobs(), true);
+    nlh_qrx_plan_step s;
+    while (plan.next(s) > 0)
+        if (s.oop) return true;
+    return false;
+}
+
 // ---- The launches: one switch per form enum.
 struct QrxLaunch {      // what the launches of one factorisation share
     hipStream_t stream;
     int nprob, m, n, ld, coff;
     size_t tst, vst;
-    double *T, *R;
+    double *T[2], *R;      // T[s.tcur]: the copy of the working matrix step s reads (T[1]: nullptr when every flush is in place)
     LmVecs v;
     const LmState *st;
     QrxWs w;
@@ -2068,7 +2127,7 @@ struct QrxLaunch {      // what the launches of one factorisation share
 static bool launch_pivot(const QrxLaunch &a, const nlh_qrx_plan_step &s)
 {
     auto pivot = [&](auto kernel, int threads, int pf) {
-        hipLaunchKernelGGL(kernel, dim3(a.nprob), dim3(threads), 0, a.stream, 0, a.m, a.n, a.ld, a.coff, a.tst, a.vst, s.j, s.cur, s.np, pf, a.T, a.w, a.R, a.v, a.st);
+        hipLaunchKernelGGL(kernel, dim3(a.nprob), dim3(threads), 0, a.stream, 0, a.m, a.n, a.ld, a.coff, a.tst, a.vst, s.j, s.cur, s.np, pf, a.T[s.tcur], a.w, a.R, a.v, a.st);
     };
     auto scale = [&] {
         hipLaunchKernelGGL(k_qrx_scale_long, dim3((unsigned)(((a.m - s.j) / 2 + 1023) / 1024 + 1), a.nprob), dim3(256), 0, a.stream, a.m, a.vst, s.j, s.cur, s.np,
@@ -2093,7 +2152,7 @@ static bool launch_pivot(const QrxLaunch &a, const nlh_qrx_plan_step &s)
     case NLH_QRX_PIVOT_LONG_SPLIT:                                      // flag 8: gather and NORM2 too
         pivot(k_qrx_pivot<64, true>, QRX_LONG_THREADS, s.pf | 4 | 8);
         hipLaunchKernelGGL(k_qrx_gather_long, dim3((unsigned)(((a.m - (s.j & ~7)) / 2 + 1023) / 1024 + 1), a.nprob), dim3(256), 0, a.stream, a.m, a.ld, a.tst,
-                           a.vst, s.j, s.cur, s.np, s.pf, a.T, a.w, a.st);
+                           a.vst, s.j, s.cur, s.np, s.pf, a.T[s.tcur], a.w, a.st);
         hipLaunchKernelGGL(k_qrx_norm_long, dim3(a.nprob), dim3(QRX_NORM_THREADS), 0, a.stream, a.m, a.n, a.vst, s.j, s.cur, s.np, s.pf, a.w, a.st);
         scale();
         return true;
@@ -2110,7 +2169,11 @@ static bool launch_pass(const QrxLaunch &a, const nlh_qrx_plan_step &s)
     const int npl = a.w.plist ? a.w.ny : a.nprob;
     auto pass = [&](auto kernel, int nprob, unsigned grid, int threads, auto... list) {
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), (size_t)s.lds, a.stream, 0, nprob, s.gwin, s.lo, a.m, a.n, a.ld, a.coff, a.tst, a.vst, s.j, s.cur,
-                           a.T, a.w.V, a.w.tp, a.w.src, a.w.slotof, a.w.rdiag, a.w.wa, a.w.step, a.R, a.v.qtf, a.st, list...);
+                           a.T[s.tcur], a.w.V, a.w.tp, a.w.src, a.w.slotof, a.w.rdiag, a.w.wa, a.w.step, a.R, a.v.qtf, a.st, list...);
+    };
+    auto lane = [&](auto kernel, unsigned grid, int threads) {        // k_qrx_pass: its flush writes T[tcur ^ oop]
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), (size_t)s.lds, a.stream, 0, a.nprob, s.gwin, s.lo, a.m, a.n, a.ld, a.coff, a.tst, a.vst, s.j,
+                           s.cur, a.T[s.tcur], a.T[s.tcur ^ s.oop], a.w.V, a.w.tp, a.w.src, a.w.slotof, a.w.rdiag, a.w.wa, a.w.step, a.R, a.v.qtf, a.st);
     };
     auto tiles = [&](int nprob) { return (unsigned)(((nprob + 7) / 8) * 8 * s.gwin); };
     switch (s.pass) {
@@ -2123,8 +2186,8 @@ static bool launch_pass(const QrxLaunch &a, const nlh_qrx_plan_step &s)
     case NLH_QRX_PASS_FOUR_WAVE:
         if constexpr (NP < 8) { pass(k_qrx_pass_rp<NP, FLUSH, 4>, npl, tiles(npl), 64 * 4, a.w.plist); return true; }
         break;
-    case NLH_QRX_PASS_WAVE: pass(k_qrx_pass<NP, FLUSH, false>, a.nprob, tiles(a.nprob), 64); return true;
-    case NLH_QRX_PASS_WAVE_SHARED: pass(k_qrx_pass<NP, FLUSH, true>, a.nprob, (unsigned)a.nprob, 64 * s.gwin); return true;
+    case NLH_QRX_PASS_WAVE: lane(k_qrx_pass<NP, FLUSH, false>, tiles(a.nprob), 64); return true;
+    case NLH_QRX_PASS_WAVE_SHARED: lane(k_qrx_pass<NP, FLUSH, true>, (unsigned)a.nprob, 64 * s.gwin); return true;
     }
     return false;
 }
@@ -2146,7 +2209,7 @@ static bool launch_pass(const QrxLaunch &a, const nlh_qrx_plan_step &s)
 {
     if (s.pass != NLH_QRX_PASS_COLUMN) return dispatch_pass(a, s);
     auto col = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(s.gwin, a.w.ny), dim3(256), (size_t)s.lds, a.stream, a.m, a.n, a.ld, a.tst, a.vst, s.j, s.cur, a.T, a.w.V, a.w.tp,
+        hipLaunchKernelGGL(kernel, dim3(s.gwin, a.w.ny), dim3(256), (size_t)s.lds, a.stream, a.m, a.n, a.ld, a.tst, a.vst, s.j, s.cur, a.T[s.tcur], a.w.V, a.w.tp,
                            a.w.src, a.w.rdiag, a.w.wa, a.w.step, a.R, a.v.qtf, a.st, a.w.plist);
     };
     if (s.np) col(k_qrx_pass_col<true>); else col(k_qrx_pass_col<false>);
@@ -2175,12 +2238,12 @@ void qrx_init_device()
     qrx_rpw_attr<0>();
 }
 
-int qrx_factor(hipStream_t stream, int nprob, int m, int n, const double *J, double *T, const double *fvec,
+int qrx_factor(hipStream_t stream, int nprob, int m, int n, const double *J, double *T, double *T2, const double *fvec,
                double *R, LmVecs v, double *wa4, double *scratch, const double *x, LmState *st, double factor,
                double gtol, void *ws, const QrxTimer *tm, int nact)
 {
-    QrxPlanner plan(nprob, m, n, nact, st != nullptr, qrx_knobs());
-    QrxLaunch a{stream, nprob, m, n, qrx_ld(n), qrx_coff(n), qrx_tstride(m, n), qrx_vstride(m), T, R, v, st, {}};
+    QrxPlanner plan(nprob, m, n, nact, st != nullptr, qrx_knobs(), T2 != nullptr && qrx_oop_mode() != 0);
+    QrxLaunch a{stream, nprob, m, n, qrx_ld(n), qrx_coff(n), qrx_tstride(m, n), qrx_vstride(m), {T, T2}, R, v, st, {}};
     qrx_carve(ws, nprob, m, n, &a.w);
     if (!plan.head.use_list) a.w.plist = nullptr;
     a.w.ny = plan.head.ny;
@@ -2219,7 +2282,7 @@ int qrx_factor(hipStream_t stream, int nprob, int m, int n, const double *J, dou
     }
     if (more < 0) return more;
     tb(2);
-    hipLaunchKernelGGL(k_qrx_finish, dim3(nprob), dim3(256), 0, stream, m, n, a.ld, a.coff, a.tst, a.vst, plan.cur, plan.np, (const double *)T, w, R, v,
+    hipLaunchKernelGGL(k_qrx_finish, dim3(nprob), dim3(256), 0, stream, m, n, a.ld, a.coff, a.tst, a.vst, plan.cur, plan.np, (const double *)a.T[plan.tcur], w, R, v,
                        wa4, scratch, x, st, factor, gtol);
     te(2);
     return 0;

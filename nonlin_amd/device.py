@@ -1157,6 +1157,11 @@ class DeviceSolver:
                                                  wa4.data_ptr()), "nlh_lmfactor_exact")
         return R, ipvt, rdiag, acnorm, qtf, wa4
 
+    def qrx_second_matrix_bytes(self):
+        """Bytes this solver's handle (sub-batch workers included) holds for second copies of the exact factorisation's
+        working matrix (nlh_qrx_second_matrix_bytes): 0 until an out-of-place flush wanted one and the device had room."""
+        return int(self.lib.nlh_qrx_second_matrix_bytes(self.h.ptr))
+
     def lmpar(self, R, ipvt, diag, qtf, delta, tailsq, par):
         """R [nprob, n, ldr] column-major n-by-n blocks with leading dimension ldr."""
         nprob, n, ldr = R.shape
