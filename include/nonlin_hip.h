@@ -777,17 +777,20 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
  * GRAMMAR (blanks are ignored; operators are left-associative; -a^2 is -(a^2); a^2^3 is an error):
  *   expr  := term (('+'|'-') term)*            term  := unary (('*'|'/') unary)*
  *   unary := ('-'|'+') unary | power           power := atom ('^' ['-'] number)?
- *   atom  := number | name | func '(' expr ')' | '(' expr ')'
+ *   atom  := number | name | func '(' expr (',' expr)* ')' | '(' expr ')'
  * number: what strtod reads in the C locale from a digit or '.'; name: a variable, a parameter or pi (the only named
- * constant); func: exp log sqrt sin cos tanh atan abs.  vars: 1 .. 4 comma-separated names; params: 1 .. 32, their order is
+ * constant); func: exp log sqrt sin cos tanh atan abs erf erfc erfcx voigt.  voigt takes exactly three arguments
+ * (x, sigma, gamma), every other function one; another count is an error that names its column.  vars: 1 .. 4 comma-separated names; params: 1 .. 32, their order is
  * the order of x.  A name is [A-Za-z_][A-Za-z0-9_]*, not pi and not a function.
  * THE PROGRAM IS THE POSTFIX OF THE PARSE TREE: no constant folding, no reassociation, no sharing of common subexpressions
  * (a unary '+' emits nothing; every literal and every pi is a constant of its own).  Instructions (op, arg):
  *   CONST i (consts[i])   VAR v   PARAM k   NEG   ADD   SUB   MUL   DIV   (b on top of the stack, a below it)
  *   IPOW k   an integer literal exponent, 2 <= |k| <= 16          POWC i   any other literal exponent c = consts[i]
- *   EXP LOG SQRT SIN COS TANH ATAN ABS
+ *   EXP LOG SQRT SIN COS TANH ATAN ABS   ERF ERFC ERFCX   VOIGT (pops x, sigma, gamma -- gamma on top -- and pushes one)
  * THE ARITHMETIC IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation, the device library's
- * functions -- so that a restatement in any IEEE language reproduces an exp-free formula bit for bit:
+ * functions -- so that a restatement in any IEEE language reproduces bit for bit an exp-free formula: one without a
+ * library function (POWC EXP LOG SIN COS TANH ATAN ERF ERFC ERFCX).  VOIGT is not one: a formula whose only function is
+ * voigt stays in the bit-exact class (the Faddeeva function below is stated arithmetic, not a library call).
  *   values     the obvious operation per instruction;  POWC: pow(a, c);  NEG, ABS: sign operations;
  *              IPOW k: v = a; v = v*a (|k| - 1 times in all); for k < 0 then v = 1.0/v
  *   column j of the Jacobian: forward mode with STRUCTURAL zeros.  A node's tangent is absent (Z) or a double: CONST, VAR,
@@ -800,6 +803,21 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
  *     POWC  (c*pow(a, c - 1.0))*da
  *     EXP   v*da          LOG  da/a                 SQRT  da/(2.0*v)          SIN  cos(a)*da       COS  -(sin(a)*da)
  *     TANH  (1.0 - v*v)*da                          ATAN  da/(1.0 + a*a)      ABS  a < 0 ? -da : da
+ *     with C1 = 2/sqrt(pi) = 1.1283791670955126, SQRT2 = 1.4142135623730951, SQRTPI = 1.772453850905516:
+ *     ERF   v = erf(a):    (C1*exp(-(a*a)))*da      ERFC  v = erfc(a):  -((C1*exp(-(a*a)))*da)
+ *     ERFCX v = erfcx(a):  ((2.0*a)*v - C1)*da      (the device library's erf, erfc, erfcx, exp)
+ *     VOIGT voigt(x, sigma, gamma) = Re w(z)/(|sigma| sqrt(2 pi)), z = (x + i|gamma|)/(|sigma| sqrt(2)): the Gaussian of
+ *           standard deviation sigma convolved with the Lorentzian of half width gamma, unit area; defined for sigma != 0
+ *           s = |sigma|; g = |gamma|; u = s*SQRT2; zr = x/u; zi = g/u; (wr, wi) = w(zr, zi) (nlh_faddeeva below)
+ *           nrm = u*SQRTPI; v = wr/nrm
+ *           w' = -2zw + i C1:  dwr = -(2.0*(zr*wr - zi*wi));  dwi = C1 - 2.0*(zr*wi + zi*wr);  un = u*nrm
+ *           gx = dwr/un;  gs = -((v + (zr*dwr - zi*dwi)/nrm)/s);  gg = -(dwi/un);
+ *           sigma < 0: gs = -gs;  gamma < 0: gg = -gg  (the ABS rule)
+ *           tangent, with dx, ds, dg the operands' tangents, the present ones in this order:
+ *             gx*dx + gs*ds + gg*dg | gx*dx + gs*ds | gx*dx + gg*dg | gs*ds + gg*dg | gx*dx | gs*ds | gg*dg
+ *           (sums left to right).  w is evaluated once per pass over the program and serves the value and every column
+ *           the pass carries.  gs is computed through a cancellation in the Lorentzian wings (|x| >> sigma): its error
+ *           is small against V(0)/sigma, not against itself.
  *     a root that is Z writes +0.0
  *   "structural": the compiler records per instruction the 32-bit mask of the parameters its subtree names; the tangent of a
  *   node for column j is present exactly when bit j of that mask is set, whatever the values are.
@@ -830,9 +848,13 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
 #define NLH_EXPR_TANH  15
 #define NLH_EXPR_ATAN  16
 #define NLH_EXPR_ABS   17
+#define NLH_EXPR_ERF   18
+#define NLH_EXPR_ERFC  19
+#define NLH_EXPR_ERFCX 20
+#define NLH_EXPR_VOIGT 21
 typedef struct nlh_expr nlh_expr;
 /* Compile (host code only, thread-safe).  Errors -- a syntax error, an unknown name, a name in both lists, a duplicate or
- * reserved name, an empty list or item, too many names, more than 256 instructions, 64 constants or a stack deeper than 16
+ * reserved name ("'erf' is a function"), a wrong number of arguments, an empty list or item, too many names, more than 256 instructions, 64 constants or a stack deeper than 16
  * -- return NLH_INVALID_INPUT_ERROR, leave *e NULL and set the message nlh_expr_error() returns (thread-local), e.g.
  * "col 17: unknown name 'foo'" (0-based column of the formula; "vars col 2: ..." / "params col 2: ..." for the lists). */
 int nlh_expr_compile(const char *formula, const char *vars, const char *params, nlh_expr **e);
@@ -843,6 +865,29 @@ void nlh_expr_shape(const nlh_expr *e, int32_t *nvar, int32_t *nparams, int32_t 
 /* Read-back, for restatements: op, arg [ninstr], consts [nconst] (any may be NULL).  The dependency masks: nlh_expr_masks. */
 int nlh_expr_program(const nlh_expr *e, int32_t *op, int32_t *arg, double *consts);
 int nlh_expr_masks(const nlh_expr *e, uint32_t *mask);
+/* Operand roots [ninstr] (either may be NULL): aroot, the instruction that produced the lower operand of a binary
+ * instruction or VOIGT's x; broot, the one that produced VOIGT's sigma (0 elsewhere).  The top operand's is i - 1.  The code
+ * word is op | (arg & 0xff) << 8 | aroot << 16 | broot << 24, so all of VOIGT's dependency masks are structural. */
+int nlh_expr_roots(const nlh_expr *e, int32_t *aroot, int32_t *broot);
+
+/* The Faddeeva function w(z) = exp(-z^2) erfc(-iz), Im z >= 0, in double precision, by Weideman's rational approximation
+ * with N = 40 terms -- one formula over the whole half plane, no branch, no library function:
+ *   L = sqrt(N/sqrt(2));  Z = (L + iz)/(L - iz);  w = 2 p(Z)/(L - iz)^2 + (1/sqrt(pi))/(L - iz),  p of degree 39.
+ * THE ARITHMETIC IS PART OF THE INTERFACE (one IEEE operation per step, no fused operation), for z = zr + i zi:
+ *   dr = L + zi;  di = -zr;  nr = L - zi;  ni = zr;  den = dr*dr + di*di
+ *   Zr = (nr*dr + ni*di)/den;  Zi = (ni*dr - nr*di)/den
+ *   pr = a[0]; pi = 0;  for k = 1 .. 39:  tr = pr*Zr - pi*Zi;  ti = pr*Zi + pi*Zr;  pr = tr + a[k];  pi = ti
+ *   ir = dr/den;  ii = -(di/den);  qr = ir*ir - ii*ii;  qi = 2.0*(ir*ii)
+ *   wr = 2.0*(pr*qr - pi*qi) + ISQRTPI*ir;  wi = 2.0*(pr*qi + pi*qr) + ISQRTPI*ii     (ISQRTPI = 0.5641895835477563)
+ * L and a[0 .. 39] (highest power first) are literal constants of the library; nlh_faddeeva_table reads them back (either
+ * output may be NULL).  Host code and the kernels run the same text, so nlh_faddeeva, nlh_faddeeva_batch and the VOIGT
+ * instruction give the same bits, and a restatement in any IEEE language reproduces them.  Accuracy: DESIGN 4e.
+ * nlh_faddeeva (host; needs no GPU) refuses Im z < 0 or NaN and NULL outputs with NLH_INVALID_INPUT_ERROR.
+ * nlh_faddeeva_batch: DEVICE pointers, a thread per element, on the handle's stream; Im z < 0 is outside its domain (what
+ * it writes there is not w).  NLH_ERR_BAD_HANDLE, NLH_INVALID_INPUT_ERROR (count < 0, a NULL array with count > 0). */
+int nlh_faddeeva(double re, double im, double *wre, double *wim);
+void nlh_faddeeva_table(double *L, double *a40);
+int nlh_faddeeva_batch(nlh_handle *h, int64_t count, const double *dre, const double *dim, double *dwre, double *dwim);
 typedef struct nlh_expr_ctx {
     const nlh_expr *e;
     int32_t shared_t;     /* dt is [nvar][m], the same abscissae for every problem */

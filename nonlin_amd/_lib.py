@@ -243,6 +243,10 @@ SYMBOLS = {
     "nlh_expr_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
     "nlh_expr_program": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_double_p]),
     "nlh_expr_masks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "nlh_expr_roots": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p]),
+    "nlh_faddeeva": (C.c_int, [C.c_double, C.c_double, c_double_p, c_double_p]),
+    "nlh_faddeeva_table": (None, [c_double_p, c_double_p]),
+    "nlh_faddeeva_batch": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_expr_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "nlh_expr_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "nlh_expr_model_create": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32,
@@ -482,6 +486,32 @@ def curve_nparams(kind, ncomp=1, baseline=-1):
 # opcodes of a compiled formula (include/nonlin_hip.h: NLH_EXPR_*), in order
 EXPR_OPS = ("CONST", "VAR", "PARAM", "NEG", "ADD", "SUB", "MUL", "DIV", "IPOW", "POWC", "EXP", "LOG", "SQRT", "SIN", "COS", "TANH",
             "ATAN", "ABS")
+# ... and of the special functions, numbered on from len(EXPR_OPS) = 18 (NLH_EXPR_ERF ..)
+EXPR_SPECIAL_OPS = ("ERF", "ERFC", "ERFCX", "VOIGT")
+
+
+def faddeeva_table():
+    """(L, a): the constants of the library's Faddeeva function, a [40] highest power first (nlh_faddeeva_table)."""
+    import numpy as np
+    L, a = C.c_double(), np.zeros(40)
+    load().nlh_faddeeva_table(C.byref(L), a.ctypes.data_as(c_double_p))
+    return L.value, a
+
+
+def wofz(z):
+    """The Faddeeva function w(z) = exp(-z^2) erfc(-iz) of a complex number or array with Im z >= 0, on the host
+    (nlh_faddeeva: needs no GPU; the bits of DeviceSolver.wofz_batch and of the formulas' voigt).  ValueError below the axis."""
+    import numpy as np
+    lib = load()
+    zz = np.asarray(z, dtype=np.complex128)
+    out = np.empty(zz.shape, dtype=np.complex128)
+    wr, wi = C.c_double(), C.c_double()
+    flat, oflat = zz.reshape(-1), out.reshape(-1)
+    for k in range(flat.size):
+        if lib.nlh_faddeeva(flat[k].real, flat[k].imag, C.byref(wr), C.byref(wi)):
+            raise ValueError(f"wofz: Im z >= 0 is required, got {flat[k]!r}")
+        oflat[k] = complex(wr.value, wi.value)
+    return out if out.ndim else complex(out)
 
 
 def _names(v):
@@ -491,7 +521,9 @@ def _names(v):
 class Expr:
     """A formula model (nlh_expr_compile: host code, needs no GPU): formula is an expression over the variables vars (1 .. 4
     names) and the parameters params (1 .. 32 names, in the order of x), e.g. Expr("a*exp(-k*t)+c", ("t",), ("a", "k", "c")).
-    Operators + - * / ^ (a literal exponent), functions exp log sqrt sin cos tanh atan abs, the constant pi.  Raises
+    Operators + - * / ^ (a literal exponent), functions exp log sqrt sin cos tanh atan abs erf erfc erfcx of one argument
+    and voigt(x, sigma, gamma) -- the unit-area Voigt profile, Gaussian sigma and Lorentzian half width gamma -- the constant
+    pi.  Function names and pi are reserved: no variable or parameter may carry one.  Raises
     ValueError with the compiler's message ("col 17: unknown name 'foo'").  close() frees it (so does garbage collection)."""
 
     def __init__(self, formula, vars=("t",), params=()):
@@ -517,6 +549,15 @@ class Expr:
         if rc:
             raise RuntimeError(f"nlh_expr_program returned {rc}")
         return op, arg, consts, mask
+
+    def roots(self):
+        """(aroot, broot), int32 [ninstr]: the instruction that produced a binary instruction's lower operand or VOIGT's x, and
+        the one that produced VOIGT's sigma (nlh_expr_roots)."""
+        import numpy as np
+        a, b = np.zeros(self.ninstr, dtype=np.int32), np.zeros(self.ninstr, dtype=np.int32)
+        if self.lib.nlh_expr_roots(self.ptr, a.ctypes.data_as(c_int32_p), b.ctypes.data_as(c_int32_p)):
+            raise RuntimeError("nlh_expr_roots failed")
+        return a, b
 
     def close(self):
         if getattr(self, "ptr", None) is not None and self.ptr.value:

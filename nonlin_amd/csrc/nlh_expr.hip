@@ -1,7 +1,8 @@
 // nlh_expr.hip -- formula models (include/nonlin_hip.h: nlh_expr_*): a model the user writes as an expression string.
 // First the compiler, pure host code that needs no GPU: a recursive-descent parser of the header's grammar that emits the
 // postfix of the parse tree as it goes -- no folding, no reassociation, no sharing -- with, per instruction, the mask of
-// the parameters its subtree names and the instruction that produced its left operand.  Then the launchers of the open
+// the parameters its subtree names and the instruction that produced its left operand (VOIGT: its two lower operands).  Then
+// the Faddeeva function's entry points (nlh_kernels_specfun.h), the launchers of the open
 // device-residual path (kernels and arithmetic: nlh_kernels_expr.h), which form a call runs and how many Jacobian
 // columns a pass carries, model values (nlh_expr_eval_batch) and the eight one-call fits nlh_expr_fit_batch*: a formula as
 // the FitSource of the pipeline (nlh_fit.hip).  The model object that owns its program and data is nlh_expr_model_create
@@ -18,7 +19,8 @@
 static thread_local std::string expr_err;
 const char *nlh_expr_error(void) { return expr_err.c_str(); }
 
-static const char *const EXPR_FUNCS[] = {"exp", "log", "sqrt", "sin", "cos", "tanh", "atan", "abs"};   // NLH_EXPR_EXP ..
+static const char *const EXPR_FUNCS[] = {"exp", "log", "sqrt", "sin", "cos", "tanh", "atan", "abs",   // NLH_EXPR_EXP ..
+                                         "erf", "erfc", "erfcx", "voigt"};                               // NLH_EXPR_ERF ..
 
 namespace {
 struct ExprFail {};
@@ -44,14 +46,18 @@ struct ExprParser {
         if (P->ninstr >= NLH_EXPR_MAX_INSTR) fail(col, "more than " + std::to_string(NLH_EXPR_MAX_INSTR) + " instructions");
         const int pc = P->ninstr++;
         uint32_t mask = op == NLH_EXPR_PARAM ? 1u << arg : 0u;
-        int aroot = 0;
-        if (pops == 2) { aroot = root[sp - 2]; mask = P->mask[aroot] | P->mask[root[sp - 1]]; }
+        int aroot = 0, broot = 0;
+        if (pops == 3) {                       // VOIGT: x, sigma, gamma
+            aroot = root[sp - 3]; broot = root[sp - 2];
+            mask = P->mask[aroot] | P->mask[broot] | P->mask[root[sp - 1]];
+        }
+        else if (pops == 2) { aroot = root[sp - 2]; mask = P->mask[aroot] | P->mask[root[sp - 1]]; }
         else if (pops == 1) mask = P->mask[root[sp - 1]];
         sp -= pops;
         if (sp >= NLH_EXPR_MAX_DEPTH) fail(col, "the evaluation stack gets deeper than " + std::to_string(NLH_EXPR_MAX_DEPTH));
         root[sp++] = pc;
         if (sp > P->depth) P->depth = sp;
-        P->code[pc] = (uint32_t)op | ((uint32_t)(arg & 0xff) << 8) | ((uint32_t)aroot << 16);
+        P->code[pc] = (uint32_t)op | ((uint32_t)(arg & 0xff) << 8) | ((uint32_t)aroot << 16) | ((uint32_t)broot << 24);
         P->mask[pc] = mask;
     }
     int constant(size_t col, double v)
@@ -143,10 +149,18 @@ struct ExprParser {
             if (name == EXPR_FUNCS[f]) {
                 if (peek() != '(') fail(at, "'(' expected after the function '" + name + "'");
                 ++at;
+                const int op = NLH_EXPR_EXP + (int)f, want = op == NLH_EXPR_VOIGT ? 3 : 1;
+                int have = 1;
                 expr();
+                for (; peek() == ','; ++have) {
+                    if (have == want) fail(at, "'" + name + "' takes " + (want == 1 ? "one argument" : "three arguments"));
+                    ++at;
+                    expr();
+                }
                 if (peek() != ')') fail(at, "')' expected");
+                if (have != want) fail(at, "'" + name + "' takes " + (want == 1 ? "one argument" : "three arguments"));
                 ++at;
-                emit(col, NLH_EXPR_EXP + (int)f, 0, 1);
+                emit(col, op, 0, want);
                 return;
             }
         if (name == "pi") { emit(col, NLH_EXPR_CONST, constant(col, 3.14159265358979323846), 0); return; }
@@ -239,10 +253,49 @@ int nlh_expr_program(const nlh_expr *e, int32_t *op, int32_t *arg, double *const
     return 0;
 }
 
+int nlh_expr_roots(const nlh_expr *e, int32_t *aroot, int32_t *broot)
+{
+    if (!e) return NLH_INVALID_INPUT_ERROR;
+    for (int i = 0; i < e->prog.ninstr; ++i) {
+        if (aroot) aroot[i] = EXPR_AROOT(e->prog.code[i]);
+        if (broot) broot[i] = EXPR_BROOT(e->prog.code[i]);
+    }
+    return 0;
+}
+
 int nlh_expr_masks(const nlh_expr *e, uint32_t *mask)
 {
     if (!e || !mask) return NLH_INVALID_INPUT_ERROR;
     memcpy(mask, e->prog.mask, sizeof(uint32_t) * e->prog.ninstr);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the Faddeeva function (nlh_kernels_specfun.h): the host entry, the table, a thread per element on the device
+// ---------------------------------------------------------------------------------------------------------------------
+int nlh_faddeeva(double re, double im, double *wre, double *wim)
+{
+    if (!wre || !wim || !(im >= 0.0)) return NLH_INVALID_INPUT_ERROR;
+    faddeeva_w(re, im, wre, wim);
+    return 0;
+}
+
+void nlh_faddeeva_table(double *L, double *a40)
+{
+    if (L) *L = NLH_FADDEEVA_L;
+    if (a40) memcpy(a40, NLH_FADDEEVA_A, sizeof(NLH_FADDEEVA_A));
+}
+
+int nlh_faddeeva_batch(nlh_handle *h, int64_t count, const double *dre, const double *dim, double *dwre, double *dwim)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (count < 0) return NLH_INVALID_INPUT_ERROR;
+    if (count == 0) return 0;
+    if (!dre || !dim || !dwre || !dwim) return NLH_INVALID_INPUT_ERROR;
+    if ((count + 255) / 256 > 0x7fffffffLL) return NLH_ARRAY_SIZE_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_faddeeva, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, (long long)count, dre, dim, dwre, dwim);
+    HIPCHK(h, hipGetLastError());
     return 0;
 }
 

@@ -323,8 +323,9 @@ void nlh_expr_init_device(int lds_max);          // nlh_expr.hip: the formula in
 void nlh_sep_init_device(int lds_max);           // nlh_sep.hip: the separable fits' kernels keep a point's panel in LDS
 
 // A compiled formula (nlh_expr.hip; include/nonlin_hip.h: nlh_expr_*).  ExprProg is what the kernels read, passed by value in
-// the kernel arguments: code[i] = op | (arg & 0xff) << 8 | aroot << 16, aroot the instruction that produced the operand a
-// of a binary instruction (b's is i - 1, as is a unary instruction's operand); mask[i]: the parameters instruction i's
+// the kernel arguments: code[i] = op | (arg & 0xff) << 8 | aroot << 16 | broot << 24, aroot the instruction that produced the
+// operand a of a binary instruction (b's is i - 1, as is a unary instruction's operand); VOIGT, the one ternary instruction:
+// aroot is x's producer, broot sigma's, gamma's is i - 1 (broot is 0 elsewhere); mask[i]: the parameters instruction i's
 // subtree names.
 struct ExprProg {
     int32_t ninstr, nvar, nparams, depth;

@@ -19,6 +19,7 @@
 #pragma once
 #include "nlh_internal.h"
 #include "nlh_kernels_place.h"
+#include "nlh_kernels_specfun.h"
 
 struct ExprData {                      // what the kernels read of an nlh_expr_ctx
     int shared_t, m;
@@ -29,6 +30,14 @@ struct ExprData {                      // what the kernels read of an nlh_expr_c
 #define EXPR_OP(c)     ((int)((c) & 0xffu))
 #define EXPR_ARG(c)    ((int)(int8_t)(((c) >> 8) & 0xffu))
 #define EXPR_AROOT(c)  ((int)(((c) >> 16) & 0xffu))
+#define EXPR_BROOT(c)  ((int)(((c) >> 24) & 0xffu))   // VOIGT only: the producer of its second operand
+
+// The device library's erf, erfc and erfcx behind one call: inlined three times into the interpreter they cost it 70 VGPRs
+// (and k_expr_fcn a wave per SIMD) whether or not a formula uses them.
+__device__ static __noinline__ double expr_erf_family(int op, double a)
+{
+    return op == NLH_EXPR_ERF ? erf(a) : (op == NLH_EXPR_ERFC ? erfc(a) : erfcx(a));
+}
 
 // One pass over the program.  vs: this thread's column of the value stack (slot s at vs[s * 256]); ts: of the C tangent
 // stacks (column c, slot s at ts[(c * depth + s) * 256]), columns j0 .. j0 + C - 1 (C = 0: values only).  Returns the
@@ -80,6 +89,25 @@ __device__ static inline double expr_run(const ExprProg &P, const double *xq, co
             --sp;
             continue;
         }
+        if (op == NLH_EXPR_VOIGT) {                               // ternary: x below sigma below gamma; w(z) once per pass
+            const double a = V(sp - 3), b = V(sp - 2), c3 = V(sp - 1);
+            const uint32_t ma = (P.mask[EXPR_AROOT(code)] >> j0) & cm, mb = (P.mask[EXPR_BROOT(code)] >> j0) & cm,
+                           mc = (P.mask[pc - 1] >> j0) & cm;
+            double gx, gs, gg;
+            const double v = voigt_eval(a, b, c3, &gx, &gs, &gg);
+            for (uint32_t mm = ma | mb | mc; mm; mm &= mm - 1) {
+                const int c = __builtin_ctz(mm);
+                const bool ha = (ma >> c) & 1u, hb = (mb >> c) & 1u, hc = (mc >> c) & 1u;
+                double d = 0.0;
+                if (ha) d = gx * T(c, sp - 3);
+                if (hb) d = ha ? d + gs * T(c, sp - 2) : gs * T(c, sp - 2);
+                if (hc) d = ha || hb ? d + gg * T(c, sp - 1) : gg * T(c, sp - 1);
+                T(c, sp - 3) = d;
+            }
+            V(sp - 3) = v;
+            sp -= 2;
+            continue;
+        }
         // unary: the operand is the instruction before
         const double a = V(sp - 1);
         const uint32_t ma = (P.mask[pc - 1] >> j0) & cm;
@@ -108,6 +136,9 @@ __device__ static inline double expr_run(const ExprProg &P, const double *xq, co
         case NLH_EXPR_COS: v = cos(a); if (ma) g = sin(a); break;
         case NLH_EXPR_TANH: v = tanh(a); break;
         case NLH_EXPR_ATAN: v = atan(a); break;
+        case NLH_EXPR_ERF: v = expr_erf_family(op, a); if (ma) g = NLH_SF_C1 * exp(-(a * a)); break;
+        case NLH_EXPR_ERFC: v = expr_erf_family(op, a); if (ma) g = NLH_SF_C1 * exp(-(a * a)); break;
+        case NLH_EXPR_ERFCX: v = expr_erf_family(op, a); break;
         default: v = fabs(a); break;                              // NLH_EXPR_ABS
         }
         for (uint32_t mm = ma; mm; mm &= mm - 1) {
@@ -125,6 +156,9 @@ __device__ static inline double expr_run(const ExprProg &P, const double *xq, co
             case NLH_EXPR_COS: d = -(g * da); break;
             case NLH_EXPR_TANH: d = (1.0 - v * v) * da; break;
             case NLH_EXPR_ATAN: d = da / (1.0 + a * a); break;
+            case NLH_EXPR_ERF: d = g * da; break;
+            case NLH_EXPR_ERFC: d = -(g * da); break;
+            case NLH_EXPR_ERFCX: d = ((2.0 * a) * v - NLH_SF_C1) * da; break;
             default: d = a < 0.0 ? -da : da; break;
             }
             T(c, sp - 1) = d;

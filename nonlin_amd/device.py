@@ -497,6 +497,19 @@ class DeviceSolver:
             raise RuntimeError(f"nlh_expr_eval_batch returned {rc}")
         return y
 
+    def wofz_batch(self, z):
+        """The Faddeeva function w(z) of a complex128 device tensor with Im z >= 0 (nlh_faddeeva_batch: a thread per element; the
+        bits of nonlin_amd.wofz).  Below the real axis is outside the domain: what comes back there is not w."""
+        if z.dtype != torch.complex128:
+            raise ValueError("z must be complex128")
+        re, im = z.real.contiguous().reshape(-1), z.imag.contiguous().reshape(-1)
+        wr, wi = torch.empty_like(re), torch.empty_like(re)
+        rc = self.lib.nlh_faddeeva_batch(self.h.ptr, re.numel(), re.data_ptr(), im.data_ptr(), wr.data_ptr(), wi.data_ptr())
+        self.h.check(rc, "nlh_faddeeva_batch")
+        if rc:
+            raise RuntimeError(f"nlh_faddeeva_batch returned {rc}")
+        return torch.complex(wr, wi).reshape(z.shape)
+
     def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None,
                        pmap=None, loss=None, stat=None, group=None, conv=None, sep=None):
         """Fit + errors of y.shape[0] data sets to a formula in one call (nlh_expr_fit_batch): curve_fit_batch with an Expr in
