@@ -929,6 +929,66 @@ int nlh_expr_fit_batch_h(nlh_handle *h, const nlh_options *opts, const nlh_expr 
                          const double *xu, double *x, double *fvec, double *sigma, double *cov, double *chi2, int32_t *rank,
                          nlh_iteration_behavior *ib, int32_t *status);
 
+/* ---- confidence and prediction bands (no counterpart in nonlin v2.2.0): a fit's parameter covariance propagated through
+ * any vector function g(x) of the parameters -- the delta method.  With G the Jacobian of g at the solution and C the
+ * parameter covariance, var g_i = G_i C G_i^T: the 1-sigma confidence band of the model (g = the model on a plotting grid),
+ * the prediction band for a new observation (the same plus a noise variance), the standard error of a derived quantity (g = a
+ * formula of the parameters, e.g. a lifetime 1/k, evaluated as a one-row model).
+ * nlh_propagate, the kernel: dJ [npoints][n][m], each point's Jacobian column-major exactly as nlh_device_jacfcn writes
+ * it; dcov [npoints][n][n]; dnoise [npoints] or NULL; dsd [npoints][m] out.  DEVICE pointers.
+ * THE OPERATION ORDER IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation.  Row i of point p, with
+ * J_k = J[p][k][i] and C = cov[p]:
+ *   v = 0
+ *   for j = 0 .. n-1:   s = 0;  s = s + C[j][k]*J_k for k = 0 .. j-1;  s = 2.0*s;  s = s + C[j][j]*J_j;  v = v + J_j*s
+ *   v = v + noise[p] when noise is given;   v < 0.0: v = 0.0 (a NaN passes through);   sd = sqrt(v)
+ * A MATRIX IS READ BY ITS LOWER TRIANGLE: only the entries C[j][k] with k <= j (cov[p*n*n + j*n + k]); what nlh_covar and
+ * the parameter maps write is exactly symmetric, a caller's own matrix counts as symmetric with that triangle.  No sum
+ * crosses a thread -- one thread owns one (point, row) -- so a row's bits depend neither on the workgroup form (row: a
+ * workgroup per (point, 256 rows); flat: several points per workgroup while two or more fit, m <= 128;
+ * NLH_BAND_FORM = row | flat, environment, read at each call, forces one for the sizes it can hold: flat m <= 256 and
+ * n <= 200) nor on where the matrix is kept (packed in LDS while n (n + 1) / 2 doubles fit the 161,792-byte cap, n <= 200;
+ * read from global memory beyond) nor on the batch.  Any m, n >= 1.
+ * noise is a per-problem VARIANCE added once to every row.  NULL: the confidence band of g.  The fit's chi2 -- with the
+ * scaled covariance of an unweighted fit, whose residual variance chi2 estimates -- gives the prediction band of a new
+ * observation.  sd is ONE standard deviation: the coverage factor (a Student-t quantile at the fit's degrees of freedom,
+ * or the normal 1.96) is the caller's to apply.  A problem whose fit failed has NaN in cov and gets NaN in sd.
+ * Errors (every entry point of this section, in this order, before anything is evaluated): NLH_ERR_BAD_HANDLE (NULL
+ * handle), NLH_UNDEFINED_FUNCTION_ERROR (NULL fcn), NLH_INVALID_INPUT_ERROR (a negative count, m, n or npts < 1, an unknown
+ * model; then, for a batch that is not empty, a NULL required array).  An empty batch returns 0. */
+int nlh_propagate(nlh_handle *h, int32_t npoints, int32_t m, int32_t n, const double *dJ, const double *dcov,
+                  const double *dnoise, double *dsd);
+/* The chain for nprob problems of a launcher pair AT THE GIVEN x (dx [nprob][n], device, not modified): dval = F(x), one
+ * launcher call, skipped when dval is NULL (and no forward difference needs it); J by vfh_jac_fcn's rule exactly as
+ * nlh_fd_jacobian_device (jacfcn, or forward differences when it is NULL); nlh_propagate.  dcov [nprob][n][n], dnoise
+ * [nprob] or NULL, dval [nprob][m] or NULL, dsd [nprob][m].  m < n is fine (a derived quantity is a one-row model).  The
+ * Jacobian lives in a workspace of the handle that no solver uses, at most 1 GiB of it per call (NLH_BAND_SCRATCH,
+ * environment, read at each call: fewer bytes; tests): beyond it the problems go in slices, the launchers seeing dprob, dX
+ * and the outputs offset as in every sliced call.  A problem's bits do not depend on the batch it sits in. */
+int nlh_propagate_batch_device(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn,
+                               nlh_device_jacfcn jacfcn, void *ctx, const double *dx, const double *dcov,
+                               const double *dnoise, double *dval, double *dsd);
+/* ... behind HOST arrays x, cov, noise, val, sd. */
+int nlh_propagate_batch_device_h(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn,
+                                 nlh_device_jacfcn jacfcn, void *ctx, const double *x, const double *cov,
+                                 const double *noise, double *val, double *sd);
+/* nlh_curve_eval_batch / nlh_expr_eval_batch plus the band: the model -- no data term, no weights -- at arbitrary abscissae
+ * dt (shapes as the eval calls document) with its analytic Jacobian, on a context of the call's own.  dy [nprob][npts] (the
+ * bits of the eval call) may be NULL; dsd [nprob][npts].  DEVICE pointers.  After a fit with a parameter map, a separable
+ * fit, a loss or Poisson counts the one-call fits return full-size x and cov: these two apply as they are. */
+int nlh_curve_band_batch(nlh_handle *h, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t npts,
+                         const double *dt, int32_t shared_t, const double *dx, const double *dcov, const double *dnoise,
+                         double *dy, double *dsd);
+int nlh_expr_band_batch(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32_t npts, const double *dt, int32_t shared_t,
+                        const double *dx, const double *dcov, const double *dnoise, double *dy, double *dsd);
+/* ... for every problem of a launcher-backed model object (curve, formula, a user's launchers, any wrapping model): its
+ * jacfcn if it has one, forward differences otherwise; host arrays x [nprob][n], cov [nprob][n][n], noise [nprob] or NULL,
+ * val [nprob][m] or NULL, sd [nprob][m].  val is the model's F(x): a curve or formula model created with y = 0 and no
+ * weights gives the model values.  A dense-quadratic model (the only kind a device set deals over several devices) is
+ * refused with NLH_INVALID_INPUT_ERROR, as the wrapping models refuse it.  What the Fortran shim's
+ * least_squares_solver%propagate_batch calls. */
+int nlh_dq_model_propagate(nlh_handle *h, const nlh_dq_model *model, const double *x, const double *cov,
+                           const double *noise, double *val, double *sd);
+
 /* ---- parameter maps (no counterpart in nonlin v2.2.0): fixed and tied parameters for ANY device model.  The model keeps
  * its N FULL parameters; the solver sees n <= N FREE unknowns.  Each full parameter k is free, fixed at a per-problem
  * value, or tied to another parameter: p_k = scale_k*p_src + offset_k.  The map is a pair of wrapping launchers around any

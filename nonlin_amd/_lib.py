@@ -258,6 +258,16 @@ SYMBOLS = {
     "nlh_expr_fit_batch_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p,
                                        C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                        c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
+    "nlh_propagate": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_propagate_batch_device": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_propagate_batch_device_h": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, c_double_p, c_double_p,
+                                               c_double_p, c_double_p, c_double_p]),
+    "nlh_curve_band_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_expr_band_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "nlh_dq_model_propagate": (C.c_int, [_H, C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "nlh_pmap_create": (C.c_int, [C.c_int32, c_int32_p, c_int32_p, c_double_p, c_double_p, C.POINTER(C.c_void_p)]),
     "nlh_pmap_destroy": (None, [C.c_void_p]),
     "nlh_pmap_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p]),

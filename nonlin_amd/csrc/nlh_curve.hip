@@ -94,6 +94,39 @@ int nlh_curve_eval_batch(nlh_handle *h, int32_t kind, int32_t ncomp, int32_t nba
     return 0;
 }
 
+// The model itself as a launcher pair -- no data term, no weights: what nlh_curve_eval_batch launches, with a problem list --
+// for the band (nlh_band.hip), on a context of the call's own.
+static int curve_value_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m,
+                           double *dF)
+{
+    const nlh_curve_ctx *c = (const nlh_curve_ctx *)ctx;
+    if (!c || m != c->m || !dprob) return NLH_INVALID_INPUT_ERROR;
+    return curve_launch(false, c->kind, c->ncomp, c->nbase, c->shared_t, c->m, c->dt, nullptr, nullptr, npoints, dprob, n, dX, dF,
+                        (hipStream_t)hip_stream);
+}
+
+static int curve_value_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m,
+                           double *dJ)
+{
+    const nlh_curve_ctx *c = (const nlh_curve_ctx *)ctx;
+    if (!c || m != c->m || !dprob) return NLH_INVALID_INPUT_ERROR;
+    return curve_launch(true, c->kind, c->ncomp, c->nbase, c->shared_t, c->m, c->dt, nullptr, nullptr, npoints, dprob, n, dX, dJ,
+                        (hipStream_t)hip_stream);
+}
+
+int nlh_curve_band_batch(nlh_handle *h, int32_t kind, int32_t ncomp, int32_t nbase, int32_t nprob, int32_t npts, const double *dt,
+                         int32_t shared_t, const double *dx, const double *dcov, const double *dnoise, double *dy, double *dsd)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    const int32_t n = nlh_curve_nparams(kind, ncomp, nbase);
+    if (n < 0 || nprob < 0 || npts < 1) return NLH_INVALID_INPUT_ERROR;
+    if (nprob == 0) return 0;
+    if (!dt || !dx || !dcov || !dsd) return NLH_INVALID_INPUT_ERROR;
+    nlh_curve_ctx c;
+    c.kind = kind; c.ncomp = ncomp; c.nbase = nbase; c.shared_t = shared_t != 0; c.m = npts; c.dt = dt; c.dy = nullptr; c.dw = nullptr;
+    return nlh_propagate_batch_device(h, nprob, npts, n, curve_value_fcn, curve_value_jac, &c, dx, dcov, dnoise, dy, dsd);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // fit + errors: the pipeline of nlh_fit.hip on a curve model
 // ---------------------------------------------------------------------------------------------------------------------

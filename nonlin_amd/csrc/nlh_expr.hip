@@ -391,6 +391,37 @@ int nlh_expr_eval_batch(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32_t
     return 0;
 }
 
+// The formula itself as a launcher pair -- no data term, no weights: what nlh_expr_eval_batch launches, with a problem list
+// -- for the band (nlh_band.hip), on a context of the call's own.
+static int expr_value_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m,
+                          double *dF)
+{
+    const nlh_expr_ctx *c = (const nlh_expr_ctx *)ctx;
+    if (!c || m != c->m || !dprob) return NLH_INVALID_INPUT_ERROR;
+    return expr_launch(false, c->e, c->shared_t, c->m, c->dt_stride, c->dt, nullptr, nullptr, npoints, dprob, n, dX, dF, (hipStream_t)hip_stream);
+}
+
+static int expr_value_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m,
+                          double *dJ)
+{
+    const nlh_expr_ctx *c = (const nlh_expr_ctx *)ctx;
+    if (!c || m != c->m || !dprob) return NLH_INVALID_INPUT_ERROR;
+    return expr_launch(true, c->e, c->shared_t, c->m, c->dt_stride, c->dt, nullptr, nullptr, npoints, dprob, n, dX, dJ, (hipStream_t)hip_stream);
+}
+
+int nlh_expr_band_batch(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32_t npts, const double *dt, int32_t shared_t, const double *dx,
+                        const double *dcov, const double *dnoise, double *dy, double *dsd)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (!e || nprob < 0 || npts < 1) return NLH_INVALID_INPUT_ERROR;
+    if (nprob == 0) return 0;
+    if (!dt || !dx || !dcov || !dsd) return NLH_INVALID_INPUT_ERROR;
+    nlh_expr_ctx c;
+    c.e = e; c.shared_t = shared_t != 0; c.m = npts; c.dt = dt; c.dy = nullptr; c.dw = nullptr;
+    c.dt_stride = shared_t ? (int64_t)npts : (int64_t)nprob * npts;
+    return nlh_propagate_batch_device(h, nprob, npts, e->prog.nparams, expr_value_fcn, expr_value_jac, &c, dx, dcov, dnoise, dy, dsd);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // fit + errors: the pipeline of nlh_fit.hip on a formula
 // ---------------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@
 //   nlh_poly.hip       polynomial%fit
 //   nlh_polyroots.hip  polynomial%roots, batched evaluate
 //   nlh_covar.hip      parameter covariance
+//   nlh_band.hip       confidence and prediction bands: the covariance propagated through any launcher pair
 //   nlh_devfcn.hip     user device residuals: the open launcher path, the built-in family as launchers
 //   nlh_curve.hip      built-in curve models: launchers, values, the eight nlh_curve_fit_batch* entry points
 //   nlh_expr.hip       formula models: compiler, launchers, values, the eight nlh_expr_fit_batch* entry points
@@ -77,7 +78,8 @@ struct nlh_handle {
            dvX, dvF, dvIdx, dvP,          // user device residuals: points, compact residuals, problem lists, panel chunk (nlh_devfcn.hip)
            cvW, cvT, cvH,                 // covariance (nlh_covar.hip): the chain's arrays, the global-memory window, host-array staging
            crv,                           // one-call fits (nlh_fit.hip): status, non-zero-weight counts, a covariance nobody asked to keep
-           sepx;                          // one-call separable fits (nlh_fit.hip): the nonlinear unknowns and, of a group, the outer ones
+           sepx,                          // one-call separable fits (nlh_fit.hip): the nonlinear unknowns and, of a group, the outer ones
+           bdW, bdH;                      // bands (nlh_band.hip): the chain's Jacobian and values, host-array staging
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     DevBuf cholmc;                     // side buffer of the multi-CU Cholesky (solved panels, bad-pivot flags)
@@ -321,6 +323,7 @@ void nlh_covar_init_device(int lds_max);        // nlh_covar.hip (covar, nlh_lm_
 void nlh_devfcn_init_device(int lds_max);        // nlh_devfcn.hip: the built-in family's launcher kernels keep x in LDS
 void nlh_expr_init_device(int lds_max);          // nlh_expr.hip: the formula interpreter keeps its stacks in LDS
 void nlh_sep_init_device(int lds_max);           // nlh_sep.hip: the separable fits' kernels keep a point's panel in LDS
+void nlh_band_init_device(int lds_max);          // nlh_band.hip: the band kernel keeps a point's packed covariance in LDS
 
 // A compiled formula (nlh_expr.hip; include/nonlin_hip.h: nlh_expr_*).  ExprProg is what the kernels read, passed by value in
 // the kernel arguments: code[i] = op | (arg & 0xff) << 8 | aroot << 16 | broot << 24, aroot the instruction that produced the

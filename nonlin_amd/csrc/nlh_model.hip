@@ -580,6 +580,18 @@ int nlh_dq_model_lm_covariance(nlh_handle *h, const nlh_dq_model *md, const doub
     return 0;
 }
 
+// The model's values at x and their standard deviations under the parameter covariance cov (nlh_propagate_batch_device_h:
+// the model's jacfcn if it has one, forward differences otherwise).  Host arrays: x [nprob][n], cov [nprob][n][n], noise
+// [nprob] or NULL, val [nprob][m] or NULL, sd [nprob][m].  Launcher-backed models only: the built-in dense-quadratic family
+// -- the only one a device set deals over several devices -- is refused, as the wrapping models refuse it.
+int nlh_dq_model_propagate(nlh_handle *h, const nlh_dq_model *md, const double *x, const double *cov, const double *noise, double *val,
+                           double *sd)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (!md || !md->ufcn || !x || !cov || !sd) return NLH_INVALID_INPUT_ERROR;
+    return nlh_propagate_batch_device_h(h, md->nprob, md->m, md->n, md->ufcn, md->ujac, md->uctx, x, cov, noise, val, sd);
+}
+
 // newton_solver%solve on every (square) problem of the model; analytic != 0: the model's own Jacobian
 // J(i,j) = (1 + 2 gamma u_i) A(i,j) plays the role of a jacobianfcn, otherwise forward differences.
 int nlh_dq_model_newton_solve(nlh_handle *h, const nlh_options *o, const nlh_dq_model *md, int32_t analytic, double *x,

@@ -1329,6 +1329,94 @@ class DeviceSolver:
             raise RuntimeError(f"nlh_lm_covariance_batch_device returned {rc}")
         return cov, sigma, rank, chi2
 
+    # -- confidence and prediction bands: the covariance propagated through a function of the parameters ---------------
+    @staticmethod
+    def _band_args(nprob, n, cov, noise):
+        _chk(cov, (nprob, n, n), "cov")
+        if noise is not None:
+            _chk(noise, (nprob,), "noise")
+        return noise.data_ptr() if noise is not None else None
+
+    def propagate(self, J, cov, noise=None):
+        """The delta method, the raw kernel (nlh_propagate): sd [npoints, m] = sqrt(J_i cov J_i^T) for every row i of the
+        Jacobians J [npoints, n, m] (each point column-major m x n, as a Jacobian launcher writes it) under the covariances
+        cov [npoints, n, n], read by their lower triangle.  noise [npoints]: a variance added once to every row of its
+        point (None: none).  One standard deviation: the coverage factor is the caller's.  A NaN matrix gives NaN rows."""
+        npoints, n, m = J.shape
+        _chk(J, (npoints, n, m), "J")
+        pn = self._band_args(npoints, n, cov, noise)
+        sd = torch.empty((npoints, m), dtype=torch.float64, device=J.device)
+        rc = self.lib.nlh_propagate(self.h.ptr, npoints, m, n, J.data_ptr(), cov.data_ptr(), pn, sd.data_ptr())
+        self.h.check(rc, "nlh_propagate")
+        if rc:
+            raise RuntimeError(f"nlh_propagate returned {rc}")
+        return sd
+
+    def propagate_batch_device(self, fcn, ctx, m, x, cov, jac=None, noise=None):
+        """Values and standard deviations of ANY launcher pair at x [nprob, n] under the parameter covariances cov
+        [nprob, n, n] (nlh_propagate_batch_device): val = F(x) [nprob, m], a Jacobian (jac, or forward differences by
+        fd_jacobian_device's rule), then propagate.  Returns (val, sd).  noise [nprob]: a variance added to every row --
+        None gives the confidence band, the fit's chi2 (with the scaled covariance of an unweighted fit) the prediction
+        band.  m may be smaller than n: the standard error of a derived quantity is this call on a one-row model, e.g. an
+        Expr of the parameters through expr_launchers with y = 0.
+        After a fit with conv=: run it over conv_launchers around the plotting grid's launchers with y = 0.  After a fit
+        with group=: run it over group_launchers, with the per-group cov the fit returned and x = group_gather(group, x)."""
+        nprob, n = x.shape
+        _chk(x, (nprob, n), "x")
+        pn = self._band_args(nprob, n, cov, noise)
+        m = int(m)
+        val = torch.empty((nprob, m), dtype=torch.float64, device=x.device)
+        sd = torch.empty((nprob, m), dtype=torch.float64, device=x.device)
+        rc = self.lib.nlh_propagate_batch_device(self.h.ptr, nprob, m, n, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx),
+                                                 x.data_ptr(), cov.data_ptr(), pn, val.data_ptr(), sd.data_ptr())
+        self.h.check(rc, "nlh_propagate_batch_device")
+        if rc:
+            raise RuntimeError(f"nlh_propagate_batch_device returned {rc}")
+        return val, sd
+
+    def curve_band(self, kind, x, cov, t, ncomp=1, baseline=-1, noise=None):
+        """curve_eval plus the band (nlh_curve_band_batch): the model values y [nprob, npts] of x [nprob, n] at the abscissae
+        t [nprob, npts] (or one shared [npts] tensor) and their standard deviations sd [nprob, npts] under the parameter
+        covariances cov [nprob, n, n], with the analytic Jacobian.  Returns (y, sd); noise as in propagate_batch_device.
+        After a fit with pmap=, sep=, loss= or stat= the one-call fits return full-size x and cov: this applies as it
+        is (a fixed parameter's zero row and column contribute nothing).  conv= and group=: propagate_batch_device."""
+        k = curve_kind(kind)
+        nprob, n = x.shape
+        _chk(x, (nprob, n), "x")
+        if n != curve_nparams(k, ncomp, baseline):
+            raise ValueError(f"x has {n} columns, the model {curve_nparams(k, ncomp, baseline)} parameters")
+        shared = t.dim() == 1
+        npts = t.shape[-1]
+        _chk(t, (npts,) if shared else (nprob, npts), "t")
+        pn = self._band_args(nprob, n, cov, noise)
+        y = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
+        sd = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
+        rc = self.lib.nlh_curve_band_batch(self.h.ptr, k, int(ncomp), int(baseline), nprob, npts, t.data_ptr(), int(shared),
+                                           x.data_ptr(), cov.data_ptr(), pn, y.data_ptr(), sd.data_ptr())
+        self.h.check(rc, "nlh_curve_band_batch")
+        if rc:
+            raise RuntimeError(f"nlh_curve_band_batch returned {rc}")
+        return y, sd
+
+    def expr_band(self, expr, x, cov, t, noise=None):
+        """expr_eval plus the band (nlh_expr_band_batch): curve_band with an Expr in the place of (kind, ncomp, baseline); t
+        as expr_eval takes it.  Returns (y, sd).  The same rules after pmap=, sep=, loss=, stat=, conv= and group= fits."""
+        nprob, n = x.shape
+        _chk(x, (nprob, n), "x")
+        if n != expr.nparams:
+            raise ValueError(f"x has {n} columns, the formula {expr.nparams} parameters")
+        npts = t.shape[-1]
+        shared = self._expr_t(expr, t, nprob, npts)
+        pn = self._band_args(nprob, n, cov, noise)
+        y = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
+        sd = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
+        rc = self.lib.nlh_expr_band_batch(self.h.ptr, expr.ptr, nprob, npts, t.data_ptr(), int(shared), x.data_ptr(),
+                                          cov.data_ptr(), pn, y.data_ptr(), sd.data_ptr())
+        self.h.check(rc, "nlh_expr_band_batch")
+        if rc:
+            raise RuntimeError(f"nlh_expr_band_batch returned {rc}")
+        return y, sd
+
     def chol_rank1(self, Rt, u, downdate=False):
         """In place on the row-major upper Cholesky factor Rt (n x n): R1^T R1 = R^T R +- u u^T.  Returns info."""
         n = Rt.shape[0]

@@ -424,6 +424,15 @@ module nonlin_hip_c
             integer(c_int32_t), intent(out) :: rank(*)
             integer(c_int) :: rc
         end function
+        function nlh_dq_model_propagate(h, model, x, cov, noise, val, sd) &
+                bind(C, name="nlh_dq_model_propagate") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: h, model
+            real(c_double), intent(in) :: x(*), cov(*)
+            type(c_ptr), value :: noise, val                 ! real(c_double) arrays, or c_null_ptr: none
+            real(c_double), intent(out) :: sd(*)
+            integer(c_int) :: rc
+        end function
         function nlh_dq_model_newton_solve(h, opts, model, analytic, x, fvec, ib, status) &
                 bind(C, name="nlh_dq_model_newton_solve") result(rc)
             import :: c_ptr, c_int, c_int32_t, c_double, nlh_options, nlh_iteration_behavior

@@ -26,6 +26,7 @@ module nonlin_least_squares
         procedure, public :: solve_batch => lm_solve_many
         procedure, public :: covariance => lm_covariance_one
         procedure, public :: covariance_batch => lm_covariance_many
+        procedure, public :: propagate_batch => lm_propagate_many
     end type
 
     type, abstract, extends(least_squares_solver) :: constrained_equation_solver
@@ -266,6 +267,49 @@ contains
         if (present(sigma)) sigma = swork
         if (present(rank)) rank = r
         if (present(chi2)) chi2 = q
+    end subroutine
+
+    !> Extension: the band of a fit -- the values of every problem of a device model batch (a user's device fcn, a curve,
+    !> a formula, any wrapping model; not the built-in dense-quadratic family) AT x and their standard deviations under the
+    !> parameter covariance cov (nlh_dq_model_propagate): x(n, nprob), cov(n, n, nprob) as covariance_batch returns it,
+    !> val(m, nprob) = F(x), sd(m, nprob) = sqrt(J_i cov J_i^T), ONE standard deviation.  noise(nprob): a variance added
+    !> once to every row of its problem (absent: the confidence band; the fit's chi2: the prediction band).  A model made on
+    !> a plotting grid with y = 0 gives the model's values there.  x and cov are not changed.
+    subroutine lm_propagate_many(this, model, x, cov, val, sd, noise)
+        class(least_squares_solver), intent(inout) :: this
+        class(device_model_batch), intent(in) :: model
+        real(real64), intent(in), dimension(:,:) :: x
+        real(real64), intent(in), dimension(:,:,:) :: cov
+        real(real64), intent(out), dimension(:,:) :: val, sd
+        real(real64), intent(in), dimension(:), optional :: noise
+
+        real(c_double), allocatable, target :: vwork(:,:), nwork(:)
+        real(c_double), allocatable :: xwork(:,:), cwork(:,:,:), swork(:,:)
+        type(c_ptr) :: pnoise
+        integer(c_int) :: rc
+        integer(int32) :: m, n, count
+
+        if (.not.model%is_defined()) error stop NL_UNDEFINED_FUNCTION_ERROR
+        m = model%get_equation_count()
+        n = model%get_variable_count()
+        count = model%get_problem_count()
+        if (any(shape(x) /= [n, count])) error stop 3
+        if (any(shape(cov) /= [n, n, count])) error stop 4
+        if (any(shape(val) /= [m, count])) error stop 5
+        if (any(shape(sd) /= [m, count])) error stop 6
+        pnoise = c_null_ptr
+        if (present(noise)) then
+            if (size(noise) /= count) error stop 7
+            allocate(nwork(count), source = noise)
+            pnoise = c_loc(nwork)
+        end if
+        allocate(xwork(n, count), source = x)
+        allocate(cwork(n, n, count), source = cov)
+        allocate(vwork(m, count), swork(m, count))
+        rc = nlh_dq_model_propagate(nlh_default_handle(), model%c_handle(), xwork, cwork, pnoise, c_loc(vwork), swork)
+        if (rc /= 0) error stop rc
+        val = vwork
+        sd = swork
     end subroutine
 
     ! ---- constrained_equation_solver: the box -------------------------------------------------------------------
