@@ -69,13 +69,47 @@ class QrxPlanStep(C.Structure):
                                              "tcur", "oop")]
 
 
-# every symbol include/nonlin_hip.h declares: name -> (restype, argtypes)
 _H = C.c_void_p
+# a launcher that is a symbol of the library: DEVFCN's signature, (ctx, hip_stream, npoints, dprob, n, dX, m, dF | dJ) -> int
+_LAUNCHER = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p])
+# nlh_*_destroy and nlh_*_unwrap: what gives a pointer of the library's back to it
+_RELEASE = (None, [C.c_void_p])
+
+# The argument list of a one-call fit nlh_{curve,expr}_fit_batch{variant}{,_h} after the handle, as "name:type" -- the model,
+# the data, what the variant adds, the outputs.  The ctypes signatures below come from it, and so do the argument values of
+# DeviceSolver's fit path.  Types: i int32, d double, p void*, O nlh_options*, D double* (host), B nlh_iteration_behavior*,
+# S int32* (host); A and I are arrays of doubles and of int32 on the device (void*) or, in the _h form, on the host.
+FIT_MODEL = {"curve": "kind:i ncomp:i nbase:i", "expr": "expr:p"}
+FIT_DATA = "nprob:i m:i t:A shared_t:i y:A w:A analytic:i xl:D xu:D"
+FIT_VARIANT = {"": "",
+               "_pmap": "pm:p",
+               "_loss": "pm:p loss:i scale:A shared_scale:i",
+               "_pois": "pm:p mu_floor:d",
+               "_group": "g:p loss:i scale:A shared_scale:i stat:i mu_floor:d",
+               "_conv": "g:p pm:p cv:p loss:i scale:A shared_scale:i stat:i mu_floor:d",
+               "_sep": "g:p cv:p sp:p"}
+FIT_OUTPUTS = "x:A fvec:A sigma:A cov:A chi2:A rank:I ib:B status:S"
+
+
+def fit_args(model, variant):
+    """[(name, type)] of the arguments of nlh_<model>_fit_batch<variant> after the handle."""
+    spec = " ".join(("opts:O", FIT_MODEL[model], FIT_DATA, FIT_VARIANT[variant], FIT_OUTPUTS))
+    return [tuple(a.split(":")) for a in spec.split()]
+
+
+def _fit_signature(model, variant, host):
+    types = {"i": C.c_int32, "d": C.c_double, "p": C.c_void_p, "O": C.POINTER(Options), "D": c_double_p,
+             "B": C.POINTER(IterationBehavior), "S": c_int32_p,
+             "A": c_double_p if host else C.c_void_p, "I": c_int32_p if host else C.c_void_p}
+    return (C.c_int, [_H] + [types[t] for _, t in fit_args(model, variant)])
+
+
+# every symbol include/nonlin_hip.h declares: name -> (restype, argtypes); the 28 one-call fits are added below the table
 SYMBOLS = {
     "nlh_default_options": (None, [C.POINTER(Options)]),
     "nlh_format_status": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_char_p, C.c_int32]),
     "nlh_create": (C.c_int, [C.POINTER(_H), C.c_int32, C.c_void_p]),
-    "nlh_destroy": (None, [_H]),
+    "nlh_destroy": _RELEASE,
     "nlh_device_count": (C.c_int, []),
     "nlh_last_error": (C.c_char_p, [_H]),
     "nlh_version": (C.c_char_p, []),
@@ -147,14 +181,14 @@ SYMBOLS = {
     "nlh_poly_eval_complex_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_dq_model_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, C.c_double, C.POINTER(C.c_void_p)]),
     "nlh_device_set_create": (C.c_int, [C.POINTER(C.c_void_p), c_int32_p, C.c_int32]),
-    "nlh_device_set_destroy": (None, [C.c_void_p]),
+    "nlh_device_set_destroy": _RELEASE,
     "nlh_device_set_size": (C.c_int32, [C.c_void_p]),
     "nlh_device_set_handle": (C.c_void_p, [C.c_void_p, C.c_int32]),
     "nlh_device_set_last_error": (C.c_char_p, [C.c_void_p]),
     "nlh_dq_model_create_on": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, C.c_double,
                                          C.POINTER(C.c_void_p)]),
     "nlh_dq_model_device_count": (C.c_int32, [C.c_void_p]),
-    "nlh_dq_model_destroy": (None, [C.c_void_p]),
+    "nlh_dq_model_destroy": _RELEASE,
     "nlh_dq_model_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p]),
     "nlh_dq_model_eval": (C.c_int, [_H, C.c_void_p, c_double_p, c_double_p]),
     "nlh_dq_model_lm_solve": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, c_double_p, c_double_p,
@@ -212,8 +246,8 @@ SYMBOLS = {
     "nlh_quasi_newton_solve_batch_device_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, DEVFCN, DEVFCN,
                                                         C.c_void_p, c_double_p, c_double_p, C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_device_fcn_model_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "nlh_dq_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    "nlh_dq_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_dq_device_fcn": _LAUNCHER,
+    "nlh_dq_device_jac": _LAUNCHER,
     "nlh_covar": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
     "nlh_covar_lds_bytes": (C.c_int64, [C.c_int32]),
     "nlh_lm_covariance_batch_device": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, C.c_void_p,
@@ -224,22 +258,16 @@ SYMBOLS = {
                                     c_double_p, c_double_p, c_int32_p, c_double_p]),
     "nlh_dq_model_lm_covariance": (C.c_int, [_H, C.c_void_p, c_double_p, C.c_int32, C.c_double, c_double_p, c_double_p, c_int32_p,
                                              c_double_p]),
-    "nlh_curve_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    "nlh_curve_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_curve_device_fcn": _LAUNCHER,
+    "nlh_curve_device_jac": _LAUNCHER,
     "nlh_curve_nparams": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
     "nlh_curve_model_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p,
                                          c_double_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "nlh_curve_eval_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                        C.c_void_p]),
-    "nlh_curve_fit_batch": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                      C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_curve_fit_batch_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32,
-                                        c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
-                                        c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_expr_compile": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "nlh_expr_error": (C.c_char_p, []),
-    "nlh_expr_destroy": (None, [C.c_void_p]),
+    "nlh_expr_destroy": _RELEASE,
     "nlh_expr_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
     "nlh_expr_program": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_double_p]),
     "nlh_expr_masks": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
@@ -247,17 +275,11 @@ SYMBOLS = {
     "nlh_faddeeva": (C.c_int, [C.c_double, C.c_double, c_double_p, c_double_p]),
     "nlh_faddeeva_table": (None, [c_double_p, c_double_p]),
     "nlh_faddeeva_batch": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nlh_expr_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    "nlh_expr_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_expr_device_fcn": _LAUNCHER,
+    "nlh_expr_device_jac": _LAUNCHER,
     "nlh_expr_model_create": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32,
                                         C.POINTER(C.c_void_p)]),
     "nlh_expr_eval_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    "nlh_expr_fit_batch": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                     C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_expr_fit_batch_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p,
-                                       C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
-                                       c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_propagate": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_propagate_batch_device": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -269,156 +291,58 @@ SYMBOLS = {
                                       C.c_void_p, C.c_void_p]),
     "nlh_dq_model_propagate": (C.c_int, [_H, C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "nlh_pmap_create": (C.c_int, [C.c_int32, c_int32_p, c_int32_p, c_double_p, c_double_p, C.POINTER(C.c_void_p)]),
-    "nlh_pmap_destroy": (None, [C.c_void_p]),
+    "nlh_pmap_destroy": _RELEASE,
     "nlh_pmap_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p]),
     "nlh_pmap_tables": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_int32_p]),
     "nlh_pmap_wrap": (C.c_int, [_H, C.c_void_p, DEVFCN, DEVFCN, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
-    "nlh_pmap_unwrap": (None, [C.c_void_p]),
-    "nlh_pmap_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    "nlh_pmap_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_pmap_unwrap": _RELEASE,
+    "nlh_pmap_device_fcn": _LAUNCHER,
+    "nlh_pmap_device_jac": _LAUNCHER,
     "nlh_pmap_gather_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "nlh_pmap_expand_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "nlh_pmap_cov_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nlh_curve_fit_batch_pmap": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior),
-                                           c_int32_p]),
-    "nlh_curve_fit_batch_pmap_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p,
-                                             C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, c_double_p,
-                                             c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior),
-                                             c_int32_p]),
-    "nlh_expr_fit_batch_pmap": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
-                                          C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_expr_fit_batch_pmap_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p,
-                                            c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, c_double_p, c_double_p, c_double_p,
-                                            c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_pmap_model_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, c_double_p, C.c_int32, C.POINTER(C.c_void_p)]),
-    "nlh_curve_fit_batch_sep": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                          C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_curve_fit_batch_sep_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p,
-                                            C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
-                                            C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_expr_fit_batch_sep": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
-                                         C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior),
-                                         c_int32_p]),
-    "nlh_expr_fit_batch_sep_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p,
-                                           c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, c_double_p,
-                                           c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior),
-                                           c_int32_p]),
     "nlh_sep_model_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "nlh_sep_create": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, C.POINTER(C.c_void_p)]),
-    "nlh_sep_destroy": (None, [C.c_void_p]),
+    "nlh_sep_destroy": _RELEASE,
     "nlh_sep_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p]),
     "nlh_sep_tables": (C.c_int, [C.c_void_p, c_int32_p, c_int32_p]),
     "nlh_sep_wrap": (C.c_int, [_H, C.c_void_p, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "nlh_sep_unwrap": (None, [C.c_void_p]),
-    "nlh_sep_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    "nlh_sep_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_sep_unwrap": _RELEASE,
+    "nlh_sep_device_fcn": _LAUNCHER,
+    "nlh_sep_device_jac": _LAUNCHER,
     "nlh_sep_gather_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "nlh_sep_solve_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_loss_wrap": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "nlh_loss_unwrap": (None, [C.c_void_p]),
-    "nlh_loss_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    "nlh_loss_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_loss_unwrap": _RELEASE,
+    "nlh_loss_device_fcn": _LAUNCHER,
+    "nlh_loss_device_jac": _LAUNCHER,
     "nlh_loss_apply_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
-    "nlh_curve_fit_batch_loss": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32,
-                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_curve_fit_batch_loss_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p,
-                                             C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32,
-                                             c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
-                                             C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_expr_fit_batch_loss": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
-                                          C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_expr_fit_batch_loss_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p,
-                                            c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, c_double_p, C.c_int32,
-                                            c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
-                                            C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_loss_model_create": (C.c_int, [_H, C.c_void_p, C.c_int32, c_double_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "nlh_pois_wrap": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_double, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "nlh_pois_unwrap": (None, [C.c_void_p]),
-    "nlh_pois_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    "nlh_pois_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_pois_unwrap": _RELEASE,
+    "nlh_pois_device_fcn": _LAUNCHER,
+    "nlh_pois_device_jac": _LAUNCHER,
     "nlh_pois_apply_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
-    "nlh_curve_fit_batch_pois": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_double,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_curve_fit_batch_pois_h": (C.c_int, [_H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p,
-                                             C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_double,
-                                             c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
-                                             C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_expr_fit_batch_pois": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
-                                          C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_double,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_expr_fit_batch_pois_h": (C.c_int, [_H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p,
-                                            c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_double,
-                                            c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
-                                            C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_pois_model_create": (C.c_int, [_H, C.c_void_p, c_double_p, c_double_p, C.c_double, C.POINTER(C.c_void_p)]),
     "nlh_conv_wrap": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "nlh_conv_unwrap": (None, [C.c_void_p]),
-    "nlh_conv_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    "nlh_conv_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_conv_unwrap": _RELEASE,
+    "nlh_conv_device_fcn": _LAUNCHER,
+    "nlh_conv_device_jac": _LAUNCHER,
     "nlh_conv_apply_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "nlh_group_create": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.POINTER(C.c_void_p)]),
-    "nlh_group_destroy": (None, [C.c_void_p]),
+    "nlh_group_destroy": _RELEASE,
     "nlh_group_shape": (None, [C.c_void_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
     "nlh_group_index": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32]),
     "nlh_group_wrap": (C.c_int, [_H, C.c_void_p, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
-    "nlh_group_unwrap": (None, [C.c_void_p]),
-    "nlh_group_device_fcn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
-    "nlh_group_device_jac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "nlh_group_unwrap": _RELEASE,
+    "nlh_group_device_fcn": _LAUNCHER,
+    "nlh_group_device_jac": _LAUNCHER,
     "nlh_group_gather_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "nlh_group_expand_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "nlh_group_sigma_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "nlh_curve_fit_batch_group": (C.c_int, [
-        _H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-        C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_curve_fit_batch_group_h": (C.c_int, [
-        _H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-        c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, c_double_p, C.c_int32,
-        C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_expr_fit_batch_group": (C.c_int, [
-        _H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32,
-        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-        C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_expr_fit_batch_group_h": (C.c_int, [
-        _H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32,
-        c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_int32, c_double_p, C.c_int32,
-        C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p, C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_curve_fit_batch_conv": (C.c_int, [
-        _H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-        C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-        C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_curve_fit_batch_conv_h": (C.c_int, [
-        _H, C.POINTER(Options), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-        c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-        c_double_p, C.c_int32, C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
-        C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_expr_fit_batch_conv": (C.c_int, [
-        _H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32,
-        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-        C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-        C.POINTER(IterationBehavior), c_int32_p]),
-    "nlh_expr_fit_batch_conv_h": (C.c_int, [
-        _H, C.POINTER(Options), C.c_void_p, C.c_int32, C.c_int32,
-        c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-        c_double_p, C.c_int32, C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p,
-        C.POINTER(IterationBehavior), c_int32_p]),
     "nlh_conv_model_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, c_double_p, c_double_p, C.POINTER(C.c_void_p)]),
     "nlh_group_model_create": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "nlh_timing_enable": (None, [_H, C.c_int32]),
@@ -427,6 +351,8 @@ SYMBOLS = {
     "nlh_timing_samples": (C.c_int64, [_H, C.c_int32, C.POINTER(C.c_float), C.c_int64]),
     "nlh_kernel_name": (C.c_char_p, [C.c_int32]),
 }
+SYMBOLS.update({f"nlh_{model}_fit_batch{variant}{h}": _fit_signature(model, variant, bool(h))
+                for model in FIT_MODEL for variant in FIT_VARIANT for h in ("", "_h")})
 
 KERNEL_IDS = {
     "dq_residual": 0, "dq_panel": 1, "fd_jacobian": 2, "gram": 3, "gram_reduce": 4, "jtf": 5,
@@ -528,13 +454,32 @@ def _names(v):
     return ",".join(v) if isinstance(v, (tuple, list)) else str(v)
 
 
-class Expr:
+class Owner:
+    """Owns one pointer of the library's, the attribute _slot names: close() gives it back through the library's function
+    _free names, once; so does garbage collection."""
+    _slot, _free = "ptr", None
+
+    def close(self):
+        p = getattr(self, self._slot, None)
+        if p is not None and p.value:
+            getattr(self.lib, self._free)(p)
+            setattr(self, self._slot, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Expr(Owner):
     """A formula model (nlh_expr_compile: host code, needs no GPU): formula is an expression over the variables vars (1 .. 4
     names) and the parameters params (1 .. 32 names, in the order of x), e.g. Expr("a*exp(-k*t)+c", ("t",), ("a", "k", "c")).
     Operators + - * / ^ (a literal exponent), functions exp log sqrt sin cos tanh atan abs erf erfc erfcx of one argument
     and voigt(x, sigma, gamma) -- the unit-area Voigt profile, Gaussian sigma and Lorentzian half width gamma -- the constant
     pi.  Function names and pi are reserved: no variable or parameter may carry one.  Raises
     ValueError with the compiler's message ("col 17: unknown name 'foo'").  close() frees it (so does garbage collection)."""
+    _free = "nlh_expr_destroy"
 
     def __init__(self, formula, vars=("t",), params=()):
         self.lib = load()
@@ -569,28 +514,18 @@ class Expr:
             raise RuntimeError("nlh_expr_roots failed")
         return a, b
 
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.lib.nlh_expr_destroy(self.ptr)
-            self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # kinds of a parameter of a map (include/nonlin_hip.h: NLH_PMAP_*)
 PMAP_FREE, PMAP_FIXED, PMAP_TIED = 0, 1, 2
 
 
-class ParamMap:
+class ParamMap(Owner):
     """A parameter map (nlh_pmap_create: host code, needs no GPU): which of a model's nfull parameters are free, fixed at a
     per-problem value, or tied to another one by p_k = scale * p_src + offset.  fixed: the indices of the fixed parameters;
     tied: {k: (src, scale, offset)}.  E.g. ParamMap(7, fixed=(6,), tied={5: (2, 1.25, 0.0)}).  Raises ValueError for what the
     library refuses (an index out of range, a chain of ties, a tie with scale 0, no free parameter, ...).  Free unknown j
     is the j-th free parameter in ascending index.  close() frees it (so does garbage collection)."""
+    _free = "nlh_pmap_destroy"
 
     def __init__(self, nfull, fixed=(), tied=None):
         import numpy as np
@@ -641,19 +576,8 @@ class ParamMap:
             raise RuntimeError(f"nlh_pmap_tables returned {rc}")
         return kind, index, scale, offset, f2f
 
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.lib.nlh_pmap_destroy(self.ptr)
-            self.ptr = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Group:
+class Group(Owner):
     """A group of data sets for a global fit (nlh_group_create: host code, needs no GPU): nsets data sets of one model with
     nparams parameters, of which the ones listed in shared have one value for the whole group and the others are free per data
     set.  E.g. Group(3, shared=(1,), nsets=8): eight decays a*exp(-k*t)+c with one k.  The outer unknowns are nouter =
@@ -661,6 +585,7 @@ class Group:
     each in ascending index; index(set, k) is the outer unknown of parameter k of data set `set`.  Raises ValueError for what
     the library refuses (an index out of range or repeated, nsets < 1).  A group's Jacobian is dense to the solver: nsets of
     tens, not thousands.  close() frees it (so does garbage collection)."""
+    _free = "nlh_group_destroy"
 
     def __init__(self, nparams, shared=(), nsets=1):
         import numpy as np
@@ -693,22 +618,11 @@ class Group:
             raise IndexError(f"Group.index({set}, {k}): outside {self.nsets} data sets of {self.nparams} parameters")
         return j
 
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.lib.nlh_group_destroy(self.ptr)
-            self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 SEP_MAX_L = 32
 
 
-class Separable:
+class Separable(Owner):
     """Which of a model's nparams parameters are linear (nlh_sep_create: host code, needs no GPU), for a separable fit:
     variable projection solves for them exactly at every trial point, the solver iterates over the others.  linear: their
     indices, in any order.  E.g. Separable(5, linear=(0, 2, 4)) for a1*exp(-k1*t) + a2*exp(-k2*t) + c.  The nonlinear unknowns
@@ -716,6 +630,7 @@ class Separable:
     fixed nonlinear ones (DeviceSolver.sep_check measures it).  Raises ValueError for what the library refuses (no or more than
     32 linear parameters, none left nonlinear, an index out of range or repeated).  close() frees it (so does garbage
     collection)."""
+    _free = "nlh_sep_destroy"
 
     def __init__(self, nparams, linear=()):
         import numpy as np
@@ -757,17 +672,6 @@ class Separable:
         if rc:
             raise RuntimeError(f"nlh_sep_tables returned {rc}")
         return lin, nl
-
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.lib.nlh_sep_destroy(self.ptr)
-            self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # kinds of a robust loss (include/nonlin_hip.h: NLH_LOSS_*)
@@ -893,8 +797,9 @@ class Convolve:
         return ConvStruct(self.L, self.origin, self.ext, int(self.shared), kptr)
 
 
-class Handle:
+class Handle(Owner):
     """Owns an nlh_handle bound to a device and (optionally) an existing HIP stream."""
+    _slot, _free = "_h", "nlh_destroy"
 
     def __init__(self, device=0, stream=None):
         lib = load()
@@ -946,14 +851,3 @@ class Handle:
         buf = (C.c_float * n)()
         n = self.lib.nlh_timing_samples(self._h, kid, buf, n)
         return [float(buf[i]) for i in range(n)]
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.nlh_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -11,17 +11,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import (CURVE_GAUSS, CURVE_LORENTZ, CURVE_EXPDECAY, CURVE_KINDS, curve_kind, curve_nparams,  # noqa: F401
+                   Expr, ParamMap, Loss, Poisson, Convolve)
 
 # nlh_iteration_behavior as a numpy structured dtype (the batch forms of the one-variable solvers return arrays of it)
 IB_DTYPE = np.dtype([(k, np.int32) for k, _ in _lib.IterationBehavior._fields_])
-
-
-from ._lib import CURVE_GAUSS, CURVE_LORENTZ, CURVE_EXPDECAY, CURVE_KINDS, curve_kind, curve_nparams  # noqa: E402,F401
-from ._lib import Expr  # noqa: E402,F401
-from ._lib import ParamMap  # noqa: E402,F401
-from ._lib import Loss  # noqa: E402,F401
-from ._lib import Poisson  # noqa: E402,F401
-from ._lib import Convolve  # noqa: E402,F401
 
 
 def _chk(t, shape, name):
@@ -83,67 +77,12 @@ def house_plan(nprob, rows, ncA, ncE):
     return {"form": HOUSE_FORMS[rc], "tiles": int(tiles.value)}
 
 
-class _PmapCtx:
-    """The context of a map's wrapping launchers (nlh_pmap_ctx), with everything it points at kept alive."""
+class _Wrapped(_lib.Owner):
+    """The context of a pair of wrapping launchers (nlh_pmap_ctx, nlh_loss_ctx, ...: what an nlh_*_wrap made), with everything
+    it points at kept alive; free: the name of the nlh_*_unwrap that takes it back."""
 
-    def __init__(self, lib, ptr, keep):
-        self.lib, self.ptr, self._keep = lib, ptr, keep
-
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.lib.nlh_pmap_unwrap(self.ptr)
-            self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class _LossCtx(_PmapCtx):
-    """The context of a loss's wrapping launchers (nlh_loss_ctx), with everything it points at kept alive."""
-
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.lib.nlh_loss_unwrap(self.ptr)
-            self.ptr = C.c_void_p()
-
-
-class _PoisCtx(_PmapCtx):
-    """The context of the Poisson wrapping launchers (nlh_pois_ctx), with everything it points at kept alive."""
-
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.lib.nlh_pois_unwrap(self.ptr)
-            self.ptr = C.c_void_p()
-
-
-class _ConvCtx(_PmapCtx):
-    """The context of the convolving launchers (nlh_conv_ctx), with everything it points at kept alive."""
-
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.lib.nlh_conv_unwrap(self.ptr)
-            self.ptr = C.c_void_p()
-
-
-class _GroupCtx(_PmapCtx):
-    """The context of a group's wrapping launchers (nlh_group_ctx), with everything it points at kept alive."""
-
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.lib.nlh_group_unwrap(self.ptr)
-            self.ptr = C.c_void_p()
-
-
-class _SepCtx(_PmapCtx):
-    """The context of a separable fit's wrapping launchers (nlh_sep_ctx), with everything it points at kept alive."""
-
-    def close(self):
-        if getattr(self, "ptr", None) is not None and self.ptr.value:
-            self.lib.nlh_sep_unwrap(self.ptr)
-            self.ptr = C.c_void_p()
+    def __init__(self, lib, ptr, keep, free):
+        self.lib, self.ptr, self._keep, self._free = lib, ptr, keep, free
 
 
 class DeviceSolver:
@@ -160,6 +99,16 @@ class DeviceSolver:
 
     def check(self, rc, what):
         return self.h.check(rc, what)
+
+    def _checked(self, rc, what):
+        """A return code that must be 0: Handle.check's error, with the library's message, for a negative one."""
+        self.h.check(rc, what)
+        if rc:
+            raise RuntimeError(f"{what} returned {rc}")
+
+    def _call(self, name, *args):
+        """The library's entry point `name` on this solver's handle, checked."""
+        self._checked(getattr(self.lib, name)(self.h.ptr, *args), name)
 
     def model(self, A, b, gamma):
         """A device residual model behind host arrays on this solver's device (HostModel)."""
@@ -200,11 +149,8 @@ class DeviceSolver:
         ib = (_lib.IterationBehavior * nprob)()
         status = (C.c_int32 * nprob)()
         o = opts or self.options()
-        rc = self.lib.nlh_dq_lm_solve_batch(self.h.ptr, C.byref(o), nprob, m, n, A.data_ptr(), b.data_ptr(),
-                                            float(gamma), x.data_ptr(), fvec.data_ptr(), ib, status)
-        self.h.check(rc, "nlh_dq_lm_solve_batch")
-        if rc:
-            raise RuntimeError(f"nlh_dq_lm_solve_batch returned {rc}")
+        self._call("nlh_dq_lm_solve_batch", C.byref(o), nprob, m, n, A.data_ptr(), b.data_ptr(),
+                   float(gamma), x.data_ptr(), fvec.data_ptr(), ib, status)
         return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
 
     def newton_solve_batch(self, A, b, gamma, x, analytic=True, opts=None):
@@ -216,12 +162,8 @@ class DeviceSolver:
         ib = (_lib.IterationBehavior * nprob)()
         status = (C.c_int32 * nprob)()
         o = opts or self.options()
-        rc = self.lib.nlh_dq_newton_solve_batch(self.h.ptr, C.byref(o), nprob, n, A.data_ptr(), b.data_ptr(),
-                                                float(gamma), int(analytic), x.data_ptr(), fvec.data_ptr(),
-                                                ib, status)
-        self.h.check(rc, "nlh_dq_newton_solve_batch")
-        if rc:
-            raise RuntimeError(f"nlh_dq_newton_solve_batch returned {rc}")
+        self._call("nlh_dq_newton_solve_batch", C.byref(o), nprob, n, A.data_ptr(), b.data_ptr(),
+                   float(gamma), int(analytic), x.data_ptr(), fvec.data_ptr(), ib, status)
         return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
 
     def quasi_newton_solve_batch(self, A, b, gamma, x, analytic=True, opts=None, jdelta=5):
@@ -233,12 +175,8 @@ class DeviceSolver:
         ib = (_lib.IterationBehavior * nprob)()
         status = (C.c_int32 * nprob)()
         o = opts or self.options()
-        rc = self.lib.nlh_dq_quasi_newton_solve_batch(self.h.ptr, C.byref(o), int(jdelta), nprob, n, A.data_ptr(),
-                                                      b.data_ptr(), float(gamma), int(analytic), x.data_ptr(),
-                                                      fvec.data_ptr(), ib, status)
-        self.h.check(rc, "nlh_dq_quasi_newton_solve_batch")
-        if rc:
-            raise RuntimeError(f"nlh_dq_quasi_newton_solve_batch returned {rc}")
+        self._call("nlh_dq_quasi_newton_solve_batch", C.byref(o), int(jdelta), nprob, n, A.data_ptr(),
+                   b.data_ptr(), float(gamma), int(analytic), x.data_ptr(), fvec.data_ptr(), ib, status)
         return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
 
     def cls_solve_batch(self, A, b, gamma, x, opts=None, lower=None, upper=None, delta=1.0, stepscale=1.0):
@@ -254,12 +192,8 @@ class DeviceSolver:
         hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
         plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
         phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
-        rc = self.lib.nlh_dq_cls_solve_batch(self.h.ptr, C.byref(o), float(delta), float(stepscale), plo, phi, nprob, m, n,
-                                             A.data_ptr(), b.data_ptr(), float(gamma), x.data_ptr(), fvec.data_ptr(),
-                                             ib, status)
-        self.h.check(rc, "nlh_dq_cls_solve_batch")
-        if rc:
-            raise RuntimeError(f"nlh_dq_cls_solve_batch returned {rc}")
+        self._call("nlh_dq_cls_solve_batch", C.byref(o), float(delta), float(stepscale), plo, phi, nprob, m, n,
+                   A.data_ptr(), b.data_ptr(), float(gamma), x.data_ptr(), fvec.data_ptr(), ib, status)
         return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
 
     def bfgs_solve_batch(self, A, b, gamma, x, opts=None):
@@ -271,11 +205,8 @@ class DeviceSolver:
         status = (C.c_int32 * nprob)()
         fout = (C.c_double * nprob)()
         o = opts or self.options(max_evals=500)
-        rc = self.lib.nlh_dq_bfgs_solve_batch(self.h.ptr, C.byref(o), nprob, m, n, A.data_ptr(), b.data_ptr(), float(gamma),
-                                              x.data_ptr(), fout, ib, status)
-        self.h.check(rc, "nlh_dq_bfgs_solve_batch")
-        if rc:
-            raise RuntimeError(f"nlh_dq_bfgs_solve_batch returned {rc}")
+        self._call("nlh_dq_bfgs_solve_batch", C.byref(o), nprob, m, n, A.data_ptr(), b.data_ptr(), float(gamma),
+                   x.data_ptr(), fout, ib, status)
         return [float(v) for v in fout], [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
 
     # -- user-supplied device residuals (launchers) ------------------------------
@@ -328,11 +259,8 @@ class DeviceSolver:
         npts = t.shape[-1]
         _chk(t, (npts,) if shared else (nprob, npts), "t")
         y = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
-        rc = self.lib.nlh_curve_eval_batch(self.h.ptr, k, int(ncomp), int(baseline), nprob, npts, t.data_ptr(), int(shared),
-                                           x.data_ptr(), y.data_ptr())
-        self.h.check(rc, "nlh_curve_eval_batch")
-        if rc:
-            raise RuntimeError(f"nlh_curve_eval_batch returned {rc}")
+        self._call("nlh_curve_eval_batch", k, int(ncomp), int(baseline), nprob, npts, t.data_ptr(), int(shared),
+                   x.data_ptr(), y.data_ptr())
         return y
 
     @staticmethod
@@ -401,49 +329,48 @@ class DeviceSolver:
         nprob, m, shared = self._curve_data(t, y, weights)
         n = curve_nparams(k, ncomp, baseline)
         _chk(x0, (nprob, n), "x0")
+        return self._fit("curve", dict(kind=k, ncomp=int(ncomp), nbase=int(baseline)), n, m, t, shared, y, weights, x0, lower, upper,
+                         analytic, covariance, opts, pmap, loss, stat, group, conv, sep)
+
+    def _fit(self, model, head, n, m, t, shared, y, weights, x0, lower, upper, analytic, covariance, opts, pmap, loss, stat, group,
+             conv, sep):
+        """The one-call fit behind curve_fit_batch ("curve") and expr_fit_batch ("expr") once they have checked their data: what
+        the features refuse, the entry point they select, its outputs -- per group with a group, per data set without --, and
+        the call, its arguments in the order of _lib.fit_args.  head: the model's own arguments by name.  A feature that is
+        None gives what the entry points read as "none": a NULL pointer, kind 0, shared 0, stat 0, mu_floor 0.0."""
+        nprob = x0.shape[0]
         if sep is not None:
-            call = lambda *rest: self.lib.nlh_curve_fit_batch_sep(self.h.ptr, rest[0], k, int(ncomp), int(baseline), *rest[1:])
-            return self._sep_fit("nlh_curve_fit_batch_sep", call, sep, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights,
-                                 x0, lower, upper, analytic, covariance, opts)
-        if conv is not None:
-            call = lambda *rest: self.lib.nlh_curve_fit_batch_conv(self.h.ptr, rest[0], k, int(ncomp), int(baseline), *rest[1:])
-            return self._conv_fit("nlh_curve_fit_batch_conv", call, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
-                                  lower, upper, analytic, covariance, opts)
+            if pmap is not None or loss is not None or stat is not None:
+                raise ValueError("sep excludes pmap, loss and stat: a map, a loss and a statistic are nonlinear in the projected parameters")
+            if sep.nparams != n:
+                raise ValueError(f"sep is over {sep.nparams} parameters, the model has {n}")
         if group is not None:
-            call = lambda *rest: self.lib.nlh_curve_fit_batch_group(self.h.ptr, rest[0], k, int(ncomp), int(baseline), *rest[1:])
-            return self._group_fit("nlh_curve_fit_batch_group", call, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
-                                   lower, upper, analytic, covariance, opts)
+            if pmap is not None:
+                raise ValueError("group and pmap exclude each other: a map inside a group works through pmap_launchers and group_launchers")
+            if group.nparams != n:
+                raise ValueError(f"group is over {group.nparams} parameters, the model has {n}")
+            if nprob % group.nsets:
+                raise ValueError(f"{nprob} data sets: no multiple of the group's {group.nsets}")
         if pmap is not None and pmap.nfull != n:
-            raise ValueError(f"pmap maps {pmap.nfull} parameters, the model has {n}")
-        dev = y.device
-        x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, nprob, n)
+            raise ValueError(f"pmap maps {pmap.nfull} parameters, the {'formula' if model == 'expr' and conv is None else 'model'} has {n}")
+        variant = ("_sep" if sep is not None else "_conv" if conv is not None else "_group" if group is not None else
+                   "_pois" if stat is not None else "_loss" if loss is not None else "_pmap" if pmap is not None else "")
+        nsolve, nunk = (nprob // group.nsets, group.nouter) if group is not None else (nprob, n)
+        x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, nsolve, nunk)
         lo, hi, plo, phi = self._fit_bounds(lower, upper, n)
         o = opts or self.options()
+        dscale, sh = self._loss_scale(loss, nprob, y.device) if loss is not None else (None, 0)     # dscale, dk: alive across the call
+        cv, dk = self._conv_struct(conv, nprob, y.device) if conv is not None else (None, None)
         ptr = lambda a: a.data_ptr() if a is not None else None
-        if stat is not None:
-            rc = self.lib.nlh_curve_fit_batch_pois(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
-                                                   y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
-                                                   pmap.ptr if pmap is not None else None, stat.mu_floor,
-                                                   x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        elif loss is not None:
-            dscale, sh = self._loss_scale(loss, nprob, dev)
-            rc = self.lib.nlh_curve_fit_batch_loss(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
-                                                   y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
-                                                   pmap.ptr if pmap is not None else None, loss.kind, dscale.data_ptr(), sh,
-                                                   x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        elif pmap is None:
-            rc = self.lib.nlh_curve_fit_batch(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
-                                              y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
-                                              x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        else:
-            rc = self.lib.nlh_curve_fit_batch_pmap(self.h.ptr, C.byref(o), k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared,
-                                                   y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr,
-                                                   x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        name = "nlh_curve_fit_batch_pois" if stat is not None else "nlh_curve_fit_batch_loss" if loss is not None else "nlh_curve_fit_batch" if pmap is None else "nlh_curve_fit_batch_pmap"
-        self.h.check(rc, name)
-        if rc:
-            raise RuntimeError(f"{name} returned {rc}")
-        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nprob)], [int(status[p]) for p in range(nprob)])
+        obj = lambda a: a.ptr if a is not None else None
+        val = dict(head, opts=C.byref(o), nprob=nprob, m=m, t=t.data_ptr(), shared_t=shared, y=y.data_ptr(), w=ptr(weights),
+                   analytic=int(bool(analytic)), xl=plo, xu=phi, pm=obj(pmap), g=obj(group), sp=obj(sep),
+                   cv=C.byref(cv) if cv is not None else None, loss=loss.kind if loss is not None else 0, scale=ptr(dscale),
+                   shared_scale=sh, stat=1 if stat is not None else 0, mu_floor=stat.mu_floor if stat is not None else 0.0,
+                   x=x.data_ptr(), fvec=fvec.data_ptr(), sigma=ptr(sigma), cov=ptr(cov), chi2=ptr(chi2), rank=ptr(rank), ib=ib,
+                   status=status)
+        self._call(f"nlh_{model}_fit_batch{variant}", *[val[name] for name, _ in _lib.fit_args(model, variant)])
+        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nsolve)], [int(status[p]) for p in range(nsolve)])
 
     # -- formula models ----------------------------------------------------------
     @staticmethod
@@ -491,10 +418,7 @@ class DeviceSolver:
         npts = t.shape[-1]
         shared = self._expr_t(expr, t, nprob, npts)
         y = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
-        rc = self.lib.nlh_expr_eval_batch(self.h.ptr, expr.ptr, nprob, npts, t.data_ptr(), int(shared), x.data_ptr(), y.data_ptr())
-        self.h.check(rc, "nlh_expr_eval_batch")
-        if rc:
-            raise RuntimeError(f"nlh_expr_eval_batch returned {rc}")
+        self._call("nlh_expr_eval_batch", expr.ptr, nprob, npts, t.data_ptr(), int(shared), x.data_ptr(), y.data_ptr())
         return y
 
     def wofz_batch(self, z):
@@ -504,10 +428,7 @@ class DeviceSolver:
             raise ValueError("z must be complex128")
         re, im = z.real.contiguous().reshape(-1), z.imag.contiguous().reshape(-1)
         wr, wi = torch.empty_like(re), torch.empty_like(re)
-        rc = self.lib.nlh_faddeeva_batch(self.h.ptr, re.numel(), re.data_ptr(), im.data_ptr(), wr.data_ptr(), wi.data_ptr())
-        self.h.check(rc, "nlh_faddeeva_batch")
-        if rc:
-            raise RuntimeError(f"nlh_faddeeva_batch returned {rc}")
+        self._call("nlh_faddeeva_batch", re.numel(), re.data_ptr(), im.data_ptr(), wr.data_ptr(), wi.data_ptr())
         return torch.complex(wr, wi).reshape(z.shape)
 
     def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None,
@@ -521,49 +442,9 @@ class DeviceSolver:
         nprob, m, shared = self._expr_data(expr, t, y, weights)
         n = expr.nparams
         _chk(x0, (nprob, n), "x0")
-        if sep is not None:                                           # (a Separable, e.g. Separable.for_expr(expr, linear=("a", "c")): as in curve_fit_batch)
-            call = lambda *rest: self.lib.nlh_expr_fit_batch_sep(self.h.ptr, rest[0], expr.ptr, *rest[1:])
-            return self._sep_fit("nlh_expr_fit_batch_sep", call, sep, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights,
-                                 x0, lower, upper, analytic, covariance, opts)
-        if conv is not None:                                          # (a Convolve: as in curve_fit_batch)
-            call = lambda *rest: self.lib.nlh_expr_fit_batch_conv(self.h.ptr, rest[0], expr.ptr, *rest[1:])
-            return self._conv_fit("nlh_expr_fit_batch_conv", call, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
-                                  lower, upper, analytic, covariance, opts)
-        if group is not None:
-            call = lambda *rest: self.lib.nlh_expr_fit_batch_group(self.h.ptr, rest[0], expr.ptr, *rest[1:])
-            return self._group_fit("nlh_expr_fit_batch_group", call, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0,
-                                   lower, upper, analytic, covariance, opts)
-        if pmap is not None and pmap.nfull != n:
-            raise ValueError(f"pmap maps {pmap.nfull} parameters, the formula has {n}")
-        dev = y.device
-        x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, nprob, n)
-        lo, hi, plo, phi = self._fit_bounds(lower, upper, n)
-        o = opts or self.options()
-        ptr = lambda a: a.data_ptr() if a is not None else None
-        if stat is not None:
-            rc = self.lib.nlh_expr_fit_batch_pois(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(),
-                                                  ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr if pmap is not None else None,
-                                                  stat.mu_floor,
-                                                  x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        elif loss is not None:
-            dscale, sh = self._loss_scale(loss, nprob, dev)
-            rc = self.lib.nlh_expr_fit_batch_loss(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(),
-                                                  ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr if pmap is not None else None,
-                                                  loss.kind, dscale.data_ptr(), sh,
-                                                  x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        elif pmap is None:
-            rc = self.lib.nlh_expr_fit_batch(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(), ptr(weights),
-                                             int(bool(analytic)), plo, phi,
-                                             x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        else:
-            rc = self.lib.nlh_expr_fit_batch_pmap(self.h.ptr, C.byref(o), expr.ptr, nprob, m, t.data_ptr(), shared, y.data_ptr(),
-                                                  ptr(weights), int(bool(analytic)), plo, phi, pmap.ptr,
-                                                  x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        name = "nlh_expr_fit_batch_pois" if stat is not None else "nlh_expr_fit_batch_loss" if loss is not None else "nlh_expr_fit_batch" if pmap is None else "nlh_expr_fit_batch_pmap"
-        self.h.check(rc, name)
-        if rc:
-            raise RuntimeError(f"{name} returned {rc}")
-        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nprob)], [int(status[p]) for p in range(nprob)])
+        # conv (a Convolve) and sep (a Separable, e.g. Separable.for_expr(expr, linear=("a", "c"))): as in curve_fit_batch
+        return self._fit("expr", dict(expr=expr.ptr), n, m, t, shared, y, weights, x0, lower, upper, analytic, covariance, opts,
+                         pmap, loss, stat, group, conv, sep)
 
     # -- parameter maps ------------------------------------------------------------
     def pmap_launchers(self, pmap, fcn, jac, ctx, full):
@@ -576,25 +457,14 @@ class DeviceSolver:
         garbage collection)."""
         shared = full.dim() == 1
         _chk(full, (pmap.nfull,) if shared else (full.shape[0], pmap.nfull), "full")
-        out = C.c_void_p()
-        rc = self.lib.nlh_pmap_wrap(self.h.ptr, pmap.ptr, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), full.data_ptr(),
-                                    int(shared), C.byref(out))
-        self.h.check(rc, "nlh_pmap_wrap")
-        if rc:
-            raise RuntimeError(f"nlh_pmap_wrap returned {rc}")
-        wrapped = _PmapCtx(self.lib, out, (pmap, fcn, jac, ctx, full))
-        return (C.cast(self.lib.nlh_pmap_device_fcn, _lib.DEVFCN),
-                C.cast(self.lib.nlh_pmap_device_jac, _lib.DEVFCN) if jac is not None else None, wrapped)
+        return self._wrap("pmap", (pmap, fcn, jac, ctx, full), fcn, jac, ctx, (pmap.ptr,), (full.data_ptr(), int(shared)))
 
     def pmap_gather(self, pmap, full):
         """The free unknowns x [nprob, nfree] of full parameters [nprob, nfull] (nlh_pmap_gather_batch)."""
         nprob = full.shape[0]
         _chk(full, (nprob, pmap.nfull), "full")
         x = torch.empty((nprob, pmap.nfree), dtype=torch.float64, device=full.device)
-        rc = self.lib.nlh_pmap_gather_batch(self.h.ptr, pmap.ptr, nprob, full.data_ptr(), x.data_ptr())
-        self.h.check(rc, "nlh_pmap_gather_batch")
-        if rc:
-            raise RuntimeError(f"nlh_pmap_gather_batch returned {rc}")
+        self._call("nlh_pmap_gather_batch", pmap.ptr, nprob, full.data_ptr(), x.data_ptr())
         return x
 
     def pmap_expand(self, pmap, x, full):
@@ -605,10 +475,7 @@ class DeviceSolver:
         shared = full.dim() == 1
         _chk(full, (pmap.nfull,) if shared else (nprob, pmap.nfull), "full")
         p = torch.empty((nprob, pmap.nfull), dtype=torch.float64, device=x.device)
-        rc = self.lib.nlh_pmap_expand_batch(self.h.ptr, pmap.ptr, nprob, x.data_ptr(), full.data_ptr(), int(shared), p.data_ptr())
-        self.h.check(rc, "nlh_pmap_expand_batch")
-        if rc:
-            raise RuntimeError(f"nlh_pmap_expand_batch returned {rc}")
+        self._call("nlh_pmap_expand_batch", pmap.ptr, nprob, x.data_ptr(), full.data_ptr(), int(shared), p.data_ptr())
         return p
 
     def pmap_cov(self, pmap, cov, sigma, fail=None):
@@ -618,11 +485,8 @@ class DeviceSolver:
         _chk(cov, (nprob, pmap.nfree, pmap.nfree), "cov"); _chk(sigma, (nprob, pmap.nfree), "sigma")
         cf = torch.empty((nprob, pmap.nfull, pmap.nfull), dtype=torch.float64, device=cov.device)
         sf = torch.empty((nprob, pmap.nfull), dtype=torch.float64, device=cov.device)
-        rc = self.lib.nlh_pmap_cov_batch(self.h.ptr, pmap.ptr, nprob, cov.data_ptr(), sigma.data_ptr(),
-                                         fail.data_ptr() if fail is not None else None, cf.data_ptr(), sf.data_ptr())
-        self.h.check(rc, "nlh_pmap_cov_batch")
-        if rc:
-            raise RuntimeError(f"nlh_pmap_cov_batch returned {rc}")
+        self._call("nlh_pmap_cov_batch", pmap.ptr, nprob, cov.data_ptr(), sigma.data_ptr(),
+                   fail.data_ptr() if fail is not None else None, cf.data_ptr(), sf.data_ptr())
         return cf, sf
 
     # -- global fits ---------------------------------------------------------------
@@ -634,14 +498,7 @@ class DeviceSolver:
         with m = group.nsets * m rows: y, weights and fvec [nprob, m] are [ngroup, nsets * m] as they stand.  jac is None
         without an inner Jacobian launcher (pass jac=None to the solver: forward differences over the outer unknowns).  Keep
         the returned ctx alive while solving; ctx.close() frees it (so does garbage collection)."""
-        out = C.c_void_p()
-        rc = self.lib.nlh_group_wrap(self.h.ptr, group.ptr, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), C.byref(out))
-        self.h.check(rc, "nlh_group_wrap")
-        if rc:
-            raise RuntimeError(f"nlh_group_wrap returned {rc}")
-        wrapped = _GroupCtx(self.lib, out, (group, fcn, jac, ctx))
-        return (C.cast(self.lib.nlh_group_device_fcn, _lib.DEVFCN),
-                C.cast(self.lib.nlh_group_device_jac, _lib.DEVFCN) if jac is not None else None, wrapped)
+        return self._wrap("group", (group, fcn, jac, ctx), fcn, jac, ctx, (group.ptr,))
 
     def group_gather(self, group, full):
         """The outer unknowns x [ngroup, nouter] of per-data-set parameters [ngroup * nsets, nparams] (nlh_group_gather_batch):
@@ -652,10 +509,7 @@ class DeviceSolver:
             raise ValueError(f"full has {nprob} rows: no multiple of the group's {group.nsets} data sets")
         ngroup = nprob // group.nsets
         x = torch.empty((ngroup, group.nouter), dtype=torch.float64, device=full.device)
-        rc = self.lib.nlh_group_gather_batch(self.h.ptr, group.ptr, ngroup, full.data_ptr(), x.data_ptr())
-        self.h.check(rc, "nlh_group_gather_batch")
-        if rc:
-            raise RuntimeError(f"nlh_group_gather_batch returned {rc}")
+        self._call("nlh_group_gather_batch", group.ptr, ngroup, full.data_ptr(), x.data_ptr())
         return x
 
     def group_expand(self, group, x):
@@ -663,10 +517,7 @@ class DeviceSolver:
         ngroup = x.shape[0]
         _chk(x, (ngroup, group.nouter), "x")
         p = torch.empty((ngroup * group.nsets, group.nparams), dtype=torch.float64, device=x.device)
-        rc = self.lib.nlh_group_expand_batch(self.h.ptr, group.ptr, ngroup, x.data_ptr(), p.data_ptr())
-        self.h.check(rc, "nlh_group_expand_batch")
-        if rc:
-            raise RuntimeError(f"nlh_group_expand_batch returned {rc}")
+        self._call("nlh_group_expand_batch", group.ptr, ngroup, x.data_ptr(), p.data_ptr())
         return p
 
     def group_sigma(self, group, sigma, fail=None):
@@ -675,96 +526,9 @@ class DeviceSolver:
         ngroup = sigma.shape[0]
         _chk(sigma, (ngroup, group.nouter), "sigma")
         sf = torch.empty((ngroup * group.nsets, group.nparams), dtype=torch.float64, device=sigma.device)
-        rc = self.lib.nlh_group_sigma_batch(self.h.ptr, group.ptr, ngroup, sigma.data_ptr(), fail.data_ptr() if fail is not None else None,
-                                            sf.data_ptr())
-        self.h.check(rc, "nlh_group_sigma_batch")
-        if rc:
-            raise RuntimeError(f"nlh_group_sigma_batch returned {rc}")
+        self._call("nlh_group_sigma_batch", group.ptr, ngroup, sigma.data_ptr(), fail.data_ptr() if fail is not None else None,
+                   sf.data_ptr())
         return sf
-
-    def _group_fit(self, name, call, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0, lower, upper, analytic,
-                   covariance, opts):
-        """The one-call global fit behind curve_fit_batch / expr_fit_batch with group=; call(opts, nprob, m, ...) is the entry
-        point with the model's own arguments bound."""
-        if pmap is not None:
-            raise ValueError("group and pmap exclude each other: a map inside a group works through pmap_launchers and group_launchers")
-        if group.nparams != n:
-            raise ValueError(f"group is over {group.nparams} parameters, the model has {n}")
-        if nprob % group.nsets:
-            raise ValueError(f"{nprob} data sets: no multiple of the group's {group.nsets}")
-        ngroup, no = nprob // group.nsets, group.nouter
-        dev = y.device
-        x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, ngroup, no)
-        lo, hi, plo, phi = self._fit_bounds(lower, upper, n)
-        o = opts or self.options()
-        ptr = lambda a: a.data_ptr() if a is not None else None
-        dscale, sh = self._loss_scale(loss, nprob, dev) if loss is not None else (None, 0)
-        rc = call(C.byref(o), nprob, m, t.data_ptr(), shared, y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi, group.ptr,
-                  loss.kind if loss is not None else 0, ptr(dscale), sh, 1 if stat is not None else 0,
-                  stat.mu_floor if stat is not None else 0.0, x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank),
-                  ib, status)
-        self.h.check(rc, name)
-        if rc:
-            raise RuntimeError(f"{name} returned {rc}")
-        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(ngroup)], [int(status[p]) for p in range(ngroup)])
-
-    def _conv_fit(self, name, call, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0, lower, upper, analytic,
-                  covariance, opts):
-        """The one-call fit with an instrument response behind curve_fit_batch / expr_fit_batch with conv=; call(opts, nprob, m,
-        ...) is the entry point with the model's own arguments bound.  What comes back is per group with a group, per data set
-        without."""
-        if group is not None and pmap is not None:
-            raise ValueError("group and pmap exclude each other: a map inside a group works through pmap_launchers and group_launchers")
-        if group is not None and group.nparams != n:
-            raise ValueError(f"group is over {group.nparams} parameters, the model has {n}")
-        if group is not None and nprob % group.nsets:
-            raise ValueError(f"{nprob} data sets: no multiple of the group's {group.nsets}")
-        if pmap is not None and pmap.nfull != n:
-            raise ValueError(f"pmap maps {pmap.nfull} parameters, the model has {n}")
-        nsolve, nunk = (nprob // group.nsets, group.nouter) if group is not None else (nprob, n)
-        dev = y.device
-        x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, nsolve, nunk)
-        lo, hi, plo, phi = self._fit_bounds(lower, upper, n)
-        o = opts or self.options()
-        ptr = lambda a: a.data_ptr() if a is not None else None
-        dscale, sh = self._loss_scale(loss, nprob, dev) if loss is not None else (None, 0)
-        cv, dk = self._conv_struct(conv, nprob, dev)
-        rc = call(C.byref(o), nprob, m, t.data_ptr(), shared, y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
-                  group.ptr if group is not None else None, pmap.ptr if pmap is not None else None, C.byref(cv),
-                  loss.kind if loss is not None else 0, ptr(dscale), sh, 1 if stat is not None else 0,
-                  stat.mu_floor if stat is not None else 0.0, x.data_ptr(), fvec.data_ptr(), ptr(sigma), ptr(cov), ptr(chi2), ptr(rank),
-                  ib, status)
-        self.h.check(rc, name)
-        if rc:
-            raise RuntimeError(f"{name} returned {rc}")
-        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nsolve)], [int(status[p]) for p in range(nsolve)])
-
-    def _sep_fit(self, name, call, sep, conv, group, pmap, loss, stat, nprob, m, n, t, shared, y, weights, x0, lower, upper, analytic,
-                 covariance, opts):
-        """The one-call separable fit behind curve_fit_batch / expr_fit_batch with sep=; call(opts, nprob, m, ...) is the entry
-        point with the model's own arguments bound."""
-        if pmap is not None or loss is not None or stat is not None:
-            raise ValueError("sep excludes pmap, loss and stat: a map, a loss and a statistic are nonlinear in the projected parameters")
-        if sep.nparams != n:
-            raise ValueError(f"sep is over {sep.nparams} parameters, the model has {n}")
-        if group is not None and group.nparams != n:
-            raise ValueError(f"group is over {group.nparams} parameters, the model has {n}")
-        if group is not None and nprob % group.nsets:
-            raise ValueError(f"{nprob} data sets: no multiple of the group's {group.nsets}")
-        nsolve, nunk = (nprob // group.nsets, group.nouter) if group is not None else (nprob, n)
-        dev = y.device
-        x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, nsolve, nunk)
-        lo, hi, plo, phi = self._fit_bounds(lower, upper, n)
-        o = opts or self.options()
-        ptr = lambda a: a.data_ptr() if a is not None else None
-        cv, dk = self._conv_struct(conv, nprob, dev) if conv is not None else (None, None)
-        rc = call(C.byref(o), nprob, m, t.data_ptr(), shared, y.data_ptr(), ptr(weights), int(bool(analytic)), plo, phi,
-                  group.ptr if group is not None else None, C.cast(C.byref(cv), C.c_void_p) if cv is not None else None, sep.ptr, x.data_ptr(), fvec.data_ptr(), ptr(sigma),
-                  ptr(cov), ptr(chi2), ptr(rank), ib, status)
-        self.h.check(rc, name)
-        if rc:
-            raise RuntimeError(f"{name} returned {rc}")
-        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nsolve)], [int(status[p]) for p in range(nsolve)])
 
     # -- robust losses -------------------------------------------------------------
     def _loss_scale(self, loss, nprob, dev=None):
@@ -780,15 +544,7 @@ class DeviceSolver:
         None without an inner Jacobian launcher (pass jac=None to the solver: forward differences of the wrapped residual).
         Keep the returned ctx alive while solving; ctx.close() frees it (so does garbage collection)."""
         dscale, sh = self._loss_scale(loss, len(loss.scale) if nprob is None or loss.shared else nprob)
-        out = C.c_void_p()
-        rc = self.lib.nlh_loss_wrap(self.h.ptr, loss.kind, dscale.data_ptr(), sh, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx),
-                                    C.byref(out))
-        self.h.check(rc, "nlh_loss_wrap")
-        if rc:
-            raise RuntimeError(f"nlh_loss_wrap returned {rc}")
-        wrapped = _LossCtx(self.lib, out, (loss, fcn, jac, ctx, dscale))
-        return (C.cast(self.lib.nlh_loss_device_fcn, _lib.DEVFCN),
-                C.cast(self.lib.nlh_loss_device_jac, _lib.DEVFCN) if jac is not None else None, wrapped)
+        return self._wrap("loss", (loss, fcn, jac, ctx, dscale), fcn, jac, ctx, (loss.kind, dscale.data_ptr(), sh))
 
     def loss_apply(self, loss, r):
         """(out, g, wgt) of raw residuals r [nprob, m] under a Loss (nlh_loss_apply_batch): the transformed residual rho~, the
@@ -798,11 +554,8 @@ class DeviceSolver:
         _chk(r, (nprob, m), "r")
         dscale, sh = self._loss_scale(loss, nprob, r.device)
         out, g, wgt = (torch.empty_like(r) for _ in range(3))
-        rc = self.lib.nlh_loss_apply_batch(self.h.ptr, loss.kind, nprob, m, dscale.data_ptr(), sh, r.data_ptr(), out.data_ptr(),
-                                           g.data_ptr(), wgt.data_ptr())
-        self.h.check(rc, "nlh_loss_apply_batch")
-        if rc:
-            raise RuntimeError(f"nlh_loss_apply_batch returned {rc}")
+        self._call("nlh_loss_apply_batch", loss.kind, nprob, m, dscale.data_ptr(), sh, r.data_ptr(), out.data_ptr(),
+                   g.data_ptr(), wgt.data_ptr())
         return out, g, wgt
 
     # -- Poisson likelihood fits ---------------------------------------------------
@@ -818,15 +571,8 @@ class DeviceSolver:
         _chk(y, (nprob, m), "y")
         if weights is not None:
             _chk(weights, (nprob, m), "weights")
-        out = C.c_void_p()
-        rc = self.lib.nlh_pois_wrap(self.h.ptr, y.data_ptr(), weights.data_ptr() if weights is not None else None, stat.mu_floor,
-                                    self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), C.byref(out))
-        self.h.check(rc, "nlh_pois_wrap")
-        if rc:
-            raise RuntimeError(f"nlh_pois_wrap returned {rc}")
-        wrapped = _PoisCtx(self.lib, out, (stat, fcn, jac, ctx, y, weights))
-        return (C.cast(self.lib.nlh_pois_device_fcn, _lib.DEVFCN),
-                C.cast(self.lib.nlh_pois_device_jac, _lib.DEVFCN) if jac is not None else None, wrapped)
+        return self._wrap("pois", (stat, fcn, jac, ctx, y, weights), fcn, jac, ctx,
+                          (y.data_ptr(), weights.data_ptr() if weights is not None else None, stat.mu_floor))
 
     def pois_apply(self, stat, r, y, weights=None):
         """(out, g, dev) of raw residuals r = model - y [nprob, m] for counts y under a Poisson (nlh_pois_apply_batch): the
@@ -836,11 +582,8 @@ class DeviceSolver:
         if weights is not None:
             _chk(weights, (nprob, m), "weights")
         out, g, dev = (torch.empty_like(r) for _ in range(3))
-        rc = self.lib.nlh_pois_apply_batch(self.h.ptr, nprob, m, y.data_ptr(), weights.data_ptr() if weights is not None else None,
-                                           stat.mu_floor, r.data_ptr(), out.data_ptr(), g.data_ptr(), dev.data_ptr())
-        self.h.check(rc, "nlh_pois_apply_batch")
-        if rc:
-            raise RuntimeError(f"nlh_pois_apply_batch returned {rc}")
+        self._call("nlh_pois_apply_batch", nprob, m, y.data_ptr(), weights.data_ptr() if weights is not None else None,
+                   stat.mu_floor, r.data_ptr(), out.data_ptr(), g.data_ptr(), dev.data_ptr())
         return out, g, dev
 
     # -- instrument-response fits ---------------------------------------------------
@@ -863,15 +606,8 @@ class DeviceSolver:
         if weights is not None:
             _chk(weights, (nprob, m), "weights")
         cv, dk = self._conv_struct(conv, nprob, y.device)
-        out = C.c_void_p()
-        rc = self.lib.nlh_conv_wrap(self.h.ptr, C.byref(cv), y.data_ptr(), weights.data_ptr() if weights is not None else None,
-                                    self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), C.byref(out))
-        self.h.check(rc, "nlh_conv_wrap")
-        if rc:
-            raise RuntimeError(f"nlh_conv_wrap returned {rc}")
-        wrapped = _ConvCtx(self.lib, out, (conv, dk, fcn, jac, ctx, y, weights))
-        return (C.cast(self.lib.nlh_conv_device_fcn, _lib.DEVFCN),
-                C.cast(self.lib.nlh_conv_device_jac, _lib.DEVFCN) if jac is not None else None, wrapped)
+        return self._wrap("conv", (conv, dk, fcn, jac, ctx, y, weights), fcn, jac, ctx,
+                          (C.byref(cv), y.data_ptr(), weights.data_ptr() if weights is not None else None))
 
     def conv_apply(self, conv, v):
         """The bare convolution of columns v [nprob, m] or [nprob, ncol, m] under a Convolve (nlh_conv_apply_batch), e.g. of
@@ -883,10 +619,7 @@ class DeviceSolver:
         _chk(v, v.shape, "v")
         cv, dk = self._conv_struct(conv, nprob, v.device)
         out = torch.empty_like(v)
-        rc = self.lib.nlh_conv_apply_batch(self.h.ptr, C.byref(cv), nprob, m, ncol, v.data_ptr(), out.data_ptr())
-        self.h.check(rc, "nlh_conv_apply_batch")
-        if rc:
-            raise RuntimeError(f"nlh_conv_apply_batch returned {rc}")
+        self._call("nlh_conv_apply_batch", C.byref(cv), nprob, m, ncol, v.data_ptr(), out.data_ptr())
         torch.cuda.current_stream(v.device).synchronize()             # (dk goes with this frame)
         return out
 
@@ -900,23 +633,14 @@ class DeviceSolver:
         solving; ctx.close() frees its scratch."""
         if jac is None:
             raise ValueError("sep_launchers: the inner Jacobian launcher is required (its linear columns are the basis)")
-        out = C.c_void_p()
-        rc = self.lib.nlh_sep_wrap(self.h.ptr, sep.ptr, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), C.byref(out))
-        self.h.check(rc, "nlh_sep_wrap")
-        if rc:
-            raise RuntimeError(f"nlh_sep_wrap returned {rc}")
-        wrapped = _SepCtx(self.lib, out, (sep, fcn, jac, ctx))
-        return (C.cast(self.lib.nlh_sep_device_fcn, _lib.DEVFCN), C.cast(self.lib.nlh_sep_device_jac, _lib.DEVFCN), wrapped)
+        return self._wrap("sep", (sep, fcn, jac, ctx), fcn, jac, ctx, (sep.ptr,))
 
     def sep_gather(self, sep, full):
         """The nonlinear unknowns alpha [nprob, nnonlin] of full parameters [nprob, nparams] (nlh_sep_gather_batch)."""
         nprob = full.shape[0]
         _chk(full, (nprob, sep.nparams), "full")
         x = torch.empty((nprob, sep.nnonlin), dtype=torch.float64, device=full.device)
-        rc = self.lib.nlh_sep_gather_batch(self.h.ptr, sep.ptr, nprob, full.data_ptr(), x.data_ptr())
-        self.h.check(rc, "nlh_sep_gather_batch")
-        if rc:
-            raise RuntimeError(f"nlh_sep_gather_batch returned {rc}")
+        self._call("nlh_sep_gather_batch", sep.ptr, nprob, full.data_ptr(), x.data_ptr())
         return x
 
     def sep_solve(self, sep_ctx, m, alpha):
@@ -928,10 +652,7 @@ class DeviceSolver:
         _chk(alpha, (nprob, sep.nnonlin), "alpha")
         full = torch.empty((nprob, sep.nparams), dtype=torch.float64, device=alpha.device)
         rank = torch.empty((nprob,), dtype=torch.int32, device=alpha.device)
-        rc = self.lib.nlh_sep_solve_batch(self.h.ptr, sep_ctx.ptr, nprob, int(m), alpha.data_ptr(), full.data_ptr(), rank.data_ptr())
-        self.h.check(rc, "nlh_sep_solve_batch")
-        if rc:
-            raise RuntimeError(f"nlh_sep_solve_batch returned {rc}")
+        self._call("nlh_sep_solve_batch", sep_ctx.ptr, nprob, int(m), alpha.data_ptr(), full.data_ptr(), rank.data_ptr())
         return full, rank
 
     def sep_check(self, sep, fcn, jac, ctx, m, full):
@@ -948,9 +669,19 @@ class DeviceSolver:
         return float(torch.max(torch.abs(J1 - J2))) / scale if scale > 0.0 else float(torch.max(torch.abs(J2)))
 
     def _ctxp(self, ctx):
-        if isinstance(ctx, _PmapCtx):
+        if isinstance(ctx, _Wrapped):
             return ctx.ptr
         return ctx if isinstance(ctx, (int, C.c_void_p)) or ctx is None else C.cast(C.byref(ctx), C.c_void_p)
+
+    def _wrap(self, kind, keep, fcn, jac, ctx, before, after=()):
+        """The tail of every *_launchers: nlh_<kind>_wrap around the inner (fcn, jac, ctx), its other arguments before and
+        after them, then (fcn, jac -- None without an inner one --, ctx) of the wrapping launchers; ctx owns what the wrap
+        made and keeps `keep` alive."""
+        out = C.c_void_p()
+        self._call(f"nlh_{kind}_wrap", *before, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), *after, C.byref(out))
+        launcher = lambda f: C.cast(getattr(self.lib, f"nlh_{kind}_device_{f}"), _lib.DEVFCN)
+        return (launcher("fcn"), launcher("jac") if jac is not None else None,
+                _Wrapped(self.lib, out, keep, f"nlh_{kind}_unwrap"))
 
     def lm_solve_batch_device(self, fcn, ctx, m, x, jac=None, opts=None):
         """least_squares_solver%solve on x.shape[0] problems of a USER'S device residual (launcher fcn, context ctx).
@@ -961,11 +692,8 @@ class DeviceSolver:
         ib = (_lib.IterationBehavior * nprob)()
         status = (C.c_int32 * nprob)()
         o = opts or self.options()
-        rc = self.lib.nlh_lm_solve_batch_device(self.h.ptr, C.byref(o), nprob, m, n, self._devfcn(fcn), self._devfcn(jac),
-                                                self._ctxp(ctx), x.data_ptr(), fvec.data_ptr(), ib, status)
-        self.h.check(rc, "nlh_lm_solve_batch_device")
-        if rc:
-            raise RuntimeError(f"nlh_lm_solve_batch_device returned {rc}")
+        self._call("nlh_lm_solve_batch_device", C.byref(o), nprob, m, n, self._devfcn(fcn), self._devfcn(jac),
+                   self._ctxp(ctx), x.data_ptr(), fvec.data_ptr(), ib, status)
         return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
 
     def cls_solve_batch_device(self, fcn, ctx, m, x, jac=None, opts=None, lower=None, upper=None, delta=1.0, stepscale=1.0):
@@ -981,12 +709,8 @@ class DeviceSolver:
         hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
         plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
         phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
-        rc = self.lib.nlh_cls_solve_batch_device(self.h.ptr, C.byref(o), float(delta), float(stepscale), plo, phi, nprob, m, n,
-                                                 self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), x.data_ptr(), fvec.data_ptr(),
-                                                 ib, status)
-        self.h.check(rc, "nlh_cls_solve_batch_device")
-        if rc:
-            raise RuntimeError(f"nlh_cls_solve_batch_device returned {rc}")
+        self._call("nlh_cls_solve_batch_device", C.byref(o), float(delta), float(stepscale), plo, phi, nprob, m, n,
+                   self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), x.data_ptr(), fvec.data_ptr(), ib, status)
         return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
 
     def square_solve_batch_device(self, fcn, ctx, x, jac=None, opts=None, broyden=False, jdelta=5):
@@ -997,18 +721,11 @@ class DeviceSolver:
         ib = (_lib.IterationBehavior * nprob)()
         status = (C.c_int32 * nprob)()
         o = opts or self.options()
+        tail = (nprob, n, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), x.data_ptr(), fvec.data_ptr(), ib, status)
         if broyden:
-            name = "nlh_quasi_newton_solve_batch_device"
-            rc = self.lib.nlh_quasi_newton_solve_batch_device(self.h.ptr, C.byref(o), int(jdelta), nprob, n, self._devfcn(fcn),
-                                                              self._devfcn(jac), self._ctxp(ctx), x.data_ptr(), fvec.data_ptr(),
-                                                              ib, status)
+            self._call("nlh_quasi_newton_solve_batch_device", C.byref(o), int(jdelta), *tail)
         else:
-            name = "nlh_newton_solve_batch_device"
-            rc = self.lib.nlh_newton_solve_batch_device(self.h.ptr, C.byref(o), nprob, n, self._devfcn(fcn), self._devfcn(jac),
-                                                        self._ctxp(ctx), x.data_ptr(), fvec.data_ptr(), ib, status)
-        self.h.check(rc, name)
-        if rc:
-            raise RuntimeError(f"{name} returned {rc}")
+            self._call("nlh_newton_solve_batch_device", C.byref(o), *tail)
         return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
 
     def bfgs_solve_batch_device(self, fcn, ctx, x, grad=None, opts=None):
@@ -1021,11 +738,8 @@ class DeviceSolver:
         status = (C.c_int32 * nprob)()
         fout = (C.c_double * nprob)()
         o = opts or self.options(max_evals=500)
-        rc = self.lib.nlh_bfgs_solve_batch_device(self.h.ptr, C.byref(o), nprob, n, self._devfcn(fcn), self._devfcn(grad), self._ctxp(ctx),
-                                                  x.data_ptr(), fout, ib, status)
-        self.h.check(rc, "nlh_bfgs_solve_batch_device")
-        if rc:
-            raise RuntimeError(f"nlh_bfgs_solve_batch_device returned {rc}")
+        self._call("nlh_bfgs_solve_batch_device", C.byref(o), nprob, n, self._devfcn(fcn), self._devfcn(grad), self._ctxp(ctx),
+                   x.data_ptr(), fout, ib, status)
         return [float(v) for v in fout], [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
 
     def nelder_mead_solve_batch_device(self, fcn, ctx, x, simplex=None, init_size=1.0, opts=None):
@@ -1041,12 +755,9 @@ class DeviceSolver:
         status = (C.c_int32 * nprob)()
         fout = (C.c_double * nprob)()
         o = opts or self.options(max_evals=500)
-        rc = self.lib.nlh_nelder_mead_solve_batch_device(self.h.ptr, C.byref(o), float(init_size), nprob, n, self._devfcn(fcn),
-                                                         self._ctxp(ctx), x.data_ptr(), simplex.data_ptr() if simplex is not None else None,
-                                                         0 if simplex is None else 1, fout, ib, status)
-        self.h.check(rc, "nlh_nelder_mead_solve_batch_device")
-        if rc:
-            raise RuntimeError(f"nlh_nelder_mead_solve_batch_device returned {rc}")
+        self._call("nlh_nelder_mead_solve_batch_device", C.byref(o), float(init_size), nprob, n, self._devfcn(fcn),
+                   self._ctxp(ctx), x.data_ptr(), simplex.data_ptr() if simplex is not None else None,
+                   0 if simplex is None else 1, fout, ib, status)
         return [float(v) for v in fout], [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
 
     def _root1v_batch(self, entry, fcns, ctx, lim, x, opts):
@@ -1058,12 +769,8 @@ class DeviceSolver:
         status = np.zeros(nprob, dtype=np.int32)
         fout = np.zeros(nprob, dtype=np.float64)
         o = opts or self.options()
-        rc = getattr(self.lib, entry)(self.h.ptr, C.byref(o), nprob, *[self._devfcn(f) for f in fcns], self._ctxp(ctx),
-                                      lim.data_ptr(), x.data_ptr(), fout.ctypes.data_as(_lib.c_double_p), ibc,
-                                      status.ctypes.data_as(_lib.c_int32_p))
-        self.h.check(rc, entry)
-        if rc:
-            raise RuntimeError(f"{entry} returned {rc}")
+        self._call(entry, C.byref(o), nprob, *[self._devfcn(f) for f in fcns], self._ctxp(ctx), lim.data_ptr(), x.data_ptr(),
+                   fout.ctypes.data_as(_lib.c_double_p), ibc, status.ctypes.data_as(_lib.c_int32_p))
         return fout, status, ib
 
     def brent_solve_batch_device(self, fcn, ctx, lim, x, opts=None):
@@ -1082,11 +789,8 @@ class DeviceSolver:
         nprob, n = x.shape
         _chk(x, (nprob, n), "x")
         J = torch.empty((nprob, n, m), dtype=torch.float64, device=x.device)
-        rc = self.lib.nlh_fd_jacobian_device(self.h.ptr, nprob, m, n, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx),
-                                             x.data_ptr(), fv.data_ptr() if fv is not None else None, J.data_ptr())
-        self.h.check(rc, "nlh_fd_jacobian_device")
-        if rc:
-            raise RuntimeError(f"nlh_fd_jacobian_device returned {rc}")
+        self._call("nlh_fd_jacobian_device", nprob, m, n, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx),
+                   x.data_ptr(), fv.data_ptr() if fv is not None else None, J.data_ptr())
         return J
 
     # -- stage-level kernels (parity tests, roofline) --------------------------
@@ -1205,10 +909,7 @@ class DeviceSolver:
         _chk(B, (nprob, n, n), "B")
         Q = torch.empty_like(B)
         Rt = torch.empty_like(B)
-        rc = self.h.check(self.lib.nlh_qr_factor_full(self.h.ptr, nprob, n, B.data_ptr(), Q.data_ptr(), Rt.data_ptr()),
-                          "nlh_qr_factor_full")
-        if rc:
-            raise RuntimeError(f"nlh_qr_factor_full returned {rc}")
+        self._call("nlh_qr_factor_full", nprob, n, B.data_ptr(), Q.data_ptr(), Rt.data_ptr())
         return Q, Rt
 
     def house_steps(self, A, E):
@@ -1228,18 +929,13 @@ class DeviceSolver:
         """In place: Q1 R1 = Q R + u v^T."""
         nprob, n, _ = Q.shape
         _chk(Q, (nprob, n, n), "Q"); _chk(Rt, (nprob, n, n), "Rt"); _chk(u, (nprob, n), "u"); _chk(v, (nprob, n), "v")
-        rc = self.h.check(self.lib.nlh_qr_rank1_update(self.h.ptr, nprob, n, Q.data_ptr(), Rt.data_ptr(), u.data_ptr(),
-                                                       v.data_ptr()), "nlh_qr_rank1_update")
-        if rc:
-            raise RuntimeError(f"nlh_qr_rank1_update returned {rc}")
+        self._call("nlh_qr_rank1_update", nprob, n, Q.data_ptr(), Rt.data_ptr(), u.data_ptr(), v.data_ptr())
         return Q, Rt
 
     def solve_upper(self, Rt, x):
         nprob, n, _ = Rt.shape
         _chk(Rt, (nprob, n, n), "Rt"); _chk(x, (nprob, n), "x")
-        rc = self.h.check(self.lib.nlh_solve_upper(self.h.ptr, nprob, n, Rt.data_ptr(), x.data_ptr()), "nlh_solve_upper")
-        if rc:
-            raise RuntimeError(f"nlh_solve_upper returned {rc}")
+        self._call("nlh_solve_upper", nprob, n, Rt.data_ptr(), x.data_ptr())
         return x
 
     def poly_fit_batch(self, x, y, order, thru_zero=False):
@@ -1247,11 +943,7 @@ class DeviceSolver:
         nprob, npts = x.shape
         _chk(x, (nprob, npts), "x"); _chk(y, (nprob, npts), "y")
         coef = torch.empty((nprob, order + 1), dtype=torch.float64, device=x.device)
-        rc = self.lib.nlh_poly_fit_batch(self.h.ptr, nprob, npts, int(order), int(thru_zero), x.data_ptr(), y.data_ptr(),
-                                         coef.data_ptr())
-        self.h.check(rc, "nlh_poly_fit_batch")
-        if rc:
-            raise RuntimeError(f"nlh_poly_fit_batch returned {rc}")
+        self._call("nlh_poly_fit_batch", nprob, npts, int(order), int(thru_zero), x.data_ptr(), y.data_ptr(), coef.data_ptr())
         return coef
 
     def poly_roots_batch(self, coef):
@@ -1263,10 +955,7 @@ class DeviceSolver:
         order = ncoef - 1
         z = torch.empty((nprob, order, 2), dtype=torch.float64, device=coef.device)
         info = torch.zeros((nprob,), dtype=torch.int32, device=coef.device)
-        rc = self.lib.nlh_poly_roots_batch(self.h.ptr, nprob, order, coef.data_ptr(), z.data_ptr(), info.data_ptr())
-        self.h.check(rc, "nlh_poly_roots_batch")
-        if rc:
-            raise RuntimeError(f"nlh_poly_roots_batch returned {rc}")
+        self._call("nlh_poly_roots_batch", nprob, order, coef.data_ptr(), z.data_ptr(), info.data_ptr())
         return torch.view_as_complex(z), info
 
     def poly_eval_batch(self, coef, x):
@@ -1285,9 +974,7 @@ class DeviceSolver:
             _chk(x, (nprob, npts), "x")
             y = torch.empty_like(x)
             rc = self.lib.nlh_poly_eval_batch(self.h.ptr, nprob, ncoef - 1, npts, coef.data_ptr(), x.data_ptr(), y.data_ptr())
-        self.h.check(rc, "nlh_poly_eval_batch")
-        if rc:
-            raise RuntimeError(f"nlh_poly_eval_batch returned {rc}")
+        self._checked(rc, "nlh_poly_eval_batch")                     # (the complex entry reports under this name too)
         return y
 
     def covar(self, R, ipvt, tol=None):
@@ -1301,11 +988,8 @@ class DeviceSolver:
             raise ValueError("ipvt: expected a contiguous int32 GPU tensor of shape [nprob, n]")
         cov = torch.empty((nprob, n, n), dtype=torch.float64, device=R.device)
         rank = torch.empty((nprob,), dtype=torch.int32, device=R.device)
-        rc = self.lib.nlh_covar(self.h.ptr, nprob, n, R.data_ptr(), ipvt.data_ptr(), 0.0 if tol is None else float(tol),
-                                cov.data_ptr(), rank.data_ptr())
-        self.h.check(rc, "nlh_covar")
-        if rc:
-            raise RuntimeError(f"nlh_covar returned {rc}")
+        self._call("nlh_covar", nprob, n, R.data_ptr(), ipvt.data_ptr(), 0.0 if tol is None else float(tol),
+                   cov.data_ptr(), rank.data_ptr())
         return cov, rank
 
     def lm_covariance_batch_device(self, fcn, ctx, m, x, jac=None, scaled=True, tol=None):
@@ -1320,13 +1004,9 @@ class DeviceSolver:
         sigma = torch.empty((nprob, n), dtype=torch.float64, device=dev)
         rank = torch.empty((nprob,), dtype=torch.int32, device=dev)
         chi2 = torch.empty((nprob,), dtype=torch.float64, device=dev)
-        rc = self.lib.nlh_lm_covariance_batch_device(self.h.ptr, nprob, int(m), n, self._devfcn(fcn), self._devfcn(jac),
-                                                     self._ctxp(ctx), x.data_ptr(), int(bool(scaled)),
-                                                     0.0 if tol is None else float(tol), cov.data_ptr(), sigma.data_ptr(),
-                                                     rank.data_ptr(), chi2.data_ptr())
-        self.h.check(rc, "nlh_lm_covariance_batch_device")
-        if rc:
-            raise RuntimeError(f"nlh_lm_covariance_batch_device returned {rc}")
+        self._call("nlh_lm_covariance_batch_device", nprob, int(m), n, self._devfcn(fcn), self._devfcn(jac),
+                   self._ctxp(ctx), x.data_ptr(), int(bool(scaled)), 0.0 if tol is None else float(tol), cov.data_ptr(),
+                   sigma.data_ptr(), rank.data_ptr(), chi2.data_ptr())
         return cov, sigma, rank, chi2
 
     # -- confidence and prediction bands: the covariance propagated through a function of the parameters ---------------
@@ -1346,10 +1026,7 @@ class DeviceSolver:
         _chk(J, (npoints, n, m), "J")
         pn = self._band_args(npoints, n, cov, noise)
         sd = torch.empty((npoints, m), dtype=torch.float64, device=J.device)
-        rc = self.lib.nlh_propagate(self.h.ptr, npoints, m, n, J.data_ptr(), cov.data_ptr(), pn, sd.data_ptr())
-        self.h.check(rc, "nlh_propagate")
-        if rc:
-            raise RuntimeError(f"nlh_propagate returned {rc}")
+        self._call("nlh_propagate", npoints, m, n, J.data_ptr(), cov.data_ptr(), pn, sd.data_ptr())
         return sd
 
     def propagate_batch_device(self, fcn, ctx, m, x, cov, jac=None, noise=None):
@@ -1367,11 +1044,8 @@ class DeviceSolver:
         m = int(m)
         val = torch.empty((nprob, m), dtype=torch.float64, device=x.device)
         sd = torch.empty((nprob, m), dtype=torch.float64, device=x.device)
-        rc = self.lib.nlh_propagate_batch_device(self.h.ptr, nprob, m, n, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx),
-                                                 x.data_ptr(), cov.data_ptr(), pn, val.data_ptr(), sd.data_ptr())
-        self.h.check(rc, "nlh_propagate_batch_device")
-        if rc:
-            raise RuntimeError(f"nlh_propagate_batch_device returned {rc}")
+        self._call("nlh_propagate_batch_device", nprob, m, n, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx),
+                   x.data_ptr(), cov.data_ptr(), pn, val.data_ptr(), sd.data_ptr())
         return val, sd
 
     def curve_band(self, kind, x, cov, t, ncomp=1, baseline=-1, noise=None):
@@ -1391,11 +1065,8 @@ class DeviceSolver:
         pn = self._band_args(nprob, n, cov, noise)
         y = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
         sd = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
-        rc = self.lib.nlh_curve_band_batch(self.h.ptr, k, int(ncomp), int(baseline), nprob, npts, t.data_ptr(), int(shared),
-                                           x.data_ptr(), cov.data_ptr(), pn, y.data_ptr(), sd.data_ptr())
-        self.h.check(rc, "nlh_curve_band_batch")
-        if rc:
-            raise RuntimeError(f"nlh_curve_band_batch returned {rc}")
+        self._call("nlh_curve_band_batch", k, int(ncomp), int(baseline), nprob, npts, t.data_ptr(), int(shared),
+                   x.data_ptr(), cov.data_ptr(), pn, y.data_ptr(), sd.data_ptr())
         return y, sd
 
     def expr_band(self, expr, x, cov, t, noise=None):
@@ -1410,11 +1081,8 @@ class DeviceSolver:
         pn = self._band_args(nprob, n, cov, noise)
         y = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
         sd = torch.empty((nprob, npts), dtype=torch.float64, device=x.device)
-        rc = self.lib.nlh_expr_band_batch(self.h.ptr, expr.ptr, nprob, npts, t.data_ptr(), int(shared), x.data_ptr(),
-                                          cov.data_ptr(), pn, y.data_ptr(), sd.data_ptr())
-        self.h.check(rc, "nlh_expr_band_batch")
-        if rc:
-            raise RuntimeError(f"nlh_expr_band_batch returned {rc}")
+        self._call("nlh_expr_band_batch", expr.ptr, nprob, npts, t.data_ptr(), int(shared), x.data_ptr(),
+                   cov.data_ptr(), pn, y.data_ptr(), sd.data_ptr())
         return y, sd
 
     def chol_rank1(self, Rt, u, downdate=False):
@@ -1433,10 +1101,7 @@ class DeviceSolver:
         _chk(B, (nprob, n, n), "B")
         Rt = torch.empty_like(B)
         info = (C.c_int32 * nprob)()
-        rc = self.lib.nlh_bf_chol_factor(self.h.ptr, nprob, n, B.data_ptr(), Rt.data_ptr(), info)
-        self.h.check(rc, "nlh_bf_chol_factor")
-        if rc:
-            raise RuntimeError(f"nlh_bf_chol_factor returned {rc}")
+        self._call("nlh_bf_chol_factor", nprob, n, B.data_ptr(), Rt.data_ptr(), info)
         return Rt, [int(v) for v in info]
 
     def bf_chol_form(self, n):
@@ -1448,10 +1113,7 @@ class DeviceSolver:
         """x <- (R^T R)^-1 x in place, Rt [nprob, n, n] row-major upper factors, x [nprob, n]."""
         nprob, n, _ = Rt.shape
         _chk(Rt, (nprob, n, n), "Rt"); _chk(x, (nprob, n), "x")
-        rc = self.lib.nlh_bf_solve_cholesky(self.h.ptr, nprob, n, Rt.data_ptr(), x.data_ptr())
-        self.h.check(rc, "nlh_bf_solve_cholesky")
-        if rc:
-            raise RuntimeError(f"nlh_bf_solve_cholesky returned {rc}")
+        self._call("nlh_bf_solve_cholesky", nprob, n, Rt.data_ptr(), x.data_ptr())
         return x
 
     def lu_solve(self, LU, ipvt, b):
@@ -1461,10 +1123,11 @@ class DeviceSolver:
         return b
 
 
-class HostModel:
+class HostModel(_lib.Owner):
     """A device residual model behind HOST arrays (nlh_dq_model): the boundary object the Fortran shim's
     `device_model_batch` wraps.  A [nprob, n, m] (each problem column-major m x n), b [nprob, m] are numpy arrays;
     the copies live on one device (`owner` a DeviceSolver) or are dealt over the devices of a DeviceSet."""
+    _slot, _free = "_md", "nlh_dq_model_destroy"
 
     def __init__(self, owner, A, b, gamma):
         import numpy as np
@@ -1481,9 +1144,18 @@ class HostModel:
             rc = self.lib.nlh_dq_model_create_on(owner.ptr, self.nprob, self.m, self.n, dp(A), dp(b), float(gamma), C.byref(self._md))
         else:
             rc = self.lib.nlh_dq_model_create(owner.h.ptr, self.nprob, self.m, self.n, dp(A), dp(b), float(gamma), C.byref(self._md))
-        owner.check(rc, "nlh_dq_model_create")
+        self._checked(rc, "nlh_dq_model_create")
+
+    def _checked(self, rc, what):
+        """A return code that must be 0: the owner's error, with the library's message, for a negative one."""
+        self.owner.check(rc, what)
         if rc != 0:
-            raise RuntimeError(f"nlh_dq_model_create: {rc}")
+            raise RuntimeError(f"{what}: {rc}")
+
+    @property
+    def _hptr(self):
+        """The handle the model's entry points take: the solver's, or NULL for a model dealt over a DeviceSet."""
+        return None if isinstance(self.owner, DeviceSet) else self.owner.h.ptr
 
     @property
     def shares(self):
@@ -1496,11 +1168,8 @@ class HostModel:
         ib = (_lib.IterationBehavior * self.nprob)()
         st = (C.c_int32 * self.nprob)()
         dp = lambda a: a.ctypes.data_as(_lib.c_double_p)
-        hptr = None if isinstance(self.owner, DeviceSet) else self.owner.h.ptr
-        rc = fn(hptr, C.byref(opts if opts is not None else _lib.default_options()), self._md, *extra, dp(x), dp(f), ib, st)
-        self.owner.check(rc, fn.__name__)
-        if rc != 0:
-            raise RuntimeError(f"{fn.__name__}: {rc}")
+        rc = fn(self._hptr, C.byref(opts if opts is not None else _lib.default_options()), self._md, *extra, dp(x), dp(f), ib, st)
+        self._checked(rc, fn.__name__)
         return x, f, [ib[p].as_dict() for p in range(self.nprob)], [int(st[p]) for p in range(self.nprob)]
 
     def lm_solve(self, x, opts=None):
@@ -1534,12 +1203,9 @@ class HostModel:
         ib = (_lib.IterationBehavior * self.nprob)()
         st = (C.c_int32 * self.nprob)()
         dp = lambda a: a.ctypes.data_as(_lib.c_double_p)
-        hptr = None if isinstance(self.owner, DeviceSet) else self.owner.h.ptr
-        rc = self.lib.nlh_dq_model_bfgs_solve(hptr, C.byref(opts if opts is not None else _lib.default_options()), self._md,
+        rc = self.lib.nlh_dq_model_bfgs_solve(self._hptr, C.byref(opts if opts is not None else _lib.default_options()), self._md,
                                               dp(x), dp(f), dp(fo), ib, st)
-        self.owner.check(rc, "nlh_dq_model_bfgs_solve")
-        if rc != 0:
-            raise RuntimeError(f"nlh_dq_model_bfgs_solve: {rc}")
+        self._checked(rc, "nlh_dq_model_bfgs_solve")
         return x, f, fo, [ib[p].as_dict() for p in range(self.nprob)], [int(st[p]) for p in range(self.nprob)]
 
     def lm_covariance(self, x, scaled=True, tol=None):
@@ -1554,30 +1220,17 @@ class HostModel:
         rank = np.empty(self.nprob, dtype=np.int32)
         chi2 = np.empty(self.nprob)
         dp = lambda a: a.ctypes.data_as(_lib.c_double_p)
-        hptr = None if isinstance(self.owner, DeviceSet) else self.owner.h.ptr
-        rc = self.lib.nlh_dq_model_lm_covariance(hptr, self._md, dp(x), int(bool(scaled)), 0.0 if tol is None else float(tol),
+        rc = self.lib.nlh_dq_model_lm_covariance(self._hptr, self._md, dp(x), int(bool(scaled)), 0.0 if tol is None else float(tol),
                                                  dp(cov), dp(sigma), rank.ctypes.data_as(_lib.c_int32_p), dp(chi2))
-        self.owner.check(rc, "nlh_dq_model_lm_covariance")
-        if rc != 0:
-            raise RuntimeError(f"nlh_dq_model_lm_covariance: {rc}")
+        self._checked(rc, "nlh_dq_model_lm_covariance")
         return cov, sigma, rank, chi2
 
-    def close(self):
-        if getattr(self, "_md", None) is not None and self._md.value:
-            self.lib.nlh_dq_model_destroy(self._md)
-            self._md = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceSet:
+class DeviceSet(_lib.Owner):
     """nlh_device_set: one handle per listed device inside ONE process; models created on it are dealt over the devices
     block-cyclically and solved by one host thread per device (no collective).  devices=None: every visible device;
     an id may repeat (two shares on one GPU)."""
+    _slot, _free = "_s", "nlh_device_set_destroy"
 
     def __init__(self, devices=None):
         self.lib = _lib.load()
@@ -1607,14 +1260,3 @@ class DeviceSet:
 
     def model(self, A, b, gamma):
         return HostModel(self, A, b, gamma)
-
-    def close(self):
-        if getattr(self, "_s", None) is not None and self._s.value:
-            self.lib.nlh_device_set_destroy(self._s)
-            self._s = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
