@@ -779,18 +779,22 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
  *   unary := ('-'|'+') unary | power           power := atom ('^' ['-'] number)?
  *   atom  := number | name | func '(' expr (',' expr)* ')' | '(' expr ')'
  * number: what strtod reads in the C locale from a digit or '.'; name: a variable, a parameter or pi (the only named
- * constant); func: exp log sqrt sin cos tanh atan abs erf erfc erfcx voigt.  voigt takes exactly three arguments
- * (x, sigma, gamma), every other function one; another count is an error that names its column.  vars: 1 .. 4 comma-separated names; params: 1 .. 32, their order is
+ * constant); func: exp log sqrt sin cos tanh atan abs erf erfc erfcx voigt pow atan2 min max where.  voigt takes exactly
+ * three arguments (x, sigma, gamma), where three (c, a, b: a where c >= 0, else b), pow(a, b), atan2(y, x), min(a, b) and
+ * max(a, b) two, every other function one; another count is an error that names its column.  '^' takes a literal only: an
+ * exponent that is a parameter or an expression is pow's second argument.  vars: 1 .. 4 comma-separated names; params: 1 .. 32, their order is
  * the order of x.  A name is [A-Za-z_][A-Za-z0-9_]*, not pi and not a function.
  * THE PROGRAM IS THE POSTFIX OF THE PARSE TREE: no constant folding, no reassociation, no sharing of common subexpressions
  * (a unary '+' emits nothing; every literal and every pi is a constant of its own).  Instructions (op, arg):
  *   CONST i (consts[i])   VAR v   PARAM k   NEG   ADD   SUB   MUL   DIV   (b on top of the stack, a below it)
  *   IPOW k   an integer literal exponent, 2 <= |k| <= 16          POWC i   any other literal exponent c = consts[i]
  *   EXP LOG SQRT SIN COS TANH ATAN ABS   ERF ERFC ERFCX   VOIGT (pops x, sigma, gamma -- gamma on top -- and pushes one)
+ *   POW ATAN2 MIN MAX (b on top, a below it)   WHERE (pops c, a, b -- b on top -- and pushes one)
  * THE ARITHMETIC IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation, the device library's
  * functions -- so that a restatement in any IEEE language reproduces bit for bit an exp-free formula: one without a
- * library function (POWC EXP LOG SIN COS TANH ATAN ERF ERFC ERFCX).  VOIGT is not one: a formula whose only function is
- * voigt stays in the bit-exact class (the Faddeeva function below is stated arithmetic, not a library call).
+ * library function (POWC EXP LOG SIN COS TANH ATAN ERF ERFC ERFCX POW ATAN2).  VOIGT is not one: a formula whose only
+ * function is voigt stays in the bit-exact class (the Faddeeva function below is stated arithmetic, not a library call).
+ * MIN, MAX and WHERE are selections and stay in it too.
  *   values     the obvious operation per instruction;  POWC: pow(a, c);  NEG, ABS: sign operations;
  *              IPOW k: v = a; v = v*a (|k| - 1 times in all); for k < 0 then v = 1.0/v
  *   column j of the Jacobian: forward mode with STRUCTURAL zeros.  A node's tangent is absent (Z) or a double: CONST, VAR,
@@ -818,9 +822,25 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
  *           (sums left to right).  w is evaluated once per pass over the program and serves the value and every column
  *           the pass carries.  gs is computed through a cancellation in the Lorentzian wings (|x| >> sigma): its error
  *           is small against V(0)/sigma, not against itself.
+ *     MAX   s = b > a;  v = s ? b : a               MIN   s = b < a;  v = s ? b : a
+ *           a tie keeps a (max(-0.0, 0.0) is -0.0); a NaN b is dropped, a NaN a stays.  Tangent: the selected operand's,
+ *           s ? db : da, and +0.0 where the selected operand is Z and the other is not
+ *     WHERE s = c >= 0.0;  v = s ? a : b            (-0.0 selects a, NaN selects b)
+ *           tangent: the selected branch's, s ? da : db, +0.0 where that one is Z; dc is never read.  Both branches are
+ *           evaluated; the selection is a select, never a multiplication, so a NaN or Inf in the branch not taken
+ *           reaches neither the value nor the tangent.  A node whose only tangent is c's is present and +0.0.
+ *     ATAN2 v = atan2(a, b);  den = a*a + b*b:      (b*da - a*db)/den | (b*da)/den | -((a*db)/den)
+ *     POW   v = pow(a, b)
+ *           ga = b*pow(a, b - 1.0), computed only where a has a tangent
+ *           gb = v == 0.0 ? 0.0 : v*log(a), computed only where b has a tangent
+ *           ta = da == 0.0 ? 0.0 : ga*da;  tb = gb*db;        ta + tb | ta | tb
+ *           The two guards make a = 0 usable: gb is its limit 0 for b > 0 instead of 0*-inf, and an infinite ga
+ *           (b < 1) against a zero da is 0.  a < 0 with a tangent in b is outside the domain (log(a): NaN).
+ *           (the device library's pow, atan2, log)
  *     a root that is Z writes +0.0
- *   "structural": the compiler records per instruction the 32-bit mask of the parameters its subtree names; the tangent of a
- *   node for column j is present exactly when bit j of that mask is set, whatever the values are.
+ *   "structural": the compiler records per instruction the 32-bit mask of the parameters its subtree names -- WHERE's
+ *   condition included --; the tangent of a node for column j is present exactly when bit j of that mask is set, whatever
+ *   the values are.
  *   residual   r = f - y;  then r = w*r when weights are given; every Jacobian entry is multiplied once by w then (a row of
  *              weight 0 is exactly 0: the padding rule of the curve models)
  * No sum crosses a row: a row's bits do not depend on the launch shape, the workgroup form (NLH_EXPR_FORM = row | flat,
@@ -852,6 +872,11 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
 #define NLH_EXPR_ERFC  19
 #define NLH_EXPR_ERFCX 20
 #define NLH_EXPR_VOIGT 21
+#define NLH_EXPR_POW   22
+#define NLH_EXPR_ATAN2 23
+#define NLH_EXPR_MIN   24
+#define NLH_EXPR_MAX   25
+#define NLH_EXPR_WHERE 26
 typedef struct nlh_expr nlh_expr;
 /* Compile (host code only, thread-safe).  Errors -- a syntax error, an unknown name, a name in both lists, a duplicate or
  * reserved name ("'erf' is a function"), a wrong number of arguments, an empty list or item, too many names, more than 256 instructions, 64 constants or a stack deeper than 16
@@ -866,8 +891,9 @@ void nlh_expr_shape(const nlh_expr *e, int32_t *nvar, int32_t *nparams, int32_t 
 int nlh_expr_program(const nlh_expr *e, int32_t *op, int32_t *arg, double *consts);
 int nlh_expr_masks(const nlh_expr *e, uint32_t *mask);
 /* Operand roots [ninstr] (either may be NULL): aroot, the instruction that produced the lower operand of a binary
- * instruction or VOIGT's x; broot, the one that produced VOIGT's sigma (0 elsewhere).  The top operand's is i - 1.  The code
- * word is op | (arg & 0xff) << 8 | aroot << 16 | broot << 24, so all of VOIGT's dependency masks are structural. */
+ * instruction (POW, ATAN2, MIN, MAX included), VOIGT's x or WHERE's c; broot, the one that produced VOIGT's sigma or
+ * WHERE's a (0 elsewhere).  The top operand's is i - 1.  The code word is op | (arg & 0xff) << 8 | aroot << 16 |
+ * broot << 24, so all of VOIGT's and WHERE's dependency masks are structural. */
 int nlh_expr_roots(const nlh_expr *e, int32_t *aroot, int32_t *broot);
 
 /* The Faddeeva function w(z) = exp(-z^2) erfc(-iz), Im z >= 0, in double precision, by Weideman's rational approximation

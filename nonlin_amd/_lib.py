@@ -424,6 +424,8 @@ EXPR_OPS = ("CONST", "VAR", "PARAM", "NEG", "ADD", "SUB", "MUL", "DIV", "IPOW", 
             "ATAN", "ABS")
 # ... and of the special functions, numbered on from len(EXPR_OPS) = 18 (NLH_EXPR_ERF ..)
 EXPR_SPECIAL_OPS = ("ERF", "ERFC", "ERFCX", "VOIGT")
+# ... and of the fitted exponent, the four-quadrant angle and the selections, numbered on from 22 (NLH_EXPR_POW ..)
+EXPR_EXTENDED_OPS = ("POW", "ATAN2", "MIN", "MAX", "WHERE")
 
 
 def faddeeva_table():
@@ -477,7 +479,11 @@ class Expr(Owner):
     names) and the parameters params (1 .. 32 names, in the order of x), e.g. Expr("a*exp(-k*t)+c", ("t",), ("a", "k", "c")).
     Operators + - * / ^ (a literal exponent), functions exp log sqrt sin cos tanh atan abs erf erfc erfcx of one argument
     and voigt(x, sigma, gamma) -- the unit-area Voigt profile, Gaussian sigma and Lorentzian half width gamma -- the constant
-    pi.  Function names and pi are reserved: no variable or parameter may carry one.  Raises
+    pi.  pow(a, b) is a power whose exponent may be fitted (its Jacobian is finite at a = 0, where exp(b*log(a))'s is NaN;
+    a < 0 with a fitted exponent is outside its domain), atan2(y, x) the four-quadrant angle, min(a, b) and max(a, b) the
+    smaller and the larger (a hinge is max(t-t0, 0)), where(c, a, b) is a where c >= 0 and b elsewhere (an onset at t0:
+    where(t-t0, ..., 0)); both branches are evaluated, and a NaN in the one not taken reaches neither the value nor the
+    Jacobian.  Function names and pi are reserved: no variable or parameter may carry one.  Raises
     ValueError with the compiler's message ("col 17: unknown name 'foo'").  close() frees it (so does garbage collection)."""
     _free = "nlh_expr_destroy"
 
@@ -507,7 +513,8 @@ class Expr(Owner):
 
     def roots(self):
         """(aroot, broot), int32 [ninstr]: the instruction that produced a binary instruction's lower operand or VOIGT's x, and
-        the one that produced VOIGT's sigma (nlh_expr_roots)."""
+        the one that produced VOIGT's sigma (nlh_expr_roots).  WHERE has its condition c in aroot and its first branch a in
+        broot; the second branch is the instruction before it."""
         import numpy as np
         a, b = np.zeros(self.ninstr, dtype=np.int32), np.zeros(self.ninstr, dtype=np.int32)
         if self.lib.nlh_expr_roots(self.ptr, a.ctypes.data_as(c_int32_p), b.ctypes.data_as(c_int32_p)):

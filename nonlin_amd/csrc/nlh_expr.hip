@@ -1,7 +1,7 @@
 // nlh_expr.hip -- formula models (include/nonlin_hip.h: nlh_expr_*): a model the user writes as an expression string.
 // First the compiler, pure host code that needs no GPU: a recursive-descent parser of the header's grammar that emits the
 // postfix of the parse tree as it goes -- no folding, no reassociation, no sharing -- with, per instruction, the mask of
-// the parameters its subtree names and the instruction that produced its left operand (VOIGT: its two lower operands).  Then
+// the parameters its subtree names and the instruction that produced its left operand (VOIGT, WHERE: its two lower operands).  Then
 // the Faddeeva function's entry points (nlh_kernels_specfun.h), the launchers of the open
 // device-residual path (kernels and arithmetic: nlh_kernels_expr.h), which form a call runs and how many Jacobian
 // columns a pass carries, model values (nlh_expr_eval_batch) and the eight one-call fits nlh_expr_fit_batch*: a formula as
@@ -19,8 +19,10 @@
 static thread_local std::string expr_err;
 const char *nlh_expr_error(void) { return expr_err.c_str(); }
 
-static const char *const EXPR_FUNCS[] = {"exp", "log", "sqrt", "sin", "cos", "tanh", "atan", "abs",   // NLH_EXPR_EXP ..
-                                         "erf", "erfc", "erfcx", "voigt"};                               // NLH_EXPR_ERF ..
+static const struct { const char *name; int arity; } EXPR_FUNCS[] = {
+    {"exp", 1}, {"log", 1}, {"sqrt", 1}, {"sin", 1}, {"cos", 1}, {"tanh", 1}, {"atan", 1}, {"abs", 1},   // NLH_EXPR_EXP ..
+    {"erf", 1}, {"erfc", 1}, {"erfcx", 1}, {"voigt", 3},                                                 // NLH_EXPR_ERF ..
+    {"pow", 2}, {"atan2", 2}, {"min", 2}, {"max", 2}, {"where", 3}};                                     // NLH_EXPR_POW ..
 
 namespace {
 struct ExprFail {};
@@ -47,7 +49,7 @@ struct ExprParser {
         const int pc = P->ninstr++;
         uint32_t mask = op == NLH_EXPR_PARAM ? 1u << arg : 0u;
         int aroot = 0, broot = 0;
-        if (pops == 3) {                       // VOIGT: x, sigma, gamma
+        if (pops == 3) {                       // VOIGT: x, sigma, gamma; WHERE: c, a, b
             aroot = root[sp - 3]; broot = root[sp - 2];
             mask = P->mask[aroot] | P->mask[broot] | P->mask[root[sp - 1]];
         }
@@ -118,6 +120,8 @@ struct ExprParser {
         bool neg = false;
         if (peek() == '-') { neg = true; ++at; }
         size_t ncol;
+        const char x = peek();                 // '^' takes a literal: a name or '(' here is the exponent pow(a, b) takes
+        if (alpha(x) || x == '(') fail(at, std::string("a number expected at '") + x + "': '^' takes a literal exponent, write pow(a, b)");
         const double v = number(&ncol);
         if (v >= 2.0 && v <= 16.0 && v == (double)(int)v) emit(col, NLH_EXPR_IPOW, neg ? -(int)v : (int)v, 1);
         else emit(col, NLH_EXPR_POWC, constant(ncol, neg ? -v : v), 1);
@@ -146,19 +150,20 @@ struct ExprParser {
         const std::string name(s + at, e - at);
         at = e;
         for (size_t f = 0; f < sizeof(EXPR_FUNCS) / sizeof(EXPR_FUNCS[0]); ++f)
-            if (name == EXPR_FUNCS[f]) {
+            if (name == EXPR_FUNCS[f].name) {
                 if (peek() != '(') fail(at, "'(' expected after the function '" + name + "'");
                 ++at;
-                const int op = NLH_EXPR_EXP + (int)f, want = op == NLH_EXPR_VOIGT ? 3 : 1;
+                const int op = NLH_EXPR_EXP + (int)f, want = EXPR_FUNCS[f].arity;
+                const std::string takes = "'" + name + "' takes " + (want == 1 ? "one argument" : (want == 2 ? "two arguments" : "three arguments"));
                 int have = 1;
                 expr();
                 for (; peek() == ','; ++have) {
-                    if (have == want) fail(at, "'" + name + "' takes " + (want == 1 ? "one argument" : "three arguments"));
+                    if (have == want) fail(at, takes);
                     ++at;
                     expr();
                 }
                 if (peek() != ')') fail(at, "')' expected");
-                if (have != want) fail(at, "'" + name + "' takes " + (want == 1 ? "one argument" : "three arguments"));
+                if (have != want) fail(at, takes);
                 ++at;
                 emit(col, op, 0, want);
                 return;
@@ -188,8 +193,8 @@ bool expr_names(const char *what, const char *list, size_t most, const std::vect
         while (ExprParser::alpha(list[at]) || ExprParser::digit(list[at])) ++at;
         const std::string name(list + col, at - col);
         if (name == "pi") return fail(col, "'pi' is the constant");
-        for (const char *f : EXPR_FUNCS)
-            if (name == f) return fail(col, "'" + name + "' is a function");
+        for (const auto &f : EXPR_FUNCS)
+            if (name == f.name) return fail(col, "'" + name + "' is a function");
         for (const auto &o : out)
             if (name == o) return fail(col, "duplicate name '" + name + "'");
         for (const auto &o : others)

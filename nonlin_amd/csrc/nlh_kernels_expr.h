@@ -30,13 +30,21 @@ struct ExprData {                      // what the kernels read of an nlh_expr_c
 #define EXPR_OP(c)     ((int)((c) & 0xffu))
 #define EXPR_ARG(c)    ((int)(int8_t)(((c) >> 8) & 0xffu))
 #define EXPR_AROOT(c)  ((int)(((c) >> 16) & 0xffu))
-#define EXPR_BROOT(c)  ((int)(((c) >> 24) & 0xffu))   // VOIGT only: the producer of its second operand
+#define EXPR_BROOT(c)  ((int)(((c) >> 24) & 0xffu))   // VOIGT, WHERE: the producer of the second operand
 
 // The device library's erf, erfc and erfcx behind one call: inlined three times into the interpreter they cost it 70 VGPRs
 // (and k_expr_fcn a wave per SIMD) whether or not a formula uses them.
 __device__ static __noinline__ double expr_erf_family(int op, double a)
 {
     return op == NLH_EXPR_ERF ? erf(a) : (op == NLH_EXPR_ERFC ? erfc(a) : erfcx(a));
+}
+
+// The device library's pow, atan2 and the log of POW's exponent partial behind one call (sel: NLH_EXPR_POW, NLH_EXPR_ATAN2,
+// anything else log(a)), for the same reason: k_expr_fcn sits a few VGPRs under its occupancy step, so pow is
+// not inlined a second and third time, log a second and atan2 a first.
+__device__ static __noinline__ double expr_pow_family(int sel, double a, double b)
+{
+    return sel == NLH_EXPR_POW ? pow(a, b) : (sel == NLH_EXPR_ATAN2 ? atan2(a, b) : log(a));
 }
 
 // One pass over the program.  vs: this thread's column of the value stack (slot s at vs[s * 256]); ts: of the C tangent
@@ -89,23 +97,67 @@ __device__ static inline double expr_run(const ExprProg &P, const double *xq, co
             --sp;
             continue;
         }
-        if (op == NLH_EXPR_VOIGT) {                               // ternary: x below sigma below gamma; w(z) once per pass
-            const double a = V(sp - 3), b = V(sp - 2), c3 = V(sp - 1);
-            const uint32_t ma = (P.mask[EXPR_AROOT(code)] >> j0) & cm, mb = (P.mask[EXPR_BROOT(code)] >> j0) & cm,
-                           mc = (P.mask[pc - 1] >> j0) & cm;
-            double gx, gs, gg;
-            const double v = voigt_eval(a, b, c3, &gx, &gs, &gg);
-            for (uint32_t mm = ma | mb | mc; mm; mm &= mm - 1) {
-                const int c = __builtin_ctz(mm);
-                const bool ha = (ma >> c) & 1u, hb = (mb >> c) & 1u, hc = (mc >> c) & 1u;
-                double d = 0.0;
-                if (ha) d = gx * T(c, sp - 3);
-                if (hb) d = ha ? d + gs * T(c, sp - 2) : gs * T(c, sp - 2);
-                if (hc) d = ha || hb ? d + gg * T(c, sp - 1) : gg * T(c, sp - 1);
-                T(c, sp - 3) = d;
+        if (op >= NLH_EXPR_VOIGT) {                               // the functions of several operands, behind the one test VOIGT had:
+                                                                  // a test more per instruction cost the older formulas 2 - 3 %
+            if (op == NLH_EXPR_VOIGT) {                           // ternary: x below sigma below gamma; w(z) once per pass
+                const double a = V(sp - 3), b = V(sp - 2), c3 = V(sp - 1);
+                const uint32_t ma = (P.mask[EXPR_AROOT(code)] >> j0) & cm, mb = (P.mask[EXPR_BROOT(code)] >> j0) & cm,
+                               mc = (P.mask[pc - 1] >> j0) & cm;
+                double gx, gs, gg;
+                const double v = voigt_eval(a, b, c3, &gx, &gs, &gg);
+                for (uint32_t mm = ma | mb | mc; mm; mm &= mm - 1) {
+                    const int c = __builtin_ctz(mm);
+                    const bool ha = (ma >> c) & 1u, hb = (mb >> c) & 1u, hc = (mc >> c) & 1u;
+                    double d = 0.0;
+                    if (ha) d = gx * T(c, sp - 3);
+                    if (hb) d = ha ? d + gs * T(c, sp - 2) : gs * T(c, sp - 2);
+                    if (hc) d = ha || hb ? d + gg * T(c, sp - 1) : gg * T(c, sp - 1);
+                    T(c, sp - 3) = d;
+                }
+                V(sp - 3) = v;
+                sp -= 2;
+                continue;
             }
-            V(sp - 3) = v;
-            sp -= 2;
+            if (op == NLH_EXPR_WHERE) {                           // ternary: c below a below b; both branches were evaluated
+                const bool s = V(sp - 3) >= 0.0;
+                const uint32_t ma = (P.mask[EXPR_BROOT(code)] >> j0) & cm, mb = (P.mask[pc - 1] >> j0) & cm,
+                               mc = (P.mask[EXPR_AROOT(code)] >> j0) & cm;
+                for (uint32_t mm = ma | mb | mc; mm; mm &= mm - 1) {  // (c's tangent is overwritten unread)
+                    const int c = __builtin_ctz(mm);
+                    const double da = (ma >> c) & 1u ? T(c, sp - 2) : 0.0, db = (mb >> c) & 1u ? T(c, sp - 1) : 0.0;
+                    T(c, sp - 3) = s ? da : db;
+                }
+                V(sp - 3) = s ? V(sp - 2) : V(sp - 1);
+                sp -= 2;
+                continue;
+            }
+            // POW, ATAN2, MIN, MAX: binary, a below b (ADD .. DIV keep the block they had)
+            const double a = V(sp - 2), b = V(sp - 1);
+            const uint32_t ma = (P.mask[EXPR_AROOT(code)] >> j0) & cm, mb = (P.mask[pc - 1] >> j0) & cm;
+            double v, ga = 0.0, gb = 0.0;                         // POW: the partials; ATAN2: ga = den
+            bool s = false;                                       // MIN, MAX: b is selected (per lane)
+            if (op == NLH_EXPR_POW) {
+                v = expr_pow_family(NLH_EXPR_POW, a, b);
+                if (ma) ga = b * expr_pow_family(NLH_EXPR_POW, a, b - 1.0);
+                if (mb) { const double l = expr_pow_family(NLH_EXPR_LOG, a, b); gb = v == 0.0 ? 0.0 : v * l; }
+            }
+            else if (op == NLH_EXPR_ATAN2) { v = expr_pow_family(NLH_EXPR_ATAN2, a, b); ga = a * a + b * b; }
+            else { s = op == NLH_EXPR_MAX ? b > a : b < a; v = s ? b : a; }
+            for (uint32_t mm = ma | mb; mm; mm &= mm - 1) {
+                const int c = __builtin_ctz(mm);
+                const bool ha = (ma >> c) & 1u, hb = (mb >> c) & 1u;
+                const double da = ha ? T(c, sp - 2) : 0.0, db = hb ? T(c, sp - 1) : 0.0;
+                double d;
+                if (op == NLH_EXPR_POW) {
+                    const double ta = da == 0.0 ? 0.0 : ga * da, tb = gb * db;
+                    d = ha && hb ? ta + tb : (ha ? ta : tb);
+                }
+                else if (op == NLH_EXPR_ATAN2) d = ha && hb ? (b * da - a * db) / ga : (ha ? (b * da) / ga : -((a * db) / ga));
+                else d = s ? db : da;                             // (an absent operand's tangent is the +0.0 above)
+                T(c, sp - 2) = d;
+            }
+            V(sp - 2) = v;
+            --sp;
             continue;
         }
         // unary: the operand is the instruction before
