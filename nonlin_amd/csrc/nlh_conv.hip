@@ -8,15 +8,9 @@
 
 static const uint32_t CONV_MAGIC = 0x766e6f63u;
 
-struct nlh_conv_ctx {
-    uint32_t magic = CONV_MAGIC;
-    int device = 0, cus = 1;
-    nlh_device_vecfcn fcn = nullptr;
-    nlh_device_jacfcn jac = nullptr;
-    void *inner = nullptr;
+struct nlh_conv_ctx : WrapCtx {
     nlh_conv cv{};
     const double *dy = nullptr, *dw = nullptr;
-    StreamScratch scratch;             // kept until nlh_conv_unwrap
 };
 
 void conv_ctx_rebind(nlh_conv_ctx *c, const double *dy, const double *dw, const double *dk) { c->dy = dy; c->dw = dw; c->cv.k = dk; }
@@ -44,23 +38,16 @@ int nlh_conv_wrap(nlh_handle *h, const nlh_conv *cv, const double *dy, const dou
     if (!h) return NLH_ERR_BAD_HANDLE;
     if (!out || !dy || !nlh_conv_ok(cv)) return NLH_INVALID_INPUT_ERROR;
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;
-    HIPCHK(h, hipSetDevice(h->device));
-    nlh_conv_ctx *c = new nlh_conv_ctx();
-    c->device = h->device;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) c->cus = cus;
-    c->fcn = fcn; c->jac = jac; c->inner = inner_ctx; c->cv = *cv; c->dy = dy; c->dw = dw;
+    nlh_conv_ctx *c = nullptr;
+    if (const int rc = wrap_new(h, CONV_MAGIC, fcn, jac, inner_ctx, &c)) return rc;
+    c->cv = *cv; c->dy = dy; c->dw = dw;
     *out = c;
     return 0;
 }
 
 void nlh_conv_unwrap(nlh_conv_ctx *c)
 {
-    if (!c || c->magic != CONV_MAGIC) return;
-    hipSetDevice(c->device);
-    c->scratch.free_all();
-    c->magic = 0;
-    delete c;
+    if (c && c->magic == CONV_MAGIC) wrap_release(c);
 }
 
 // One launch: V [npoints][ncol][m] -> O, out of place.  Flat: 256 / m points per workgroup, a column at a time.  Row: tiles
@@ -101,11 +88,9 @@ static int conv_launch(int cus, const ConvArgs &A, int mode, int m, int ncol, in
 static int conv_call(bool jac, void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m,
                      double *out)
 {
-    nlh_conv_ctx *c = (nlh_conv_ctx *)ctx;
-    if (!c || c->magic != CONV_MAGIC || !c->fcn || !c->dy || !nlh_conv_ok(&c->cv)) return NLH_INVALID_INPUT_ERROR;
-    if (n < 1 || m < 1 || !dX || !out) return NLH_INVALID_INPUT_ERROR;
-    if (jac && !c->jac) return NLH_UNDEFINED_FUNCTION_ERROR;
-    if (npoints <= 0) return 0;
+    nlh_conv_ctx *c = wrap_ctx<nlh_conv_ctx>(ctx, CONV_MAGIC);
+    int end;
+    if (wrap_refused(c, c && c->dy && nlh_conv_ok(&c->cv) && n >= 1 && m >= 1 && dX && out, jac, npoints, &end)) return end;
     hipStream_t s = (hipStream_t)hip_stream;
     ConvArgs A;
     A.k = c->cv.k; A.L = c->cv.L; A.origin = c->cv.origin; A.ext = c->cv.ext; A.shared_k = c->cv.shared_k;
@@ -142,12 +127,10 @@ int nlh_conv_apply_batch(nlh_handle *h, const nlh_conv *cv, int32_t nprob, int32
     if (nprob == 0) return 0;
     if (!dv || !dout || dv == dout) return NLH_INVALID_INPUT_ERROR;
     HIPCHK(h, hipSetDevice(h->device));
-    int cus = 1, v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && v > 0) cus = v;
     ConvArgs A;
     A.k = cv->k; A.L = cv->L; A.origin = cv->origin; A.ext = cv->ext; A.shared_k = cv->shared_k;
     A.y = nullptr; A.w = nullptr; A.dprob = nullptr;
-    if (const int rc = conv_launch(cus, A, CONV_JAC, m, ncol, nprob, dv, dout, h->stream)) return rc;
+    if (const int rc = conv_launch(device_cus(h->device), A, CONV_JAC, m, ncol, nprob, dv, dout, h->stream)) return rc;
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -50,6 +50,60 @@ struct FitRun {
         if (pc) pmap_ctx_rebind(pc, fullc + (size_t)p0 * N);
     }
 };
+
+// run() inside a layer -- the context an nlh_*_wrap just made around r's launchers --: the stream is synchronised (the
+// context's scratch goes), the layer released, and a HIP error becomes NLH_ERR_HIP with `label` in h->err unless run's own
+// return code is not 0, which wins.
+template <class Run> int in_layer(nlh_handle *h, void *layer, const char *label, Run &&run)
+{
+    const int rc = run();
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    wrap_release(wrap_layer(layer));
+    if (!rc && e != hipSuccess) {
+        h->err = std::string(label) + hipGetErrorString(e);
+        return NLH_ERR_HIP;
+    }
+    return rc;
+}
+
+// The end of a fit through a map or a group: the stream is synchronised (st is a host vector; the buffers go), the layer
+// (NULL: none was made) and base released, and a HIP error -- e, then the synchronisation's -- wins over rc; the status comes
+// back when rc is 0.
+int mapped_end(nlh_handle *h, void *layer, void *base, const char *label, int rc, hipError_t e, const std::vector<int32_t> &st,
+               int32_t *status)
+{
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    wrap_release(wrap_layer(layer));
+    (void)hipFree(base);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) {
+        h->err = std::string(label) + hipGetErrorString(e);
+        return NLH_ERR_HIP;
+    }
+    if (!rc && status) memcpy(status, st.data(), sizeof(int32_t) * st.size());
+    return rc;
+}
+
+// The box of a solve over nu unknowns: the caller's xl / xu, which are per parameter of the model, carried to the unknowns.
+// at(g, k) for k < K of each of G sets: {u, p}, unknown u is parameter p.  A bound the caller did not give stays NULL.
+struct FitBox {
+    std::vector<double> lo, hi;
+    const double *xl() const { return lo.empty() ? nullptr : lo.data(); }
+    const double *xu() const { return hi.empty() ? nullptr : hi.data(); }
+};
+template <class At> FitBox fit_box(const FitArgs &a, int32_t nu, int32_t G, int32_t K, At &&at)
+{
+    FitBox b;
+    if (a.xl) b.lo.resize(nu);
+    if (a.xu) b.hi.resize(nu);
+    for (int32_t g = 0; g < G; ++g)
+        for (int32_t k = 0; k < K; ++k) {
+            const std::pair<int32_t, int32_t> up = at(g, k);
+            if (a.xl) b.lo[up.first] = a.xl[up.second];
+            if (a.xu) b.hi[up.first] = a.xu[up.second];
+        }
+    return b;
+}
 }   // namespace
 
 // Solve (bounded when xl or xu is given), covariance with scaled = 1 (a Poisson fit: 0) when any of dsigma, dcov, the caller's chi2 is asked for,
@@ -144,9 +198,7 @@ static int fit_mapped(FitRun r, int32_t n)
     int32_t *dfail = (int32_t *)q;
     std::vector<int32_t> f2f(nf);
     nlh_pmap_tables(a.pm, nullptr, nullptr, nullptr, nullptr, f2f.data());
-    std::vector<double> lo, hi;
-    if (a.xl) { lo.resize(nf); for (size_t j = 0; j < nf; ++j) lo[j] = a.xl[f2f[j]]; }
-    if (a.xu) { hi.resize(nf); for (size_t j = 0; j < nf; ++j) hi[j] = a.xu[f2f[j]]; }
+    const FitBox box = fit_box(a, n, 1, n, [&](int32_t, int32_t j) { return std::make_pair(j, f2f[j]); });
     std::vector<int32_t> st(np, 0);
     nlh_pmap_ctx *pc = nullptr;                                   // its copy of the tables serves the steps here too
     hipError_t e = hipSuccess;
@@ -156,7 +208,7 @@ static int fit_mapped(FitRun r, int32_t n)
         pmap_gather(pmap_ctx_tables(pc), s, a.nprob, fullc, xf);
         r.fcn = nlh_pmap_device_fcn; r.jac = r.jac ? nlh_pmap_device_jac : nullptr; r.ctx = pc;
         r.pc = pc; r.fullc = fullc;
-        rc = fit_solve(r, n, a.xl ? lo.data() : nullptr, a.xu ? hi.data() : nullptr, xf, sf, cf, st.data());
+        rc = fit_solve(r, n, box.xl(), box.xu(), xf, sf, cf, st.data());
     }
     if (e == hipSuccess && !rc) {
         // every problem, also one that was refused on its degrees of freedom and kept its x: on exit x obeys the map
@@ -167,16 +219,7 @@ static int fit_mapped(FitRun r, int32_t n)
         }
         if (e == hipSuccess) e = hipGetLastError();
     }
-    const hipError_t e2 = hipStreamSynchronize(s);                // (st is a host vector; the buffers go)
-    nlh_pmap_unwrap(pc);
-    (void)hipFree(base);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) {
-        h->err = std::string("fit through a parameter map: ") + hipGetErrorString(e);
-        return NLH_ERR_HIP;
-    }
-    if (!rc && a.status) memcpy(a.status, st.data(), sizeof(int32_t) * np);
-    return rc;
+    return mapped_end(h, pc, base, "fit through a parameter map: ", rc, e, st, a.status);
 }
 
 // ... of groups: fit_solve over the n outer unknowns of ngroup problems of M = G m rows with the group's launchers around r's,
@@ -202,13 +245,8 @@ static int fit_grouped(FitRun r, int32_t n)
     }
     double *xo = base, *so = a.sigma ? base + ng * nf : nullptr;
     int32_t *dfail = (int32_t *)(base + doubles);
-    std::vector<double> lo, hi;                                   // the bounds of parameter k at every outer unknown of k
-    for (int32_t g = 0; g < G; ++g)
-        for (int32_t k = 0; k < (int32_t)N; ++k) {
-            const int32_t j = nlh_group_index(a.grp, g, k);
-            if (a.xl) { lo.resize(nf); lo[j] = a.xl[k]; }
-            if (a.xu) { hi.resize(nf); hi[j] = a.xu[k]; }
-        }
+    // the bounds of parameter k at every outer unknown of k
+    const FitBox box = fit_box(a, n, G, r.N, [&](int32_t g, int32_t k) { return std::make_pair(nlh_group_index(a.grp, g, k), k); });
     FitArgs ga = a;                                               // what the solve sees: ngroup problems of G m rows
     ga.nprob = ngroup; ga.m = G * a.m;
     std::vector<int32_t> st(ng, 0);
@@ -219,7 +257,7 @@ static int fit_grouped(FitRun r, int32_t n)
         group_gather(group_ctx_tables(gc), s, ngroup, a.x, xo);
         r.fcn = nlh_group_device_fcn; r.jac = r.jac ? nlh_group_device_jac : nullptr; r.ctx = gc;
         r.a = &ga; r.G = G;
-        rc = fit_solve(r, n, a.xl ? lo.data() : nullptr, a.xu ? hi.data() : nullptr, xo, so, a.cov, st.data());
+        rc = fit_solve(r, n, box.xl(), box.xu(), xo, so, a.cov, st.data());
     }
     if (!rc) {
         // every group, also one that was refused on its degrees of freedom: on exit a shared parameter is equal across it
@@ -230,16 +268,7 @@ static int fit_grouped(FitRun r, int32_t n)
         }
         if (e == hipSuccess) e = hipGetLastError();
     }
-    const hipError_t e2 = hipStreamSynchronize(s);                // (st is a host vector; the buffers go)
-    nlh_group_unwrap(gc);
-    (void)hipFree(base);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) {
-        h->err = std::string("global fit: ") + hipGetErrorString(e);
-        return NLH_ERR_HIP;
-    }
-    if (!rc && a.status) memcpy(a.status, st.data(), sizeof(int32_t) * ng);
-    return rc;
+    return mapped_end(h, gc, base, "global fit: ", rc, e, st, a.status);
 }
 
 // ... of a separable model: fit_solve over the n = N - L nonlinear unknowns with the projecting launchers around r's pair,
@@ -274,13 +303,8 @@ static int fit_separated(FitRun r, bool analytic)
     }
     const int32_t nsolve = a.nprob / G;
     const size_t ns = (size_t)nsolve;
-    std::vector<double> lo, hi;                                   // the bounds of the nonlinear parameters at the unknowns of the solve
-    for (int32_t g = 0; g < G; ++g)
-        for (int32_t j = 0; j < n; ++j) {
-            const int32_t u = gred ? nlh_group_index(gred, g, j) : j;
-            if (a.xl) { lo.resize(no); lo[u] = a.xl[nl[j]]; }
-            if (a.xu) { hi.resize(no); hi[u] = a.xu[nl[j]]; }
-        }
+    // the bounds of the nonlinear parameters at the unknowns of the solve
+    const FitBox box = fit_box(a, no, G, n, [&](int32_t g, int32_t j) { return std::make_pair(gred ? nlh_group_index(gred, g, j) : j, nl[j]); });
     // the handle's buffer: alpha [nprob][n], and of a group the unknowns of the solve, those of the errors, their sigma, the flags
     const size_t doubles = np * n + (gred ? ns * no + ns * nof + (a.sigma ? ns * nof : 0) : 0);
     int rc = ensure(h, h->sepx, sizeof(double) * doubles + sizeof(int32_t) * ns + 64);
@@ -319,8 +343,7 @@ static int fit_separated(FitRun r, bool analytic)
             *xerr = xof + (size_t)p0 * nof;
             return nlh_group_gather_batch(h, a.grp, cnt, xf, *xerr);
         };
-        rc = fit_solve(r, no, a.xl ? lo.data() : nullptr, a.xu ? hi.data() : nullptr, gred ? xo : alpha, gred ? (a.sigma ? so : nullptr) : a.sigma,
-                       a.cov, st.data());
+        rc = fit_solve(r, no, box.xl(), box.xu(), gred ? xo : alpha, gred ? (a.sigma ? so : nullptr) : a.sigma, a.cov, st.data());
     }
     hipError_t e = hipSuccess;
     if (!rc && gred && a.sigma) {                                 // sigma per data set, NaN for a group that did not solve
@@ -354,30 +377,14 @@ static int fit_composed(nlh_handle *h, FitRun &r, const FitArgs &a, int32_t n)
                                                                           : fit_solve(r, n, a.xl, a.xu, a.x, a.sigma, a.cov, a.status);
     };
     if (a.stat == NLH_STAT_POISSON) {
-        int rc = nlh_pois_wrap(h, a.y, a.w, a.mu_floor, fcn, jac, ctx, &r.qc);
-        if (rc) return rc;
+        if (const int rc = nlh_pois_wrap(h, a.y, a.w, a.mu_floor, fcn, jac, ctx, &r.qc)) return rc;
         r.fcn = nlh_pois_device_fcn; r.jac = jac ? nlh_pois_device_jac : nullptr; r.ctx = r.qc;
-        rc = run();
-        const hipError_t e = hipStreamSynchronize(h->stream);     // (the context's scratch goes)
-        nlh_pois_unwrap(r.qc);
-        if (!rc && e != hipSuccess) {
-            h->err = std::string("Poisson fit: ") + hipGetErrorString(e);
-            return NLH_ERR_HIP;
-        }
-        return rc;
+        return in_layer(h, r.qc, "Poisson fit: ", run);
     }
     if (a.loss == NLH_LOSS_LINEAR) return run();
-    int rc = nlh_loss_wrap(h, a.loss, a.scale, a.shared_scale, fcn, jac, ctx, &r.lc);
-    if (rc) return rc;
+    if (const int rc = nlh_loss_wrap(h, a.loss, a.scale, a.shared_scale, fcn, jac, ctx, &r.lc)) return rc;
     r.fcn = nlh_loss_device_fcn; r.jac = jac ? nlh_loss_device_jac : nullptr; r.ctx = r.lc;
-    rc = run();
-    const hipError_t e = hipStreamSynchronize(h->stream);         // (the context's scratch goes)
-    nlh_loss_unwrap(r.lc);
-    if (!rc && e != hipSuccess) {
-        h->err = std::string("fit with a loss: ") + hipGetErrorString(e);
-        return NLH_ERR_HIP;
-    }
-    return rc;
+    return in_layer(h, r.lc, "fit with a loss: ", run);
 }
 
 // ... with an instrument response (FitArgs::cv) first: the convolving pair wraps the model's launchers, the model bound
@@ -388,17 +395,9 @@ static int fit_device(nlh_handle *h, const nlh_options *opts, const FitSource &s
     const nlh_device_jacfcn mjac = a.sp ? a.sp_jac : src.jac;
     FitRun r{h, opts, &src, &a, src.N, src.fcn, mjac, src.ctx};
     if (!a.cv) return fit_composed(h, r, a, n);
-    int rc = nlh_conv_wrap(h, a.cv, a.y, a.stat == NLH_STAT_POISSON ? nullptr : a.w, src.fcn, mjac, src.ctx, &r.cc);
-    if (rc) return rc;
+    if (const int rc = nlh_conv_wrap(h, a.cv, a.y, a.stat == NLH_STAT_POISSON ? nullptr : a.w, src.fcn, mjac, src.ctx, &r.cc)) return rc;
     r.fcn = nlh_conv_device_fcn; r.jac = mjac ? nlh_conv_device_jac : nullptr; r.ctx = r.cc;
-    rc = fit_composed(h, r, a, n);
-    const hipError_t e = hipStreamSynchronize(h->stream);         // (the context's scratch goes)
-    nlh_conv_unwrap(r.cc);
-    if (!rc && e != hipSuccess) {
-        h->err = std::string("fit with an instrument response: ") + hipGetErrorString(e);
-        return NLH_ERR_HIP;
-    }
-    return rc;
+    return in_layer(h, r.cc, "fit with an instrument response: ", [&]() { return fit_composed(h, r, a, n); });
 }
 
 // ... behind HOST arrays t, y, w, x, fvec, sigma, cov, chi2, rank (and the scales, which dscale is the device copy of): one

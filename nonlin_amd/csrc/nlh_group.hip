@@ -116,17 +116,11 @@ static int group_device_tables(nlh_handle *h, const nlh_group *g, GroupTables *T
 // ---------------------------------------------------------------------------------------------------------------------
 static const uint32_t GROUP_MAGIC = 0x70755267u;
 
-struct nlh_group_ctx {
-    uint32_t magic = GROUP_MAGIC;
-    int device = 0, cus = 1;
-    GroupDev tab;
-    nlh_device_vecfcn fcn = nullptr;
-    nlh_device_jacfcn jac = nullptr;
-    void *inner = nullptr;
-    StreamScratch scratch;             // kept until nlh_group_unwrap
+struct nlh_group_ctx : WrapCtx {
+    GroupTables T;                     // the context's own copy of the tables (WrapCtx::tables: their allocation)
 };
 
-const GroupTables *group_ctx_tables(const nlh_group_ctx *c) { return &c->tab.T; }
+const GroupTables *group_ctx_tables(const nlh_group_ctx *c) { return &c->T; }
 
 int nlh_group_wrap(nlh_handle *h, const nlh_group *g, nlh_device_vecfcn fcn, nlh_device_jacfcn jac, void *inner_ctx, nlh_group_ctx **out)
 {
@@ -134,27 +128,19 @@ int nlh_group_wrap(nlh_handle *h, const nlh_group *g, nlh_device_vecfcn fcn, nlh
     if (!h) return NLH_ERR_BAD_HANDLE;
     if (!out || !g) return NLH_INVALID_INPUT_ERROR;
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;
-    HIPCHK(h, hipSetDevice(h->device));
-    nlh_group_ctx *c = new nlh_group_ctx();
-    c->device = h->device;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) c->cus = cus;
-    c->tab.device = h->device;
-    const int rc = group_upload(g, &c->tab);
-    if (rc) { h->err = "group: tables to the device"; delete c; return rc; }
-    c->fcn = fcn; c->jac = jac; c->inner = inner_ctx;
+    nlh_group_ctx *c = nullptr;
+    int rc = wrap_new(h, GROUP_MAGIC, fcn, jac, inner_ctx, &c);
+    if (rc) return rc;
+    GroupDev tab;
+    if ((rc = group_upload(g, &tab))) { h->err = "group: tables to the device"; delete c; return rc; }
+    c->T = tab.T; c->tables = tab.base;
     *out = c;
     return 0;
 }
 
 void nlh_group_unwrap(nlh_group_ctx *c)
 {
-    if (!c || c->magic != GROUP_MAGIC) return;
-    hipSetDevice(c->device);
-    c->scratch.free_all();
-    hipFree(c->tab.base);
-    c->magic = 0;
-    delete c;
+    if (c && c->magic == GROUP_MAGIC) wrap_release(c);
 }
 
 static unsigned group_blocks(size_t threads) { return (unsigned)((threads + 255) / 256); }
@@ -162,7 +148,7 @@ static unsigned group_blocks(size_t threads) { return (unsigned)((threads + 255)
 // the scatter of npoints outer points: the grid is jac_grid's over the npoints G inner points and the n outer columns
 static void group_launch_jac(const nlh_group_ctx *c, int m, int npoints, const double *Jf, double *J, hipStream_t s)
 {
-    const GroupTables &T = c->tab.T;
+    const GroupTables &T = c->T;
     const int npin = npoints * T.G;
     const JacGrid g = jac_grid("NLH_GROUP_FORM", "NLH_GROUP_SPLIT", c->cus, m, T.n, npin);
     if (g.flat) hipLaunchKernelGGL(k_group_jac<true>, g.grid, dim3(256), 0, s, T, m, g.nblk, g.ppw, g.cpg, npin, Jf, J);
@@ -175,12 +161,10 @@ static void group_launch_jac(const nlh_group_ctx *c, int m, int npoints, const d
 static int group_call(bool jac, void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t M,
                       double *out)
 {
-    nlh_group_ctx *c = (nlh_group_ctx *)ctx;
-    if (!c || c->magic != GROUP_MAGIC || !c->fcn) return NLH_INVALID_INPUT_ERROR;
-    const GroupTables &T = c->tab.T;
-    if (n != T.n || M < 1 || M % T.G != 0 || !dX || !out) return NLH_INVALID_INPUT_ERROR;
-    if (jac && !c->jac) return NLH_UNDEFINED_FUNCTION_ERROR;
-    if (npoints <= 0) return 0;
+    nlh_group_ctx *c = wrap_ctx<nlh_group_ctx>(ctx, GROUP_MAGIC);
+    int end;
+    if (wrap_refused(c, c && n == c->T.n && M >= 1 && M % c->T.G == 0 && dX && out, jac, npoints, &end)) return end;
+    const GroupTables &T = c->T;
     if ((int64_t)npoints * T.G > 0x7fffffff) return NLH_ARRAY_SIZE_ERROR;
     hipStream_t s = (hipStream_t)hip_stream;
     const int m = M / T.G;

@@ -25,7 +25,7 @@
 //   nlh_model.hip      device sets, device residual models behind host arrays
 //   nlh_qrx.hip        the exact lmfactor
 // Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it launches.  nlh_launch.h:
-// the host side of the (point, row) kernels' two workgroup forms and what the pairs of wrapping launchers share.
+// the host side of the (point, row) kernels' two workgroup forms and what the six pairs of wrapping launchers share.
 #pragma once
 #include "../../include/nonlin_hip.h"
 
@@ -387,6 +387,12 @@ struct FitArgs {
 // NLH_STAT_POISSON: the model is bound without weights, the Poisson wrapper sits where the loss sits, the covariance is
 // unscaled, and chi2 = deviance / dof with dof = unmasked rows - n.
 int nlh_fit_run(nlh_handle *h, const nlh_options *opts, const FitSource &src, const FitArgs &a, bool host);
+// A layer: the context of any of the six pairs of wrapping launchers by its base (nlh_launch.h: WrapCtx, which every nlh_*_ctx
+// derives from alone, so the address is the same).  wrap_release is what every nlh_*_unwrap does once it has checked the
+// kind: set the device, free the scratch, free the kind's tables, clear the magic, delete; NULL does nothing (nlh_pmap.hip).
+struct WrapCtx;
+static inline WrapCtx *wrap_layer(void *ctx) { return reinterpret_cast<WrapCtx *>(ctx); }
+void wrap_release(WrapCtx *c);
 // what the pipeline needs of a wrapping context besides the public nlh_*_wrap / _unwrap: where a run of problems starts in
 // the caller's arrays (nlh_loss.hip, nlh_pmap.hip), and the map's three small launches on the context's copy of the tables
 struct PmapTables;                     // nlh_kernels_pmap.h

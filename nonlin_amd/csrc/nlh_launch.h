@@ -1,6 +1,8 @@
-// nlh_launch.h -- the host side of the (point, row) kernels' two workgroup forms (nlh_kernels_place.h), and what the
-// pairs of wrapping launchers -- parameter maps (nlh_pmap.hip), robust losses (nlh_loss.hip), Poisson fits (nlh_pois.hip) -- share: the per-stream
-// scratch of a context, its cap, the column groups and grid of a column-split Jacobian kernel, and the slice loop of a call.
+// nlh_launch.h -- the host side of the (point, row) kernels' two workgroup forms (nlh_kernels_place.h), and what the six
+// pairs of wrapping launchers -- parameter maps (nlh_pmap.hip), robust losses (nlh_loss.hip), Poisson fits (nlh_pois.hip),
+// global fits (nlh_group.hip), instrument responses (nlh_conv.hip), separable fits (nlh_sep.hip) -- share: WrapCtx, the base
+// of their contexts, with how one is made and what its launchers refuse; the per-stream scratch of a context, its cap, the
+// column groups and grid of a column-split Jacobian kernel, and the slice loop of a call.
 // Every environment variable is read at every call (tests set them between calls).
 #pragma once
 #include "nlh_internal.h"
@@ -41,8 +43,67 @@ struct StreamScratch {
         }
         return b->p;
     }
-    void free_all() { for (Buf &b : bufs) hipFree(b.p); }           // (hipFree waits for the work that still uses it)
+    void free_all()                                              // (hipFree waits for the work that still uses it)
+    {
+        for (Buf &b : bufs) hipFree(b.p);
+        bufs.clear();
+    }
 };
+
+// The compute units of a device (1 when the runtime does not say): what jac_grid and the convolution deal columns over.
+static inline int device_cus(int device)
+{
+    int cus = 0;
+    return hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0 ? cus : 1;
+}
+
+// The base of the six wrapping contexts: what a layer around an inner launcher pair (fcn, jac -- NULL: none --, inner) holds
+// whatever it computes.  Each nlh_*_ctx derives from it alone and adds its own fields, so a context's address is its base's:
+// the launchers read magic -- one value per kind -- through the void * they are handed, and nlh_model.hip and nlh_fit.hip
+// hold a layer of any kind as a WrapCtx * (nlh_internal.h: wrap_layer, wrap_release).  tables: the kind's own device
+// allocation, if it has one.
+struct WrapCtx {
+    uint32_t magic = 0;
+    int device = 0, cus = 1;
+    nlh_device_vecfcn fcn = nullptr;
+    nlh_device_jacfcn jac = nullptr;
+    void *inner = nullptr;
+    void *tables = nullptr;
+    StreamScratch scratch;             // kept until wrap_release
+    virtual ~WrapCtx() = default;      // (wrap_release deletes a context of any kind through this base)
+};
+
+// The common part of every nlh_*_wrap, after the kind's own refusals: a context of the kind on the handle's device.
+template <class Ctx>
+static int wrap_new(nlh_handle *h, uint32_t magic, nlh_device_vecfcn fcn, nlh_device_jacfcn jac, void *inner, Ctx **out)
+{
+    static_assert(std::is_base_of<WrapCtx, Ctx>::value, "a wrapping context derives from WrapCtx");
+    HIPCHK(h, hipSetDevice(h->device));
+    Ctx *c = new Ctx();
+    c->magic = magic; c->device = h->device; c->cus = device_cus(h->device);
+    c->fcn = fcn; c->jac = jac; c->inner = inner;
+    *out = c;
+    return 0;
+}
+
+// What the launchers of every kind refuse before any launch, in this order.  wrap_ctx: the live context of the kind with an
+// inner fcn behind ctx, or NULL.  wrap_refused: no such context, or `ok` -- what else the kind asks of its context, its shape
+// check, the caller's pointers; the caller's expression, which reads c only where there is one -- fails:
+// NLH_INVALID_INPUT_ERROR; a Jacobian asked for without an inner one: NLH_UNDEFINED_FUNCTION_ERROR; no points: 0.  true: the
+// call ends with *rc.
+template <class Ctx> static inline Ctx *wrap_ctx(void *ctx, uint32_t magic)
+{
+    Ctx *c = (Ctx *)ctx;
+    return c && c->magic == magic && c->fcn ? c : nullptr;
+}
+static inline bool wrap_refused(const WrapCtx *c, bool ok, bool jac, int npoints, int *rc)
+{
+    if (!c || !ok) *rc = NLH_INVALID_INPUT_ERROR;
+    else if (jac && !c->jac) *rc = NLH_UNDEFINED_FUNCTION_ERROR;
+    else if (npoints <= 0) *rc = 0;
+    else return false;
+    return true;
+}
 
 // Scratch bytes per call, so per stream; beyond it the points go in slices.  `env` asks for less.
 static inline size_t scratch_cap(const char *env)

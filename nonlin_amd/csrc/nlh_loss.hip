@@ -9,16 +9,10 @@
 
 static const uint32_t LOSS_MAGIC = 0x73736f6cu;
 
-struct nlh_loss_ctx {
-    uint32_t magic = LOSS_MAGIC;
-    int device = 0, cus = 1;
+struct nlh_loss_ctx : WrapCtx {
     int kind = NLH_LOSS_LINEAR;
-    nlh_device_vecfcn fcn = nullptr;
-    nlh_device_jacfcn jac = nullptr;
-    void *inner = nullptr;
     const double *dscale = nullptr;
     int shared_scale = 0;
-    StreamScratch scratch;             // kept until nlh_loss_unwrap
 };
 
 void loss_ctx_rebind(nlh_loss_ctx *c, const double *dscale) { c->dscale = dscale; }
@@ -43,23 +37,16 @@ int nlh_loss_wrap(nlh_handle *h, int32_t kind, const double *dscale, int32_t sha
     if (!out || !nlh_loss_kind_ok(kind)) return NLH_INVALID_INPUT_ERROR;
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;
     if (kind != NLH_LOSS_LINEAR && !dscale) return NLH_INVALID_INPUT_ERROR;
-    HIPCHK(h, hipSetDevice(h->device));
-    nlh_loss_ctx *c = new nlh_loss_ctx();
-    c->device = h->device;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) c->cus = cus;
-    c->kind = kind; c->fcn = fcn; c->jac = jac; c->inner = inner_ctx; c->dscale = dscale; c->shared_scale = shared_scale != 0;
+    nlh_loss_ctx *c = nullptr;
+    if (const int rc = wrap_new(h, LOSS_MAGIC, fcn, jac, inner_ctx, &c)) return rc;
+    c->kind = kind; c->dscale = dscale; c->shared_scale = shared_scale != 0;
     *out = c;
     return 0;
 }
 
 void nlh_loss_unwrap(nlh_loss_ctx *c)
 {
-    if (!c || c->magic != LOSS_MAGIC) return;
-    hipSetDevice(c->device);
-    c->scratch.free_all();
-    c->magic = 0;
-    delete c;
+    if (c && c->magic == LOSS_MAGIC) wrap_release(c);
 }
 
 static void loss_launch_jac(const nlh_loss_ctx *c, const LossArgs &A, int m, int n, int npoints, const double *R, double *J, hipStream_t s)
@@ -75,11 +62,9 @@ static void loss_launch_jac(const nlh_loss_ctx *c, const LossArgs &A, int m, int
 static int loss_call(bool jac, void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m,
                      double *out)
 {
-    nlh_loss_ctx *c = (nlh_loss_ctx *)ctx;
-    if (!c || c->magic != LOSS_MAGIC || !c->fcn) return NLH_INVALID_INPUT_ERROR;
-    if (n < 1 || m < 1 || !dX || !out) return NLH_INVALID_INPUT_ERROR;
-    if (jac && !c->jac) return NLH_UNDEFINED_FUNCTION_ERROR;
-    if (npoints <= 0) return 0;
+    nlh_loss_ctx *c = wrap_ctx<nlh_loss_ctx>(ctx, LOSS_MAGIC);
+    int end;
+    if (wrap_refused(c, n >= 1 && m >= 1 && dX && out, jac, npoints, &end)) return end;
     const bool lin = c->kind == NLH_LOSS_LINEAR;                  // no kernel of the table, no R: the inner pair's output as it is
     hipStream_t s = (hipStream_t)hip_stream;
     const bool needR = jac && !lin;

@@ -84,7 +84,7 @@ struct nlh_dq_model {
     nlh_device_vecfcn ufcn = nullptr;
     nlh_device_jacfcn ujac = nullptr;
     void *uctx = nullptr;
-    // The four launcher-backed kinds the library makes itself: uctx is the kind's context below, which the model owns
+    // The launcher-backed kinds the library makes itself: uctx is the kind's context below, which the model owns
     // together with the device copy of the host arrays behind it -- one allocation, owned, on owned_device.
     void *owned = nullptr;
     int owned_device = 0;
@@ -93,18 +93,9 @@ struct nlh_dq_model {
     // a formula model (nlh_expr_model_create): t, y, w, and a copy of the program
     nlh_expr_ctx *expr = nullptr;
     nlh_expr *expr_prog = nullptr;
-    // a mapped model (nlh_pmap_model_create): the wrapping context around another model's launchers; the full parameters
-    nlh_pmap_ctx *pmap = nullptr;
-    // a model with a loss (nlh_loss_model_create): the wrapping context around another model's launchers; the scales
-    nlh_loss_ctx *loss = nullptr;
-    // a Poisson model (nlh_pois_model_create): the wrapping context around another model's launchers; the counts and the mask
-    nlh_pois_ctx *pois = nullptr;
-    // a convolved model (nlh_conv_model_create): the wrapping context around another model's launchers; the data, weights and taps
-    nlh_conv_ctx *conv = nullptr;
-    // a global model (nlh_group_model_create): the wrapping context around another model's launchers; nothing else
-    nlh_group_ctx *group = nullptr;
-    // a separable model (nlh_sep_model_create): the projecting context around another model's launchers; nothing else
-    nlh_sep_ctx *sep = nullptr;
+    // a model around another model's launchers (nlh_{pmap,loss,pois,conv,group,sep}_model_create): uctx is this layer, the
+    // wrapping context of its kind; owned: the arrays behind it -- full parameters, scales, counts and mask, data and taps
+    WrapCtx *layer = nullptr;
 };
 
 // Host arrays, one after the other, into one device allocation on the handle's device; synchronised (nlh_internal.h).
@@ -272,6 +263,19 @@ int nlh_expr_model_create(nlh_handle *h, const nlh_expr *e, int32_t nprob, int32
     return 0;
 }
 
+// The model around an inner model's launchers: nprob problems of m rows over n unknowns through the wrapping pair (fcn, jac)
+// on the context `layer`, which the model owns with `owned` on `device`.  It has a Jacobian launcher if the inner model has
+// (a separable model's always has: nlh_sep_wrap refuses an inner model without).
+static nlh_dq_model *layer_model(const nlh_dq_model *inner, int32_t nprob, int32_t m, int32_t n, nlh_device_vecfcn fcn, nlh_device_jacfcn jac,
+                                 void *layer, void *owned, int device)
+{
+    nlh_dq_model *md = new nlh_dq_model();
+    md->nprob = nprob; md->m = m; md->n = n; md->gamma = 0.0;
+    md->ufcn = fcn; md->ujac = inner->ujac ? jac : nullptr; md->uctx = layer;
+    md->layer = wrap_layer(layer); md->owned = owned; md->owned_device = device;
+    return md;
+}
+
 // A model of the free unknowns of a parameter map over a launcher-backed inner model (nlh_pmap.hip: the wrapping launchers).
 int nlh_pmap_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_pmap *pm, const double *full, int32_t shared_full,
                           nlh_dq_model **out)
@@ -288,11 +292,7 @@ int nlh_pmap_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_pm
     nlh_pmap_ctx *pc = nullptr;
     const int rc = nlh_pmap_wrap(h, pm, inner->ufcn, inner->ujac, inner->uctx, base, shared_full, &pc);
     if (rc) { hipFree(base); return rc; }
-    nlh_dq_model *md = new nlh_dq_model();
-    md->nprob = inner->nprob; md->m = inner->m; md->n = n; md->gamma = 0.0;
-    md->ufcn = nlh_pmap_device_fcn; md->ujac = inner->ujac ? nlh_pmap_device_jac : nullptr; md->uctx = pc;
-    md->pmap = pc; md->owned = base; md->owned_device = h->device;
-    *out = md;
+    *out = layer_model(inner, inner->nprob, inner->m, n, nlh_pmap_device_fcn, nlh_pmap_device_jac, pc, base, h->device);
     return 0;
 }
 
@@ -309,11 +309,7 @@ int nlh_loss_model_create(nlh_handle *h, const nlh_dq_model *inner, int32_t kind
     nlh_loss_ctx *lc = nullptr;
     const int rc = nlh_loss_wrap(h, kind, base, shared_scale, inner->ufcn, inner->ujac, inner->uctx, &lc);
     if (rc) { hipFree(base); return rc; }
-    nlh_dq_model *md = new nlh_dq_model();
-    md->nprob = inner->nprob; md->m = inner->m; md->n = inner->n; md->gamma = 0.0;
-    md->ufcn = nlh_loss_device_fcn; md->ujac = inner->ujac ? nlh_loss_device_jac : nullptr; md->uctx = lc;
-    md->loss = lc; md->owned = base; md->owned_device = h->device;
-    *out = md;
+    *out = layer_model(inner, inner->nprob, inner->m, inner->n, nlh_loss_device_fcn, nlh_loss_device_jac, lc, base, h->device);
     return 0;
 }
 
@@ -333,11 +329,7 @@ int nlh_conv_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_co
     nlh_conv_ctx *cc = nullptr;
     const int rc = nlh_conv_wrap(h, &dcv, base, w ? base + pm + kd : nullptr, inner->ufcn, inner->ujac, inner->uctx, &cc);
     if (rc) { hipFree(base); return rc; }
-    nlh_dq_model *md = new nlh_dq_model();
-    md->nprob = inner->nprob; md->m = inner->m; md->n = inner->n; md->gamma = 0.0;
-    md->ufcn = nlh_conv_device_fcn; md->ujac = inner->ujac ? nlh_conv_device_jac : nullptr; md->uctx = cc;
-    md->conv = cc; md->owned = base; md->owned_device = h->device;
-    *out = md;
+    *out = layer_model(inner, inner->nprob, inner->m, inner->n, nlh_conv_device_fcn, nlh_conv_device_jac, cc, base, h->device);
     return 0;
 }
 
@@ -354,11 +346,7 @@ int nlh_pois_model_create(nlh_handle *h, const nlh_dq_model *inner, const double
     nlh_pois_ctx *qc = nullptr;
     const int rc = nlh_pois_wrap(h, base, w ? base + pm : nullptr, mu_floor, inner->ufcn, inner->ujac, inner->uctx, &qc);
     if (rc) { hipFree(base); return rc; }
-    nlh_dq_model *md = new nlh_dq_model();
-    md->nprob = inner->nprob; md->m = inner->m; md->n = inner->n; md->gamma = 0.0;
-    md->ufcn = nlh_pois_device_fcn; md->ujac = inner->ujac ? nlh_pois_device_jac : nullptr; md->uctx = qc;
-    md->pois = qc; md->owned = base; md->owned_device = h->device;
-    *out = md;
+    *out = layer_model(inner, inner->nprob, inner->m, inner->n, nlh_pois_device_fcn, nlh_pois_device_jac, qc, base, h->device);
     return 0;
 }
 
@@ -375,11 +363,7 @@ int nlh_group_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_g
     nlh_group_ctx *gc = nullptr;
     const int rc = nlh_group_wrap(h, g, inner->ufcn, inner->ujac, inner->uctx, &gc);
     if (rc) return rc;
-    nlh_dq_model *md = new nlh_dq_model();
-    md->nprob = inner->nprob / G; md->m = G * inner->m; md->n = n; md->gamma = 0.0;
-    md->ufcn = nlh_group_device_fcn; md->ujac = inner->ujac ? nlh_group_device_jac : nullptr; md->uctx = gc;
-    md->group = gc;
-    *out = md;
+    *out = layer_model(inner, inner->nprob / G, G * inner->m, n, nlh_group_device_fcn, nlh_group_device_jac, gc, nullptr, h->device);
     return 0;
 }
 
@@ -396,23 +380,14 @@ int nlh_sep_model_create(nlh_handle *h, const nlh_dq_model *inner, const nlh_sep
     nlh_sep_ctx *sc = nullptr;
     const int rc = nlh_sep_wrap(h, sp, inner->ufcn, inner->ujac, inner->uctx, &sc);
     if (rc) return rc;
-    nlh_dq_model *md = new nlh_dq_model();
-    md->nprob = inner->nprob; md->m = inner->m; md->n = n; md->gamma = 0.0;
-    md->ufcn = nlh_sep_device_fcn; md->ujac = nlh_sep_device_jac; md->uctx = sc;
-    md->sep = sc;
-    *out = md;
+    *out = layer_model(inner, inner->nprob, inner->m, n, nlh_sep_device_fcn, nlh_sep_device_jac, sc, nullptr, h->device);
     return 0;
 }
 
 void nlh_dq_model_destroy(nlh_dq_model *md)
 {
     if (!md) return;
-    nlh_sep_unwrap(md->sep);
-    nlh_group_unwrap(md->group);
-    nlh_pmap_unwrap(md->pmap);
-    nlh_loss_unwrap(md->loss);
-    nlh_pois_unwrap(md->pois);
-    nlh_conv_unwrap(md->conv);
+    wrap_release(md->layer);
     delete md->expr;
     delete md->expr_prog;
     if (md->owned) { hipSetDevice(md->owned_device); hipFree(md->owned); }

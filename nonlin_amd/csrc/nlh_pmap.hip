@@ -154,19 +154,13 @@ static int pmap_device_tables(nlh_handle *h, const nlh_pmap *pm, PmapTables *T)
 // ---------------------------------------------------------------------------------------------------------------------
 static const uint32_t PMAP_MAGIC = 0x70614d70u;
 
-struct nlh_pmap_ctx {
-    uint32_t magic = PMAP_MAGIC;
-    int device = 0, cus = 1;
-    PmapDev tab;
-    nlh_device_vecfcn fcn = nullptr;
-    nlh_device_jacfcn jac = nullptr;
-    void *inner = nullptr;
+struct nlh_pmap_ctx : WrapCtx {
+    PmapTables T;                      // the context's own copy of the tables (WrapCtx::tables: their allocation)
     const double *dfull = nullptr;
     int shared_full = 0;
-    StreamScratch scratch;             // kept until nlh_pmap_unwrap
 };
 
-const PmapTables *pmap_ctx_tables(const nlh_pmap_ctx *c) { return &c->tab.T; }
+const PmapTables *pmap_ctx_tables(const nlh_pmap_ctx *c) { return &c->T; }
 void pmap_ctx_rebind(nlh_pmap_ctx *c, const double *dfull) { c->dfull = dfull; }
 
 int nlh_pmap_wrap(nlh_handle *h, const nlh_pmap *pm, nlh_device_vecfcn fcn, nlh_device_jacfcn jac, void *inner_ctx, const double *dfull,
@@ -177,32 +171,35 @@ int nlh_pmap_wrap(nlh_handle *h, const nlh_pmap *pm, nlh_device_vecfcn fcn, nlh_
     if (!out || !pm) return NLH_INVALID_INPUT_ERROR;
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;
     if (pm->any_fixed && !dfull) return NLH_INVALID_INPUT_ERROR;
-    HIPCHK(h, hipSetDevice(h->device));
-    nlh_pmap_ctx *c = new nlh_pmap_ctx();
-    c->device = h->device;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) c->cus = cus;
-    c->tab.device = h->device;
-    const int rc = pmap_upload(pm, &c->tab);
-    if (rc) { h->err = "parameter map: tables to the device"; delete c; return rc; }
-    c->fcn = fcn; c->jac = jac; c->inner = inner_ctx; c->dfull = dfull; c->shared_full = shared_full != 0;
+    nlh_pmap_ctx *c = nullptr;
+    int rc = wrap_new(h, PMAP_MAGIC, fcn, jac, inner_ctx, &c);
+    if (rc) return rc;
+    PmapDev tab;
+    if ((rc = pmap_upload(pm, &tab))) { h->err = "parameter map: tables to the device"; delete c; return rc; }
+    c->T = tab.T; c->tables = tab.base; c->dfull = dfull; c->shared_full = shared_full != 0;
     *out = c;
     return 0;
 }
 
-void nlh_pmap_unwrap(nlh_pmap_ctx *c)
+// The one release of a wrapping context of any kind (nlh_internal.h).
+void wrap_release(WrapCtx *c)
 {
-    if (!c || c->magic != PMAP_MAGIC) return;
+    if (!c) return;
     hipSetDevice(c->device);
     c->scratch.free_all();
-    hipFree(c->tab.base);
+    if (c->tables) hipFree(c->tables);
     c->magic = 0;
     delete c;
 }
 
+void nlh_pmap_unwrap(nlh_pmap_ctx *c)
+{
+    if (c && c->magic == PMAP_MAGIC) wrap_release(c);
+}
+
 static void pmap_launch_jac(const nlh_pmap_ctx *c, int m, int npoints, const double *Jf, double *J, hipStream_t s)
 {
-    const PmapTables &T = c->tab.T;
+    const PmapTables &T = c->T;
     const JacGrid g = jac_grid("NLH_PMAP_FORM", "NLH_PMAP_SPLIT", c->cus, m, T.n, npoints);
     if (g.flat) hipLaunchKernelGGL(k_pmap_jac<true>, g.grid, dim3(256), 0, s, T, m, g.nblk, g.ppw, g.cpg, npoints, Jf, J);
     else hipLaunchKernelGGL(k_pmap_jac<false>, g.grid, dim3(256), 0, s, T, m, g.nblk, g.ppw, g.cpg, npoints, Jf, J);
@@ -214,12 +211,10 @@ static void pmap_launch_jac(const nlh_pmap_ctx *c, int m, int npoints, const dou
 static int pmap_call(bool jac, void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m,
                      double *out)
 {
-    nlh_pmap_ctx *c = (nlh_pmap_ctx *)ctx;
-    if (!c || c->magic != PMAP_MAGIC || !c->fcn) return NLH_INVALID_INPUT_ERROR;
-    const PmapTables &T = c->tab.T;
-    if (n != T.n || m < 1 || !dX || !out) return NLH_INVALID_INPUT_ERROR;
-    if (jac && !c->jac) return NLH_UNDEFINED_FUNCTION_ERROR;
-    if (npoints <= 0) return 0;
+    nlh_pmap_ctx *c = wrap_ctx<nlh_pmap_ctx>(ctx, PMAP_MAGIC);
+    int end;
+    if (wrap_refused(c, c && n == c->T.n && m >= 1 && dX && out, jac, npoints, &end)) return end;
+    const PmapTables &T = c->T;
     hipStream_t s = (hipStream_t)hip_stream;
     const size_t N = (size_t)T.N;
     // scratch per point: the full parameters P and, for a Jacobian call, the inner Jacobian Jf over them

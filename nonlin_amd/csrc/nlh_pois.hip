@@ -9,15 +9,9 @@
 
 static const uint32_t POIS_MAGIC = 0x73696f70u;
 
-struct nlh_pois_ctx {
-    uint32_t magic = POIS_MAGIC;
-    int device = 0, cus = 1;
-    nlh_device_vecfcn fcn = nullptr;
-    nlh_device_jacfcn jac = nullptr;
-    void *inner = nullptr;
+struct nlh_pois_ctx : WrapCtx {
     const double *dy = nullptr, *dw = nullptr;
     double mu_floor = 0.0;
-    StreamScratch scratch;             // kept until nlh_pois_unwrap
 };
 
 void pois_ctx_rebind(nlh_pois_ctx *c, const double *dy, const double *dw) { c->dy = dy; c->dw = dw; }
@@ -43,23 +37,16 @@ int nlh_pois_wrap(nlh_handle *h, const double *dy, const double *dw, double mu_f
     if (!h) return NLH_ERR_BAD_HANDLE;
     if (!out || !dy) return NLH_INVALID_INPUT_ERROR;
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;
-    HIPCHK(h, hipSetDevice(h->device));
-    nlh_pois_ctx *c = new nlh_pois_ctx();
-    c->device = h->device;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) c->cus = cus;
-    c->fcn = fcn; c->jac = jac; c->inner = inner_ctx; c->dy = dy; c->dw = dw; c->mu_floor = mu_floor;
+    nlh_pois_ctx *c = nullptr;
+    if (const int rc = wrap_new(h, POIS_MAGIC, fcn, jac, inner_ctx, &c)) return rc;
+    c->dy = dy; c->dw = dw; c->mu_floor = mu_floor;
     *out = c;
     return 0;
 }
 
 void nlh_pois_unwrap(nlh_pois_ctx *c)
 {
-    if (!c || c->magic != POIS_MAGIC) return;
-    hipSetDevice(c->device);
-    c->scratch.free_all();
-    c->magic = 0;
-    delete c;
+    if (c && c->magic == POIS_MAGIC) wrap_release(c);
 }
 
 static void pois_launch_jac(const nlh_pois_ctx *c, const PoisArgs &A, int m, int n, int npoints, const double *R, double *J, hipStream_t s)
@@ -75,11 +62,9 @@ static void pois_launch_jac(const nlh_pois_ctx *c, const PoisArgs &A, int m, int
 static int pois_call(bool jac, void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m,
                      double *out)
 {
-    nlh_pois_ctx *c = (nlh_pois_ctx *)ctx;
-    if (!c || c->magic != POIS_MAGIC || !c->fcn || !c->dy) return NLH_INVALID_INPUT_ERROR;
-    if (n < 1 || m < 1 || !dX || !out) return NLH_INVALID_INPUT_ERROR;
-    if (jac && !c->jac) return NLH_UNDEFINED_FUNCTION_ERROR;
-    if (npoints <= 0) return 0;
+    nlh_pois_ctx *c = wrap_ctx<nlh_pois_ctx>(ctx, POIS_MAGIC);
+    int end;
+    if (wrap_refused(c, c && c->dy && n >= 1 && m >= 1 && dX && out, jac, npoints, &end)) return end;
     hipStream_t s = (hipStream_t)hip_stream;
     PoisArgs A;
     A.y = c->dy; A.w = c->dw; A.mu_floor = c->mu_floor;

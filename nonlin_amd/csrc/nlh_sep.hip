@@ -61,14 +61,8 @@ static SepTables sep_tables(const nlh_sep *sp)
 // ---------------------------------------------------------------------------------------------------------------------
 static const uint32_t SEP_MAGIC = 0x70655373u;
 
-struct nlh_sep_ctx {
-    uint32_t magic = SEP_MAGIC;
-    int device = 0;
+struct nlh_sep_ctx : WrapCtx {         // (cus: never read)
     SepTables T{};
-    nlh_device_vecfcn fcn = nullptr;
-    nlh_device_jacfcn jac = nullptr;
-    void *inner = nullptr;
-    StreamScratch scratch;             // kept until nlh_sep_unwrap
 };
 
 void nlh_sep_init_device(int lds_max)
@@ -83,22 +77,16 @@ int nlh_sep_wrap(nlh_handle *h, const nlh_sep *sp, nlh_device_vecfcn fcn, nlh_de
     if (!h) return NLH_ERR_BAD_HANDLE;
     if (!out || !sp) return NLH_INVALID_INPUT_ERROR;
     if (!fcn || !jac) return NLH_UNDEFINED_FUNCTION_ERROR;       // the linear columns of the inner Jacobian are the basis
-    HIPCHK(h, hipSetDevice(h->device));
-    nlh_sep_ctx *c = new nlh_sep_ctx();
-    c->device = h->device;
+    nlh_sep_ctx *c = nullptr;
+    if (const int rc = wrap_new(h, SEP_MAGIC, fcn, jac, inner_ctx, &c)) return rc;
     c->T = sep_tables(sp);
-    c->fcn = fcn; c->jac = jac; c->inner = inner_ctx;
     *out = c;
     return 0;
 }
 
 void nlh_sep_unwrap(nlh_sep_ctx *c)
 {
-    if (!c || c->magic != SEP_MAGIC) return;
-    hipSetDevice(c->device);
-    c->scratch.free_all();
-    c->magic = 0;
-    delete c;
+    if (c && c->magic == SEP_MAGIC) wrap_release(c);
 }
 
 // The form of a call: lds while m (L + 1 + n) doubles -- the panel [Phi | f0] and the columns of D -- fit a workgroup's LDS
@@ -120,11 +108,10 @@ enum { SEP_FCN, SEP_JAC, SEP_SOLVE };
 static int sep_call(int mode, void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m,
                     double *out, int32_t *drank)
 {
-    nlh_sep_ctx *c = (nlh_sep_ctx *)ctx;
-    if (!c || c->magic != SEP_MAGIC || !c->fcn || !c->jac) return NLH_INVALID_INPUT_ERROR;
+    nlh_sep_ctx *c = wrap_ctx<nlh_sep_ctx>(ctx, SEP_MAGIC);
+    int end;
+    if (wrap_refused(c, c && c->jac && n == c->T.n && m >= c->T.N && dX && out, false, npoints, &end)) return end;
     const SepTables &T = c->T;
-    if (n != T.n || m < T.N || !dX || !out) return NLH_INVALID_INPUT_ERROR;
-    if (npoints <= 0) return 0;
     hipStream_t s = (hipStream_t)hip_stream;
     const size_t N = (size_t)T.N, L = (size_t)T.L, ms = (size_t)m;
     const bool jac = mode == SEP_JAC, solve = mode == SEP_SOLVE;
