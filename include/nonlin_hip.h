@@ -841,8 +841,10 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
  *   "structural": the compiler records per instruction the 32-bit mask of the parameters its subtree names -- WHERE's
  *   condition included --; the tangent of a node for column j is present exactly when bit j of that mask is set, whatever
  *   the values are.
- *   residual   r = f - y;  then r = w*r when weights are given; every Jacobian entry is multiplied once by w then (a row of
- *              weight 0 is exactly 0: the padding rule of the curve models)
+ *   residual   r = f - y;  then r = w*r when weights are given; every Jacobian entry is multiplied once by w then (the
+ *              padding rule of the curve models: a row of weight 0 is a zero -- of either sign, 0 times the value's --
+ *              where the value is finite; the product is a multiplication, not a store, so 0 times a non-finite value
+ *              is NaN)
  * No sum crosses a row: a row's bits do not depend on the launch shape, the workgroup form (NLH_EXPR_FORM = row | flat,
  * environment, read at each call, as NLH_CURVE_FORM), the number of Jacobian columns a pass carries, or the batch. ---- */
 #define NLH_EXPR_MAX_INSTR   256
@@ -932,6 +934,18 @@ int nlh_expr_device_fcn(void *ctx, void *hip_stream, int32_t npoints, const int3
                         int32_t m, double *dF);
 int nlh_expr_device_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX,
                         int32_t m, double *dJ);
+/* The launch shape of the formula kernels for a program of this depth with n parameters on m rows: host code, needs no GPU;
+ * the function the launchers themselves dispatch through.  jac = 0: the residual kernel (chunk = 0).  Reads NLH_EXPR_FORM
+ * and NLH_EXPR_CHUNK as the launchers do.  Returns 0, or NLH_INVALID_INPUT_ERROR (depth outside 1 .. 16, n outside 1 .. 32,
+ * m < 1, npoints < 0, a NULL output), NLH_ARRAY_SIZE_ERROR as the launchers.
+ * flat: 1 the flat form (ppw = 256 / m points per workgroup, nblk = 1), 0 the row form (ppw = 1, nblk = ceil(m / 256) row
+ * blocks per point); grid: workgroups, ceil(npoints / ppw) or npoints * nblk; chunk: the Jacobian columns a pass over the
+ * program carries, 1 .. min(n, 8) -- the most with which the launch stays within half of the 161,792 bytes of LDS a
+ * workgroup may ask for, or 1 where even that does not fit half; lds_bytes: the dynamic LDS of the launch,
+ * 8 * (ppw * n + 256 * depth * (1 + chunk)): x of the workgroup's points, the value stack, chunk tangent stacks.  The
+ * largest launch is 131,072 bytes (depth 16, n = 32, m = 1, the Jacobian). */
+int32_t nlh_expr_plan(int32_t depth, int32_t n, int32_t m, int32_t npoints, int32_t jac,
+                      int32_t *flat, int32_t *ppw, int32_t *nblk, int64_t *grid, int32_t *chunk, int64_t *lds_bytes);
 /* A formula model as a MODEL object of the device-function kind, from HOST arrays t [nvar][nprob][m] (shared_t: [nvar][m]),
  * y, w (NULL: no weights): the model owns a copy of the program, its context and device copies of the data (the caller may
  * destroy e at once); nlh_dq_model_destroy frees them.  Errors (every entry point below, in this order):

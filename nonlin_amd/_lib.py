@@ -277,6 +277,8 @@ SYMBOLS = {
     "nlh_faddeeva_batch": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nlh_expr_device_fcn": _LAUNCHER,
     "nlh_expr_device_jac": _LAUNCHER,
+    "nlh_expr_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p,
+                                  C.POINTER(C.c_int64), c_int32_p, C.POINTER(C.c_int64)]),
     "nlh_expr_model_create": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, C.c_int32,
                                         C.POINTER(C.c_void_p)]),
     "nlh_expr_eval_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -336,6 +336,37 @@ static int expr_chunk(int depth, int n, size_t xbytes)
     return C;
 }
 
+// The launch shape of a call: the form, the points a flat workgroup holds, the row blocks of a point, the grid's x, the
+// columns a Jacobian pass carries (0: the residual kernel) and the dynamic LDS -- x of the workgroup's points, the value
+// stack, C tangent stacks.  Pure host code: expr_launch dispatches through it, nlh_expr_plan reports it.
+struct ExprPlan {
+    bool flat;
+    int ppw, nblk, C;
+    size_t grid, lds;
+};
+static int expr_plan(int depth, int n, int m, int npoints, bool jac, ExprPlan &p)
+{
+    if (depth < 1 || depth > NLH_EXPR_MAX_DEPTH || n < 1 || n > NLH_EXPR_MAX_PARAMS || m < 1 || npoints < 0) return NLH_INVALID_INPUT_ERROR;
+    if ((size_t)npoints * ((size_t)(m + 255) / 256) > 0x7fffffffu) return NLH_ARRAY_SIZE_ERROR;
+    p.flat = expr_flat(m);
+    p.ppw = p.flat ? 256 / m : 1; p.nblk = p.flat ? 1 : (m + 255) / 256;
+    p.grid = p.flat ? (size_t)((npoints + p.ppw - 1) / p.ppw) : (size_t)npoints * p.nblk;
+    const size_t xbytes = sizeof(double) * (size_t)p.ppw * n, stack = sizeof(double) * 256 * (size_t)depth;
+    p.C = jac ? expr_chunk(depth, n, xbytes) : 0;
+    p.lds = xbytes + stack * (size_t)(1 + p.C);
+    return 0;
+}
+
+int32_t nlh_expr_plan(int32_t depth, int32_t n, int32_t m, int32_t npoints, int32_t jac, int32_t *flat, int32_t *ppw, int32_t *nblk,
+                      int64_t *grid, int32_t *chunk, int64_t *lds_bytes)
+{
+    if (!flat || !ppw || !nblk || !grid || !chunk || !lds_bytes) return NLH_INVALID_INPUT_ERROR;
+    ExprPlan p;
+    if (const int rc = expr_plan(depth, n, m, npoints, jac != 0, p)) return rc;
+    *flat = p.flat; *ppw = p.ppw; *nblk = p.nblk; *grid = (int64_t)p.grid; *chunk = p.C; *lds_bytes = (int64_t)p.lds;
+    return 0;
+}
+
 // Checks everything, launches nothing when anything is wrong.  y == nullptr: model values (no data term, no weights).
 static int expr_launch(bool jac, const nlh_expr *e, int shared_t, int m, int64_t stride, const double *t, const double *y, const double *w,
                        int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, double *out, hipStream_t s)
@@ -344,23 +375,19 @@ static int expr_launch(bool jac, const nlh_expr *e, int shared_t, int m, int64_t
     if (stride == 0 && shared_t) stride = m;
     if (e->prog.nvar > 1 && stride < m) return NLH_INVALID_INPUT_ERROR;
     if (npoints <= 0) return 0;
-    if ((size_t)npoints * ((size_t)(m + 255) / 256) > 0x7fffffffu) return NLH_ARRAY_SIZE_ERROR;
+    ExprPlan p;
+    if (const int rc = expr_plan(e->prog.depth, n, m, npoints, jac, p)) return rc;
     ExprData ed;
     ed.shared_t = shared_t != 0; ed.m = m; ed.tstride = stride; ed.t = t; ed.y = y; ed.w = w;
-    const bool flat = expr_flat(m);
-    const int ppw = flat ? 256 / m : 1, nblk = flat ? 1 : (m + 255) / 256;
-    const dim3 grid(flat ? (unsigned)((npoints + ppw - 1) / ppw) : (unsigned)((size_t)npoints * nblk));
-    const size_t xbytes = sizeof(double) * (size_t)ppw * n, stack = sizeof(double) * 256 * (size_t)e->prog.depth;
+    const dim3 grid((unsigned)p.grid);
+    const int ppw = p.ppw, nblk = p.nblk, C = p.C;
     if (!jac) {
-        const size_t lds = xbytes + stack;
-        if (flat) hipLaunchKernelGGL(k_expr_fcn<true>, grid, dim3(256), lds, s, e->prog, ed, n, nblk, ppw, npoints, dprob, dX, out);
-        else hipLaunchKernelGGL(k_expr_fcn<false>, grid, dim3(256), lds, s, e->prog, ed, n, nblk, ppw, npoints, dprob, dX, out);
+        if (p.flat) hipLaunchKernelGGL(k_expr_fcn<true>, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, dprob, dX, out);
+        else hipLaunchKernelGGL(k_expr_fcn<false>, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, dprob, dX, out);
         return 0;
     }
-    const int C = expr_chunk(e->prog.depth, n, xbytes);
-    const size_t lds = xbytes + stack * (size_t)(1 + C);
-    if (flat) hipLaunchKernelGGL(k_expr_jac<true>, grid, dim3(256), lds, s, e->prog, ed, n, nblk, ppw, npoints, C, dprob, dX, out);
-    else hipLaunchKernelGGL(k_expr_jac<false>, grid, dim3(256), lds, s, e->prog, ed, n, nblk, ppw, npoints, C, dprob, dX, out);
+    if (p.flat) hipLaunchKernelGGL(k_expr_jac<true>, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, C, dprob, dX, out);
+    else hipLaunchKernelGGL(k_expr_jac<false>, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, C, dprob, dX, out);
     return 0;
 }
 

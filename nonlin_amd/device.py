@@ -77,6 +77,21 @@ def house_plan(nprob, rows, ncA, ncE):
     return {"form": HOUSE_FORMS[rc], "tiles": int(tiles.value)}
 
 
+def expr_plan(depth, n, m, npoints=1, jac=True):
+    """The launch shape of the formula kernels for a program of stack depth `depth` with n parameters on m rows, npoints
+    points in the call (nlh_expr_plan: host code, needs no GPU; the function the launchers themselves dispatch through), under
+    this process's NLH_EXPR_FORM / NLH_EXPR_CHUNK environment as it is now.  jac: the Jacobian kernel (False: the residual
+    kernel, chunk 0).  Returns {"flat", "ppw", "nblk", "grid", "chunk", "lds_bytes"}."""
+    flat, ppw, nblk, chunk = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    grid, lds = C.c_int64(), C.c_int64()
+    rc = _lib.load().nlh_expr_plan(depth, n, m, npoints, int(bool(jac)), C.byref(flat), C.byref(ppw), C.byref(nblk), C.byref(grid),
+                                   C.byref(chunk), C.byref(lds))
+    if rc:
+        raise ValueError(f"nlh_expr_plan({depth}, {n}, {m}, {npoints}): error {rc}")
+    return {"flat": bool(flat.value), "ppw": int(ppw.value), "nblk": int(nblk.value), "grid": int(grid.value),
+            "chunk": int(chunk.value), "lds_bytes": int(lds.value)}
+
+
 class _Wrapped(_lib.Owner):
     """The context of a pair of wrapping launchers (nlh_pmap_ctx, nlh_loss_ctx, ...: what an nlh_*_wrap made), with everything
     it points at kept alive; free: the name of the nlh_*_unwrap that takes it back."""

@@ -63,9 +63,14 @@ def test_fit_calls_match_the_parent(recorded, group):
         assert got["ret"] == want["ret"], k
 
 
+# entry points added since the golden was recorded, with their signatures: nothing else may differ from it
+ADDED = {"nlh_expr_plan": "i i i i i i I I I LP_c_long I LP_c_long"}
+
+
 def test_signature_table_matches_the_parent():
     got = FC.symbols_snapshot()
     assert got["types"] == SYMBOLS["types"]
-    assert len(SYMBOLS["symbols"]) == 206 and set(got["symbols"]) == set(SYMBOLS["symbols"])
-    for name, sig in SYMBOLS["symbols"].items():
+    assert len(SYMBOLS["symbols"]) == 206 and set(got["symbols"]) == set(SYMBOLS["symbols"]) | set(ADDED)
+    assert not set(ADDED) & set(SYMBOLS["symbols"])
+    for name, sig in list(SYMBOLS["symbols"].items()) + list(ADDED.items()):
         assert got["symbols"][name] == sig, name
