@@ -774,7 +774,8 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
  * "a*exp(-((t-mu)/s)^2/2)+c" with vars "t" and params "a,mu,s,c".  nlh_expr_compile (pure host code, needs no GPU) turns it
  * into a small postfix program; the kernels behind nlh_expr_device_fcn / _jac interpret it, a thread per (point, row), so a
  * curve fitter needs neither hipcc nor device code.
- * GRAMMAR (blanks are ignored; operators are left-associative; -a^2 is -(a^2); a^2^3 is an error):
+ * GRAMMAR (blanks and newlines are ignored; operators are left-associative; -a^2 is -(a^2); a^2^3 is an error):
+ *   formula := (name '=' expr ';')* expr
  *   expr  := term (('+'|'-') term)*            term  := unary (('*'|'/') unary)*
  *   unary := ('-'|'+') unary | power           power := atom ('^' ['-'] number)?
  *   atom  := number | name | func '(' expr (',' expr)* ')' | '(' expr ')'
@@ -784,12 +785,25 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
  * max(a, b) two, every other function one; another count is an error that names its column.  '^' takes a literal only: an
  * exponent that is a parameter or an expression is pow's second argument.  vars: 1 .. 4 comma-separated names; params: 1 .. 32, their order is
  * the order of x.  A name is [A-Za-z_][A-Za-z0-9_]*, not pi and not a function.
- * THE PROGRAM IS THE POSTFIX OF THE PARSE TREE: no constant folding, no reassociation, no sharing of common subexpressions
- * (a unary '+' emits nothing; every literal and every pi is a constant of its own).  Instructions (op, arg):
+ * DEFINITIONS: name = expr; in front of the formula names a value that is computed once, e.g. with vars "x,y" and params
+ * "a,x0,y0,sx,sy,th,b" the rotated elliptical Gaussian
+ *   dx = x-x0; dy = y-y0; c = cos(th); s = sin(th);  u = dx*c + dy*s;  v = dy*c - dx*s;
+ *   b + a*exp(-(u^2/(2*sx^2) + v^2/(2*sy^2)))
+ * A definition's name follows the name rule and is not a variable, a parameter, a function, pi or an earlier definition
+ * (single assignment); it may be used in every later statement, any number of times, also never.  The last statement is
+ * the model value and has no name; a trailing ';' or an empty statement is an error.  A formula without ';' compiles to
+ * the program it always did.
+ * THE PROGRAM IS THE POSTFIX OF THE PARSE TREE: no constant folding, no reassociation, no sharing the user did not write
+ * (a unary '+' emits nothing; every literal and every pi is a constant of its own; a definition is written once however
+ * often it is used, and counts once toward the 256 instructions and 64 constants).  THE FRAME: statement k is compiled with
+ * k slots of the stack in use, so its root lands in slot k and stays there -- no instruction stores --, the next statement
+ * evaluates on top of it, and the model value ends in slot ndef, the number of definitions.  depth (nlh_expr_shape) is
+ * that frame: the most slots in use, definitions included, 16 at most.  Instructions (op, arg):
  *   CONST i (consts[i])   VAR v   PARAM k   NEG   ADD   SUB   MUL   DIV   (b on top of the stack, a below it)
  *   IPOW k   an integer literal exponent, 2 <= |k| <= 16          POWC i   any other literal exponent c = consts[i]
  *   EXP LOG SQRT SIN COS TANH ATAN ABS   ERF ERFC ERFCX   VOIGT (pops x, sigma, gamma -- gamma on top -- and pushes one)
  *   POW ATAN2 MIN MAX (b on top, a below it)   WHERE (pops c, a, b -- b on top -- and pushes one)
+ *   LOAD k   pushes a copy of slot k, the value of definition k
  * THE ARITHMETIC IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation, the device library's
  * functions -- so that a restatement in any IEEE language reproduces bit for bit an exp-free formula: one without a
  * library function (POWC EXP LOG SIN COS TANH ATAN ERF ERFC ERFCX POW ATAN2).  VOIGT is not one: a formula whose only
@@ -837,7 +851,11 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
  *           The two guards make a = 0 usable: gb is its limit 0 for b > 0 instead of 0*-inf, and an infinite ga
  *           (b < 1) against a zero da is 0.  a < 0 with a tangent in b is outside the domain (log(a): NaN).
  *           (the device library's pow, atan2, log)
+ *     LOAD k  v = the value in slot k;  tangent: the one in slot k, Z where definition k's is (a copy: no operation)
  *     a root that is Z writes +0.0
+ *   A program with definitions gives, bit for bit, the value and every Jacobian column of the formula with each definition
+ *   substituted in parentheses: the operations on the operands are the same, and each IEEE operation and each library
+ *   function is deterministic.  Whether a formula is in the bit-exact class is decided by the functions it uses, as before.
  *   "structural": the compiler records per instruction the 32-bit mask of the parameters its subtree names -- WHERE's
  *   condition included --; the tangent of a node for column j is present exactly when bit j of that mask is set, whatever
  *   the values are.
@@ -879,22 +897,24 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
 #define NLH_EXPR_MIN   24
 #define NLH_EXPR_MAX   25
 #define NLH_EXPR_WHERE 26
+#define NLH_EXPR_LOAD  27
 typedef struct nlh_expr nlh_expr;
 /* Compile (host code only, thread-safe).  Errors -- a syntax error, an unknown name, a name in both lists, a duplicate or
- * reserved name ("'erf' is a function"), a wrong number of arguments, an empty list or item, too many names, more than 256 instructions, 64 constants or a stack deeper than 16
+ * reserved name ("'erf' is a function"), a definition whose name is taken ("'t' is a variable", "'u' is already defined"), a wrong number of arguments, an empty list or item, too many names, more than 256 instructions, 64 constants or a stack deeper than 16
  * -- return NLH_INVALID_INPUT_ERROR, leave *e NULL and set the message nlh_expr_error() returns (thread-local), e.g.
  * "col 17: unknown name 'foo'" (0-based column of the formula; "vars col 2: ..." / "params col 2: ..." for the lists). */
 int nlh_expr_compile(const char *formula, const char *vars, const char *params, nlh_expr **e);
 const char *nlh_expr_error(void);
 void nlh_expr_destroy(nlh_expr *e);
-/* Any of the outputs may be NULL.  depth: the deepest the evaluation stack gets. */
+/* Any of the outputs may be NULL.  depth: the deepest the evaluation stack gets, the definitions' slots included. */
 void nlh_expr_shape(const nlh_expr *e, int32_t *nvar, int32_t *nparams, int32_t *ninstr, int32_t *nconst, int32_t *depth);
 /* Read-back, for restatements: op, arg [ninstr], consts [nconst] (any may be NULL).  The dependency masks: nlh_expr_masks. */
 int nlh_expr_program(const nlh_expr *e, int32_t *op, int32_t *arg, double *consts);
 int nlh_expr_masks(const nlh_expr *e, uint32_t *mask);
 /* Operand roots [ninstr] (either may be NULL): aroot, the instruction that produced the lower operand of a binary
  * instruction (POW, ATAN2, MIN, MAX included), VOIGT's x or WHERE's c; broot, the one that produced VOIGT's sigma or
- * WHERE's a (0 elsewhere).  The top operand's is i - 1.  The code word is op | (arg & 0xff) << 8 | aroot << 16 |
+ * WHERE's a (0 elsewhere).  The top operand's is i - 1.  LOAD k is a leaf for both rules; its own aroot is the instruction
+ * that produced definition k, and its mask that instruction's.  The code word is op | (arg & 0xff) << 8 | aroot << 16 |
  * broot << 24, so all of VOIGT's and WHERE's dependency masks are structural. */
 int nlh_expr_roots(const nlh_expr *e, int32_t *aroot, int32_t *broot);
 

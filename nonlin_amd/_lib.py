@@ -428,6 +428,8 @@ EXPR_OPS = ("CONST", "VAR", "PARAM", "NEG", "ADD", "SUB", "MUL", "DIV", "IPOW", 
 EXPR_SPECIAL_OPS = ("ERF", "ERFC", "ERFCX", "VOIGT")
 # ... and of the fitted exponent, the four-quadrant angle and the selections, numbered on from 22 (NLH_EXPR_POW ..)
 EXPR_EXTENDED_OPS = ("POW", "ATAN2", "MIN", "MAX", "WHERE")
+# ... and of a use of a definition, 27 (NLH_EXPR_LOAD)
+EXPR_DEF_OPS = ("LOAD",)
 
 
 def faddeeva_table():
@@ -485,8 +487,22 @@ class Expr(Owner):
     a < 0 with a fitted exponent is outside its domain), atan2(y, x) the four-quadrant angle, min(a, b) and max(a, b) the
     smaller and the larger (a hinge is max(t-t0, 0)), where(c, a, b) is a where c >= 0 and b elsewhere (an onset at t0:
     where(t-t0, ..., 0)); both branches are evaluated, and a NaN in the one not taken reaches neither the value nor the
-    Jacobian.  Function names and pi are reserved: no variable or parameter may carry one.  Raises
-    ValueError with the compiler's message ("col 17: unknown name 'foo'").  close() frees it (so does garbage collection)."""
+    Jacobian.  Function names and pi are reserved: no variable or parameter may carry one.
+
+    Definitions, formula := (name '=' expr ';')* expr, name a value that is computed once (blanks and newlines are ignored):
+
+        Expr("dx = x-x0; dy = y-y0; c = cos(th); s = sin(th);"
+             "u = dx*c + dy*s;  v = dy*c - dx*s;"
+             "b + a*exp(-(u^2/(2*sx^2) + v^2/(2*sy^2)))", "x,y", "a,x0,y0,sx,sy,th,b")
+
+    A definition's name is not a variable, a parameter, a function, pi or an earlier definition; it may be used in every later
+    statement, any number of times.  The last statement is the model value.  defs is the tuple of the definitions' names, in
+    order.  Statement k leaves its value in slot k of the stack, where LOAD k reads it, so depth counts the definitions' slots
+    (the frame, 16 at most) and a definition counts once toward the 256 instructions and 64 constants.  The value and every
+    Jacobian column are, bit for bit, those of the formula with each definition substituted in parentheses.
+
+    Raises ValueError with the compiler's message ("col 17: unknown name 'foo'").  close() frees it (so does garbage
+    collection)."""
     _free = "nlh_expr_destroy"
 
     def __init__(self, formula, vars=("t",), params=()):
@@ -500,10 +516,22 @@ class Expr(Owner):
         s = [C.c_int32() for _ in range(5)]
         self.lib.nlh_expr_shape(self.ptr, *[C.byref(v) for v in s])
         self.nvar, self.nparams, self.ninstr, self.nconst, self.depth = (v.value for v in s)
+        self.defs = tuple(st.split("=")[0].strip() for st in formula.split(";")[:-1])    # (it compiled: name '=' expr ';' each)
+        if len(self.defs) != self._ndef():                            # the compiler's own count: the slot the model value ends in
+            raise RuntimeError(f"Expr: {len(self.defs)} names read from the text, {self._ndef()} definitions in the program")
+
+    def _ndef(self):
+        """The definitions of the compiled program, from the program alone: every statement leaves one slot in use, so the
+        stack ends ndef + 1 deep."""
+        sp = 0
+        for o in self.program()[0]:
+            sp += 1 if o <= 2 or o == 27 else (-1 if 4 <= o <= 7 or 22 <= o <= 25 else (-2 if o in (21, 26) else 0))
+        return sp - 1
 
     def program(self):
         """(op, arg, consts, mask): the postfix program as int32 arrays [ninstr], its constants [nconst] and per instruction
-        the uint32 mask of the parameters its subtree names."""
+        the uint32 mask of the parameters its subtree names.  LOAD k (a use of definition k): arg = k, the mask of the
+        instruction that produced the definition."""
         import numpy as np
         op, arg = np.zeros(self.ninstr, dtype=np.int32), np.zeros(self.ninstr, dtype=np.int32)
         consts, mask = np.zeros(self.nconst), np.zeros(self.ninstr, dtype=np.uint32)
@@ -516,7 +544,8 @@ class Expr(Owner):
     def roots(self):
         """(aroot, broot), int32 [ninstr]: the instruction that produced a binary instruction's lower operand or VOIGT's x, and
         the one that produced VOIGT's sigma (nlh_expr_roots).  WHERE has its condition c in aroot and its first branch a in
-        broot; the second branch is the instruction before it."""
+        broot; the second branch is the instruction before it.  LOAD k has the instruction that produced definition k in
+        aroot."""
         import numpy as np
         a, b = np.zeros(self.ninstr, dtype=np.int32), np.zeros(self.ninstr, dtype=np.int32)
         if self.lib.nlh_expr_roots(self.ptr, a.ctypes.data_as(c_int32_p), b.ctypes.data_as(c_int32_p)):

@@ -1,6 +1,7 @@
 // nlh_expr.hip -- formula models (include/nonlin_hip.h: nlh_expr_*): a model the user writes as an expression string.
 // First the compiler, pure host code that needs no GPU: a recursive-descent parser of the header's grammar that emits the
-// postfix of the parse tree as it goes -- no folding, no reassociation, no sharing -- with, per instruction, the mask of
+// postfix of the parse tree as it goes -- no folding, no reassociation, no sharing the user did not write (a definition,
+// name = expr;, is computed once and read by LOAD) -- with, per instruction, the mask of
 // the parameters its subtree names and the instruction that produced its left operand (VOIGT, WHERE: its two lower operands).  Then
 // the Faddeeva function's entry points (nlh_kernels_specfun.h), the launchers of the open
 // device-residual path (kernels and arithmetic: nlh_kernels_expr.h), which form a call runs and how many Jacobian
@@ -30,7 +31,7 @@ struct ExprFail {};
 struct ExprParser {
     const char *s;
     size_t at = 0;
-    std::vector<std::string> vars, params;
+    std::vector<std::string> vars, params, defs;   // defs[k]: the name of statement k, whose value stays in slot k
     ExprProg *P;
     int nconst = 0, sp = 0;
     int root[NLH_EXPR_MAX_DEPTH + 1];          // the instruction that produced each stack slot
@@ -49,7 +50,8 @@ struct ExprParser {
         const int pc = P->ninstr++;
         uint32_t mask = op == NLH_EXPR_PARAM ? 1u << arg : 0u;
         int aroot = 0, broot = 0;
-        if (pops == 3) {                       // VOIGT: x, sigma, gamma; WHERE: c, a, b
+        if (op == NLH_EXPR_LOAD) { aroot = root[arg]; mask = P->mask[aroot]; }   // a leaf that names its definition's producer
+        else if (pops == 3) {                       // VOIGT: x, sigma, gamma; WHERE: c, a, b
             aroot = root[sp - 3]; broot = root[sp - 2];
             mask = P->mask[aroot] | P->mask[broot] | P->mask[root[sp - 1]];
         }
@@ -83,6 +85,37 @@ struct ExprParser {
         return v;
     }
 
+    // formula := { name '=' expr ';' } expr.  Statement k is compiled with k slots in use, so its root lands in slot k and
+    // stays there: a definition needs no store, the next statement evaluates on top of it, the model value ends in slot ndef.
+    void formula()
+    {
+        for (;;) {
+            blanks();
+            size_t e = at;
+            if (alpha(s[e])) while (alpha(s[e]) || digit(s[e])) ++e;
+            size_t q = e;
+            while (s[q] == ' ' || s[q] == '\t' || s[q] == '\n' || s[q] == '\r') ++q;
+            if (e == at || s[q] != '=') break;                  // the last statement: the model value
+            const size_t col = at;
+            const std::string name(s + at, e - at);
+            for (const auto &f : EXPR_FUNCS)
+                if (name == f.name) fail(col, "'" + name + "' is a function");
+            if (name == "pi") fail(col, "'pi' is the constant");
+            for (const auto &v : vars)
+                if (name == v) fail(col, "'" + name + "' is a variable");
+            for (const auto &p : params)
+                if (name == p) fail(col, "'" + name + "' is a parameter");
+            for (const auto &d : defs)
+                if (name == d) fail(col, "'" + name + "' is already defined");
+            at = q + 1;
+            expr();
+            if (peek() != ';') fail(at, "';' expected after the definition of '" + name + "'");
+            ++at;
+            defs.push_back(name);                               // (usable from the next statement on)
+        }
+        expr();
+        if (peek()) fail(at, std::string("unexpected '") + s[at] + "'");
+    }
     void expr()
     {
         term();
@@ -173,6 +206,8 @@ struct ExprParser {
             if (name == vars[v]) { emit(col, NLH_EXPR_VAR, (int)v, 0); return; }
         for (size_t k = 0; k < params.size(); ++k)
             if (name == params[k]) { emit(col, NLH_EXPR_PARAM, (int)k, 0); return; }
+        for (size_t k = 0; k < defs.size(); ++k)
+            if (name == defs[k]) { emit(col, NLH_EXPR_LOAD, (int)k, 0); return; }
         fail(col, "unknown name '" + name + "'");
     }
 };
@@ -223,8 +258,7 @@ int nlh_expr_compile(const char *formula, const char *vars, const char *params, 
         return NLH_INVALID_INPUT_ERROR;
     }
     try {
-        ps.expr();
-        if (ps.peek()) ps.fail(ps.at, std::string("unexpected '") + ps.s[ps.at] + "'");
+        ps.formula();
     } catch (const ExprFail &) {
         delete x;
         return NLH_INVALID_INPUT_ERROR;
@@ -232,6 +266,7 @@ int nlh_expr_compile(const char *formula, const char *vars, const char *params, 
     x->prog.nvar = (int32_t)ps.vars.size();
     x->prog.nparams = (int32_t)ps.params.size();
     x->nconst = ps.nconst;
+    x->ndef = (int32_t)ps.defs.size();
     *e = x;
     return 0;
 }
@@ -309,10 +344,10 @@ int nlh_faddeeva_batch(nlh_handle *h, int64_t count, const double *dre, const do
 // ---------------------------------------------------------------------------------------------------------------------
 void nlh_expr_init_device(int lds_max)
 {
-    (void)hipFuncSetAttribute((const void *)k_expr_fcn<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    (void)hipFuncSetAttribute((const void *)k_expr_fcn<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    (void)hipFuncSetAttribute((const void *)k_expr_jac<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    (void)hipFuncSetAttribute((const void *)k_expr_jac<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    for (const void *k : {(const void *)k_expr_fcn<false, false>, (const void *)k_expr_fcn<true, false>, (const void *)k_expr_fcn<false, true>,
+                          (const void *)k_expr_fcn<true, true>, (const void *)k_expr_jac<false, false>, (const void *)k_expr_jac<true, false>,
+                          (const void *)k_expr_jac<false, true>, (const void *)k_expr_jac<true, true>})
+        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
 }
 
 // The form a launch runs, as the curve models choose it: flat (several points per workgroup) while two points or more fit
@@ -381,13 +416,11 @@ static int expr_launch(bool jac, const nlh_expr *e, int shared_t, int m, int64_t
     ed.shared_t = shared_t != 0; ed.m = m; ed.tstride = stride; ed.t = t; ed.y = y; ed.w = w;
     const dim3 grid((unsigned)p.grid);
     const int ppw = p.ppw, nblk = p.nblk, C = p.C;
-    if (!jac) {
-        if (p.flat) hipLaunchKernelGGL(k_expr_fcn<true>, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, dprob, dX, out);
-        else hipLaunchKernelGGL(k_expr_fcn<false>, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, dprob, dX, out);
-        return 0;
-    }
-    if (p.flat) hipLaunchKernelGGL(k_expr_jac<true>, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, C, dprob, dX, out);
-    else hipLaunchKernelGGL(k_expr_jac<false>, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, C, dprob, dX, out);
+    // (a program without definitions runs the instantiations that know none: the kernels it always ran)
+    const auto fcn = e->ndef ? (p.flat ? k_expr_fcn<true, true> : k_expr_fcn<false, true>) : (p.flat ? k_expr_fcn<true, false> : k_expr_fcn<false, false>);
+    const auto jk = e->ndef ? (p.flat ? k_expr_jac<true, true> : k_expr_jac<false, true>) : (p.flat ? k_expr_jac<true, false> : k_expr_jac<false, false>);
+    if (!jac) hipLaunchKernelGGL(fcn, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, dprob, dX, out);
+    else hipLaunchKernelGGL(jk, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, C, dprob, dX, out);
     return 0;
 }
 

@@ -48,11 +48,14 @@ __device__ static __noinline__ double expr_pow_family(int sel, double a, double 
 }
 
 // One pass over the program.  vs: this thread's column of the value stack (slot s at vs[s * 256]); ts: of the C tangent
-// stacks (column c, slot s at ts[(c * depth + s) * 256]), columns j0 .. j0 + C - 1 (C = 0: values only).  Returns the
-// root's value; the root's tangents are left in slot 0.
-template <bool TAN>
+// stacks (column c, slot s at ts[(c * depth + s) * 256]), columns j0 .. j0 + C - 1 (C = 0: values only).  Statement k of a
+// formula with definitions leaves its root in slot k, where LOAD k reads it; nothing stores.  Returns the root's value; the
+// root's tangents are left in the slot it ends in: slot 0 without definitions, slot ndef with them, which `slot` receives.
+// DEFS: the program has definitions.  The launcher chooses; without them the interpreter is, instruction for instruction,
+// the one it was before definitions existed -- no LOAD block, the result in slot 0 -- so the older formulas run the code they ran.
+template <bool TAN, bool DEFS>
 __device__ static inline double expr_run(const ExprProg &P, const double *xq, const double (&tv)[NLH_EXPR_MAX_VARS], double *vs, double *ts,
-                                         int j0, int C)
+                                         int j0, int C, int &slot)
 {
     const int depth = P.depth;
     const uint32_t cm = !TAN ? 0u : (C >= 32 ? 0xffffffffu : (1u << C) - 1u);   // (values only: every tangent test folds away)
@@ -97,7 +100,7 @@ __device__ static inline double expr_run(const ExprProg &P, const double *xq, co
             --sp;
             continue;
         }
-        if (op >= NLH_EXPR_VOIGT) {                               // the functions of several operands, behind the one test VOIGT had:
+        if (op >= NLH_EXPR_VOIGT) {                               // the functions of several operands and LOAD, behind the one test VOIGT had:
                                                                   // a test more per instruction cost the older formulas 2 - 3 %
             if (op == NLH_EXPR_VOIGT) {                           // ternary: x below sigma below gamma; w(z) once per pass
                 const double a = V(sp - 3), b = V(sp - 2), c3 = V(sp - 1);
@@ -129,6 +132,16 @@ __device__ static inline double expr_run(const ExprProg &P, const double *xq, co
                 }
                 V(sp - 3) = s ? V(sp - 2) : V(sp - 1);
                 sp -= 2;
+                continue;
+            }
+            if (DEFS && op == NLH_EXPR_LOAD) {                    // a use of definition arg: a copy of slot arg, the value and the
+                                                                  // tangents its mask names; the slot itself stays
+                for (uint32_t mm = (P.mask[pc] >> j0) & cm; mm; mm &= mm - 1) {
+                    const int c = __builtin_ctz(mm);
+                    T(c, sp) = T(c, arg);
+                }
+                V(sp) = V(arg);
+                ++sp;
                 continue;
             }
             // POW, ATAN2, MIN, MAX: binary, a below b (ADD .. DIV keep the block they had)
@@ -217,6 +230,7 @@ __device__ static inline double expr_run(const ExprProg &P, const double *xq, co
         }
         V(sp - 1) = v;
     }
+    if (DEFS) { slot = sp - 1; return V(sp - 1); }
     return V(0);
 #undef V
 #undef T
@@ -230,7 +244,7 @@ __device__ static inline void expr_load_vars(const ExprData &ed, int nvar, size_
     for (int v = 0; v < NLH_EXPR_MAX_VARS; ++v) tv[v] = ed.t[v < nvar ? o + (size_t)v * (size_t)ed.tstride : o];
 }
 
-template <bool FLAT>
+template <bool FLAT, bool DEFS>
 static __global__ void __launch_bounds__(256)
 k_expr_fcn(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints, const int32_t *__restrict__ dprob,
            const double *__restrict__ X, double *__restrict__ F)
@@ -248,13 +262,14 @@ k_expr_fcn(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints,
     const double w = ed.w ? ed.w[at] : 1.0;
     if (!on) return;
     double *vs = lds + (FLAT ? ppw : 1) * n + threadIdx.x;
-    double r = expr_run<false>(P, xq, tv, vs, vs, 0, 0);
+    int slot = 0;
+    double r = expr_run<false, DEFS>(P, xq, tv, vs, vs, 0, 0, slot);
     if (ed.y) r = r - y;
     if (ed.w) r = w * r;
     F[(size_t)q * ed.m + i] = r;
 }
 
-template <bool FLAT>
+template <bool FLAT, bool DEFS>
 static __global__ void __launch_bounds__(256)
 k_expr_jac(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints, int C, const int32_t *__restrict__ dprob,
            const double *__restrict__ X, double *__restrict__ J)
@@ -276,11 +291,12 @@ k_expr_jac(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints,
     double *ts = vs + P.depth * 256;
     double *Jq = J + (size_t)q * m * n + i;
     const uint32_t root = P.mask[P.ninstr - 1];
+    int slot = 0;                                                 // the slot the root ends in (a skipped pass reads none)
     for (int j0 = 0; j0 < n; j0 += C) {
         const int cc = min(C, n - j0);
-        if ((root >> j0) & (cc >= 32 ? 0xffffffffu : (1u << cc) - 1u)) expr_run<true>(P, xq, tv, vs, ts, j0, cc);
+        if ((root >> j0) & (cc >= 32 ? 0xffffffffu : (1u << cc) - 1u)) expr_run<true, DEFS>(P, xq, tv, vs, ts, j0, cc, slot);
         for (int c = 0; c < cc; ++c) {
-            const double d = (root >> (j0 + c)) & 1u ? ts[(c * P.depth) * 256] : 0.0;
+            const double d = (root >> (j0 + c)) & 1u ? ts[(c * P.depth + (DEFS ? slot : 0)) * 256] : 0.0;
             Jq[(size_t)(j0 + c) * m] = hw ? w * d : d;
         }
     }
