@@ -587,6 +587,167 @@ __device__ double norm2_flang_block_lanes(Get get, int len, double *cd, double *
     return r;
 }
 
+// norm2_flang_block_lanes with the chain of a chunk on TWO waves, for kernels whose registers decide how many workgroups a
+// compute unit holds: a chunk of 4096 elements is 128 runs of 32 consecutive elements instead of 64 runs of 64; run r
+// belongs to lane r % 64 of chain wave r / 64, which holds 32 terms (64 registers) instead of 64 (128).  The first chain
+// wave carries the running sum down its lanes exactly as above and hands it to the second through LDS across one
+// workgroup barrier; the second goes on from there.  The additions, their operands and their order are those of
+// norm2_flang_serial: bit-identical for every length.  A chunk of at most 2048 elements never reaches the second wave
+// (nor the barrier).  256 threads, 16 elements each (the preparation is the code above at E = 16, two threads per run);
+// cd: 128 * 34 doubles of LDS, 16-byte aligned; aux: 40 doubles + 256 ints (aux[34 .. 39] are the caller's).
+//
+// One chain wave's part: the sum t (the same in every lane) plus the terms of runs 0 .. nl - 1, run l in lane l's d[],
+// nm the new-maximum bits of the lane's run; returns the sum in every lane.
+__device__ __forceinline__ double nlh_chain_lanes32(const double (&d)[32], unsigned nm, double t, int nl)
+{
+    const unsigned long long mask = __ballot(nm == 0);               // runs without a new maximum
+    const int ntrip = (nl + 7) >> 3;                                 // (the terms behind the chunk's end are +0.0, see above)
+#pragma unroll 1
+    for (int g = 0; g < ntrip; ++g) {
+        const unsigned m8 = (unsigned)(mask >> (8 * g)) & 0xffu;
+        if (m8 == 0xffu) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                t = nlh_wave_shr1(t);
+#pragma unroll
+                for (int u = 0; u < 32; ++u) t = t + d[u];
+            }
+        } else {
+#pragma unroll 1
+            for (int q = 0; q < 8; ++q) {
+                t = nlh_wave_shr1(t);
+                if ((m8 >> q) & 1u) {
+#pragma unroll
+                    for (int u = 0; u < 32; ++u) t = t + d[u];
+                } else {
+                    // s <- s * c + d with c = d at a new maximum, 1 elsewhere; the flags of lane l serve every lane
+                    const unsigned nml = (unsigned)__builtin_amdgcn_readlane((int)nm, 8 * g + q);
+#pragma unroll
+                    for (int qd = 0; qd < 32; qd += 16) {
+                        if (((nml >> qd) & 0xffffu) == 0) {
+#pragma unroll
+                            for (int u = qd; u < qd + 16; ++u) t = t + d[u];
+                        } else {
+#pragma unroll
+                            for (int u = qd; u < qd + 16; ++u) {
+                                t = t * (((nml >> u) & 1u) ? d[u] : 1.0);
+                                t = t + d[u];
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+    const int lo = __builtin_amdgcn_readlane(__double2loint(t), 8 * ntrip - 1);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(t), 8 * ntrip - 1);
+    return __hiloint2double(hi, lo);
+}
+
+// The three parts of norm2_flang_block_lanes2, for a caller that holds a thread's elements in registers anyway (the pivot
+// kernel scales them afterwards): begin, one call per chunk with the thread's 16 consecutive elements x[] of any sign
+// (zeros behind the chunk's end; cl elements in the chunk), result.  All 256 threads call all three.
+__device__ __forceinline__ void norm2_lanes2_begin(double *aux)
+{
+    __syncthreads();
+    if (threadIdx.x == 0) { aux[32] = 0.0; aux[33] = 0.0; }
+}
+__device__ __forceinline__ void norm2_lanes2_chunk(const double (&x)[16], int cl, double *cd, double *aux)
+{
+    constexpr int EL = 32, E = 16, TPR = EL / E, nw = 4;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int cw = nlh_chain_wave(nw), cw2 = (cw + 1) & (nw - 1);       // the two waves that run the serial recurrence
+    double *dsv = cd, *wmax = aux, *carry = aux + 32;
+    int *tflags = reinterpret_cast<int *>(aux + 40);
+    const int i0 = tid * E;
+    double lm = 0.0;
+#pragma unroll
+    for (int u = 0; u < E; ++u) lm = fmax(lm, fabs(x[u]));
+    double sc = lm;                                                  // inclusive prefix maximum over the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double o = __shfl_up(sc, off, 64);
+        if (lane >= off) sc = fmax(sc, o);
+    }
+    double ex = __shfl_up(sc, 1, 64);
+    if (lane == 0) ex = 0.0;
+    __syncthreads();                                                 // carry of the previous chunk is final; every x[] is in registers
+    if (lane == 63) wmax[wid] = sc;
+    __syncthreads();
+    const double mx_in = carry[0];
+    double prev = fmax(mx_in, ex);
+    for (int w = 0; w < wid; ++w) prev = fmax(prev, wmax[w]);
+    unsigned newmax = 0;                                             // a bit per element that is a new maximum (c = d there)
+    // element i of the chunk lives at i + 2 * (i / EL): two doubles of padding behind every run
+    double2 *ddst = reinterpret_cast<double2 *>(dsv + i0 + 2 * (i0 / EL));
+#pragma unroll
+    for (int u = 0; u < E; u += 2) {
+        double dd[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const double av = fabs(x[u + h]);                        // branch-free, see norm2_flang_block_lanes
+            const bool gt = av > prev;
+            const double t = (gt ? prev : av) / (gt ? av : prev), tsq = t * t;
+            const double d = (prev == 0.0) ? 0.0 : tsq;
+            if (gt && prev != 0.0 && tsq != 1.0) newmax |= 1u << (u + h);        // s <- s * tsq + tsq
+            dd[h] = d;
+            prev = fmax(prev, av);
+        }
+        ddst[u >> 1] = make_double2(dd[0], dd[1]);
+    }
+    tflags[tid] = (int)newmax;
+    __syncthreads();
+    const int nl = (cl + EL - 1) / EL;                               // runs in use: 0 .. 63 on the first wave, the rest on the second
+    const bool two = nl > 64;                                        // (uniform over the workgroup)
+    const bool first = (wid == cw), second = two && (wid == cw2);
+    double d[EL];
+    unsigned nm = 0;
+    if (first || second) {                                           // (the second wave has its terms in registers before it waits)
+        const int run = (first ? 0 : 64) + lane;
+        const double2 *mine = reinterpret_cast<const double2 *>(dsv + run * (EL + 2));
+#pragma unroll
+        for (int u = 0; u < EL / 2; ++u) { const double2 v2 = mine[u]; d[2 * u] = v2.x; d[2 * u + 1] = v2.y; }
+#pragma unroll
+        for (int k = 0; k < TPR; ++k) nm |= (unsigned)tflags[run * TPR + k] << (k * E);
+    }
+    if (first) {
+        const double s = nlh_chain_lanes32(d, nm, carry[1], min(nl, 64));
+        double mx = mx_in;
+#pragma unroll
+        for (int w = 0; w < nw; ++w) mx = fmax(mx, wmax[w]);
+        if (lane == 0) { carry[1] = s; carry[0] = mx; }
+    }
+    if (two) {
+        __syncthreads();                                             // the first wave's sum is in carry[1]
+        if (second) {
+            const double s = nlh_chain_lanes32(d, nm, carry[1], nl - 64);
+            if (lane == 0) carry[1] = s;
+        }
+    }
+}
+__device__ __forceinline__ double norm2_lanes2_result(const double *aux)
+{
+    __syncthreads();
+    const double r = aux[32] * sqrt(1.0 + aux[33]);
+    __syncthreads();
+    return r;
+}
+
+template <typename Get>
+__device__ double norm2_flang_block_lanes2(Get get, int len, double *cd, double *aux)
+{
+    constexpr int CAP = 128 * 32, E = 16;
+    norm2_lanes2_begin(aux);
+    for (int base = 0; base < len; base += CAP) {
+        const int cl = min(CAP, len - base), i0 = threadIdx.x * E;
+        double x[E];
+#pragma unroll
+        for (int u = 0; u < E; ++u) x[u] = (i0 + u < cl) ? get(base + i0 + u) : 0.0;
+        norm2_lanes2_chunk(x, cl, cd, aux);
+    }
+    return norm2_lanes2_result(aux);
+}
+
 // Workgroup barrier that orders LDS traffic only: __syncthreads() would also drain the global loads in flight
 // (s_waitcnt vmcnt(0)) -- a full memory latency per round of a pipelined loop.
 __device__ __forceinline__ void nlh_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

@@ -301,10 +301,12 @@ k_qrx_init(int m, int n, int ld, int coff, size_t tst, double *__restrict__ T, c
 #define QRX_LONG_SU 4                                            // sectors per thread in flight in the long-column scaling
 #endif
 #ifndef QRX_PIV64_WG
-#define QRX_PIV64_WG 1                                           // workgroups per CU the batch instance of the 4096-row pivot kernel is compiled for
+#define QRX_PIV64_WG 4                                           // workgroups per CU the batch instance of the 4096-row pivot kernel is compiled for
 #endif
 #define QRX_LONG_MAXCH 96                                        // chunks the pipelined NORM2 keeps maxima for
-template <int QRX_NL, bool LONG = false, bool FEW = false>       // FEW: a handful of problems (the workgroup has its CU to itself)
+// STEP0 (the batch instance of the 4096-row kernel only): whether the instance can do step 0's physical interchange --
+// steps 1 .. n - 1 run the instance without it and do not carry its second load stream's registers.
+template <int QRX_NL, bool LONG = false, bool FEW = false, bool STEP0 = true>       // FEW: a handful of problems (the workgroup has its CU to itself)
 // (QRX_NL = 32, m <= 2048: 133 registers would leave three workgroups per CU; held to 128 -- four dwords spilled -- a launch of
 // 1024 problems is one round instead of two: 1024 x 2048x128 solves 1.8 % faster)
 __global__ void __launch_bounds__(LONG ? QRX_LONG_THREADS : 256, (QRX_NL == 32 && !FEW) ? 4 : (QRX_NL == 64 && !FEW && !LONG) ? QRX_PIV64_WG : 1)
@@ -315,7 +317,12 @@ k_qrx_pivot(int p0, int m, int n, int ld, int coff, size_t tst, size_t vst, int 
     // pipelined NORM2 -- three preparing waves and the chain wave, one wave per SIMD (with four preparing waves, 320
     // threads, the chain wave shared its SIMD with one of them: 253 us per 65536-row step against 241), 105 KB of LDS,
     // one workgroup per CU, which is all a handful of long-column problems need
-    __shared__ __attribute__((aligned(16))) double cd[LONG ? 2 * (64 * QRX_LONG_EL + 128) : (64 * QRX_NL + (FEW ? 256 : 128))];
+    // B64, the batch instance of the 4096-row kernel: held to 128 registers, four workgroups per CU -- a launch of 2048
+    // problems is two rounds of residency instead of four.  What that took: the chain of NORM2 on two waves of 32 terms
+    // per lane (norm2_flang_block_lanes2), the multipliers and the winner's entries in scalar registers, STEP0.
+    constexpr bool B64 = (QRX_NL == 64 && !LONG && !FEW);
+    static_assert(STEP0 || B64, "only the batch instance of the 4096-row kernel has a form without step 0");
+    __shared__ __attribute__((aligned(16))) double cd[LONG ? 2 * (64 * QRX_LONG_EL + 128) : (64 * QRX_NL + (B64 ? 512 : FEW ? 256 : 128))];
     __shared__ __attribute__((aligned(16))) double aux[LONG ? 8 + 256 : 40 + 128];
     __shared__ double wmx[LONG ? 3 * QRX_LONG_MAXCH : 1];
     __shared__ double red[64];
@@ -383,13 +390,17 @@ k_qrx_pivot(int p0, int m, int n, int ld, int coff, size_t tst, size_t vst, int 
         pub[tid - 1] = tpc[(size_t)(tid - 1) * ldp + kmax];
     }
     __syncthreads();
-    const int srck = pubi[0];
+    // (B64: what the winner published is the same in every lane -- scalar registers, operands of the multiplies below)
+    const int srck = B64 ? __builtin_amdgcn_readfirstlane(pubi[0]) : pubi[0];
 #ifdef QRX_DBG_CLK
     clk[1] = wall_clock64();
 #endif
     double tk[QRX_C];
 #pragma unroll
-    for (int q = 0; q < QRX_C; ++q) tk[q] = (q < QRX_C - 1 && q < np) ? pub[q] : 0.0;
+    for (int q = 0; q < QRX_C; ++q) {
+        tk[q] = (q < QRX_C - 1 && q < np) ? pub[q] : 0.0;
+        if (B64) tk[q] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(tk[q])), __builtin_amdgcn_readfirstlane(__double2loint(tk[q])));
+    }
     if (kmax != j) {
         if (tid == 0) {
             rdiag[kmax] = rd_j;
@@ -416,7 +427,7 @@ k_qrx_pivot(int p0, int m, int n, int ld, int coff, size_t tst, size_t vst, int 
     } else if (tid == 0) {
         slotof[srck] = -1;                                       // the pivot column is consumed
     }
-    const bool move0 = (j == 0 && kmax != 0);                   // see above: slot 0's column takes the pivot column's place
+    const bool move0 = STEP0 && (j == 0 && kmax != 0);          // see above: slot 0's column takes the pivot column's place
     if (LONG && (flush & 8)) {
         // split long-column step, part 1 of 3: the search and the bookkeeping only; the gather (k_qrx_gather_long, the
         // whole chip) and NORM2 (k_qrx_norm_long) follow as launches of their own
@@ -440,7 +451,8 @@ k_qrx_pivot(int p0, int m, int n, int ld, int coff, size_t tst, size_t vst, int 
     double *stage = cd;
     // (handful instances: a word of padding per NORM2 thread's KEEP consecutive elements -- read back at a stride of KEEP
     // doubles, every lane of a wave hit the same two banks: 1.2 us of a 4096-row step)
-    auto spos = [](int i) __attribute__((always_inline)) { return FEW ? i + i / (64 * QRX_NL / 256) : i; };
+    // (B64: two words behind every 16 -- a thread's 16 consecutive elements for NORM2, 16-byte accesses 144 bytes apart)
+    auto spos = [](int i) __attribute__((always_inline)) { return B64 ? i + 2 * (i / 16) : FEW ? i + i / (64 * QRX_NL / 256) : i; };
     // ... and in that case every thread KEEPS its rows (at most 64 * QRX_NL / 256 of them) in registers for the scaling
     // below: the raw column then never goes to memory -- one write of the reflector instead of write, read, write.
     constexpr int KEEP = 64 * QRX_NL / 256;                      // rows per thread when staged (16 or 8), four per iteration
@@ -492,7 +504,7 @@ k_qrx_pivot(int p0, int m, int n, int ld, int coff, size_t tst, size_t vst, int 
                 gather4(i0, e);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    keep[it * 4 + u] = e[u];
+                    if (!B64) keep[it * 4 + u] = e[u];           // (B64 keeps NORM2's elements instead, see below)
                     if (i0 + u * BS < m) stage[spos(i0 + u * BS - j)] = e[u];
                 }
             }
@@ -537,20 +549,64 @@ k_qrx_pivot(int p0, int m, int n, int ld, int coff, size_t tst, size_t vst, int 
         }
     }
     __syncthreads();
-    const double ejj = staged ? stage[0] : Vn[j];                 // (spos(0) = 0)
+    double ejj = 0.0;                                             // (spos(0) = 0)
+    if constexpr (B64) { if (tid == 0) aux[34] = staged ? stage[0] : Vn[j]; }    // waits in LDS behind NORM2's carry: a register pair less across it
+    else ejj = staged ? stage[0] : Vn[j];
 #ifdef QRX_DBG_CLK
     clk[2] = wall_clock64();
 #endif
                  // the diagonal entry before scaling (read before NORM2 reuses the region)
-    double ajnorm;                                                // :642
+    double ajnorm, ajj0 = 0.0;                                    // :642
     if constexpr (LONG) ajnorm = norm2_flang_block_lanes_pipe<QRX_LONG_EL, 192>([&](int i) { return Vn[j + i]; }, m - j, cd, aux, wmx);
+    else if constexpr (B64) {
+        if (staged) {
+            // The thread's 16 consecutive elements go through NORM2 and stay in registers for the scaling -- the rows a
+            // thread gathered (256 apart) would be 32 more registers live across NORM2.  The scaled elements change
+            // hands through LDS once more so that the reflector is stored a row per lane.
+            const int cl = m - j, e0 = tid * 16;
+            double x[16];
+            const double2 *sp = reinterpret_cast<const double2 *>(stage + spos(e0));
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const double2 v2 = sp[u];
+                x[2 * u] = (e0 + 2 * u < cl) ? v2.x : 0.0;
+                x[2 * u + 1] = (e0 + 2 * u + 1 < cl) ? v2.y : 0.0;
+            }
+            norm2_lanes2_begin(aux);
+            norm2_lanes2_chunk(x, cl, cd, aux);
+            ajnorm = norm2_lanes2_result(aux);
+            ejj = aux[34];
+#ifdef QRX_DBG_CLK
+            clk[3] = wall_clock64();
+#endif
+            if (ajnorm != 0.0 && ejj < 0.0) ajnorm = -ajnorm;     // :644
+            const double dn = (ajnorm != 0.0) ? ajnorm : 1.0;     // :645-646, see the staged form below
+#pragma unroll
+            for (int u = 0; u < 16; ++u) x[u] = x[u] / dn;
+            if (ajnorm != 0.0 && tid == 0) { x[0] = x[0] + 1.0; ajj0 = x[0]; }
+            double2 *dp = reinterpret_cast<double2 *>(stage + spos(e0));
+#pragma unroll
+            for (int u = 0; u < 8; ++u) dp[u] = make_double2(x[2 * u], x[2 * u + 1]);
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const int i = tid + u * BS;
+                if (i < cl) Vn[j + i] = stage[spos(i)];
+            }
+        } else {
+            ajnorm = norm2_flang_block_lanes2([&](int i) { return Vn[j + i]; }, m - j, cd, aux);
+            ejj = aux[34];
+        }
+    }
     else ajnorm = staged ? norm2_flang_block_lanes<QRX_NL, 256, FEW>([&](int i) { return stage[spos(i)]; }, m - j, cd, aux)
                          : norm2_flang_block_lanes<QRX_NL, 256, FEW>([&](int i) { return Vn[j + i]; }, m - j, cd, aux);
 #ifdef QRX_DBG_CLK
-    clk[3] = wall_clock64();
+    if (!(B64 && staged)) clk[3] = wall_clock64();
 #endif
-    double ajj = 0.0;
-    if (staged) {
+    double ajj = ajj0;
+    if (B64 && staged) {
+        // (scaled and stored above)
+    } else if (staged) {
         // :645-646 from the registers (ajnorm == 0: the column is zero; the reflector slot still gets the column)
         if (ajnorm != 0.0 && ejj < 0.0) ajnorm = -ajnorm;         // :644
         // the divisions of all the thread's rows first, unconditionally (x / 1.0 == x stands for "no reflector"): under
@@ -2143,7 +2199,10 @@ static bool launch_pivot(const QrxLaunch &a, const nlh_qrx_plan_step &s)
     case NLH_QRX_PIVOT_FEW32: pivot(k_qrx_pivot<32, false, true>, 256, s.pf); return true;
     case NLH_QRX_PIVOT_BATCH32: pivot(k_qrx_pivot<32>, 256, s.pf); return true;
     case NLH_QRX_PIVOT_FEW64: pivot(k_qrx_pivot<64, false, true>, 256, s.pf); return true;
-    case NLH_QRX_PIVOT_BATCH64: pivot(k_qrx_pivot<64>, 256, s.pf); return true;
+    case NLH_QRX_PIVOT_BATCH64:                                         // step 0's physical interchange: an instance of its own
+        if (s.j == 0) pivot(k_qrx_pivot<64, false, false, true>, 256, s.pf);
+        else pivot(k_qrx_pivot<64, false, false, false>, 256, s.pf);
+        return true;
     case NLH_QRX_PIVOT_LONG: pivot(k_qrx_pivot<64, true>, QRX_LONG_THREADS, s.pf); return true;
     case NLH_QRX_PIVOT_LONG_SCALED:                                     // flag 4: the scaling is left to k_qrx_scale_long
         pivot(k_qrx_pivot<64, true>, QRX_LONG_THREADS, s.pf | 4);
