@@ -780,7 +780,8 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
  *   unary := ('-'|'+') unary | power           power := atom ('^' ['-'] number)?
  *   atom  := number | name | func '(' expr (',' expr)* ')' | '(' expr ')'
  * number: what strtod reads in the C locale from a digit or '.'; name: a variable, a parameter or pi (the only named
- * constant); func: exp log sqrt sin cos tanh atan abs erf erfc erfcx voigt pow atan2 min max where.  voigt takes exactly
+ * constant); func: exp log sqrt sin cos tanh atan abs erf erfc erfcx voigt pow atan2 min max where j0 j1 i0e i1e lgamma expm1
+ * log1p.  voigt takes exactly
  * three arguments (x, sigma, gamma), where three (c, a, b: a where c >= 0, else b), pow(a, b), atan2(y, x), min(a, b) and
  * max(a, b) two, every other function one; another count is an error that names its column.  '^' takes a literal only: an
  * exponent that is a parameter or an expression is pow's second argument.  vars: 1 .. 4 comma-separated names; params: 1 .. 32, their order is
@@ -804,11 +805,15 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
  *   EXP LOG SQRT SIN COS TANH ATAN ABS   ERF ERFC ERFCX   VOIGT (pops x, sigma, gamma -- gamma on top -- and pushes one)
  *   POW ATAN2 MIN MAX (b on top, a below it)   WHERE (pops c, a, b -- b on top -- and pushes one)
  *   LOAD k   pushes a copy of slot k, the value of definition k
+ *   J0 J1 (the Bessel functions of the first kind)   I0E I1E (exp(-|a|) I0(a), exp(-|a|) I1(a): the scaled modified Bessel
+ *   functions; I0 itself overflows at 713)   LGAMMA (log |Gamma(a)|)   EXPM1 (exp(a) - 1)   LOG1P (log(1 + a)): one operand each
  * THE ARITHMETIC IS PART OF THE INTERFACE -- one IEEE operation per step, no fused operation, the device library's
  * functions -- so that a restatement in any IEEE language reproduces bit for bit an exp-free formula: one without a
- * library function (POWC EXP LOG SIN COS TANH ATAN ERF ERFC ERFCX POW ATAN2).  VOIGT is not one: a formula whose only
+ * library function (POWC EXP LOG SIN COS TANH ATAN ERF ERFC ERFCX POW ATAN2 J0 J1 LGAMMA EXPM1 LOG1P; a formula that uses
+ * them is within the running bound of the restatement, not bit for bit).  VOIGT is not one: a formula whose only
  * function is voigt stays in the bit-exact class (the Faddeeva function below is stated arithmetic, not a library call).
- * MIN, MAX and WHERE are selections and stay in it too.
+ * MIN, MAX and WHERE are selections and stay in it too.  I0E and I1E are stated arithmetic as well (+ - * / and sqrt): a
+ * formula whose only functions are i0e and i1e stays in the bit-exact class.
  *   values     the obvious operation per instruction;  POWC: pow(a, c);  NEG, ABS: sign operations;
  *              IPOW k: v = a; v = v*a (|k| - 1 times in all); for k < 0 then v = 1.0/v
  *   column j of the Jacobian: forward mode with STRUCTURAL zeros.  A node's tangent is absent (Z) or a double: CONST, VAR,
@@ -852,6 +857,33 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
  *           (b < 1) against a zero da is 0.  a < 0 with a tangent in b is outside the domain (log(a): NaN).
  *           (the device library's pow, atan2, log)
  *     LOAD k  v = the value in slot k;  tangent: the one in slot k, Z where definition k's is (a copy: no operation)
+ *     the unary functions below: g is computed only where the operand has a tangent
+ *     EXPM1  v = expm1(a)          g = exp(a)                         g*da     (not v + 1.0: it cancels for a << 0)
+ *     LOG1P  v = log1p(a)          da/(1.0 + a)
+ *     J0     v = j0(a)             g = j1(a)                          -(g*da)
+ *     J1     v = j1(a)             g = a == 0.0 ? 0.5 : j0(a) - v/a   g*da
+ *     I0E    v = i0e(a)            s = a < 0.0 ? -v : v;  g = i1e(a) - s                                   g*da
+ *     I1E    v = i1e(a)            s = a < 0.0 ? -v : v;  g = a == 0.0 ? 0.5 : (i0e(a) - s) - v/a          g*da
+ *     LGAMMA v = lgamma(a)         g = digamma(a)                     g*da
+ *            (the device library's expm1, log1p, j0, j1, lgamma, exp; i0e, i1e and digamma are stated here)
+ *       cheb(y, c[0 .. N-1]), Clenshaw's recurrence, the coefficients highest degree first:
+ *            b0 = c[0]; b1 = 0.0; b2 = 0.0;  for k = 1 .. N-1:  b2 = b1;  b1 = b0;  b0 = (y*b1 - b2) + c[k];   0.5*(b0 - b2)
+ *       i0e(a):  x = |a|;  x <= 8.0:  cheb(x/2.0 - 2.0, I0E_A[30])         else  cheb(32.0/x - 2.0, I0E_B[25])/sqrt(x)
+ *       i1e(a):  x = |a|;  x <= 1.0:  cheb(x*4.0 - 2.0, I1E_A[15])*x       else  x <= 8.0:  cheb((x - 4.5)/1.75, I1E_M[28])
+ *                                                                           else  cheb(32.0/x - 2.0, I1E_B[25])/sqrt(x)
+ *                then a < 0.0 ? -v : v   (odd; i1e(-0.0) is +0.0).  A NaN a takes the last range and stays NaN.
+ *            The five tables are the Chebyshev coefficients, in T_k(y/2) on -2 <= y <= 2, of exp(-x) I0(x) (x = 2(y + 2)),
+ *            of exp(-x) I1(x)/x (x = (y + 2)/4) and exp(-x) I1(x) (x = 4.5 + 1.75 y), and of sqrt(x) exp(-x) I0(x) and
+ *            sqrt(x) exp(-x) I1(x) (x = 32/(y + 2)): literal constants of the library
+ *            (nonlin_amd/csrc/nlh_kernels_specfun2.h), derived at 40 digits by tests/golden/make_specfun2_tables.py.
+ *            (i1e has a middle range because the series of exp(-x) I1(x)/x, taken up to 8, cancels to a thirtieth of its
+ *            terms there.)  Measured against 40-digit values, a uniform sample of [-8, 8] among them: i0e within
+ *            3.5 * 2^-52 of the true value, relatively, i1e within 1.7 * 2^-52.
+ *       digamma(a), a > 0 (NaN for a <= 0 and for a NaN a: outside the domain, as POW's log(a)), B[k] = B_2k+2/(2k + 2),
+ *            k = 0 .. 6: 1/12, -1/120, 1/252, -1/240, 1/132, -691/32760, 1/12:
+ *            r = 0.0;  while a < 10.0:  r = r + 1.0/a;  a = a + 1.0          (ten steps at most)
+ *            z = 1.0/(a*a);  p = B[6];  for k = 5 .. 0:  p = p*z + B[k];   p = p*z
+ *            ((log(a) - 0.5/a) - p) - r                                      (the device library's log)
  *     a root that is Z writes +0.0
  *   A program with definitions gives, bit for bit, the value and every Jacobian column of the formula with each definition
  *   substituted in parentheses: the operations on the operands are the same, and each IEEE operation and each library
@@ -898,9 +930,16 @@ int nlh_curve_fit_batch_h(nlh_handle *h, const nlh_options *opts, int32_t kind, 
 #define NLH_EXPR_MAX   25
 #define NLH_EXPR_WHERE 26
 #define NLH_EXPR_LOAD  27
+#define NLH_EXPR_J0    28
+#define NLH_EXPR_J1    29
+#define NLH_EXPR_I0E   30
+#define NLH_EXPR_I1E   31
+#define NLH_EXPR_LGAMMA 32
+#define NLH_EXPR_EXPM1 33
+#define NLH_EXPR_LOG1P 34
 typedef struct nlh_expr nlh_expr;
 /* Compile (host code only, thread-safe).  Errors -- a syntax error, an unknown name, a name in both lists, a duplicate or
- * reserved name ("'erf' is a function"), a definition whose name is taken ("'t' is a variable", "'u' is already defined"), a wrong number of arguments, an empty list or item, too many names, more than 256 instructions, 64 constants or a stack deeper than 16
+ * reserved name ("'erf' is a function", "'lgamma' is a function"), a definition whose name is taken ("'t' is a variable", "'u' is already defined"), a wrong number of arguments, an empty list or item, too many names, more than 256 instructions, 64 constants or a stack deeper than 16
  * -- return NLH_INVALID_INPUT_ERROR, leave *e NULL and set the message nlh_expr_error() returns (thread-local), e.g.
  * "col 17: unknown name 'foo'" (0-based column of the formula; "vars col 2: ..." / "params col 2: ..." for the lists). */
 int nlh_expr_compile(const char *formula, const char *vars, const char *params, nlh_expr **e);

@@ -9,7 +9,7 @@ from .api import (  # noqa: F401
     fcnnvar_helper, equation_optimizer, line_search_optimizer, bfgs, nelder_mead,
     value_pair, fcn1var_helper, equation_solver_1var, brent_solver, newton_1var_solver,
     CURVE_GAUSS, CURVE_LORENTZ, CURVE_EXPDECAY, CURVE_KINDS, curve_nparams,
-    Expr, EXPR_OPS, EXPR_SPECIAL_OPS, EXPR_EXTENDED_OPS, EXPR_DEF_OPS, wofz,
+    Expr, EXPR_OPS, EXPR_SPECIAL_OPS, EXPR_EXTENDED_OPS, EXPR_DEF_OPS, EXPR_SPECIAL2_OPS, wofz,
     ParamMap, PMAP_FREE, PMAP_FIXED, PMAP_TIED,
     Loss, LOSS_LINEAR, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY, LOSS_KINDS,
     Poisson,

@@ -430,6 +430,8 @@ EXPR_SPECIAL_OPS = ("ERF", "ERFC", "ERFCX", "VOIGT")
 EXPR_EXTENDED_OPS = ("POW", "ATAN2", "MIN", "MAX", "WHERE")
 # ... and of a use of a definition, 27 (NLH_EXPR_LOAD)
 EXPR_DEF_OPS = ("LOAD",)
+# ... and of the Bessel functions, the log-gamma function and the two cancellation-free forms, numbered on from 28 (NLH_EXPR_J0 ..)
+EXPR_SPECIAL2_OPS = ("J0", "J1", "I0E", "I1E", "LGAMMA", "EXPM1", "LOG1P")
 
 
 def faddeeva_table():
@@ -487,7 +489,10 @@ class Expr(Owner):
     a < 0 with a fitted exponent is outside its domain), atan2(y, x) the four-quadrant angle, min(a, b) and max(a, b) the
     smaller and the larger (a hinge is max(t-t0, 0)), where(c, a, b) is a where c >= 0 and b elsewhere (an onset at t0:
     where(t-t0, ..., 0)); both branches are evaluated, and a NaN in the one not taken reaches neither the value nor the
-    Jacobian.  Function names and pi are reserved: no variable or parameter may carry one.
+    Jacobian.  j0 and j1 are the Bessel functions of the first kind, i0e(a) = exp(-|a|) I0(a) and i1e(a) = exp(-|a|) I1(a) the
+    scaled modified ones (I0 itself overflows at 713), lgamma the logarithm of |Gamma| (its Jacobian is digamma, for a > 0),
+    expm1(a) = exp(a) - 1 and log1p(a) = log(1 + a) without the cancellation at small a.  2*j1(u)/u is 0/0 at u = 0: write
+    where(abs(u)-1e-4, 2*j1(u)/u, 1-u^2/8).  Function names and pi are reserved: no variable or parameter may carry one.
 
     Definitions, formula := (name '=' expr ';')* expr, name a value that is computed once (blanks and newlines are ignored):
 

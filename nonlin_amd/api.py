@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import CURVE_GAUSS, CURVE_LORENTZ, CURVE_EXPDECAY, CURVE_KINDS, curve_nparams  # noqa: F401  (built-in curve models)
-from ._lib import Expr, EXPR_OPS, EXPR_SPECIAL_OPS, EXPR_EXTENDED_OPS, EXPR_DEF_OPS, wofz  # noqa: F401  (formula models, their special functions)
+from ._lib import Expr, EXPR_OPS, EXPR_SPECIAL_OPS, EXPR_EXTENDED_OPS, EXPR_DEF_OPS, EXPR_SPECIAL2_OPS, wofz  # noqa: F401  (formula models, their special functions)
 from ._lib import ParamMap, PMAP_FREE, PMAP_FIXED, PMAP_TIED  # noqa: F401  (parameter maps)
 from ._lib import Group  # noqa: F401  (global fits)
 from ._lib import Loss, LOSS_LINEAR, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY, LOSS_KINDS  # noqa: F401  (robust losses)

@@ -3,7 +3,7 @@
 // postfix of the parse tree as it goes -- no folding, no reassociation, no sharing the user did not write (a definition,
 // name = expr;, is computed once and read by LOAD) -- with, per instruction, the mask of
 // the parameters its subtree names and the instruction that produced its left operand (VOIGT, WHERE: its two lower operands).  Then
-// the Faddeeva function's entry points (nlh_kernels_specfun.h), the launchers of the open
+// the Faddeeva function's entry points (nlh_kernels_specfun.h; J0 .. LOG1P: nlh_kernels_specfun2.h), the launchers of the open
 // device-residual path (kernels and arithmetic: nlh_kernels_expr.h), which form a call runs and how many Jacobian
 // columns a pass carries, model values (nlh_expr_eval_batch) and the eight one-call fits nlh_expr_fit_batch*: a formula as
 // the FitSource of the pipeline (nlh_fit.hip).  The model object that owns its program and data is nlh_expr_model_create
@@ -23,7 +23,9 @@ const char *nlh_expr_error(void) { return expr_err.c_str(); }
 static const struct { const char *name; int arity; } EXPR_FUNCS[] = {
     {"exp", 1}, {"log", 1}, {"sqrt", 1}, {"sin", 1}, {"cos", 1}, {"tanh", 1}, {"atan", 1}, {"abs", 1},   // NLH_EXPR_EXP ..
     {"erf", 1}, {"erfc", 1}, {"erfcx", 1}, {"voigt", 3},                                                 // NLH_EXPR_ERF ..
-    {"pow", 2}, {"atan2", 2}, {"min", 2}, {"max", 2}, {"where", 3}};                                     // NLH_EXPR_POW ..
+    {"pow", 2}, {"atan2", 2}, {"min", 2}, {"max", 2}, {"where", 3},                                      // NLH_EXPR_POW ..
+    {"j0", 1}, {"j1", 1}, {"i0e", 1}, {"i1e", 1}, {"lgamma", 1}, {"expm1", 1}, {"log1p", 1}};            // NLH_EXPR_J0 .. (LOAD lies between)
+static const int EXPR_FUNCS_OLD = NLH_EXPR_WHERE - NLH_EXPR_EXP + 1;   // the functions numbered on from NLH_EXPR_EXP
 
 namespace {
 struct ExprFail {};
@@ -186,7 +188,7 @@ struct ExprParser {
             if (name == EXPR_FUNCS[f].name) {
                 if (peek() != '(') fail(at, "'(' expected after the function '" + name + "'");
                 ++at;
-                const int op = NLH_EXPR_EXP + (int)f, want = EXPR_FUNCS[f].arity;
+                const int op = (int)f < EXPR_FUNCS_OLD ? NLH_EXPR_EXP + (int)f : NLH_EXPR_J0 + ((int)f - EXPR_FUNCS_OLD), want = EXPR_FUNCS[f].arity;
                 const std::string takes = "'" + name + "' takes " + (want == 1 ? "one argument" : (want == 2 ? "two arguments" : "three arguments"));
                 int have = 1;
                 expr();
@@ -267,6 +269,8 @@ int nlh_expr_compile(const char *formula, const char *vars, const char *params, 
     x->prog.nparams = (int32_t)ps.params.size();
     x->nconst = ps.nconst;
     x->ndef = (int32_t)ps.defs.size();
+    for (int i = 0; i < x->prog.ninstr; ++i)
+        if (EXPR_OP(x->prog.code[i]) >= NLH_EXPR_J0) x->sf2 = 1;
     *e = x;
     return 0;
 }
@@ -344,9 +348,10 @@ int nlh_faddeeva_batch(nlh_handle *h, int64_t count, const double *dre, const do
 // ---------------------------------------------------------------------------------------------------------------------
 void nlh_expr_init_device(int lds_max)
 {
-    for (const void *k : {(const void *)k_expr_fcn<false, false>, (const void *)k_expr_fcn<true, false>, (const void *)k_expr_fcn<false, true>,
-                          (const void *)k_expr_fcn<true, true>, (const void *)k_expr_jac<false, false>, (const void *)k_expr_jac<true, false>,
-                          (const void *)k_expr_jac<false, true>, (const void *)k_expr_jac<true, true>})
+    for (const void *k : {(const void *)k_expr_fcn<false, EXPR_PLAIN>, (const void *)k_expr_fcn<true, EXPR_PLAIN>, (const void *)k_expr_fcn<false, EXPR_DEFS>,
+                          (const void *)k_expr_fcn<true, EXPR_DEFS>, (const void *)k_expr_fcn<false, EXPR_SF2>, (const void *)k_expr_fcn<true, EXPR_SF2>,
+                          (const void *)k_expr_jac<false, EXPR_PLAIN>, (const void *)k_expr_jac<true, EXPR_PLAIN>, (const void *)k_expr_jac<false, EXPR_DEFS>,
+                          (const void *)k_expr_jac<true, EXPR_DEFS>, (const void *)k_expr_jac<false, EXPR_SF2>, (const void *)k_expr_jac<true, EXPR_SF2>})
         (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
 }
 
@@ -416,9 +421,14 @@ static int expr_launch(bool jac, const nlh_expr *e, int shared_t, int m, int64_t
     ed.shared_t = shared_t != 0; ed.m = m; ed.tstride = stride; ed.t = t; ed.y = y; ed.w = w;
     const dim3 grid((unsigned)p.grid);
     const int ppw = p.ppw, nblk = p.nblk, C = p.C;
-    // (a program without definitions runs the instantiations that know none: the kernels it always ran)
-    const auto fcn = e->ndef ? (p.flat ? k_expr_fcn<true, true> : k_expr_fcn<false, true>) : (p.flat ? k_expr_fcn<true, false> : k_expr_fcn<false, false>);
-    const auto jk = e->ndef ? (p.flat ? k_expr_jac<true, true> : k_expr_jac<false, true>) : (p.flat ? k_expr_jac<true, false> : k_expr_jac<false, false>);
+    // (a program without definitions runs the instantiations that know none, one without J0 .. LOG1P those that know none
+    // of them: the kernels they always ran)
+    const auto fcn = e->sf2 ? (p.flat ? k_expr_fcn<true, EXPR_SF2> : k_expr_fcn<false, EXPR_SF2>)
+                   : e->ndef ? (p.flat ? k_expr_fcn<true, EXPR_DEFS> : k_expr_fcn<false, EXPR_DEFS>)
+                             : (p.flat ? k_expr_fcn<true, EXPR_PLAIN> : k_expr_fcn<false, EXPR_PLAIN>);
+    const auto jk = e->sf2 ? (p.flat ? k_expr_jac<true, EXPR_SF2> : k_expr_jac<false, EXPR_SF2>)
+                  : e->ndef ? (p.flat ? k_expr_jac<true, EXPR_DEFS> : k_expr_jac<false, EXPR_DEFS>)
+                            : (p.flat ? k_expr_jac<true, EXPR_PLAIN> : k_expr_jac<false, EXPR_PLAIN>);
     if (!jac) hipLaunchKernelGGL(fcn, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, dprob, dX, out);
     else hipLaunchKernelGGL(jk, grid, dim3(256), p.lds, s, e->prog, ed, n, nblk, ppw, npoints, C, dprob, dX, out);
     return 0;

@@ -331,8 +331,9 @@ void nlh_band_init_device(int lds_max);          // nlh_band.hip: the band kerne
 // aroot is x's producer, broot sigma's, gamma's is i - 1 (broot is 0 elsewhere); mask[i]: the parameters instruction i's
 // subtree names.  LOAD k (a use of definition k, whose value stays in slot k): arg = k, aroot the instruction that produced
 // the definition, mask that instruction's.  depth: the frame, the most slots in use, definitions included.  ndef (host side,
-// nlh_expr): the definitions, so the slot the model value ends in; the launchers run the kernels' DEFS instantiations when it
-// is not 0, and ExprProg is what it was for the formulas without definitions.
+// nlh_expr): the definitions, so the slot the model value ends in; the launchers run the kernels' EXPR_DEFS instantiations when it
+// is not 0, and ExprProg is what it was for the formulas without definitions.  sf2 (host side): the program holds an
+// instruction of NLH_EXPR_J0 .. NLH_EXPR_LOG1P; the launchers then run the EXPR_SF2 instantiations, with definitions or none.
 struct ExprProg {
     int32_t ninstr, nvar, nparams, depth;
     uint32_t code[NLH_EXPR_MAX_INSTR];
@@ -341,7 +342,7 @@ struct ExprProg {
 };
 struct nlh_expr {
     ExprProg prog;
-    int32_t nconst, ndef;
+    int32_t nconst, ndef, sf2;
 };
 
 // The one-call fit + errors of the twenty-eight entry points nlh_{curve,expr}_fit_batch{,_pmap,_loss,_pois,_group,_conv,_sep}{,_h} (nlh_fit.hip).

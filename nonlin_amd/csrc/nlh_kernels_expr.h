@@ -20,6 +20,7 @@
 #include "nlh_internal.h"
 #include "nlh_kernels_place.h"
 #include "nlh_kernels_specfun.h"
+#include "nlh_kernels_specfun2.h"
 
 struct ExprData {                      // what the kernels read of an nlh_expr_ctx
     int shared_t, m;
@@ -47,13 +48,42 @@ __device__ static __noinline__ double expr_pow_family(int sel, double a, double 
     return sel == NLH_EXPR_POW ? pow(a, b) : (sel == NLH_EXPR_ATAN2 ? atan2(a, b) : log(a));
 }
 
+// The functions of NLH_EXPR_J0 .. NLH_EXPR_LOG1P behind one call, value and g of the header's table returned by value (a
+// pointer out-parameter costs every lane 16 bytes of scratch): the device library's j0, j1, lgamma, expm1, log1p, exp and
+// the stated i0e, i1e and digamma (nlh_kernels_specfun2.h), each inlined once.  tan: the operand has a tangent in this
+// pass (uniform); g is computed only then.  LOG1P's g is the divisor 1.0 + a.
+struct ExprSf2 { double v, g; };
+__device__ static __noinline__ ExprSf2 expr_sf2_family(int op, double a, bool tan)
+{
+    ExprSf2 r;
+    r.g = 0.0;
+    if (op <= NLH_EXPR_J1) {
+        const double f0 = op == NLH_EXPR_J0 || tan ? j0(a) : 0.0, f1 = op == NLH_EXPR_J1 || tan ? j1(a) : 0.0;
+        if (op == NLH_EXPR_J0) { r.v = f0; r.g = f1; }
+        else { r.v = f1; if (tan) r.g = a == 0.0 ? 0.5 : f0 - f1 / a; }
+    }
+    else if (op <= NLH_EXPR_I1E) {
+        const double f0 = op == NLH_EXPR_I0E || tan ? sf2_i0e(a) : 0.0, f1 = op == NLH_EXPR_I1E || tan ? sf2_i1e(a) : 0.0;
+        if (op == NLH_EXPR_I0E) { r.v = f0; if (tan) { const double s = a < 0.0 ? -f0 : f0; r.g = f1 - s; } }
+        else { r.v = f1; if (tan) { const double s = a < 0.0 ? -f1 : f1; r.g = a == 0.0 ? 0.5 : (f0 - s) - f1 / a; } }
+    }
+    else if (op == NLH_EXPR_LGAMMA) { r.v = lgamma(a); if (tan) r.g = sf2_digamma(a); }
+    else if (op == NLH_EXPR_EXPM1) { r.v = expm1(a); if (tan) r.g = exp(a); }
+    else { r.v = log1p(a); r.g = 1.0 + a; }
+    return r;
+}
+
 // One pass over the program.  vs: this thread's column of the value stack (slot s at vs[s * 256]); ts: of the C tangent
 // stacks (column c, slot s at ts[(c * depth + s) * 256]), columns j0 .. j0 + C - 1 (C = 0: values only).  Statement k of a
 // formula with definitions leaves its root in slot k, where LOAD k reads it; nothing stores.  Returns the root's value; the
 // root's tangents are left in the slot it ends in: slot 0 without definitions, slot ndef with them, which `slot` receives.
-// DEFS: the program has definitions.  The launcher chooses; without them the interpreter is, instruction for instruction,
-// the one it was before definitions existed -- no LOAD block, the result in slot 0 -- so the older formulas run the code they ran.
-template <bool TAN, bool DEFS>
+// KIND: what the program holds beyond the older instruction set -- EXPR_PLAIN nothing, EXPR_DEFS definitions, EXPR_SF2 an
+// instruction of NLH_EXPR_J0 .. NLH_EXPR_LOG1P (and definitions or none: with ndef = 0 the frame costs nothing).  The
+// launcher chooses; a lower kind is, instruction for instruction, the interpreter it was before the higher one existed --
+// EXPR_PLAIN: no LOAD block, the result in slot 0; below EXPR_SF2: no block of the newer functions and no call of their
+// family -- so the older formulas run the code they ran.
+enum { EXPR_PLAIN = 0, EXPR_DEFS = 1, EXPR_SF2 = 2 };
+template <bool TAN, int KIND>
 __device__ static inline double expr_run(const ExprProg &P, const double *xq, const double (&tv)[NLH_EXPR_MAX_VARS], double *vs, double *ts,
                                          int j0, int C, int &slot)
 {
@@ -134,7 +164,7 @@ __device__ static inline double expr_run(const ExprProg &P, const double *xq, co
                 sp -= 2;
                 continue;
             }
-            if (DEFS && op == NLH_EXPR_LOAD) {                    // a use of definition arg: a copy of slot arg, the value and the
+            if (KIND >= EXPR_DEFS && op == NLH_EXPR_LOAD) {       // a use of definition arg: a copy of slot arg, the value and the
                                                                   // tangents its mask names; the slot itself stays
                 for (uint32_t mm = (P.mask[pc] >> j0) & cm; mm; mm &= mm - 1) {
                     const int c = __builtin_ctz(mm);
@@ -142,6 +172,18 @@ __device__ static inline double expr_run(const ExprProg &P, const double *xq, co
                 }
                 V(sp) = V(arg);
                 ++sp;
+                continue;
+            }
+            if (KIND >= EXPR_SF2 && op >= NLH_EXPR_J0) {          // J0 .. LOG1P: unary, one call for the value and g
+                const double a = V(sp - 1);
+                const uint32_t ma = (P.mask[pc - 1] >> j0) & cm;
+                const ExprSf2 f = expr_sf2_family(op, a, ma != 0u);
+                for (uint32_t mm = ma; mm; mm &= mm - 1) {
+                    const int c = __builtin_ctz(mm);
+                    const double da = T(c, sp - 1);
+                    T(c, sp - 1) = op == NLH_EXPR_LOG1P ? da / f.g : (op == NLH_EXPR_J0 ? -(f.g * da) : f.g * da);
+                }
+                V(sp - 1) = f.v;
                 continue;
             }
             // POW, ATAN2, MIN, MAX: binary, a below b (ADD .. DIV keep the block they had)
@@ -230,7 +272,7 @@ __device__ static inline double expr_run(const ExprProg &P, const double *xq, co
         }
         V(sp - 1) = v;
     }
-    if (DEFS) { slot = sp - 1; return V(sp - 1); }
+    if (KIND >= EXPR_DEFS) { slot = sp - 1; return V(sp - 1); }
     return V(0);
 #undef V
 #undef T
@@ -244,7 +286,7 @@ __device__ static inline void expr_load_vars(const ExprData &ed, int nvar, size_
     for (int v = 0; v < NLH_EXPR_MAX_VARS; ++v) tv[v] = ed.t[v < nvar ? o + (size_t)v * (size_t)ed.tstride : o];
 }
 
-template <bool FLAT, bool DEFS>
+template <bool FLAT, int KIND>
 static __global__ void __launch_bounds__(256)
 k_expr_fcn(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints, const int32_t *__restrict__ dprob,
            const double *__restrict__ X, double *__restrict__ F)
@@ -263,13 +305,13 @@ k_expr_fcn(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints,
     if (!on) return;
     double *vs = lds + (FLAT ? ppw : 1) * n + threadIdx.x;
     int slot = 0;
-    double r = expr_run<false, DEFS>(P, xq, tv, vs, vs, 0, 0, slot);
+    double r = expr_run<false, KIND>(P, xq, tv, vs, vs, 0, 0, slot);
     if (ed.y) r = r - y;
     if (ed.w) r = w * r;
     F[(size_t)q * ed.m + i] = r;
 }
 
-template <bool FLAT, bool DEFS>
+template <bool FLAT, int KIND>
 static __global__ void __launch_bounds__(256)
 k_expr_jac(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints, int C, const int32_t *__restrict__ dprob,
            const double *__restrict__ X, double *__restrict__ J)
@@ -294,9 +336,9 @@ k_expr_jac(const ExprProg P, ExprData ed, int n, int nblk, int ppw, int npoints,
     int slot = 0;                                                 // the slot the root ends in (a skipped pass reads none)
     for (int j0 = 0; j0 < n; j0 += C) {
         const int cc = min(C, n - j0);
-        if ((root >> j0) & (cc >= 32 ? 0xffffffffu : (1u << cc) - 1u)) expr_run<true, DEFS>(P, xq, tv, vs, ts, j0, cc, slot);
+        if ((root >> j0) & (cc >= 32 ? 0xffffffffu : (1u << cc) - 1u)) expr_run<true, KIND>(P, xq, tv, vs, ts, j0, cc, slot);
         for (int c = 0; c < cc; ++c) {
-            const double d = (root >> (j0 + c)) & 1u ? ts[(c * P.depth + (DEFS ? slot : 0)) * 256] : 0.0;
+            const double d = (root >> (j0 + c)) & 1u ? ts[(c * P.depth + (KIND >= EXPR_DEFS ? slot : 0)) * 256] : 0.0;
             Jq[(size_t)(j0 + c) * m] = hw ? w * d : d;
         }
     }
