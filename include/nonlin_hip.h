@@ -1758,4 +1758,10 @@ const char *nlh_kernel_name(int32_t kernel_id);
 #ifdef __cplusplus
 }
 #endif
+
+/* ---- starting values for the built-in curve models: x0 for the one-call curve fits from the data alone, on the device.  The
+ * entry points, their flags and their stated arithmetic are in nonlin_hip_guess.h, a part of this ABI that this header
+ * includes: whoever includes nonlin_hip.h has them. ---- */
+#include "nonlin_hip_guess.h"
+
 #endif /* NONLIN_HIP_H */

@@ -16,6 +16,7 @@ from .api import (  # noqa: F401
     Convolve, CONV_ZERO, CONV_HOLD,
     Group,
     Separable,
+    GUESS_FALLBACK, GUESS_RANKDEF, GUESS_NONE, GUESS_MAX_M,
     NL_NO_ERROR, NL_INVALID_INPUT_ERROR, NL_ARRAY_SIZE_ERROR, NL_OUT_OF_MEMORY_ERROR,
     NL_INVALID_OPERATION_ERROR, NL_CONVERGENCE_ERROR, NL_DIVERGENT_BEHAVIOR_ERROR,
     NL_SPURIOUS_CONVERGENCE_ERROR, NL_TOLERANCE_TOO_SMALL_ERROR, NL_INDEX_OUT_OF_RANGE_ERROR,

@@ -356,6 +356,15 @@ SYMBOLS = {
 SYMBOLS.update({f"nlh_{model}_fit_batch{variant}{h}": _fit_signature(model, variant, bool(h))
                 for model in FIT_MODEL for variant in FIT_VARIANT for h in ("", "_h")})
 
+# The entry points of include/nonlin_hip_guess.h (the part of the ABI that nonlin_hip.h includes): SYMBOLS is the table of what
+# nonlin_hip.h itself declares, and tests hold it to that header and to a recorded table.
+GUESS_SYMBOLS = {
+    "nlh_curve_guess_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_curve_guess_batch_h": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32, c_double_p,
+                                          c_double_p, C.c_int32, c_double_p, c_int32_p]),
+}
+
 KERNEL_IDS = {
     "dq_residual": 0, "dq_panel": 1, "fd_jacobian": 2, "gram": 3, "gram_reduce": 4, "jtf": 5,
     "chol": 6, "lmpar": 7, "qr": 8, "update": 9, "lu": 10, "dq_jacobian": 11, "qrx_pass": 12, "qrx_pivot": 13,
@@ -385,7 +394,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(GUESS_SYMBOLS.items()):
         fn = getattr(lib, name)       # AttributeError if the ABI and this table drift
         fn.restype = res
         fn.argtypes = args
@@ -419,6 +428,11 @@ def curve_nparams(kind, ncomp=1, baseline=-1):
     if n < 0:
         raise ValueError(f"no curve model of kind {kind!r} with {ncomp} components and baseline degree {baseline}")
     return n
+
+
+# flags of a guessed problem (include/nonlin_hip.h: NLH_GUESS_*) and the most rows curve_guess takes
+GUESS_FALLBACK, GUESS_RANKDEF, GUESS_NONE = 1, 2, 4
+GUESS_MAX_M = 8192
 
 
 # opcodes of a compiled formula (include/nonlin_hip.h: NLH_EXPR_*), in order

@@ -19,6 +19,7 @@ from ._lib import CURVE_GAUSS, CURVE_LORENTZ, CURVE_EXPDECAY, CURVE_KINDS, curve
 from ._lib import Expr, EXPR_OPS, EXPR_SPECIAL_OPS, EXPR_EXTENDED_OPS, EXPR_DEF_OPS, EXPR_SPECIAL2_OPS, wofz  # noqa: F401  (formula models, their special functions)
 from ._lib import ParamMap, PMAP_FREE, PMAP_FIXED, PMAP_TIED  # noqa: F401  (parameter maps)
 from ._lib import Group  # noqa: F401  (global fits)
+from ._lib import GUESS_FALLBACK, GUESS_RANKDEF, GUESS_NONE, GUESS_MAX_M  # noqa: F401  (flags of DeviceSolver.curve_guess)
 from ._lib import Loss, LOSS_LINEAR, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY, LOSS_KINDS  # noqa: F401  (robust losses)
 from ._lib import Poisson  # noqa: F401  (Poisson likelihood fits)
 from ._lib import Convolve, CONV_ZERO, CONV_HOLD  # noqa: F401  (instrument-response fits)

@@ -22,6 +22,7 @@
 //   nlh_conv.hip       instrument-response fits: the wrapping launchers, apply, the check of a transform
 //   nlh_group.hip      global fits: the group object, the wrapping launchers, gather / expand / sigma
 //   nlh_sep.hip        separable fits: the object, the wrapping launchers (variable projection), gather / solve
+//   nlh_guess.hip      starting values for the curve models: the nonlinear stage's kernels, then nlh_sep_solve_batch
 //   nlh_model.hip      device sets, device residual models behind host arrays
 //   nlh_qrx.hip        the exact lmfactor
 // Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it launches.  nlh_launch.h:
@@ -79,7 +80,8 @@ struct nlh_handle {
            cvW, cvT, cvH,                 // covariance (nlh_covar.hip): the chain's arrays, the global-memory window, host-array staging
            crv,                           // one-call fits (nlh_fit.hip): status, non-zero-weight counts, a covariance nobody asked to keep
            sepx,                          // one-call separable fits (nlh_fit.hip): the nonlinear unknowns and, of a group, the outer ones
-           bdW, bdH;                      // bands (nlh_band.hip): the chain's Jacobian and values, host-array staging
+           bdW, bdH,                      // bands (nlh_band.hip): the chain's Jacobian and values, host-array staging
+           guessA, guessP, guessH;        // starting values (nlh_guess.hip): alpha / span / flags, the decays' panel, host-array staging
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     DevBuf cholmc;                     // side buffer of the multi-CU Cholesky (solved panels, bad-pivot flags)
@@ -324,6 +326,7 @@ void nlh_devfcn_init_device(int lds_max);        // nlh_devfcn.hip: the built-in
 void nlh_expr_init_device(int lds_max);          // nlh_expr.hip: the formula interpreter keeps its stacks in LDS
 void nlh_sep_init_device(int lds_max);           // nlh_sep.hip: the separable fits' kernels keep a point's panel in LDS
 void nlh_band_init_device(int lds_max);          // nlh_band.hip: the band kernel keeps a point's packed covariance in LDS
+void nlh_guess_init_device(int lds_max);         // nlh_guess.hip: the guess kernels keep a problem's valid rows in LDS
 
 // A compiled formula (nlh_expr.hip; include/nonlin_hip.h: nlh_expr_*).  ExprProg is what the kernels read, passed by value in
 // the kernel arguments: code[i] = op | (arg & 0xff) << 8 | aroot << 16 | broot << 24, aroot the instruction that produced the

@@ -278,6 +278,24 @@ class DeviceSolver:
                    x.data_ptr(), y.data_ptr())
         return y
 
+    def curve_guess(self, kind, t, y, ncomp=1, baseline=-1, weights=None, smooth=2):
+        """Starting values for curve_fit_batch from the data alone (nlh_curve_guess_batch): (x0 [nprob, n], flag [nprob],
+        int32).  The positions and widths of the ncomp highest peaks of the detrended data, smoothed with a moving mean over
+        2 smooth + 1 rows -- or the rates of one or two decays from the integral-equation regression --, then the best
+        linear fit of the amplitudes and the baseline at those values, weights honoured.  Rows with weight 0 are left out.
+        flag is a sum of nonlin_amd.GUESS_FALLBACK (a width or rate is the documented fallback), GUESS_RANKDEF (a dead column in
+        the linear fit: that amplitude is 0) and GUESS_NONE (not guessed, the row of x0 is NaN: fewer valid rows than
+        parameters, a value that is not finite, abscissae that do not ascend).  Deterministic: the same data give the same
+        bits.  At most 8192 rows; peaks are positive; ncomp <= 2 for "expdecay"."""
+        k = curve_kind(kind)
+        nprob, m, shared = self._curve_data(t, y, weights)
+        n = curve_nparams(k, ncomp, baseline)
+        x0 = torch.empty((nprob, n), dtype=torch.float64, device=y.device)
+        flag = torch.empty((nprob,), dtype=torch.int32, device=y.device)
+        self._call("nlh_curve_guess_batch", k, int(ncomp), int(baseline), nprob, m, t.data_ptr(), shared, y.data_ptr(),
+                   weights.data_ptr() if weights is not None else None, int(smooth), x0.data_ptr(), flag.data_ptr())
+        return x0, flag
+
     @staticmethod
     def _fit_outputs(x0, m, covariance, nsolve, nunk):
         """What a one-call fit writes: x (a copy of x0 [nprob, n]), fvec [nprob, m], sigma [nprob, n] and, per problem of the
@@ -313,6 +331,8 @@ class DeviceSolver:
         then the scaled parameter covariance at the solution.  Rows with weight 0 pad ragged data: they do not count as
         degrees of freedom.  Returns (x, fvec, sigma, cov, chi2, rank, ibs, status); sigma, cov, chi2, rank are None with
         covariance=False, NaN / -1 for a problem whose status is not 0.
+        x0=None: the fit starts from curve_guess(kind, t, y, ncomp, baseline, weights)[0]; together with pmap or group it
+        raises ValueError.
         pmap (a ParamMap over the model's n parameters): fixed and tied parameters (nlh_curve_fit_batch_pmap).  Every array
         keeps its full size; a fixed parameter keeps the value x0 holds for its problem, tied positions of x0 are ignored,
         bound entries at fixed and tied positions are not read, and sigma / cov are those of the full parameters.
@@ -343,6 +363,10 @@ class DeviceSolver:
         k = curve_kind(kind)
         nprob, m, shared = self._curve_data(t, y, weights)
         n = curve_nparams(k, ncomp, baseline)
+        if x0 is None:
+            if pmap is not None or group is not None:
+                raise ValueError("x0=None excludes pmap and group: a fixed or a shared parameter needs the caller's value")
+            x0 = self.curve_guess(k, t, y, ncomp, baseline, weights)[0]
         _chk(x0, (nprob, n), "x0")
         return self._fit("curve", dict(kind=k, ncomp=int(ncomp), nbase=int(baseline)), n, m, t, shared, y, weights, x0, lower, upper,
                          analytic, covariance, opts, pmap, loss, stat, group, conv, sep)

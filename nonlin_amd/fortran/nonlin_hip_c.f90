@@ -179,6 +179,19 @@ module nonlin_hip_c
             type(c_ptr), intent(out) :: model
             integer(c_int) :: rc
         end function
+        ! starting values for a curve model from host data (include/nonlin_hip_guess.h: nlh_curve_guess_batch_h; w: c_null_ptr for no
+        ! weights; flag: c_null_ptr when the flags are not wanted)
+        function nlh_curve_guess_batch_h(h, kind, ncomp, nbase, nprob, m, t, shared_t, y, w, smooth, x, flag) &
+                bind(C, name="nlh_curve_guess_batch_h") result(rc)
+            import :: c_ptr, c_int, c_int32_t, c_double
+            type(c_ptr), value :: h
+            integer(c_int32_t), value :: kind, ncomp, nbase, nprob, m, shared_t, smooth
+            real(c_double), intent(in) :: t(*), y(*)
+            type(c_ptr), value :: w
+            real(c_double), intent(out) :: x(*)
+            type(c_ptr), value :: flag
+            integer(c_int) :: rc
+        end function
         ! formula models (include/nonlin_hip.h: nlh_expr_*): compile on the host, then a model object on host data
         function nlh_expr_compile(formula, vars, params, e) bind(C, name="nlh_expr_compile") result(rc)
             import :: c_ptr, c_int, c_char

@@ -27,6 +27,7 @@ module nonlin_least_squares
         procedure, public :: covariance => lm_covariance_one
         procedure, public :: covariance_batch => lm_covariance_many
         procedure, public :: propagate_batch => lm_propagate_many
+        procedure, public :: curve_guess_batch => lm_curve_guess_many
     end type
 
     type, abstract, extends(least_squares_solver) :: constrained_equation_solver
@@ -310,6 +311,50 @@ contains
         if (rc /= 0) error stop rc
         val = vwork
         sd = swork
+    end subroutine
+
+    !> Extension: starting values for a built-in curve model from the data alone (nlh_curve_guess_batch_h): kind, ncomp and
+    !> baseline as device_model_batch%define_curve takes them, t(m, nprob) -- or t(m, 1): the same abscissae for every
+    !> problem --, y(m, nprob), optional weights w(m, nprob) (a row of weight 0 is left out).  x(n, nprob): the guessed
+    !> parameters, ready to be the x of solve_batch; flag(nprob): 0, or a sum of 1 (a width or rate is the documented
+    !> fallback), 2 (a dead column in the linear fit: that amplitude is 0) and 4 (not guessed: the column of x is NaN).
+    !> smooth (default 2): the half width, in rows, of the moving mean the peaks are looked for in.
+    subroutine lm_curve_guess_many(this, kind, ncomp, baseline, t, y, x, flag, w, smooth)
+        class(least_squares_solver), intent(inout) :: this
+        integer(int32), intent(in) :: kind, ncomp, baseline
+        real(real64), intent(in), dimension(:,:) :: t, y
+        real(real64), intent(out), dimension(:,:) :: x
+        integer(int32), intent(out), dimension(:) :: flag
+        real(real64), intent(in), dimension(:,:), optional :: w
+        integer(int32), intent(in), optional :: smooth
+
+        real(c_double), allocatable :: tc(:,:), yc(:,:), xwork(:,:)
+        real(c_double), allocatable, target :: wc(:,:)
+        integer(c_int32_t), allocatable, target :: fwork(:)
+        type(c_ptr) :: wp
+        integer(c_int) :: rc
+        integer(c_int32_t) :: shared, half
+
+        if (size(t, 1) /= size(y, 1) .or. (size(t, 2) /= size(y, 2) .and. size(t, 2) /= 1)) error stop NL_ARRAY_SIZE_ERROR
+        if (size(x, 2) /= size(y, 2) .or. size(flag) /= size(y, 2)) error stop NL_ARRAY_SIZE_ERROR
+        shared = 0
+        if (size(t, 2) == 1 .and. size(y, 2) /= 1) shared = 1
+        half = 2
+        if (present(smooth)) half = int(smooth, c_int32_t)
+        tc = t                                               ! contiguous copies: the dummies may be sections
+        yc = y
+        wp = c_null_ptr
+        if (present(w)) then
+            if (any(shape(w) /= shape(y))) error stop NL_ARRAY_SIZE_ERROR
+            wc = w
+            wp = c_loc(wc)
+        end if
+        allocate(xwork(size(x, 1), size(x, 2)), fwork(size(flag)))
+        rc = nlh_curve_guess_batch_h(nlh_default_handle(), int(kind, c_int32_t), int(ncomp, c_int32_t), int(baseline, c_int32_t), &
+            int(size(y, 2), c_int32_t), int(size(y, 1), c_int32_t), tc, shared, yc, wp, half, xwork, c_loc(fwork))
+        if (rc /= 0) error stop rc
+        x = xwork
+        flag = fwork
     end subroutine
 
     ! ---- constrained_equation_solver: the box -------------------------------------------------------------------
