@@ -1764,4 +1764,9 @@ const char *nlh_kernel_name(int32_t kernel_id);
  * includes: whoever includes nonlin_hip.h has them. ---- */
 #include "nonlin_hip_guess.h"
 
+/* ---- starts: starting values for ANY device model from a box -- the cost of a residual launcher at the candidates of the box,
+ * for every problem at once, and the best of them per problem.  The entry points and their stated arithmetic are in
+ * nonlin_hip_starts.h, a part of this ABI that this header includes in the same way. ---- */
+#include "nonlin_hip_starts.h"
+
 #endif /* NONLIN_HIP_H */

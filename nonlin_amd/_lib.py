@@ -365,6 +365,19 @@ GUESS_SYMBOLS = {
                                           c_double_p, C.c_int32, c_double_p, c_int32_p]),
 }
 
+# The entry points of include/nonlin_hip_starts.h, the part of the ABI that holds the box scan: bound beside GUESS_SYMBOLS.
+_STARTS_BOX = [c_double_p, c_double_p, c_int32_p]                      # xl, xu, logscale: host arrays [n]
+STARTS_SYMBOLS = {
+    "nlh_starts_candidates": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + _STARTS_BOX + [c_double_p]),
+    "nlh_starts_search_batch_device": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, DEVFCN, C.c_void_p] + _STARTS_BOX +
+                                       [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_starts_search_batch_device_h": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, DEVFCN, C.c_void_p] + _STARTS_BOX +
+                                         [C.c_int32, C.c_int32, c_double_p, c_double_p, c_int32_p]),
+    "nlh_starts_cost_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_starts_pick_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_starts_take_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 KERNEL_IDS = {
     "dq_residual": 0, "dq_panel": 1, "fd_jacobian": 2, "gram": 3, "gram_reduce": 4, "jtf": 5,
     "chol": 6, "lmpar": 7, "qr": 8, "update": 9, "lu": 10, "dq_jacobian": 11, "qrx_pass": 12, "qrx_pivot": 13,
@@ -394,7 +407,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(GUESS_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(GUESS_SYMBOLS.items()) + list(STARTS_SYMBOLS.items()):
         fn = getattr(lib, name)       # AttributeError if the ABI and this table drift
         fn.restype = res
         fn.argtypes = args
@@ -729,6 +742,100 @@ class Separable(Owner):
         if rc:
             raise RuntimeError(f"nlh_sep_tables returned {rc}")
         return lin, nl
+
+
+# limits of the box scan (include/nonlin_hip_starts.h: NLH_STARTS_*)
+STARTS_MAX_N, STARTS_MAX_KEEP, STARTS_MAX_CAND = 32, 8, 1 << 20
+
+
+class Starts:
+    """The box scan that makes starting values (include/nonlin_hip_starts.h: nlh_starts_*; host data only, needs no GPU):
+    the cost of the model at ncand candidate points of the box lower .. upper, for every problem at once, and a fit from the
+    keep best of them, of which the best result is returned.  The box is over the model's full parameter vector, one box for
+    every problem; it is the scan's alone and independent of a fit's own lower / upper.  log: the indices of the parameters
+    whose candidates are spread evenly in the logarithm (they need lower > 0).  E.g.
+
+        Starts(lower=(0.1, 1.0, -pi, -2.0), upper=(10.0, 60.0, pi, 2.0), ncand=4096, log=(0,))
+
+    The candidates are the unscrambled Halton sequence, which degrades as the dimensions grow: scan few parameters -- with
+    sep= only the nonlinear ones are scanned -- or give the ones that are known a tight box (lower == upper is allowed).
+    Raises ValueError for what the library refuses: no or more than 32 parameters, a bound that is not finite, lower > upper,
+    a log parameter with lower <= 0, ncand outside 1 .. 2^20, keep outside 1 .. 8 or above ncand.
+    After curve_fit_batch / expr_fit_batch(..., starts=s) the record of that call is on s: s.which [nprob] (int32, the k of
+    the start whose fit was returned, -1: no fit ended with a finite cost), s.index [nprob, keep] (int32, the candidates
+    kept, -1: none) and s.cost [nprob, keep] (their cost in the scan), device tensors."""
+
+    def __init__(self, lower, upper, ncand=256, keep=1, log=()):
+        import numpy as np
+        try:
+            lo, hi = np.array(lower, dtype=np.float64), np.array(upper, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("Starts: lower and upper must be sequences of numbers") from None
+        if lo.ndim != 1 or lo.shape != hi.shape:
+            raise ValueError("Starts: lower and upper are 1-D and of one length, the model's parameters")
+        for v, name in ((ncand, "ncand"), (keep, "keep")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"Starts: {name} must be an integer, not {v!r}")
+        n = len(lo)
+        lg = np.zeros(n, dtype=np.int32)
+        for k in log:
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) < n:
+                raise ValueError(f"Starts: log holds indices in 0 .. {n - 1}, not {k!r}")
+            lg[int(k)] = 1
+        self.lower, self.upper, self.logscale = np.ascontiguousarray(lo), np.ascontiguousarray(hi), lg
+        self.n, self.ncand, self.keep = n, int(ncand), int(keep)
+        self.which = self.index = self.cost = None
+        if not 1 <= self.ncand <= STARTS_MAX_CAND:
+            raise ValueError(f"Starts: ncand must be in 1 .. {STARTS_MAX_CAND}, not {ncand}")
+        if not 1 <= self.keep <= min(STARTS_MAX_KEEP, self.ncand):
+            raise ValueError(f"Starts: keep must be in 1 .. {STARTS_MAX_KEEP} and at most ncand, not {keep}")
+        if self._candidates(self.lower, self.upper, lg, 0, 0) is None:
+            raise ValueError(f"Starts: the library refuses this box (1 .. {STARTS_MAX_N} parameters, finite bounds, lower <= upper, "
+                             "lower > 0 where log)")
+
+    @classmethod
+    def for_expr(cls, expr, lower, upper, ncand=256, keep=1, log=()):
+        """The same by the parameter names of an Expr: lower and upper are dicts that name every parameter, log names.
+        Starts.for_expr(e, lower={"a": 0.1, "k": 0.01}, upper={"a": 10.0, "k": 100.0}, log=("k",))."""
+        names = [v.strip() for v in expr.params.split(",")]
+        for given in (lower, upper, log):
+            for name in given:
+                if name not in names:
+                    raise ValueError(f"Starts: {name!r} is not a parameter of the formula ({', '.join(names)})")
+        for given in (lower, upper):
+            for name in names:
+                if name not in given:
+                    raise ValueError(f"Starts: the box has no bound for the parameter {name!r}")
+        return cls([lower[k] for k in names], [upper[k] for k in names], ncand, keep, [names.index(k) for k in log])
+
+    @staticmethod
+    def _candidates(lo, hi, lg, first, count):
+        """nlh_starts_candidates: the table [count, n], or None when the library refuses."""
+        import numpy as np
+        out = np.empty((count, len(lo)))
+        rc = load().nlh_starts_candidates(len(lo), first, count, lo.ctypes.data_as(c_double_p), hi.ctypes.data_as(c_double_p),
+                                          lg.ctypes.data_as(c_int32_p), out.ctypes.data_as(c_double_p))
+        return None if rc else out
+
+    def box(self, positions=None):
+        """(lower, upper, logscale) as the library reads them, of the parameters at `positions` (None: all), in that order:
+        dimension d of the scan is positions[d]."""
+        import numpy as np
+        if positions is None:
+            return self.lower, self.upper, self.logscale
+        pos = [int(k) for k in positions]
+        if not pos or any(not 0 <= k < self.n for k in pos) or len(set(pos)) != len(pos):
+            raise ValueError(f"Starts: positions holds distinct indices in 0 .. {self.n - 1}")
+        return tuple(np.ascontiguousarray(a[pos]) for a in (self.lower, self.upper, self.logscale))
+
+    def candidates(self, first=0, count=None, positions=None):
+        """The candidates first .. first + count - 1 (count None: up to ncand) as a table [count, n] -- or over the parameters
+        at `positions` alone -- (nlh_starts_candidates: host code)."""
+        count = self.ncand - first if count is None else count
+        out = self._candidates(*self.box(positions), int(first), int(count))
+        if out is None:
+            raise ValueError(f"Starts.candidates: first >= 0, count >= 0 and first + count <= {STARTS_MAX_CAND}")
+        return out
 
 
 # kinds of a robust loss (include/nonlin_hip.h: NLH_LOSS_*)

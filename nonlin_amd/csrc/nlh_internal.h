@@ -23,6 +23,7 @@
 //   nlh_group.hip      global fits: the group object, the wrapping launchers, gather / expand / sigma
 //   nlh_sep.hip        separable fits: the object, the wrapping launchers (variable projection), gather / solve
 //   nlh_guess.hip      starting values for the curve models: the nonlinear stage's kernels, then nlh_sep_solve_batch
+//   nlh_starts.hip     starts: the candidates of a box, the batched scan over any residual launcher, cost / pick / take
 //   nlh_model.hip      device sets, device residual models behind host arrays
 //   nlh_qrx.hip        the exact lmfactor
 // Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it launches.  nlh_launch.h:
@@ -81,7 +82,9 @@ struct nlh_handle {
            crv,                           // one-call fits (nlh_fit.hip): status, non-zero-weight counts, a covariance nobody asked to keep
            sepx,                          // one-call separable fits (nlh_fit.hip): the nonlinear unknowns and, of a group, the outer ones
            bdW, bdH,                      // bands (nlh_band.hip): the chain's Jacobian and values, host-array staging
-           guessA, guessP, guessH;        // starting values (nlh_guess.hip): alpha / span / flags, the decays' panel, host-array staging
+           guessA, guessP, guessH,        // starting values (nlh_guess.hip): alpha / span / flags, the decays' panel, host-array staging
+           startsC, startsX, startsF, startsS, startsH;   // starts (nlh_starts.hip): the candidate table, a chunk's points and problems, its
+                                          // residuals, its costs, host-array staging
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     DevBuf cholmc;                     // side buffer of the multi-CU Cholesky (solved panels, bad-pivot flags)

@@ -296,6 +296,111 @@ class DeviceSolver:
                    weights.data_ptr() if weights is not None else None, int(smooth), x0.data_ptr(), flag.data_ptr())
         return x0, flag
 
+    # -- starts: starting values for any launcher from a box ------------------------------
+    def starts_search(self, fcn, ctx, nprob, m, starts, positions=None):
+        """The box scan of a Starts for ANY residual launcher (fcn, ctx) -- a user's, curve_launchers', expr_launchers', or one
+        composed with pmap_launchers, group_launchers and the others -- over nprob problems of m rows
+        (nlh_starts_search_batch_device): the cost sum F^2 at starts.ncand candidates of the box for every problem, and per
+        problem the starts.keep candidates of smallest finite cost.  positions: the entries of the box that are the launcher's
+        unknowns, in the launcher's order (None: all of them) -- what a reduced launcher needs: Separable.tables()[1] for
+        sep_launchers, the free parameters for pmap_launchers.  Returns (x0 [nprob, keep, n], cost [nprob, keep],
+        index [nprob, keep] int32), ordered by (cost, index); a slot with no finite cost left has cost +Inf, index -1 and a
+        row of NaN.  Deterministic, and a problem's result does not depend on its batch."""
+        lo, hi, lg = starts.box(positions)
+        n, keep = len(lo), starts.keep
+        dev = self.device
+        x0 = torch.empty((nprob, keep, n), dtype=torch.float64, device=dev)
+        cost = torch.empty((nprob, keep), dtype=torch.float64, device=dev)
+        index = torch.empty((nprob, keep), dtype=torch.int32, device=dev)
+        self._call("nlh_starts_search_batch_device", int(nprob), int(m), n, self._devfcn(fcn), self._ctxp(ctx),
+                   lo.ctypes.data_as(_lib.c_double_p), hi.ctypes.data_as(_lib.c_double_p), lg.ctypes.data_as(_lib.c_int32_p),
+                   starts.ncand, keep, x0.data_ptr(), cost.data_ptr(), index.data_ptr())
+        return x0, cost, index
+
+    def starts_cost(self, F):
+        """cost [npoints] = sum F^2 of every row of F [npoints, m] in the scan's stated order (nlh_starts_cost_batch)."""
+        npoints, m = F.shape
+        _chk(F, (npoints, m), "F")
+        cost = torch.empty((npoints,), dtype=torch.float64, device=F.device)
+        self._call("nlh_starts_cost_batch", npoints, m, F.data_ptr(), cost.data_ptr())
+        return cost
+
+    def starts_pick(self, cost):
+        """which [nprob] (int32) = the k of the smallest finite cost[k, p] of cost [keep, nprob], the lowest k on a tie, -1 when
+        none is finite (nlh_starts_pick_batch)."""
+        keep, nprob = cost.shape
+        _chk(cost, (keep, nprob), "cost")
+        which = torch.empty((nprob,), dtype=torch.int32, device=cost.device)
+        self._call("nlh_starts_pick_batch", nprob, keep, cost.data_ptr(), which.data_ptr())
+        return which
+
+    def starts_take(self, src, which):
+        """dst [nprob, ...] = src[which[p], p] of src [keep, nprob, ...] (float64), NaN where which[p] is -1
+        (nlh_starts_take_batch)."""
+        keep, nprob = src.shape[:2]
+        _chk(src, src.shape, "src")
+        if not (which.is_cuda and which.dtype == torch.int32 and which.is_contiguous() and tuple(which.shape) == (nprob,)):
+            raise ValueError(f"which: expected a contiguous int32 GPU tensor of shape ({nprob},)")
+        dst = torch.empty(src.shape[1:], dtype=torch.float64, device=src.device)
+        width = dst.numel() // nprob if nprob else 1
+        self._call("nlh_starts_take_batch", nprob, keep, width, src.data_ptr(), which.data_ptr(), dst.data_ptr())
+        return dst
+
+    def _starts_fit(self, model, head, launchers, n, m, t, shared, y, weights, starts, lower, upper, analytic, covariance, opts, pmap,
+                    loss, stat, group, conv, sep):
+        """A one-call fit with starts=: the launchers of the fit composed in the order of the library's own pipeline -- the
+        model, then conv, then loss or stat, or sep around the model with conv inside --, starts_search on them, the one-call
+        fit from every kept start, and the fit of smallest cost per problem (starts_cost on fvec, starts_pick, starts_take).
+        launchers(weights): the model's own pair."""
+        if pmap is not None or group is not None:
+            raise ValueError("starts excludes pmap and group: compose pmap_launchers / group_launchers and call starts_search")
+        if starts.n != n:
+            raise ValueError(f"starts: a box over {starts.n} parameters, the model has {n}")
+        if stat is not None and loss is not None:
+            raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
+        if sep is not None and (loss is not None or stat is not None):
+            raise ValueError("sep excludes pmap, loss and stat: a map, a loss and a statistic are nonlinear in the projected parameters")
+        if sep is not None and sep.nparams != n:
+            raise ValueError(f"sep is over {sep.nparams} parameters, the model has {n}")
+        nprob = y.shape[0]
+        layers = [launchers(None if conv is not None or stat is not None else weights)]      # (every context stays alive in here)
+        if conv is not None:
+            layers.append(self.conv_launchers(conv, *layers[-1], y, None if stat is not None else weights))
+        if stat is not None:
+            layers.append(self.pois_launchers(stat, *layers[-1], y, weights))
+        if loss is not None:
+            layers.append(self.loss_launchers(loss, *layers[-1], nprob))
+        positions = None
+        if sep is not None:
+            layers.append(self.sep_launchers(sep, *layers[-1]))
+            positions = [int(k) for k in sep.tables()[1]]
+        fcn, _, ctx = layers[-1]
+        x0s, cost, index = self.starts_search(fcn, ctx, nprob, m, starts, positions)
+        runs = []
+        for k in range(starts.keep):
+            if positions is None:
+                x0 = x0s[:, k].contiguous()
+            else:                                                    # the linear positions of a separable fit's x0 are 0.0
+                x0 = torch.zeros((nprob, n), dtype=torch.float64, device=y.device)
+                x0[:, positions] = x0s[:, k]
+            runs.append(self._fit(model, head, n, m, t, shared, y, weights, x0, lower, upper, analytic, covariance, opts, None, loss, stat,
+                                  None, conv, sep))
+        which = self.starts_pick(torch.stack([self.starts_cost(r[1]) for r in runs]))
+        take = lambda j: self.starts_take(torch.stack([r[j] for r in runs]), which)
+        x, fvec = take(0), take(1)
+        sigma = cov = chi2 = rank = None
+        if covariance:
+            sigma, cov, chi2 = take(2), take(3), take(4)
+            # (rank is int32: as float64, exactly, through the same take; NaN -- no fit was picked -- is -1)
+            rank = torch.nan_to_num(self.starts_take(torch.stack([r[5] for r in runs]).to(torch.float64), which), nan=-1.0).to(torch.int32)
+        wh = which.cpu().tolist()                                    # ibs and status: the chosen fit's; of fit 0 where none was picked
+        ibs = [runs[max(k, 0)][6][p] for p, k in enumerate(wh)]
+        status = [runs[max(k, 0)][7][p] for p, k in enumerate(wh)]
+        starts.which, starts.index, starts.cost = which, index, cost
+        for layer in reversed(layers[1:]):
+            layer[2].close()
+        return x, fvec, sigma, cov, chi2, rank, ibs, status
+
     @staticmethod
     def _fit_outputs(x0, m, covariance, nsolve, nunk):
         """What a one-call fit writes: x (a copy of x0 [nprob, n]), fvec [nprob, m], sigma [nprob, n] and, per problem of the
@@ -325,7 +430,7 @@ class DeviceSolver:
                 None if hi is None else hi.ctypes.data_as(_lib.c_double_p))
 
     def curve_fit_batch(self, kind, t, y, x0, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
-                        covariance=True, opts=None, pmap=None, loss=None, stat=None, group=None, conv=None, sep=None):
+                        covariance=True, opts=None, pmap=None, loss=None, stat=None, group=None, conv=None, sep=None, starts=None):
         """Fit + errors of y.shape[0] curves in one call (nlh_curve_fit_batch): least_squares_solver%solve -- or, with lower /
         upper ([n], one box for every problem), constrained_least_squares_solver%solve -- from x0 [nprob, n] (not modified),
         then the scaled parameter covariance at the solution.  Rows with weight 0 pad ragged data: they do not count as
@@ -357,12 +462,26 @@ class DeviceSolver:
         solution with its linear parameters, fvec the model's residual there, sigma / cov / chi2 / rank those of the full
         model at x.  Bounds at linear positions must be infinite.  With group the shared parameters must all be nonlinear
         (shared lifetimes, amplitudes projected out per data set) and cov, chi2, rank, ibs, status are per group, as from
-        group= alone.  sep together with pmap, loss or stat raises ValueError: those are nonlinear in the projected parameters."""
+        group= alone.  sep together with pmap, loss or stat raises ValueError: those are nonlinear in the projected parameters.
+        starts (a Starts over the model's n parameters, with x0=None): the fit starts from a scan of the box instead of a
+        guess -- starts.ncand candidates are scored, for every problem at once, with the cost this fit minimises (through conv,
+        loss, stat; with sep over the nonlinear parameters only, the linear positions of x0 being 0.0), the fit runs from each of
+        the starts.keep best, and what comes back is, per problem, the fit of smallest final cost (sum fvec^2; NaN and rank -1
+        where no fit ended finite; ibs and status are the chosen fit's).  The record -- which start, which candidates, their
+        scan cost -- is left on the Starts object (see there).  lower / upper stay the solver's box, independent of the
+        scan's.  starts together with an x0, with pmap or with group raises ValueError.  None calls exactly what is called
+        without it."""
         if stat is not None and loss is not None:
             raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
         k = curve_kind(kind)
         nprob, m, shared = self._curve_data(t, y, weights)
         n = curve_nparams(k, ncomp, baseline)
+        if starts is not None:
+            if x0 is not None:
+                raise ValueError("starts excludes x0: the scan makes the starting values")
+            return self._starts_fit("curve", dict(kind=k, ncomp=int(ncomp), nbase=int(baseline)),
+                                    lambda w: self.curve_launchers(k, ncomp, baseline, t, y, w), n, m, t, shared, y, weights, starts,
+                                    lower, upper, analytic, covariance, opts, pmap, loss, stat, group, conv, sep)
         if x0 is None:
             if pmap is not None or group is not None:
                 raise ValueError("x0=None excludes pmap and group: a fixed or a shared parameter needs the caller's value")
@@ -471,15 +590,21 @@ class DeviceSolver:
         return torch.complex(wr, wi).reshape(z.shape)
 
     def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None,
-                       pmap=None, loss=None, stat=None, group=None, conv=None, sep=None):
+                       pmap=None, loss=None, stat=None, group=None, conv=None, sep=None, starts=None):
         """Fit + errors of y.shape[0] data sets to a formula in one call (nlh_expr_fit_batch): curve_fit_batch with an Expr in
         the place of (kind, ncomp, baseline), pmap (e.g. ParamMap.for_expr(expr, ...)), loss (a Loss), stat (a Poisson) and
         group (e.g. Group.for_expr(expr, shared=("k",), nsets=8): nlh_expr_fit_batch_group) included.  Returns (x, fvec, sigma,
-        cov, chi2, rank, ibs, status)."""
+        cov, chi2, rank, ibs, status).  x0=None with starts (e.g. Starts.for_expr(expr, lower={..}, upper={..})): the fit starts
+        from the best candidates of a box, as in curve_fit_batch."""
         if stat is not None and loss is not None:
             raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
         nprob, m, shared = self._expr_data(expr, t, y, weights)
         n = expr.nparams
+        if starts is not None:
+            if x0 is not None:
+                raise ValueError("starts excludes x0: the scan makes the starting values")
+            return self._starts_fit("expr", dict(expr=expr.ptr), lambda w: self.expr_launchers(expr, t, y, w), n, m, t, shared, y, weights,
+                                    starts, lower, upper, analytic, covariance, opts, pmap, loss, stat, group, conv, sep)
         _chk(x0, (nprob, n), "x0")
         # conv (a Convolve) and sep (a Separable, e.g. Separable.for_expr(expr, linear=("a", "c"))): as in curve_fit_batch
         return self._fit("expr", dict(expr=expr.ptr), n, m, t, shared, y, weights, x0, lower, upper, analytic, covariance, opts,
