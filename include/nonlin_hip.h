@@ -1769,4 +1769,9 @@ const char *nlh_kernel_name(int32_t kernel_id);
  * nonlin_hip_starts.h, a part of this ABI that this header includes in the same way. ---- */
 #include "nonlin_hip_starts.h"
 
+/* ---- bootstrap: confidence intervals of ANY fit from refits of resampled data -- the replicas of every data set, made on the
+ * device by a counter-based generator, and the reduction of the refits' parameters to intervals.  The entry points and their
+ * stated arithmetic are in nonlin_hip_boot.h, a part of this ABI that this header includes in the same way. ---- */
+#include "nonlin_hip_boot.h"
+
 #endif /* NONLIN_HIP_H */

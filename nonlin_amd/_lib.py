@@ -378,6 +378,15 @@ STARTS_SYMBOLS = {
     "nlh_starts_take_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# The entry points of include/nonlin_hip_boot.h, the part of the ABI that holds the bootstrap: bound beside STARTS_SYMBOLS.
+BOOT_SYMBOLS = {
+    "nlh_boot_draws": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p]),
+    "nlh_boot_resample_batch": (C.c_int, [_H, C.c_int32, C.c_uint64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_boot_summary_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+}
+
 KERNEL_IDS = {
     "dq_residual": 0, "dq_panel": 1, "fd_jacobian": 2, "gram": 3, "gram_reduce": 4, "jtf": 5,
     "chol": 6, "lmpar": 7, "qr": 8, "update": 9, "lu": 10, "dq_jacobian": 11, "qrx_pass": 12, "qrx_pivot": 13,
@@ -407,7 +416,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(GUESS_SYMBOLS.items()) + list(STARTS_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(GUESS_SYMBOLS.items()) + list(STARTS_SYMBOLS.items()) + list(BOOT_SYMBOLS.items()):
         fn = getattr(lib, name)       # AttributeError if the ABI and this table drift
         fn.restype = res
         fn.argtypes = args
@@ -841,6 +850,60 @@ class Starts:
 # kinds of a robust loss (include/nonlin_hip.h: NLH_LOSS_*)
 LOSS_LINEAR, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY = 0, 1, 2, 3
 LOSS_KINDS = {"linear": LOSS_LINEAR, "huber": LOSS_HUBER, "soft_l1": LOSS_SOFT_L1, "cauchy": LOSS_CAUCHY}
+
+
+# kinds and limits of the bootstrap (include/nonlin_hip_boot.h: NLH_BOOT_*)
+BOOT_RESIDUAL, BOOT_WILD, BOOT_PAIRS = 0, 1, 2
+BOOT_KINDS = {"residual": BOOT_RESIDUAL, "wild": BOOT_WILD, "pairs": BOOT_PAIRS}
+BOOT_MAX_ROWS, BOOT_MAX_REP = 16384, 4096
+
+
+class Bootstrap:
+    """The bootstrap of a fit (include/nonlin_hip_boot.h: nlh_boot_*; host data only, needs no GPU): nrep resampled copies of
+    every data set are refitted and the spread of their parameters is the uncertainty -- no linearisation, no Gaussian.  kind:
+    "residual" (the fit's weighted residuals, drawn with replacement, are added back to the fitted values: noise of one size),
+    "wild" (every residual keeps its row and takes a random sign: noise whose size varies along the rows), "pairs" (rows are
+    drawn with replacement: a row drawn c times weighs sqrt(c) times its weight) or a BOOT_* constant.  seed: any integer,
+    taken mod 2^64; a replica depends on (seed, problem, replica) alone.  level: the coverage of the percentile interval,
+    inside (0, 1).  centre: subtract the mean residual before drawing ("residual" only).  E.g.
+        Bootstrap(nrep=200, kind="wild", seed=7)
+    Raises ValueError for what the library refuses."""
+
+    def __init__(self, nrep=200, kind="residual", seed=0, level=0.95, centre=True):
+        import numpy as np
+        if isinstance(kind, str):
+            if kind.lower() not in BOOT_KINDS:
+                raise ValueError(f"Bootstrap: unknown kind {kind!r} (one of {', '.join(BOOT_KINDS)})")
+            kind = BOOT_KINDS[kind.lower()]
+        if isinstance(kind, bool) or not isinstance(kind, (int, np.integer)) or not BOOT_RESIDUAL <= int(kind) <= BOOT_PAIRS:
+            raise ValueError(f"Bootstrap: unknown kind {kind!r}")
+        for name, v in (("nrep", nrep), ("seed", seed)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"Bootstrap: {name} must be an integer, not {v!r}")
+        if not 1 <= int(nrep) <= BOOT_MAX_REP:
+            raise ValueError(f"Bootstrap: nrep must be in 1 .. {BOOT_MAX_REP}, not {nrep}")
+        if isinstance(level, (bool, str)) or not hasattr(level, "__float__") or not 0.0 < float(level) < 1.0:
+            raise ValueError(f"Bootstrap: level must be a number inside (0, 1), not {level!r}")
+        self.kind, self.nrep, self.seed = int(kind), int(nrep), int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.level, self.centre = float(level), bool(centre)
+
+    @property
+    def name(self):
+        return next(k for k, v in BOOT_KINDS.items() if v == self.kind)
+
+    def draws(self, p, b, first, count, cnt):
+        """nlh_boot_draws: the draws first .. first + count - 1 of the stream of problem p and replica b as int32 [count] --
+        indices below cnt, or with cnt == 0 the sign bits --, or None when the library refuses."""
+        import numpy as np
+        try:
+            args = [int(p), int(b), int(first), int(count), int(cnt)]
+        except (TypeError, ValueError):
+            return None
+        if not -(1 << 63) <= args[0] < (1 << 63) or any(not -(1 << 31) <= a < (1 << 31) for a in args[1:]):
+            return None
+        out = np.empty((max(args[3], 0),), dtype=np.int32)
+        rc = load().nlh_boot_draws(self.seed, *args, out.ctypes.data_as(c_int32_p))
+        return out if rc == 0 else None
 
 
 class Loss:

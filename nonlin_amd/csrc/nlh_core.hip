@@ -138,6 +138,7 @@ int nlh_create(nlh_handle **out, int32_t device, void *hip_stream)
     nlh_sep_init_device(lds_max);
     nlh_band_init_device(lds_max);
     nlh_guess_init_device(lds_max);
+    nlh_boot_init_device(lds_max);
     (void)hipFuncSetAttribute((const void *)k_dq_residual<RB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     (void)hipFuncSetAttribute((const void *)k_dq_residual2<RB / 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     (void)hipGetLastError();

@@ -24,6 +24,7 @@
 //   nlh_sep.hip        separable fits: the object, the wrapping launchers (variable projection), gather / solve
 //   nlh_guess.hip      starting values for the curve models: the nonlinear stage's kernels, then nlh_sep_solve_batch
 //   nlh_starts.hip     starts: the candidates of a box, the batched scan over any residual launcher, cost / pick / take
+//   nlh_boot.hip       bootstrap: the generator's draws, the resampling kernels, the summary of the refits
 //   nlh_model.hip      device sets, device residual models behind host arrays
 //   nlh_qrx.hip        the exact lmfactor
 // Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it launches.  nlh_launch.h:
@@ -83,8 +84,9 @@ struct nlh_handle {
            sepx,                          // one-call separable fits (nlh_fit.hip): the nonlinear unknowns and, of a group, the outer ones
            bdW, bdH,                      // bands (nlh_band.hip): the chain's Jacobian and values, host-array staging
            guessA, guessP, guessH,        // starting values (nlh_guess.hip): alpha / span / flags, the decays' panel, host-array staging
-           startsC, startsX, startsF, startsS, startsH;   // starts (nlh_starts.hip): the candidate table, a chunk's points and problems, its
+           startsC, startsX, startsF, startsS, startsH,   // starts (nlh_starts.hip): the candidate table, a chunk's points and problems, its
                                           // residuals, its costs, host-array staging
+           bootV;                         // bootstrap (nlh_boot.hip): which replicas of which problems are valid
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     DevBuf cholmc;                     // side buffer of the multi-CU Cholesky (solved panels, bad-pivot flags)
@@ -330,6 +332,7 @@ void nlh_expr_init_device(int lds_max);          // nlh_expr.hip: the formula in
 void nlh_sep_init_device(int lds_max);           // nlh_sep.hip: the separable fits' kernels keep a point's panel in LDS
 void nlh_band_init_device(int lds_max);          // nlh_band.hip: the band kernel keeps a point's packed covariance in LDS
 void nlh_guess_init_device(int lds_max);         // nlh_guess.hip: the guess kernels keep a problem's valid rows in LDS
+void nlh_boot_init_device(int lds_max);          // nlh_boot.hip: the resampling kernels keep a problem's active residuals in LDS
 
 // A compiled formula (nlh_expr.hip; include/nonlin_hip.h: nlh_expr_*).  ExprProg is what the kernels read, passed by value in
 // the kernel arguments: code[i] = op | (arg & 0xff) << 8 | aroot << 16 | broot << 24, aroot the instruction that produced the

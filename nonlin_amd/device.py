@@ -6,6 +6,7 @@ libnonlin_hip.so.  Layout: A [nprob, n, m] (each problem column-major m-by-n, i.
 A[p, j, i] = A_p(i, j)), b/fvec [nprob, m], x [nprob, n], all float64 on the GPU.
 """
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -400,6 +401,102 @@ class DeviceSolver:
         for layer in reversed(layers[1:]):
             layer[2].close()
         return x, fvec, sigma, cov, chi2, rank, ibs, status
+
+    # -- bootstrap: intervals of any fit from refits of resampled data --------------------
+    def boot_resample(self, boot, mu, y, weights=None, prob0=0, rep0=0, nrep=None):
+        """The replicas rep0 .. rep0 + nrep - 1 (nrep=None: boot.nrep) of a Bootstrap for the data y [nprob, m] with the fitted
+        values mu [nprob, m] -- curve_eval / expr_eval at the fit's x, through conv_apply where the fit has a response -- and
+        optional weights (nlh_boot_resample_batch): (ystar, wstar), ystar [nrep, nprob, m], replica-major, so that
+        ystar.reshape(nrep * nprob, m) is a batch for a fit; wstar the same shape for kind "pairs", None otherwise (the
+        replicas keep the caller's weights).  prob0: the index of y[0] in the caller's whole data, when y is a slice of it.
+        Rows of weight 0 stay as they are.  A replica depends on (boot.seed, problem, replica) alone."""
+        nprob, m = y.shape
+        _chk(y, (nprob, m), "y")
+        pairs = boot.kind == _lib.BOOT_PAIRS
+        if not pairs or mu is not None:
+            _chk(mu, (nprob, m), "mu")
+        if weights is not None:
+            _chk(weights, (nprob, m), "weights")
+        nrep = boot.nrep if nrep is None else int(nrep)
+        ystar = torch.empty((max(nrep, 0), nprob, m), dtype=torch.float64, device=y.device)
+        wstar = torch.empty_like(ystar) if pairs else None
+        self._call("nlh_boot_resample_batch", boot.kind, boot.seed, nprob, int(prob0), m, int(rep0), nrep,
+                   mu.data_ptr() if mu is not None else None, y.data_ptr(), weights.data_ptr() if weights is not None else None,
+                   int(boot.centre), ystar.data_ptr(), wstar.data_ptr() if pairs else None)
+        return ystar, wstar
+
+    def boot_summary(self, xs, level=0.95):
+        """(lo, hi, mean, sd [nprob, n], nvalid [nprob] int32) of xs [nrep, nprob, n], the parameters the refits of the replicas
+        gave (nlh_boot_summary_batch): a replica whose row holds a value that is not finite does not count; lo and hi are the
+        (1 - level)/2 and 1 - (1 - level)/2 quantiles of the others (linear interpolation), mean and sd their mean and
+        standard deviation.  No valid replica: NaN; one: sd is NaN."""
+        nrep, nprob, n = xs.shape
+        _chk(xs, (nrep, nprob, n), "xs")
+        lo, hi, mean, sd = (torch.empty((nprob, n), dtype=torch.float64, device=xs.device) for _ in range(4))
+        nvalid = torch.empty((nprob,), dtype=torch.int32, device=xs.device)
+        self._call("nlh_boot_summary_batch", nrep, nprob, n, xs.data_ptr(), float(level), mean.data_ptr(), sd.data_ptr(), lo.data_ptr(),
+                   hi.data_ptr(), nvalid.data_ptr())
+        return lo, hi, mean, sd, nvalid
+
+    def _boot_fit(self, model, head, evaluate, n, m, t, shared, y, x, boot, weights, lower, upper, analytic, opts, pmap, loss, stat,
+                  group, conv, sep):
+        """The one-call bootstrap behind curve_boot_batch and expr_boot_batch: the fitted values -- evaluate(x), through
+        conv_apply with conv --, then chunks of replicas whose y* stays within 256 MiB (the environment variable
+        NLH_BOOT_REPS, read at every call, sets the replicas of a chunk instead: tests), each chunk one _fit call without
+        covariance from x repeated, and the summary of what the fits returned, NaN where a fit's status is not 0."""
+        if stat is not None or group is not None:
+            raise ValueError("a bootstrap excludes stat and group: counts need a parametric sampler, a group its own resampling")
+        pairs = boot.kind == _lib.BOOT_PAIRS
+        if pairs and conv is not None:
+            raise ValueError('kind "pairs" excludes conv: a convolution needs every row')
+        nprob = y.shape[0]
+        _chk(x, (nprob, n), "x")
+        mu = None
+        if not pairs:
+            mu = evaluate(x)
+            if conv is not None:
+                mu = self.conv_apply(conv, mu)
+        per = max(1, (256 << 20) // (8 * max(nprob * m, 1)))
+        env = os.environ.get("NLH_BOOT_REPS")
+        if env is not None and int(env) >= 1:
+            per = int(env)
+        xs = torch.empty((boot.nrep, nprob, n), dtype=torch.float64, device=y.device)
+        for rep0 in range(0, boot.nrep, per):
+            r = min(per, boot.nrep - rep0)
+            ystar, wstar = self.boot_resample(boot, mu, y, weights, 0, rep0, r)
+            wc = wstar.reshape(r * nprob, m) if pairs else weights.repeat(r, 1) if weights is not None else None
+            tc = t if shared else t.repeat(1, r, 1) if t.dim() == 3 else t.repeat(r, 1)
+            lc = loss if loss is None or loss.shared else _lib.Loss(loss.kind, np.tile(loss.scale, r))
+            cc = conv if conv is None or conv.shared else _lib.Convolve(np.tile(conv.kernel, (r, 1)), conv.origin, conv.ext)
+            out = self._fit(model, head, n, m, tc, shared, ystar.reshape(r * nprob, m), wc, x.repeat(r, 1), lower, upper, analytic, False,
+                            opts, pmap, lc, None, None, cc, sep)
+            bad = torch.tensor([s != 0 for s in out[7]], dtype=torch.bool, device=y.device)
+            xs[rep0:rep0 + r] = out[0].masked_fill(bad[:, None], float("nan")).reshape(r, nprob, n)
+        return self.boot_summary(xs, boot.level) + (xs,)
+
+    def curve_boot_batch(self, kind, t, y, x, boot, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
+                         opts=None, pmap=None, loss=None, stat=None, group=None, conv=None, sep=None):
+        """The bootstrap of curve_fit_batch's fit x [nprob, n] of the data t, y (a Bootstrap: nlh_boot_resample_batch, the fit
+        itself, nlh_boot_summary_batch): boot.nrep replicas of every data set are made from the fitted values and the data,
+        each is fitted exactly as the keywords say -- the caller's bounds, pmap, loss, conv and sep, started from x, without
+        covariance --, and what comes back is (lo, hi, mean, sd, nvalid, xs): the percentile interval of boot.level, the mean
+        and the standard deviation of every parameter over the replicas whose fit ended with status 0 ([nprob, n]), how many
+        those are ([nprob], int32), and the refits' parameters themselves, xs [nrep, nprob, n], NaN where a fit failed.  The
+        result depends on (boot, the data, x) alone, not on how the replicas are chunked.  stat= and group= raise ValueError,
+        and so does kind "pairs" with conv=."""
+        k = curve_kind(kind)
+        nprob, m, shared = self._curve_data(t, y, weights)
+        n = curve_nparams(k, ncomp, baseline)
+        return self._boot_fit("curve", dict(kind=k, ncomp=int(ncomp), nbase=int(baseline)),
+                              lambda v: self.curve_eval(k, v, t, ncomp, baseline), n, m, t, shared, y, x, boot, weights, lower, upper,
+                              analytic, opts, pmap, loss, stat, group, conv, sep)
+
+    def expr_boot_batch(self, expr, t, y, x, boot, weights=None, lower=None, upper=None, analytic=True, opts=None, pmap=None,
+                        loss=None, stat=None, group=None, conv=None, sep=None):
+        """curve_boot_batch with an Expr in the place of (kind, ncomp, baseline): the bootstrap of expr_fit_batch's fit x."""
+        nprob, m, shared = self._expr_data(expr, t, y, weights)
+        return self._boot_fit("expr", dict(expr=expr.ptr), lambda v: self.expr_eval(expr, v, t), expr.nparams, m, t, shared, y, x, boot,
+                              weights, lower, upper, analytic, opts, pmap, loss, stat, group, conv, sep)
 
     @staticmethod
     def _fit_outputs(x0, m, covariance, nsolve, nunk):
