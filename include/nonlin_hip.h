@@ -1774,4 +1774,9 @@ const char *nlh_kernel_name(int32_t kernel_id);
  * stated arithmetic are in nonlin_hip_boot.h, a part of this ABI that this header includes in the same way. ---- */
 #include "nonlin_hip_boot.h"
 
+/* ---- bin-integrated fits: ANY device model integrated or averaged over the bins of a histogram or the pixels of an image -- a
+ * pair of wrapping launchers that evaluate the inner model at the nodes of a quadrature rule and sum them per bin.  The entry
+ * points and their stated arithmetic are in nonlin_hip_bin.h, a part of this ABI that this header includes in the same way. ---- */
+#include "nonlin_hip_bin.h"
+
 #endif /* NONLIN_HIP_H */

@@ -387,6 +387,16 @@ BOOT_SYMBOLS = {
                                          C.c_void_p, C.c_void_p]),
 }
 
+# The entry points of include/nonlin_hip_bin.h, the part of the ABI that holds the bin-integrated fits: bound beside BOOT_SYMBOLS.
+BIN_SYMBOLS = {
+    "nlh_bin_rule": (C.c_int, [C.c_int32, c_double_p, c_double_p]),
+    "nlh_bin_wrap": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, DEVFCN, DEVFCN, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "nlh_bin_unwrap": _RELEASE,
+    "nlh_bin_device_fcn": _LAUNCHER,
+    "nlh_bin_device_jac": _LAUNCHER,
+    "nlh_bin_apply_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+}
+
 KERNEL_IDS = {
     "dq_residual": 0, "dq_panel": 1, "fd_jacobian": 2, "gram": 3, "gram_reduce": 4, "jtf": 5,
     "chol": 6, "lmpar": 7, "qr": 8, "update": 9, "lu": 10, "dq_jacobian": 11, "qrx_pass": 12, "qrx_pivot": 13,
@@ -416,7 +426,8 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(GUESS_SYMBOLS.items()) + list(STARTS_SYMBOLS.items()) + list(BOOT_SYMBOLS.items()):
+    for name, (res, args) in (list(SYMBOLS.items()) + list(GUESS_SYMBOLS.items()) + list(STARTS_SYMBOLS.items()) + list(BOOT_SYMBOLS.items()) +
+                              list(BIN_SYMBOLS.items())):
         fn = getattr(lib, name)       # AttributeError if the ABI and this table drift
         fn.restype = res
         fn.argtypes = args
@@ -1022,6 +1033,163 @@ class Convolve:
     def struct(self, kptr):
         """nlh_conv with the taps at kptr (a device or host address, as the entry point wants them)."""
         return ConvStruct(self.L, self.origin, self.ext, int(self.shared), kptr)
+
+
+# limits of a bin-integrated fit (include/nonlin_hip_bin.h: NLH_BIN_MAX_Q; nlh_bin_rule has the orders 1 .. 8)
+BIN_MAX_Q, BIN_MAX_ORDER = 16, 8
+BIN_MODES = ("integral", "mean")
+
+
+class BinStruct(C.Structure):
+    """nlh_bin."""
+    _fields_ = [("Q", C.c_int32), ("c", C.c_double * BIN_MAX_Q), ("s", C.c_void_p), ("shared_s", C.c_int32)]
+
+
+def bin_rule(order):
+    """(xi, c): the Gauss-Legendre nodes (ascending) and weights on [-1, 1] of `order` nodes, 1 .. 8 (nlh_bin_rule: host code,
+    needs no GPU).  ValueError for another order."""
+    import numpy as np
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 1 <= int(order) <= BIN_MAX_ORDER:
+        raise ValueError(f"Binned: order must be an integer in 1 .. {BIN_MAX_ORDER}, not {order!r}")
+    xi, c = np.zeros(int(order)), np.zeros(int(order))
+    if load().nlh_bin_rule(int(order), xi.ctypes.data_as(c_double_p), c.ctypes.data_as(c_double_p)):
+        raise ValueError(f"Binned: the library has no rule of order {order!r}")
+    return xi, c
+
+
+class Binned:
+    """The bins of histogrammed data as the transform of a fit (include/nonlin_hip_bin.h: nlh_bin_*; host data only, needs no
+    GPU): the model is integrated over every bin lo .. hi (mode "integral": a density against counts) or averaged over it
+    (mode "mean": a pixel against an image) by a quadrature rule before it is compared with the data, instead of being
+    evaluated at one point.  lo, hi: the edges of the bins, [m] for every problem or [nprob, m], lo < hi.  order: the nodes of
+    the Gauss-Legendre rule per bin, 1 .. 8 (order 1 is the centre value: times the width, or as it is); the rule is exact for
+    polynomials up to degree 2 order - 1 across a bin.  rule=(xi, c): a caller's own nodes and weights on [-1, 1] instead, at
+    most 16 (order is then not read).  With mid = 0.5 (lo + hi) and half = 0.5 (hi - lo) the nodes are mid + half xi_q;
+    "integral" scales every bin's sum by half, "mean" halves the weights (exactly) and has no scale.
+    Raises ValueError for edges that are not finite numbers of one shape [m] or [nprob, m], for lo >= hi, an unknown mode, an
+    order outside 1 .. 8 and a rule that is not two finite sequences of one length 1 .. 16.
+    Attributes: m, Q, xi, c [Q] (the weights the device reads), scale (None or [1 | nprob, m]), shared, nvar (1; 2 for
+    pixels)."""
+
+    def __init__(self, lo, hi, order=3, mode="integral", rule=None):
+        import numpy as np
+        lo, hi = self._edges((lo, hi), "lo and hi")
+        xi, c = self._rule(order, rule)
+        mode = self._mode(mode)
+        mid, half = 0.5 * (lo + hi), 0.5 * (hi - lo)
+        tq = np.concatenate([mid + half * xi[q] for q in range(len(xi))], axis=-1)
+        self._set(tq, xi, c if mode == "integral" else 0.5 * c, half if mode == "integral" else None, mode, 1)
+
+    @staticmethod
+    def _edges(arrays, what):
+        """The edge arrays as float64 [1 | nprob, m] of one shape, checked."""
+        import numpy as np
+        try:
+            out = [np.array(a, dtype=np.float64) for a in arrays]
+        except (TypeError, ValueError):
+            raise ValueError(f"Binned: {what} must be sequences of numbers") from None
+        if out[0].ndim not in (1, 2) or out[0].shape[-1] < 1 or out[0].shape[0] < 1 or any(a.shape != out[0].shape for a in out):
+            raise ValueError(f"Binned: {what} are [m] or [nprob, m], of one shape, with at least one bin")
+        if not all(np.isfinite(a).all() for a in out):
+            raise ValueError(f"Binned: every edge of {what} must be finite")
+        for lo, hi in zip(out[0::2], out[1::2]):
+            if not (lo < hi).all():
+                raise ValueError("Binned: every bin needs lo < hi")
+        return [np.ascontiguousarray(a.reshape(-1, a.shape[-1])) if a.ndim == 2 else a[None, :].copy() for a in out]
+
+    @staticmethod
+    def _mode(mode):
+        if not isinstance(mode, str) or mode.lower() not in BIN_MODES:
+            raise ValueError(f"Binned: unknown mode {mode!r} (one of {', '.join(BIN_MODES)})")
+        return mode.lower()
+
+    @staticmethod
+    def _rule(order, rule):
+        import numpy as np
+        if rule is None:
+            return bin_rule(order)
+        try:
+            xi, c = (np.array(a, dtype=np.float64) for a in rule)
+        except (TypeError, ValueError):
+            raise ValueError("Binned: rule must be (xi, c), two sequences of numbers") from None
+        if xi.ndim != 1 or c.shape != xi.shape or not 1 <= len(xi) <= BIN_MAX_Q:
+            raise ValueError(f"Binned: rule is (xi, c), two 1-D sequences of one length 1 .. {BIN_MAX_Q}")
+        if not (np.isfinite(xi).all() and np.isfinite(c).all()):
+            raise ValueError("Binned: every node and weight of the rule must be finite")
+        return xi, c
+
+    def _set(self, tq, xi, c, scale, mode, nvar):
+        import numpy as np
+        self._tq = np.ascontiguousarray(tq)                          # [1 | nprob, Q m], or [2, 1 | nprob, Q m] for pixels
+        self.xi, self.c = xi, np.ascontiguousarray(c)
+        self.Q = len(self.c)
+        self.m = self._tq.shape[-1] // self.Q
+        self.scale = None if scale is None else np.ascontiguousarray(scale)
+        self.shared = self._tq.shape[-2] == 1
+        self.mode, self.nvar = mode, nvar
+
+    @classmethod
+    def edges(cls, e, order=3, mode="integral", rule=None):
+        """The bins between m + 1 ascending edges e, one set for every problem: Binned(e[:-1], e[1:], ...)."""
+        import numpy as np
+        try:
+            e = np.array(e, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("Binned.edges: the edges must be a sequence of numbers") from None
+        if e.ndim != 1 or len(e) < 2:
+            raise ValueError("Binned.edges: m + 1 edges in one 1-D sequence, m >= 1")
+        return cls(e[:-1], e[1:], order=order, mode=mode, rule=rule)
+
+    @classmethod
+    def pixels(cls, x, y, order=2, mode="mean"):
+        """The pixels xlo .. xhi by ylo .. yhi of an image for a formula of two variables: x = (xlo, xhi), y = (ylo, yhi), each
+        [m] or [nprob, m] (the pixels of an image in any order, flattened).  The rule is the tensor product of the
+        Gauss-Legendre rule of `order` nodes, 1 .. 4, with itself: Q = order^2 nodes, node q = a order + b at (x node a,
+        y node b) with weight c_a c_b -- a quarter of it under "mean" --, and the scale half_x half_y under "integral".
+        nodes() is then [2, Q m] or [2, nprob, Q m]: the two variables of the formula."""
+        import numpy as np
+        if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 1 <= int(order) <= 4:
+            raise ValueError(f"Binned.pixels: order must be an integer in 1 .. 4, not {order!r}")
+        try:
+            (xlo, xhi), (ylo, yhi) = x, y
+        except (TypeError, ValueError):
+            raise ValueError("Binned.pixels: x = (xlo, xhi) and y = (ylo, yhi)") from None
+        xlo, xhi, ylo, yhi = cls._edges((xlo, xhi, ylo, yhi), "the pixel edges")
+        mode = cls._mode(mode)
+        xi, c1 = bin_rule(order)
+        mx, hx, my, hy = 0.5 * (xlo + xhi), 0.5 * (xhi - xlo), 0.5 * (ylo + yhi), 0.5 * (yhi - ylo)
+        K = int(order)
+        tx = np.concatenate([mx + hx * xi[a] for a in range(K) for b in range(K)], axis=-1)
+        ty = np.concatenate([my + hy * xi[b] for a in range(K) for b in range(K)], axis=-1)
+        c = np.array([c1[a] * c1[b] for a in range(K) for b in range(K)])
+        self = cls.__new__(cls)
+        self._set(np.stack([tx, ty]), xi, c if mode == "integral" else 0.25 * c, hx * hy if mode == "integral" else None, mode, 2)
+        return self
+
+    def nodes(self):
+        """The abscissae the inner model is bound on, node-major -- entry q m + i is node q of bin i --: [Q m], or
+        [nprob, Q m] with edges per problem (pixels: [2, Q m] or [2, nprob, Q m])."""
+        t = self._tq[..., 0, :] if self.shared else self._tq
+        return t.copy()
+
+    def nodes_for(self, nprob):
+        """nodes(), checked against the nprob problems of a call."""
+        if not self.shared and self._tq.shape[-2] != nprob:
+            raise ValueError(f"Binned: bins for {self._tq.shape[-2]} problems, the call has {nprob}")
+        return self.nodes()
+
+    def scale_for(self, nprob):
+        """The host scale a call on nprob problems passes: (None | [m] | [nprob, m], shared flag)."""
+        if not self.shared and self._tq.shape[-2] != nprob:
+            raise ValueError(f"Binned: bins for {self._tq.shape[-2]} problems, the call has {nprob}")
+        if self.scale is None:
+            return None, 1
+        return (self.scale[0] if self.shared else self.scale), int(self.shared)
+
+    def struct(self, sptr, shared):
+        """nlh_bin with the scale at sptr (a device address, or None)."""
+        arr = (C.c_double * BIN_MAX_Q)(*([float(v) for v in self.c] + [0.0] * (BIN_MAX_Q - self.Q)))
+        return BinStruct(self.Q, arr, sptr, int(shared))
 
 
 class Handle(Owner):

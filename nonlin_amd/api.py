@@ -24,6 +24,7 @@ from ._lib import Loss, LOSS_LINEAR, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY, LOSS
 from ._lib import Poisson  # noqa: F401  (Poisson likelihood fits)
 from ._lib import Convolve, CONV_ZERO, CONV_HOLD  # noqa: F401  (instrument-response fits)
 from ._lib import Separable  # noqa: F401  (separable fits)
+from ._lib import Binned  # noqa: F401  (bin-integrated fits)
 
 # src/nonlin_error_handling.f90:10-38
 NL_NO_ERROR = 0

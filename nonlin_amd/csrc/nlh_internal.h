@@ -25,6 +25,7 @@
 //   nlh_guess.hip      starting values for the curve models: the nonlinear stage's kernels, then nlh_sep_solve_batch
 //   nlh_starts.hip     starts: the candidates of a box, the batched scan over any residual launcher, cost / pick / take
 //   nlh_boot.hip       bootstrap: the generator's draws, the resampling kernels, the summary of the refits
+//   nlh_bin.hip        bin-integrated fits: the Gauss-Legendre rules, the wrapping launchers, apply
 //   nlh_model.hip      device sets, device residual models behind host arrays
 //   nlh_qrx.hip        the exact lmfactor
 // Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it launches.  nlh_launch.h:

@@ -527,7 +527,8 @@ class DeviceSolver:
                 None if hi is None else hi.ctypes.data_as(_lib.c_double_p))
 
     def curve_fit_batch(self, kind, t, y, x0, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
-                        covariance=True, opts=None, pmap=None, loss=None, stat=None, group=None, conv=None, sep=None, starts=None):
+                        covariance=True, opts=None, pmap=None, loss=None, stat=None, group=None, conv=None, sep=None, starts=None,
+                        bins=None):
         """Fit + errors of y.shape[0] curves in one call (nlh_curve_fit_batch): least_squares_solver%solve -- or, with lower /
         upper ([n], one box for every problem), constrained_least_squares_solver%solve -- from x0 [nprob, n] (not modified),
         then the scaled parameter covariance at the solution.  Rows with weight 0 pad ragged data: they do not count as
@@ -567,10 +568,24 @@ class DeviceSolver:
         where no fit ended finite; ibs and status are the chosen fit's).  The record -- which start, which candidates, their
         scan cost -- is left on the Starts object (see there).  lower / upper stay the solver's box, independent of the
         scan's.  starts together with an x0, with pmap or with group raises ValueError.  None calls exactly what is called
-        without it."""
+        without it.
+        bins (a Binned over y's m bins): y was recorded in bins -- counts of a histogram, the pixels of an image -- and the
+        model is integrated (or averaged) over every bin by the Binned's rule before it is compared with y.  t is then not
+        read -- the model is evaluated at bins.nodes() -- and must be None.  The call is composed here from the launchers, in
+        the order of the library's own pipeline: the model on the nodes, bin_launchers, then conv_launchers, then
+        pois_launchers or loss_launchers, lm_solve_batch_device (cls_solve_batch_device with bounds) and
+        lm_covariance_batch_device; with weights the zero-weight rule of the header (dof = rows with non-zero weight - n,
+        chi2 and cov times (m - n) / dof, sigma from that cov) is applied in torch: that arithmetic is torch's, not
+        bit-stated.  A problem with dof <= 0 raises ValueError.  bins together with pmap, group, sep, starts or x0=None raises
+        ValueError: use bin_launchers with pmap_launchers, group_launchers, sep_launchers or starts_search.  There is no
+        bins= in the bootstrap calls and no curve_guess on binned data.  None calls exactly what is called without it."""
         if stat is not None and loss is not None:
             raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
         k = curve_kind(kind)
+        if bins is not None:
+            n = curve_nparams(k, ncomp, baseline)
+            return self._bin_fit(lambda tq, zero: self.curve_launchers(k, ncomp, baseline, tq, zero), n, 1, t, y, weights, x0, bins, lower,
+                                 upper, analytic, covariance, opts, pmap, loss, stat, group, conv, sep, starts)
         nprob, m, shared = self._curve_data(t, y, weights)
         n = curve_nparams(k, ncomp, baseline)
         if starts is not None:
@@ -687,14 +702,19 @@ class DeviceSolver:
         return torch.complex(wr, wi).reshape(z.shape)
 
     def expr_fit_batch(self, expr, t, y, x0, weights=None, lower=None, upper=None, analytic=True, covariance=True, opts=None,
-                       pmap=None, loss=None, stat=None, group=None, conv=None, sep=None, starts=None):
+                       pmap=None, loss=None, stat=None, group=None, conv=None, sep=None, starts=None, bins=None):
         """Fit + errors of y.shape[0] data sets to a formula in one call (nlh_expr_fit_batch): curve_fit_batch with an Expr in
         the place of (kind, ncomp, baseline), pmap (e.g. ParamMap.for_expr(expr, ...)), loss (a Loss), stat (a Poisson) and
         group (e.g. Group.for_expr(expr, shared=("k",), nsets=8): nlh_expr_fit_batch_group) included.  Returns (x, fvec, sigma,
         cov, chi2, rank, ibs, status).  x0=None with starts (e.g. Starts.for_expr(expr, lower={..}, upper={..})): the fit starts
-        from the best candidates of a box, as in curve_fit_batch."""
+        from the best candidates of a box, as in curve_fit_batch.  bins (a Binned; Binned.pixels for a formula of two
+        variables): the formula is integrated or averaged over the bins y was recorded in, as in curve_fit_batch; t is then
+        not read and must be None."""
         if stat is not None and loss is not None:
             raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
+        if bins is not None:
+            return self._bin_fit(lambda tq, zero: self.expr_launchers(expr, tq, zero), expr.nparams, expr.nvar, t, y, weights, x0, bins,
+                                 lower, upper, analytic, covariance, opts, pmap, loss, stat, group, conv, sep, starts)
         nprob, m, shared = self._expr_data(expr, t, y, weights)
         n = expr.nparams
         if starts is not None:
@@ -883,6 +903,109 @@ class DeviceSolver:
         self._call("nlh_conv_apply_batch", C.byref(cv), nprob, m, ncol, v.data_ptr(), out.data_ptr())
         torch.cuda.current_stream(v.device).synchronize()             # (dk goes with this frame)
         return out
+
+    # -- bin-integrated fits ----------------------------------------------------------
+    def _bin_struct(self, bins, nprob, dev=None):
+        """(nlh_bin of a Binned for nprob problems, the device tensor of its scale or None: keep it alive)."""
+        sc, sh = bins.scale_for(nprob)
+        dsc = None if sc is None else torch.from_numpy(np.ascontiguousarray(sc)).to(dev if dev is not None else self.device)
+        return bins.struct(dsc.data_ptr() if dsc is not None else None, sh), dsc
+
+    def bin_nodes(self, bins, nprob, dev=None):
+        """bins.nodes() for a call on nprob problems as a device tensor: the abscissae to bind the inner model on."""
+        return torch.from_numpy(np.ascontiguousarray(bins.nodes_for(nprob))).to(dev if dev is not None else self.device)
+
+    def bin_launchers(self, bins, fcn, jac, ctx, y, weights=None):
+        """The bins of a histogram or the pixels of an image for any launcher pair (a Binned): wraps (fcn, jac, ctx) -- of
+        curve_launchers or expr_launchers made on bin_nodes(bins, nprob) with a ZERO y [nprob, Q m] and WITHOUT weights, or a
+        user's own that returns model values on those rows -- in the bin-summing launchers (nlh_bin_wrap) and returns
+        (fcn, jac, ctx) for lm_solve_batch_device, cls_solve_batch_device, lm_covariance_batch_device, fd_jacobian_device,
+        conv_launchers, loss_launchers, pois_launchers, pmap_launchers and group_launchers, which then work on the m = bins.m
+        bins: the residual is the rule's sum over every bin minus y [nprob, m], times weights [nprob, m] when given.  jac is
+        None without an inner Jacobian launcher (pass jac=None to the solver: forward differences of the wrapped residual).
+        Keep the returned ctx alive while solving; ctx.close() frees it (so does garbage collection)."""
+        nprob, m = y.shape
+        _chk(y, (nprob, m), "y")
+        if m != bins.m:
+            raise ValueError(f"y has {m} columns, the Binned {bins.m} bins")
+        if weights is not None:
+            _chk(weights, (nprob, m), "weights")
+        bn, dsc = self._bin_struct(bins, nprob, y.device)
+        return self._wrap("bin", (bins, dsc, fcn, jac, ctx, y, weights), fcn, jac, ctx,
+                          (C.byref(bn), y.data_ptr(), weights.data_ptr() if weights is not None else None))
+
+    def bin_apply(self, bins, v):
+        """The bare sum over the bins of columns v [nprob, Q m] or [nprob, ncol, Q m] under a Binned (nlh_bin_apply_batch), e.g. of
+        curve_eval's model values at bin_nodes for plotting the binned model.  Returns a new tensor [nprob, m] or
+        [nprob, ncol, m]."""
+        if v.dim() not in (2, 3):
+            raise ValueError("v: expected [nprob, Q m] or [nprob, ncol, Q m]")
+        nprob = v.shape[0]
+        ncol = v.shape[1] if v.dim() == 3 else 1
+        _chk(v, tuple(v.shape[:-1]) + (bins.Q * bins.m,), "v")
+        bn, dsc = self._bin_struct(bins, nprob, v.device)
+        out = torch.empty(tuple(v.shape[:-1]) + (bins.m,), dtype=torch.float64, device=v.device)
+        self._call("nlh_bin_apply_batch", C.byref(bn), nprob, bins.m, ncol, v.data_ptr(), out.data_ptr())
+        torch.cuda.current_stream(v.device).synchronize()             # (dsc goes with this frame)
+        return out
+
+    def _bin_fit(self, launchers, n, nvar, t, y, weights, x0, bins, lower, upper, analytic, covariance, opts, pmap, loss, stat, group,
+                 conv, sep, starts):
+        """A one-call fit with bins=: the launchers of the fit composed in the order of the library's own pipeline -- the
+        model on the nodes with a zero y, the bin pair with y (and the weights, unless conv or stat take them), then conv,
+        then stat or loss --, the solve, and the covariance.  launchers(tq, zero): the model's own pair."""
+        for name, v in (("pmap", pmap), ("group", group), ("sep", sep), ("starts", starts)):
+            if v is not None:
+                raise ValueError(f"bins excludes {name}: compose bin_launchers with the other launchers and call the solver")
+        if x0 is None:
+            raise ValueError("bins excludes x0=None: there is no guess on binned data; compose bin_launchers and call starts_search")
+        if t is not None:
+            raise ValueError("bins excludes t: the model is evaluated at bins.nodes(); pass t=None")
+        if bins.nvar != nvar:
+            raise ValueError(f"bins are over {bins.nvar} variable(s), the model has {nvar}")
+        nprob, m = y.shape
+        _chk(y, (nprob, m), "y")
+        _chk(x0, (nprob, n), "x0")
+        if weights is not None:
+            _chk(weights, (nprob, m), "weights")
+            dof = (weights != 0).sum(dim=1) - n
+            if bool((dof <= 0).any()):
+                raise ValueError("bins: a problem has no degree of freedom left (rows with non-zero weight <= parameters)")
+        tq = self.bin_nodes(bins, nprob, y.device)
+        zero = torch.zeros((nprob, bins.Q * bins.m), dtype=torch.float64, device=y.device)
+        plain = conv is None and stat is None
+        layers = [launchers(tq, zero)]                               # (every context stays alive in here)
+        layers.append(self.bin_launchers(bins, *layers[-1], y, weights if plain else None))
+        if conv is not None:
+            layers.append(self.conv_launchers(conv, *layers[-1], y, None if stat is not None else weights))
+        if stat is not None:
+            layers.append(self.pois_launchers(stat, *layers[-1], y, weights))
+        if loss is not None:
+            layers.append(self.loss_launchers(loss, *layers[-1], nprob))
+        fcn, jac, ctx = layers[-1]
+        jac = jac if analytic else None
+        x = x0.clone()
+        o = opts or self.options()
+        if lower is not None or upper is not None:
+            fvec, ibs, status = self.cls_solve_batch_device(fcn, ctx, m, x, jac=jac, opts=o, lower=lower, upper=upper)
+        else:
+            fvec, ibs, status = self.lm_solve_batch_device(fcn, ctx, m, x, jac=jac, opts=o)
+        sigma = cov = chi2 = rank = None
+        if covariance:
+            cov, sigma, rank, chi2 = self.lm_covariance_batch_device(fcn, ctx, m, x, jac=jac, scaled=stat is None)
+            if weights is not None:                                  # the header's zero-weight rule, in torch
+                f = float(m - n) / dof.to(torch.float64)
+                chi2 = chi2 * f
+                if stat is None:
+                    cov = cov * f[:, None, None]
+                    sigma = torch.sqrt(torch.diagonal(cov, dim1=1, dim2=2)).contiguous()
+            bad = torch.tensor([s != 0 for s in status], dtype=torch.bool, device=y.device)
+            nan = float("nan")
+            sigma, cov, chi2 = sigma.masked_fill(bad[:, None], nan), cov.masked_fill(bad[:, None, None], nan), chi2.masked_fill(bad, nan)
+            rank = rank.masked_fill(bad, -1)
+        for layer in reversed(layers[1:]):
+            layer[2].close()
+        return x, fvec, sigma, cov, chi2, rank, ibs, status
 
     # -- separable fits (variable projection) --------------------------------------
     def sep_launchers(self, sep, fcn, jac, ctx):
