@@ -1779,4 +1779,9 @@ const char *nlh_kernel_name(int32_t kernel_id);
  * points and their stated arithmetic are in nonlin_hip_bin.h, a part of this ABI that this header includes in the same way. ---- */
 #include "nonlin_hip_bin.h"
 
+/* ---- Poisson bootstrap: the bootstrap of a fit of COUNTS (stat = Poisson) -- parametric replicas y* ~ Poisson(mu) of the fitted
+ * values, drawn on the device by inversion from the mode in stated arithmetic.  The entry points are in
+ * nonlin_hip_boot_pois.h, a part of this ABI that this header includes in the same way. ---- */
+#include "nonlin_hip_boot_pois.h"
+
 #endif /* NONLIN_HIP_H */

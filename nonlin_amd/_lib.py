@@ -397,6 +397,13 @@ BIN_SYMBOLS = {
     "nlh_bin_apply_batch": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
+# The entry points of include/nonlin_hip_boot_pois.h, the part of the ABI that holds the Poisson bootstrap: bound beside BIN_SYMBOLS.
+BOOT_POIS_SYMBOLS = {
+    "nlh_boot_poisson_draws": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p]),
+    "nlh_boot_poisson_batch": (C.c_int, [_H, C.c_uint64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 KERNEL_IDS = {
     "dq_residual": 0, "dq_panel": 1, "fd_jacobian": 2, "gram": 3, "gram_reduce": 4, "jtf": 5,
     "chol": 6, "lmpar": 7, "qr": 8, "update": 9, "lu": 10, "dq_jacobian": 11, "qrx_pass": 12, "qrx_pivot": 13,
@@ -427,7 +434,7 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SYMBOLS.items()) + list(GUESS_SYMBOLS.items()) + list(STARTS_SYMBOLS.items()) + list(BOOT_SYMBOLS.items()) +
-                              list(BIN_SYMBOLS.items())):
+                              list(BIN_SYMBOLS.items()) + list(BOOT_POIS_SYMBOLS.items())):
         fn = getattr(lib, name)       # AttributeError if the ABI and this table drift
         fn.restype = res
         fn.argtypes = args
@@ -914,6 +921,45 @@ class Bootstrap:
             return None
         out = np.empty((max(args[3], 0),), dtype=np.int32)
         rc = load().nlh_boot_draws(self.seed, *args, out.ctypes.data_as(c_int32_p))
+        return out if rc == 0 else None
+
+
+# the largest mean the Poisson bootstrap draws from (include/nonlin_hip_boot_pois.h: NLH_BOOT_POIS_MAX_MEAN)
+BOOT_POIS_MAX_MEAN = 1 << 24
+
+
+class PoissonBootstrap:
+    """The parametric bootstrap of a fit of counts (include/nonlin_hip_boot_pois.h: nlh_boot_poisson_*; host data only, needs no
+    GPU): every replica holds counts y* ~ Poisson(mu) drawn from the fitted values mu, and is refitted with the same deviance
+    (stat=Poisson()).  For counting data the kinds of Bootstrap are wrong -- a resampled residual added to a fitted value is
+    not a count and can be negative --, and at low counts, where the likelihood is skewed, the linearised x +- 1.96 sigma is
+    least trustworthy.  nrep, seed and level are Bootstrap's; a replica depends on (seed, problem, replica, mu) alone.  A
+    fitted value that is a NaN, negative or above BOOT_POIS_MAX_MEAN = 2^24 on an unmasked row makes its problem's bootstrap
+    invalid (above 2^24 counts are Gaussian to 2.5e-4: Bootstrap("wild") with weights 1/sqrt(mu) serves).  E.g.
+        PoissonBootstrap(nrep=200, seed=7)
+    Raises ValueError for what the library refuses."""
+
+    def __init__(self, nrep=200, seed=0, level=0.95):
+        try:
+            base = Bootstrap(nrep=nrep, seed=seed, level=level)        # the shared fields: Bootstrap's validation
+        except ValueError as exc:
+            raise ValueError("Poisson" + str(exc)) from None
+        self.nrep, self.seed, self.level = base.nrep, base.seed, base.level
+
+    def draws(self, p, b, first, mu):
+        """nlh_boot_poisson_draws: the draws of the rows first .. first + len(mu) - 1 of the stream of problem p and replica b
+        for the means mu, as float64 [len(mu)] -- a NaN for a mean that is a NaN, negative or above 2^24 --, or None when the
+        library refuses."""
+        import numpy as np
+        try:
+            args = [int(p), int(b), int(first)]
+            mu = np.ascontiguousarray(mu, dtype=np.float64)
+        except (TypeError, ValueError):
+            return None
+        if mu.ndim != 1 or not -(1 << 63) <= args[0] < (1 << 63) or any(not -(1 << 31) <= a < (1 << 31) for a in args[1:]):
+            return None
+        out = np.empty(mu.shape, dtype=np.float64)
+        rc = load().nlh_boot_poisson_draws(self.seed, *args, len(mu), mu.ctypes.data_as(c_double_p), out.ctypes.data_as(c_double_p))
         return out if rc == 0 else None
 
 

@@ -1,5 +1,6 @@
 // nlh_boot.hip -- bootstrap (include/nonlin_hip_boot.h: nlh_boot_*; kernels: nlh_kernels_boot.h): the generator's draws on the
 // host, the resampling kernel's launch shape, and the summary of the refits.  The fits between the two are the caller's.
+// Also the Poisson bootstrap (include/nonlin_hip_boot_pois.h: nlh_boot_poisson_*): its draws on the host and its kernel's launch.
 #include "nlh_internal.h"
 #include "nlh_kernels_boot.h"
 
@@ -59,6 +60,43 @@ int nlh_boot_resample_batch(nlh_handle *h, int32_t kind, uint64_t seed, int32_t 
     const size_t lds = kind == NLH_BOOT_RESIDUAL ? sizeof(double) * (size_t)m : pairs ? sizeof(int) * (size_t)(256 >> tsh) * m : 0;
     hipLaunchKernelGGL(boot_pick(kind, V), dim3((unsigned)nprob, (unsigned)groups), dim3(256), lds, h->stream, seed, nprob,
                        (long long)prob0, m, rep0, nrep, rpw, tsh, dmu, dy, dw, centre, dyout, dwout);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// ---- Poisson bootstrap (include/nonlin_hip_boot_pois.h) ----
+int nlh_boot_poisson_draws(uint64_t seed, int64_t p, int32_t b, int32_t first, int32_t count, const double *mu, double *out)
+{
+    if (p < 0 || b < 0 || first < 0 || count < 0 || (int64_t)first + count > NLH_BOOT_MAX_ROWS || (count > 0 && (!mu || !out)))
+        return NLH_INVALID_INPUT_ERROR;
+    const uint64_t key = boot_key(seed, (uint64_t)p, (uint64_t)b);
+    for (int32_t j = 0; j < count; ++j) {
+        const boot_pois s = boot_pois_row(true, mu[j]);
+        out[j] = s.T > 0.0 ? boot_pois_draw(s, mu[j], boot_draw(key, (uint64_t)first + (uint64_t)j))
+                           : s.T == 0.0 ? 0.0 : (double)NAN;
+    }
+    return 0;
+}
+
+int nlh_boot_poisson_batch(nlh_handle *h, uint64_t seed, int32_t nprob, int64_t prob0, int32_t m, int32_t rep0, int32_t nrep,
+                           const double *dmu, const double *dy, const double *dw, double *dyout, int32_t *dbad)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (nprob < 0 || nrep < 0 || nrep > NLH_BOOT_MAX_REP || m < 1 || m > NLH_BOOT_MAX_ROWS || prob0 < 0 || rep0 < 0 ||
+        (int64_t)rep0 + nrep > 0x7fffffffLL || !dmu || !dy || !dyout || !dbad)
+        return NLH_INVALID_INPUT_ERROR;
+    if (nprob == 0 || nrep == 0) return 0;
+    HIPCHK(h, hipSetDevice(h->device));
+    // nlh_boot_resample_batch's launch shape; several replica slots (tsh < 8, so m <= 256) share a row's setup through LDS
+    const int V = m % 2 == 0 && (uintptr_t)dyout % 16 == 0 ? 2 : 1;
+    int tsh = 0;
+    while (tsh < 8 && (1 << tsh) < m / V) ++tsh;
+    int groups = (int)std::min<int64_t>(nrep, std::max<int64_t>((nrep + BOOT_RPW - 1) / BOOT_RPW, (2048 + (int64_t)nprob - 1) / nprob));
+    const int rpw = (nrep + groups - 1) / groups;
+    groups = (nrep + rpw - 1) / rpw;
+    const size_t lds = tsh < 8 ? 6 * sizeof(double) * (size_t)m : 0;
+    hipLaunchKernelGGL(V == 2 ? k_boot_poisson<2> : k_boot_poisson<1>, dim3((unsigned)nprob, (unsigned)groups), dim3(256), lds, h->stream,
+                       seed, nprob, (long long)prob0, m, rep0, nrep, rpw, tsh, dmu, dy, dw, dyout, dbad);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -190,6 +190,165 @@ static __global__ void __launch_bounds__(256) k_boot_resample(uint64_t seed, int
     }
 }
 
+// ---- Poisson bootstrap (include/nonlin_hip_boot_pois.h states the arithmetic; host and device share these functions) ----
+static const double BOOT_POIS_EPS = 0x1p-60;
+// What a row's draws share: the mode, the weights below it, all weights, the ends of the two walks and r = 1/mu.  T > 0: an
+// ordinary row; T == 0: a zero row (its draws are +0.0); T < 0: a row that copies y (inactive or bad).
+struct boot_pois {
+    double M, L, T, kmin, kmax, r;
+};
+__host__ __device__ __forceinline__ bool boot_pois_bad(double mu) { return !(mu >= 0.0 && mu <= (double)NLH_BOOT_POIS_MAX_MEAN); }
+// mu: inside (0, NLH_BOOT_POIS_MAX_MEAN].  `!(q >= EPS)` is `q < EPS` for every number and also ends the loop on a NaN, which no
+// such mu produces: q stays inside (0, 1].
+__host__ __device__ __forceinline__ boot_pois boot_pois_setup(double mu)
+{
+    boot_pois s;
+    const double M = floor(mu), r = 1.0 / mu;
+    double L = 0.0, q = 1.0, nd = 0.0;
+    for (double k = M; k >= 1.0; k = k - 1.0) {
+        q = (q * k) * r;
+        if (!(q >= BOOT_POIS_EPS)) break;
+        L = L + q;
+        nd = nd + 1.0;
+    }
+    double U = 1.0, nu = 0.0;
+    q = 1.0;
+    for (double k = M + 1.0;; k = k + 1.0) {
+        q = (q * mu) / k;
+        if (!(q >= BOOT_POIS_EPS)) break;
+        U = U + q;
+        nu = nu + 1.0;
+    }
+    s.M = M;
+    s.L = L;
+    s.T = L + U;
+    s.kmin = M - nd;
+    s.kmax = M + nu;
+    s.r = r;
+    return s;
+}
+// the draw of an ordinary row from z = boot_draw(key, row): k moves by one per step and stays inside [kmin, kmax]
+__host__ __device__ __forceinline__ double boot_pois_draw(const boot_pois &s, double mu, uint64_t z)
+{
+    const double u = (double)(z >> 11) * 0x1p-53, t = u * s.T;
+    double k, q, r;
+    if (t < s.L) {
+        r = s.L - t;
+        k = s.M - 1.0;
+        q = s.M * s.r;
+        while (r > q && k > s.kmin) {
+            r = r - q;
+            q = (q * k) * s.r;
+            k = k - 1.0;
+        }
+    } else {
+        r = t - s.L;
+        k = s.M;
+        q = 1.0;
+        while (r >= q && k < s.kmax) {
+            r = r - q;
+            k = k + 1.0;
+            q = (q * mu) / k;
+        }
+    }
+    return k;
+}
+// a row's setup by its class; a zero or copying row runs no loop
+__host__ __device__ __forceinline__ boot_pois boot_pois_row(bool active, double mu)
+{
+    if (active && !boot_pois_bad(mu) && mu != 0.0) return boot_pois_setup(mu);
+    boot_pois s = {0.0, 0.0, active && mu == 0.0 ? 0.0 : -1.0, 0.0, 0.0, 0.0};
+    return s;
+}
+
+// k_boot_resample's skeleton for the Poisson replicas: one workgroup per (problem blockIdx.x, block blockIdx.y of at most rpw <=
+// BOOT_RPW replicas), the replicas' keys in LDS, boot_active for the mask, a thread owning V adjacent rows (V = 2: one 16-byte
+// store) of 256 >> tsh concurrent replicas.  A thread keeps its rows' setup in registers across its replicas.  Where a short
+// problem fills the workgroup with several replica slots (256 >> tsh > 1, which implies m <= 256), the setup -- 18 sqrt(mu)
+// steps against a draw's 0.8 sqrt(mu) -- is made ONCE per row, by thread i for row i, and handed to the slots through 48 m
+// bytes of dynamic LDS; otherwise every row has one owner and LDS is not used for it.  The workgroups of blockIdx.y == 0 count
+// their problem's bad rows.
+// No input can make this kernel spin: boot_pois_setup runs only for a mu inside (0, 2^24], where its first loop ends at k = 1 at
+// the latest and its second because q shrinks by mu/k <= (M+1)/(M+2) per step from the second step on (and a NaN would end
+// it, too); the draws' walks move k by one per step inside [kmin, kmax].  The lanes of a wave walk different lengths: the
+// draw of (seed, p, b, i) is the interface, so nothing is reordered to balance them.
+template <int V>
+static __global__ void __launch_bounds__(256) k_boot_poisson(uint64_t seed, int nprob, long long prob0, int m, int rep0, int nrep, int rpw,
+                                                       int tsh, const double *__restrict__ mu, const double *__restrict__ y,
+                                                       const double *__restrict__ w, double *__restrict__ yout, int32_t *__restrict__ bad)
+{
+    extern __shared__ __align__(16) unsigned char boot_lds[];
+    __shared__ unsigned long long mask[NLH_BOOT_MAX_ROWS / 64];
+    __shared__ int base[NLH_BOOT_MAX_ROWS / 64 + 1];
+    __shared__ uint64_t keys[BOOT_RPW];
+    __shared__ int nbad;
+    const int tid = threadIdx.x;
+    const int p = blockIdx.x, r0 = blockIdx.y * rpw, R = min(rpw, nrep - r0);
+    const size_t row0 = (size_t)p * m;
+    mu += row0;
+    y += row0;
+    if (w) w += row0;
+    const uint64_t pk = boot_mix(seed + BOOT_G * ((uint64_t)prob0 + (uint64_t)p + 1));
+    if (tid < R) keys[tid] = boot_mix(pk + BOOT_G * ((uint64_t)rep0 + (uint64_t)(r0 + tid) + 1));
+    if (tid == 0) nbad = 0;
+    boot_active(m, [&](int i) { return !w || w[i] != 0.0; }, mask, base);                       // (the barriers cover keys and nbad)
+    const int tpr = 1 << tsh, col = tid & (tpr - 1), slot = tid >> tsh, nslot = 256 >> tsh, mh = m / V;
+    const size_t rstride = (size_t)nprob * m;                        // from one replica to the next
+    double *const yo = yout + ((size_t)r0 * nprob + p) * m;
+    if (blockIdx.y == 0) {                                           // (the same branch for the whole workgroup)
+        int c = 0;
+        for (int i = tid; i < m; i += 256) c += boot_is_active(i, mask) && boot_pois_bad(mu[i]) ? 1 : 0;
+        if (c) atomicAdd(&nbad, c);
+        __syncthreads();
+        if (tid == 0) bad[p] = nbad;
+    }
+    const bool staged = nslot > 1;                                   // m <= 256: the host gave 6 m doubles of dynamic LDS
+    double *const sh = reinterpret_cast<double *>(boot_lds);         // [6][m]: M, L, T, kmin, kmax, r by row
+    if (staged) {
+        if (tid < m) {
+            const boot_pois s = boot_pois_row(boot_is_active(tid, mask), mu[tid]);
+            sh[tid] = s.M;
+            sh[m + tid] = s.L;
+            sh[2 * m + tid] = s.T;
+            sh[3 * m + tid] = s.kmin;
+            sh[4 * m + tid] = s.kmax;
+            sh[5 * m + tid] = s.r;
+        }
+        __syncthreads();
+    }
+    for (int u = col; u < mh; u += tpr) {
+        boot_pois st[V];
+        double mi[V], yi[V];
+        uint64_t gk[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int i = u * V + v;
+            mi[v] = mu[i];
+            yi[v] = y[i];
+            gk[v] = BOOT_G * ((uint64_t)i + 1);
+            if (staged) {
+                st[v].M = sh[i];
+                st[v].L = sh[m + i];
+                st[v].T = sh[2 * m + i];
+                st[v].kmin = sh[3 * m + i];
+                st[v].kmax = sh[4 * m + i];
+                st[v].r = sh[5 * m + i];
+            } else
+                st[v] = boot_pois_row(boot_is_active(i, mask), mi[v]);
+        }
+        for (int r = slot; r < R; r += nslot) {
+            const uint64_t key = keys[r];
+            double out[V];
+#pragma unroll
+            for (int v = 0; v < V; ++v)
+                out[v] = st[v].T > 0.0 ? boot_pois_draw(st[v], mi[v], boot_mix(key + gk[v])) : st[v].T == 0.0 ? 0.0 : yi[v];
+            double *dst = yo + (size_t)r * rstride + (size_t)u * V;
+            if (V == 2) *reinterpret_cast<double2 *>(dst) = make_double2(out[0], out[V - 1]);
+            else dst[0] = out[0];
+        }
+    }
+}
+
 // valid [nrep][nprob] (a byte each): is every one of the n parameters of replica b of problem p finite
 static __global__ void __launch_bounds__(256) k_boot_valid(size_t total, int n, const double *__restrict__ xs, unsigned char *__restrict__ valid)
 {

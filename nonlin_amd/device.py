@@ -425,6 +425,25 @@ class DeviceSolver:
                    int(boot.centre), ystar.data_ptr(), wstar.data_ptr() if pairs else None)
         return ystar, wstar
 
+    def boot_poisson(self, boot, mu, y, weights=None, prob0=0, rep0=0, nrep=None):
+        """The replicas rep0 .. rep0 + nrep - 1 (nrep=None: boot.nrep) of a PoissonBootstrap for the counts y [nprob, m] with the
+        fitted values mu [nprob, m] and the optional 0 / 1 mask weights (nlh_boot_poisson_batch): (ystar, bad), ystar
+        [nrep, nprob, m], replica-major, counts drawn from Poisson(mu) row by row -- a row of weight 0 keeps y, a row with
+        mu == 0 is 0 --; bad [nprob] int32: how many unmasked rows of each problem have a mu that is a NaN, negative or above
+        2^24 (they keep y: such a problem's replicas are not to be used).  prob0: the index of y[0] in the caller's whole data,
+        when y is a slice of it.  A replica depends on (boot.seed, problem, replica, mu) alone."""
+        nprob, m = y.shape
+        _chk(y, (nprob, m), "y")
+        _chk(mu, (nprob, m), "mu")
+        if weights is not None:
+            _chk(weights, (nprob, m), "weights")
+        nrep = boot.nrep if nrep is None else int(nrep)
+        ystar = torch.empty((max(nrep, 0), nprob, m), dtype=torch.float64, device=y.device)
+        bad = torch.zeros((nprob,), dtype=torch.int32, device=y.device)
+        self._call("nlh_boot_poisson_batch", boot.seed, nprob, int(prob0), m, int(rep0), nrep, mu.data_ptr(), y.data_ptr(),
+                   weights.data_ptr() if weights is not None else None, ystar.data_ptr(), bad.data_ptr())
+        return ystar, bad
+
     def boot_summary(self, xs, level=0.95):
         """(lo, hi, mean, sd [nprob, n], nvalid [nprob] int32) of xs [nrep, nprob, n], the parameters the refits of the replicas
         gave (nlh_boot_summary_batch): a replica whose row holds a value that is not finite does not count; lo and hi are the
@@ -443,10 +462,18 @@ class DeviceSolver:
         """The one-call bootstrap behind curve_boot_batch and expr_boot_batch: the fitted values -- evaluate(x), through
         conv_apply with conv --, then chunks of replicas whose y* stays within 256 MiB (the environment variable
         NLH_BOOT_REPS, read at every call, sets the replicas of a chunk instead: tests), each chunk one _fit call without
-        covariance from x repeated, and the summary of what the fits returned, NaN where a fit's status is not 0."""
-        if stat is not None or group is not None:
+        covariance from x repeated, and the summary of what the fits returned, NaN where a fit's status is not 0.  A
+        PoissonBootstrap takes boot_poisson's replicas and passes stat on to the refits; the refits of a problem with a bad
+        fitted value are set to NaN on the device."""
+        pois = isinstance(boot, _lib.PoissonBootstrap)
+        if pois:
+            if stat is None:
+                raise ValueError("a PoissonBootstrap needs stat=Poisson(): its replicas are counts, refitted with the deviance")
+            if group is not None:
+                raise ValueError("a PoissonBootstrap excludes group: a group needs its own resampling")
+        elif stat is not None or group is not None:
             raise ValueError("a bootstrap excludes stat and group: counts need a parametric sampler, a group its own resampling")
-        pairs = boot.kind == _lib.BOOT_PAIRS
+        pairs = not pois and boot.kind == _lib.BOOT_PAIRS
         if pairs and conv is not None:
             raise ValueError('kind "pairs" excludes conv: a convolution needs every row')
         nprob = y.shape[0]
@@ -463,15 +490,21 @@ class DeviceSolver:
         xs = torch.empty((boot.nrep, nprob, n), dtype=torch.float64, device=y.device)
         for rep0 in range(0, boot.nrep, per):
             r = min(per, boot.nrep - rep0)
-            ystar, wstar = self.boot_resample(boot, mu, y, weights, 0, rep0, r)
+            if pois:
+                ystar, nbad = self.boot_poisson(boot, mu, y, weights, 0, rep0, r)
+                wstar = None
+            else:
+                ystar, wstar = self.boot_resample(boot, mu, y, weights, 0, rep0, r)
             wc = wstar.reshape(r * nprob, m) if pairs else weights.repeat(r, 1) if weights is not None else None
             tc = t if shared else t.repeat(1, r, 1) if t.dim() == 3 else t.repeat(r, 1)
             lc = loss if loss is None or loss.shared else _lib.Loss(loss.kind, np.tile(loss.scale, r))
             cc = conv if conv is None or conv.shared else _lib.Convolve(np.tile(conv.kernel, (r, 1)), conv.origin, conv.ext)
             out = self._fit(model, head, n, m, tc, shared, ystar.reshape(r * nprob, m), wc, x.repeat(r, 1), lower, upper, analytic, False,
-                            opts, pmap, lc, None, None, cc, sep)
+                            opts, pmap, lc, stat, None, cc, sep)
             bad = torch.tensor([s != 0 for s in out[7]], dtype=torch.bool, device=y.device)
             xs[rep0:rep0 + r] = out[0].masked_fill(bad[:, None], float("nan")).reshape(r, nprob, n)
+            if pois:                                                 # a problem with a bad fitted value has no valid replica
+                xs[rep0:rep0 + r].masked_fill_((nbad > 0)[None, :, None], float("nan"))
         return self.boot_summary(xs, boot.level) + (xs,)
 
     def curve_boot_batch(self, kind, t, y, x, boot, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
@@ -483,7 +516,11 @@ class DeviceSolver:
         and the standard deviation of every parameter over the replicas whose fit ended with status 0 ([nprob, n]), how many
         those are ([nprob], int32), and the refits' parameters themselves, xs [nrep, nprob, n], NaN where a fit failed.  The
         result depends on (boot, the data, x) alone, not on how the replicas are chunked.  stat= and group= raise ValueError,
-        and so does kind "pairs" with conv=."""
+        and so does kind "pairs" with conv=.
+        Counts: boot a PoissonBootstrap together with stat=Poisson() (nlh_boot_poisson_batch) -- the replicas are counts drawn
+        from Poisson(fitted values), each refitted with stat and the caller's bounds, pmap, conv and mask; a problem whose
+        fitted values hold a NaN, a negative value or one above 2^24 on an unmasked row comes back with nvalid 0 and NaN.  A
+        PoissonBootstrap without stat=, or with group=, raises ValueError."""
         k = curve_kind(kind)
         nprob, m, shared = self._curve_data(t, y, weights)
         n = curve_nparams(k, ncomp, baseline)
