@@ -5,6 +5,8 @@ torch is plumbing only (device memory, streams); every computation is a call int
 libnonlin_hip.so.  Layout: A [nprob, n, m] (each problem column-major m-by-n, i.e.
 A[p, j, i] = A_p(i, j)), b/fvec [nprob, m], x [nprob, n], all float64 on the GPU.
 """
+import collections
+import contextlib
 import ctypes as C
 import os
 
@@ -23,6 +25,44 @@ def _chk(t, shape, name):
     if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
         raise ValueError(f"{name}: expected contiguous float64 GPU tensor of shape {tuple(shape)}, "
                          f"got {t.dtype} {tuple(t.shape)} cuda={t.is_cuda}")
+
+
+def _ib_status(nprob):
+    """(ib, status): the arrays a batched solver fills with its iteration records and status codes."""
+    return (_lib.IterationBehavior * nprob)(), (C.c_int32 * nprob)()
+
+
+def _ib_lists(ib, status):
+    """Those arrays as the solvers return them: (a list of dicts, a list of ints)."""
+    return [ib[k].as_dict() for k in range(len(ib))], [int(status[k]) for k in range(len(status))]
+
+
+def _host_bounds(lower, upper, n=None, refusal=None):
+    """(plo, phi): the box of a bounded solve as pointers to host arrays of doubles (None: no bound; a pointer keeps its
+    array).  n: the entries each must have -- not checked when None --, refusal: the text of the ValueError otherwise."""
+    lo, hi = (None if b is None else np.ascontiguousarray(b, dtype=np.float64) for b in (lower, upper))
+    if n is not None and any(b is not None and b.shape != (n,) for b in (lo, hi)):
+        raise ValueError(refusal or f"bounds: expected {n} entries")
+    return tuple(None if b is None else b.ctypes.data_as(_lib.c_double_p) for b in (lo, hi))
+
+
+# What the one-call fits and bootstraps pass around.  _Model binds a model -- a built-in curve or an Expr -- once: name
+# ("curve" / "expr"), head (the model's own arguments of _lib.fit_args by name), n parameters, nvar variables, and closures on
+# the public methods: data(t, y, weights) -> (nprob, m, shared_t) checked, launchers(t, y, weights), eval(x, t) and
+# guess(t, y, weights) (None: a formula has no guess).  _Keywords holds the keywords every path hands on; kw._replace(...)
+# copies it with some fields replaced.
+_Model = collections.namedtuple("_Model", "name head n nvar data launchers eval guess")
+_Keywords = collections.namedtuple("_Keywords", "lower upper analytic covariance opts pmap loss stat group conv sep")
+
+
+def _refuse_sep(kw, n):
+    """What a separable fit refuses, worded once."""
+    if kw.sep is None:
+        return
+    if kw.pmap is not None or kw.loss is not None or kw.stat is not None:
+        raise ValueError("sep excludes pmap, loss and stat: a map, a loss and a statistic are nonlinear in the projected parameters")
+    if kw.sep.nparams != n:
+        raise ValueError(f"sep is over {kw.sep.nparams} parameters, the model has {n}")
 
 
 # names of the NLH_QRX_SWEEP_* / INIT_* / PIVOT_* / PASS_* values of include/nonlin_hip.h, in order
@@ -162,12 +202,11 @@ class DeviceSolver:
         nprob, n, m = A.shape
         _chk(A, (nprob, n, m), "A"); _chk(b, (nprob, m), "b"); _chk(x, (nprob, n), "x")
         fvec = torch.empty((nprob, m), dtype=torch.float64, device=A.device)
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        ib, status = _ib_status(nprob)
         o = opts or self.options()
         self._call("nlh_dq_lm_solve_batch", C.byref(o), nprob, m, n, A.data_ptr(), b.data_ptr(),
                    float(gamma), x.data_ptr(), fvec.data_ptr(), ib, status)
-        return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+        return (fvec,) + _ib_lists(ib, status)
 
     def newton_solve_batch(self, A, b, gamma, x, analytic=True, opts=None):
         """newton_solver%solve for every (square) problem.  x is updated in place."""
@@ -175,12 +214,11 @@ class DeviceSolver:
         assert m == n
         _chk(A, (nprob, n, n), "A"); _chk(b, (nprob, n), "b"); _chk(x, (nprob, n), "x")
         fvec = torch.empty((nprob, n), dtype=torch.float64, device=A.device)
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        ib, status = _ib_status(nprob)
         o = opts or self.options()
         self._call("nlh_dq_newton_solve_batch", C.byref(o), nprob, n, A.data_ptr(), b.data_ptr(),
                    float(gamma), int(analytic), x.data_ptr(), fvec.data_ptr(), ib, status)
-        return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+        return (fvec,) + _ib_lists(ib, status)
 
     def quasi_newton_solve_batch(self, A, b, gamma, x, analytic=True, opts=None, jdelta=5):
         """quasi_newton_solver%solve for every (square) problem.  x is updated in place."""
@@ -188,42 +226,35 @@ class DeviceSolver:
         assert m == n
         _chk(A, (nprob, n, n), "A"); _chk(b, (nprob, n), "b"); _chk(x, (nprob, n), "x")
         fvec = torch.empty((nprob, n), dtype=torch.float64, device=A.device)
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        ib, status = _ib_status(nprob)
         o = opts or self.options()
         self._call("nlh_dq_quasi_newton_solve_batch", C.byref(o), int(jdelta), nprob, n, A.data_ptr(),
                    b.data_ptr(), float(gamma), int(analytic), x.data_ptr(), fvec.data_ptr(), ib, status)
-        return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+        return (fvec,) + _ib_lists(ib, status)
 
     def cls_solve_batch(self, A, b, gamma, x, opts=None, lower=None, upper=None, delta=1.0, stepscale=1.0):
         """constrained_least_squares_solver%solve for every problem (the same bounds for all).  x in place."""
-        import numpy as np
         nprob, n, m = A.shape
         _chk(A, (nprob, n, m), "A"); _chk(b, (nprob, m), "b"); _chk(x, (nprob, n), "x")
         fvec = torch.empty((nprob, m), dtype=torch.float64, device=A.device)
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        ib, status = _ib_status(nprob)
         o = opts or self.options()
-        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64)
-        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
-        plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
-        phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
+        plo, phi = _host_bounds(lower, upper)
         self._call("nlh_dq_cls_solve_batch", C.byref(o), float(delta), float(stepscale), plo, phi, nprob, m, n,
                    A.data_ptr(), b.data_ptr(), float(gamma), x.data_ptr(), fvec.data_ptr(), ib, status)
-        return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+        return (fvec,) + _ib_lists(ib, status)
 
     def bfgs_solve_batch(self, A, b, gamma, x, opts=None):
         """bfgs%solve on f(x) = 0.5 ||r(x)||^2 of every problem (FD gradient on the device).  x in place.
         Returns (fout list, ib list, status list)."""
         nprob, n, m = A.shape
         _chk(A, (nprob, n, m), "A"); _chk(b, (nprob, m), "b"); _chk(x, (nprob, n), "x")
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        ib, status = _ib_status(nprob)
         fout = (C.c_double * nprob)()
         o = opts or self.options(max_evals=500)
         self._call("nlh_dq_bfgs_solve_batch", C.byref(o), nprob, m, n, A.data_ptr(), b.data_ptr(), float(gamma),
                    x.data_ptr(), fout, ib, status)
-        return [float(v) for v in fout], [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+        return ([float(v) for v in fout],) + _ib_lists(ib, status)
 
     # -- user-supplied device residuals (launchers) ------------------------------
     @staticmethod
@@ -249,6 +280,15 @@ class DeviceSolver:
         if weights is not None:
             _chk(weights, (nprob, m), "weights")
         return nprob, m, int(shared)
+
+    def _curve_model(self, kind, ncomp, baseline):
+        """The _Model of a built-in curve."""
+        k = curve_kind(kind)
+        return _Model("curve", dict(kind=k, ncomp=int(ncomp), nbase=int(baseline)), curve_nparams(k, ncomp, baseline), 1,
+                      self._curve_data,
+                      lambda t, y, weights: self.curve_launchers(k, ncomp, baseline, t, y, weights),
+                      lambda x, t: self.curve_eval(k, x, t, ncomp, baseline),
+                      lambda t, y, weights: self.curve_guess(k, t, y, ncomp, baseline, weights))
 
     def curve_launchers(self, kind, ncomp, baseline, t, y, weights=None):
         """A built-in curve model (kind: "gauss", "lorentz", "expdecay" or a CURVE_* constant; ncomp components; baseline:
@@ -347,59 +387,38 @@ class DeviceSolver:
         self._call("nlh_starts_take_batch", nprob, keep, width, src.data_ptr(), which.data_ptr(), dst.data_ptr())
         return dst
 
-    def _starts_fit(self, model, head, launchers, n, m, t, shared, y, weights, starts, lower, upper, analytic, covariance, opts, pmap,
-                    loss, stat, group, conv, sep):
-        """A one-call fit with starts=: the launchers of the fit composed in the order of the library's own pipeline -- the
-        model, then conv, then loss or stat, or sep around the model with conv inside --, starts_search on them, the one-call
-        fit from every kept start, and the fit of smallest cost per problem (starts_cost on fvec, starts_pick, starts_take).
-        launchers(weights): the model's own pair."""
-        if pmap is not None or group is not None:
+    def _starts_fit(self, model, t, shared, y, weights, starts, kw):
+        """A one-call fit with starts=: starts_search on the launcher stack of the fit, the one-call fit from every kept start,
+        and the fit of smallest cost per problem (starts_cost on fvec, starts_pick, starts_take)."""
+        if kw.pmap is not None or kw.group is not None:
             raise ValueError("starts excludes pmap and group: compose pmap_launchers / group_launchers and call starts_search")
+        n = model.n
         if starts.n != n:
             raise ValueError(f"starts: a box over {starts.n} parameters, the model has {n}")
-        if stat is not None and loss is not None:
-            raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
-        if sep is not None and (loss is not None or stat is not None):
-            raise ValueError("sep excludes pmap, loss and stat: a map, a loss and a statistic are nonlinear in the projected parameters")
-        if sep is not None and sep.nparams != n:
-            raise ValueError(f"sep is over {sep.nparams} parameters, the model has {n}")
-        nprob = y.shape[0]
-        layers = [launchers(None if conv is not None or stat is not None else weights)]      # (every context stays alive in here)
-        if conv is not None:
-            layers.append(self.conv_launchers(conv, *layers[-1], y, None if stat is not None else weights))
-        if stat is not None:
-            layers.append(self.pois_launchers(stat, *layers[-1], y, weights))
-        if loss is not None:
-            layers.append(self.loss_launchers(loss, *layers[-1], nprob))
-        positions = None
-        if sep is not None:
-            layers.append(self.sep_launchers(sep, *layers[-1]))
-            positions = [int(k) for k in sep.tables()[1]]
-        fcn, _, ctx = layers[-1]
-        x0s, cost, index = self.starts_search(fcn, ctx, nprob, m, starts, positions)
-        runs = []
-        for k in range(starts.keep):
-            if positions is None:
-                x0 = x0s[:, k].contiguous()
-            else:                                                    # the linear positions of a separable fit's x0 are 0.0
-                x0 = torch.zeros((nprob, n), dtype=torch.float64, device=y.device)
-                x0[:, positions] = x0s[:, k]
-            runs.append(self._fit(model, head, n, m, t, shared, y, weights, x0, lower, upper, analytic, covariance, opts, None, loss, stat,
-                                  None, conv, sep))
-        which = self.starts_pick(torch.stack([self.starts_cost(r[1]) for r in runs]))
-        take = lambda j: self.starts_take(torch.stack([r[j] for r in runs]), which)
-        x, fvec = take(0), take(1)
-        sigma = cov = chi2 = rank = None
-        if covariance:
-            sigma, cov, chi2 = take(2), take(3), take(4)
-            # (rank is int32: as float64, exactly, through the same take; NaN -- no fit was picked -- is -1)
-            rank = torch.nan_to_num(self.starts_take(torch.stack([r[5] for r in runs]).to(torch.float64), which), nan=-1.0).to(torch.int32)
-        wh = which.cpu().tolist()                                    # ibs and status: the chosen fit's; of fit 0 where none was picked
-        ibs = [runs[max(k, 0)][6][p] for p, k in enumerate(wh)]
-        status = [runs[max(k, 0)][7][p] for p, k in enumerate(wh)]
-        starts.which, starts.index, starts.cost = which, index, cost
-        for layer in reversed(layers[1:]):
-            layer[2].close()
+        _refuse_sep(kw, n)
+        nprob, m = y.shape
+        with self._stack(model, t, y, weights, kw) as (fcn, _, ctx, positions):
+            x0s, cost, index = self.starts_search(fcn, ctx, nprob, m, starts, positions)
+            runs = []
+            for k in range(starts.keep):
+                if positions is None:
+                    x0 = x0s[:, k].contiguous()
+                else:                                                # the linear positions of a separable fit's x0 are 0.0
+                    x0 = torch.zeros((nprob, n), dtype=torch.float64, device=y.device)
+                    x0[:, positions] = x0s[:, k]
+                runs.append(self._fit(model, t, shared, y, weights, x0, kw))
+            which = self.starts_pick(torch.stack([self.starts_cost(r[1]) for r in runs]))
+            take = lambda j: self.starts_take(torch.stack([r[j] for r in runs]), which)
+            x, fvec = take(0), take(1)
+            sigma = cov = chi2 = rank = None
+            if kw.covariance:
+                sigma, cov, chi2 = take(2), take(3), take(4)
+                # (rank is int32: as float64, exactly, through the same take; NaN -- no fit was picked -- is -1)
+                rank = torch.nan_to_num(self.starts_take(torch.stack([r[5] for r in runs]).to(torch.float64), which), nan=-1.0).to(torch.int32)
+            wh = which.cpu().tolist()                                # ibs and status: the chosen fit's; of fit 0 where none was picked
+            ibs = [runs[max(k, 0)][6][p] for p, k in enumerate(wh)]
+            status = [runs[max(k, 0)][7][p] for p, k in enumerate(wh)]
+            starts.which, starts.index, starts.cost = which, index, cost
         return x, fvec, sigma, cov, chi2, rank, ibs, status
 
     # -- bootstrap: intervals of any fit from refits of resampled data --------------------
@@ -457,14 +476,27 @@ class DeviceSolver:
                    hi.data_ptr(), nvalid.data_ptr())
         return lo, hi, mean, sd, nvalid
 
-    def _boot_fit(self, model, head, evaluate, n, m, t, shared, y, x, boot, weights, lower, upper, analytic, opts, pmap, loss, stat,
-                  group, conv, sep):
-        """The one-call bootstrap behind curve_boot_batch and expr_boot_batch: the fitted values -- evaluate(x), through
+    @staticmethod
+    def _replicas(r, t, shared, weights, x, kw):
+        """(t, weights, x, kw) of a chunk of r replicas, replica-major: what is per problem -- t unless shared, the weights, x,
+        a Loss's scales and a Convolve's taps -- repeated r times."""
+        loss, conv = kw.loss, kw.conv
+        if loss is not None and not loss.shared:
+            loss = _lib.Loss(loss.kind, np.tile(loss.scale, r))
+        if conv is not None and not conv.shared:
+            conv = _lib.Convolve(np.tile(conv.kernel, (r, 1)), conv.origin, conv.ext)
+        return (t if shared else t.repeat(1, r, 1) if t.dim() == 3 else t.repeat(r, 1),
+                weights.repeat(r, 1) if weights is not None else None, x.repeat(r, 1), kw._replace(loss=loss, conv=conv))
+
+    def _boot_fit(self, model, t, y, x, boot, weights, kw):
+        """The one-call bootstrap behind curve_boot_batch and expr_boot_batch: the fitted values -- model.eval(x, t), through
         conv_apply with conv --, then chunks of replicas whose y* stays within 256 MiB (the environment variable
         NLH_BOOT_REPS, read at every call, sets the replicas of a chunk instead: tests), each chunk one _fit call without
         covariance from x repeated, and the summary of what the fits returned, NaN where a fit's status is not 0.  A
         PoissonBootstrap takes boot_poisson's replicas and passes stat on to the refits; the refits of a problem with a bad
         fitted value are set to NaN on the device."""
+        nprob, m, shared = model.data(t, y, weights)
+        n, stat, group, conv = model.n, kw.stat, kw.group, kw.conv
         pois = isinstance(boot, _lib.PoissonBootstrap)
         if pois:
             if stat is None:
@@ -476,31 +508,26 @@ class DeviceSolver:
         pairs = not pois and boot.kind == _lib.BOOT_PAIRS
         if pairs and conv is not None:
             raise ValueError('kind "pairs" excludes conv: a convolution needs every row')
-        nprob = y.shape[0]
         _chk(x, (nprob, n), "x")
         mu = None
         if not pairs:
-            mu = evaluate(x)
+            mu = model.eval(x, t)
             if conv is not None:
                 mu = self.conv_apply(conv, mu)
         per = max(1, (256 << 20) // (8 * max(nprob * m, 1)))
         env = os.environ.get("NLH_BOOT_REPS")
         if env is not None and int(env) >= 1:
             per = int(env)
+        refit = kw._replace(covariance=False, group=None)
         xs = torch.empty((boot.nrep, nprob, n), dtype=torch.float64, device=y.device)
         for rep0 in range(0, boot.nrep, per):
             r = min(per, boot.nrep - rep0)
             if pois:
                 ystar, nbad = self.boot_poisson(boot, mu, y, weights, 0, rep0, r)
-                wstar = None
             else:
                 ystar, wstar = self.boot_resample(boot, mu, y, weights, 0, rep0, r)
-            wc = wstar.reshape(r * nprob, m) if pairs else weights.repeat(r, 1) if weights is not None else None
-            tc = t if shared else t.repeat(1, r, 1) if t.dim() == 3 else t.repeat(r, 1)
-            lc = loss if loss is None or loss.shared else _lib.Loss(loss.kind, np.tile(loss.scale, r))
-            cc = conv if conv is None or conv.shared else _lib.Convolve(np.tile(conv.kernel, (r, 1)), conv.origin, conv.ext)
-            out = self._fit(model, head, n, m, tc, shared, ystar.reshape(r * nprob, m), wc, x.repeat(r, 1), lower, upper, analytic, False,
-                            opts, pmap, lc, stat, None, cc, sep)
+            tc, wc, xc, kc = self._replicas(r, t, shared, None if pairs else weights, x, refit)
+            out = self._fit(model, tc, shared, ystar.reshape(r * nprob, m), wstar.reshape(r * nprob, m) if pairs else wc, xc, kc)
             bad = torch.tensor([s != 0 for s in out[7]], dtype=torch.bool, device=y.device)
             xs[rep0:rep0 + r] = out[0].masked_fill(bad[:, None], float("nan")).reshape(r, nprob, n)
             if pois:                                                 # a problem with a bad fitted value has no valid replica
@@ -521,19 +548,14 @@ class DeviceSolver:
         from Poisson(fitted values), each refitted with stat and the caller's bounds, pmap, conv and mask; a problem whose
         fitted values hold a NaN, a negative value or one above 2^24 on an unmasked row comes back with nvalid 0 and NaN.  A
         PoissonBootstrap without stat=, or with group=, raises ValueError."""
-        k = curve_kind(kind)
-        nprob, m, shared = self._curve_data(t, y, weights)
-        n = curve_nparams(k, ncomp, baseline)
-        return self._boot_fit("curve", dict(kind=k, ncomp=int(ncomp), nbase=int(baseline)),
-                              lambda v: self.curve_eval(k, v, t, ncomp, baseline), n, m, t, shared, y, x, boot, weights, lower, upper,
-                              analytic, opts, pmap, loss, stat, group, conv, sep)
+        return self._boot_fit(self._curve_model(kind, ncomp, baseline), t, y, x, boot, weights,
+                              _Keywords(lower, upper, analytic, False, opts, pmap, loss, stat, group, conv, sep))
 
     def expr_boot_batch(self, expr, t, y, x, boot, weights=None, lower=None, upper=None, analytic=True, opts=None, pmap=None,
                         loss=None, stat=None, group=None, conv=None, sep=None):
         """curve_boot_batch with an Expr in the place of (kind, ncomp, baseline): the bootstrap of expr_fit_batch's fit x."""
-        nprob, m, shared = self._expr_data(expr, t, y, weights)
-        return self._boot_fit("expr", dict(expr=expr.ptr), lambda v: self.expr_eval(expr, v, t), expr.nparams, m, t, shared, y, x, boot,
-                              weights, lower, upper, analytic, opts, pmap, loss, stat, group, conv, sep)
+        return self._boot_fit(self._expr_model(expr), t, y, x, boot, weights,
+                              _Keywords(lower, upper, analytic, False, opts, pmap, loss, stat, group, conv, sep))
 
     @staticmethod
     def _fit_outputs(x0, m, covariance, nsolve, nunk):
@@ -550,18 +572,7 @@ class DeviceSolver:
             cov = torch.empty((nsolve, nunk, nunk), dtype=torch.float64, device=dev)
             chi2 = torch.empty((nsolve,), dtype=torch.float64, device=dev)
             rank = torch.empty((nsolve,), dtype=torch.int32, device=dev)
-        return x, fvec, sigma, cov, chi2, rank, (_lib.IterationBehavior * nsolve)(), (C.c_int32 * nsolve)()
-
-    @staticmethod
-    def _fit_bounds(lower, upper, n):
-        """(lo, hi, plo, phi): the box of a one-call fit as host arrays [n] (None: no bound) and the pointers to them."""
-        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64)
-        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
-        for b in (lo, hi):
-            if b is not None and b.shape != (n,):
-                raise ValueError(f"bounds: expected {n} entries")
-        return (lo, hi, None if lo is None else lo.ctypes.data_as(_lib.c_double_p),
-                None if hi is None else hi.ctypes.data_as(_lib.c_double_p))
+        return (x, fvec, sigma, cov, chi2, rank) + _ib_status(nsolve)
 
     def curve_fit_batch(self, kind, t, y, x0, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
                         covariance=True, opts=None, pmap=None, loss=None, stat=None, group=None, conv=None, sep=None, starts=None,
@@ -616,41 +627,39 @@ class DeviceSolver:
         bit-stated.  A problem with dof <= 0 raises ValueError.  bins together with pmap, group, sep, starts or x0=None raises
         ValueError: use bin_launchers with pmap_launchers, group_launchers, sep_launchers or starts_search.  There is no
         bins= in the bootstrap calls and no curve_guess on binned data.  None calls exactly what is called without it."""
-        if stat is not None and loss is not None:
+        return self._fit_front(self._curve_model(kind, ncomp, baseline), t, y, x0, weights, starts, bins,
+                               _Keywords(lower, upper, analytic, covariance, opts, pmap, loss, stat, group, conv, sep))
+
+    def _fit_front(self, model, t, y, x0, weights, starts, bins, kw):
+        """curve_fit_batch and expr_fit_batch once they have bound their model: what is refused before the data are looked
+        at, then bins= (_bin_fit), the data, starts= (_starts_fit), the guess of a model that has one for x0=None, and _fit."""
+        if kw.stat is not None and kw.loss is not None:
             raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
-        k = curve_kind(kind)
         if bins is not None:
-            n = curve_nparams(k, ncomp, baseline)
-            return self._bin_fit(lambda tq, zero: self.curve_launchers(k, ncomp, baseline, tq, zero), n, 1, t, y, weights, x0, bins, lower,
-                                 upper, analytic, covariance, opts, pmap, loss, stat, group, conv, sep, starts)
-        nprob, m, shared = self._curve_data(t, y, weights)
-        n = curve_nparams(k, ncomp, baseline)
+            for name, v in (("pmap", kw.pmap), ("group", kw.group), ("sep", kw.sep), ("starts", starts)):
+                if v is not None:
+                    raise ValueError(f"bins excludes {name}: compose bin_launchers with the other launchers and call the solver")
+            return self._bin_fit(model, t, y, weights, x0, bins, kw)
+        nprob, m, shared = model.data(t, y, weights)
         if starts is not None:
             if x0 is not None:
                 raise ValueError("starts excludes x0: the scan makes the starting values")
-            return self._starts_fit("curve", dict(kind=k, ncomp=int(ncomp), nbase=int(baseline)),
-                                    lambda w: self.curve_launchers(k, ncomp, baseline, t, y, w), n, m, t, shared, y, weights, starts,
-                                    lower, upper, analytic, covariance, opts, pmap, loss, stat, group, conv, sep)
-        if x0 is None:
-            if pmap is not None or group is not None:
+            return self._starts_fit(model, t, shared, y, weights, starts, kw)
+        if x0 is None and model.guess is not None:
+            if kw.pmap is not None or kw.group is not None:
                 raise ValueError("x0=None excludes pmap and group: a fixed or a shared parameter needs the caller's value")
-            x0 = self.curve_guess(k, t, y, ncomp, baseline, weights)[0]
-        _chk(x0, (nprob, n), "x0")
-        return self._fit("curve", dict(kind=k, ncomp=int(ncomp), nbase=int(baseline)), n, m, t, shared, y, weights, x0, lower, upper,
-                         analytic, covariance, opts, pmap, loss, stat, group, conv, sep)
+            x0 = model.guess(t, y, weights)[0]
+        _chk(x0, (nprob, model.n), "x0")
+        return self._fit(model, t, shared, y, weights, x0, kw)
 
-    def _fit(self, model, head, n, m, t, shared, y, weights, x0, lower, upper, analytic, covariance, opts, pmap, loss, stat, group,
-             conv, sep):
-        """The one-call fit behind curve_fit_batch ("curve") and expr_fit_batch ("expr") once they have checked their data: what
-        the features refuse, the entry point they select, its outputs -- per group with a group, per data set without --, and
-        the call, its arguments in the order of _lib.fit_args.  head: the model's own arguments by name.  A feature that is
-        None gives what the entry points read as "none": a NULL pointer, kind 0, shared 0, stat 0, mu_floor 0.0."""
-        nprob = x0.shape[0]
-        if sep is not None:
-            if pmap is not None or loss is not None or stat is not None:
-                raise ValueError("sep excludes pmap, loss and stat: a map, a loss and a statistic are nonlinear in the projected parameters")
-            if sep.nparams != n:
-                raise ValueError(f"sep is over {sep.nparams} parameters, the model has {n}")
+    def _fit(self, model, t, shared, y, weights, x0, kw):
+        """The one-call fit of a bound model on checked data: what the features refuse, the entry point they select, its
+        outputs -- per group with a group, per data set without --, and the call, its arguments in the order of
+        _lib.fit_args.  A feature that is None gives what the entry points read as "none": a NULL pointer, kind 0, shared 0,
+        stat 0, mu_floor 0.0."""
+        lower, upper, analytic, covariance, opts, pmap, loss, stat, group, conv, sep = kw
+        (nprob, m), n = y.shape, model.n
+        _refuse_sep(kw, n)
         if group is not None:
             if pmap is not None:
                 raise ValueError("group and pmap exclude each other: a map inside a group works through pmap_launchers and group_launchers")
@@ -659,25 +668,25 @@ class DeviceSolver:
             if nprob % group.nsets:
                 raise ValueError(f"{nprob} data sets: no multiple of the group's {group.nsets}")
         if pmap is not None and pmap.nfull != n:
-            raise ValueError(f"pmap maps {pmap.nfull} parameters, the {'formula' if model == 'expr' and conv is None else 'model'} has {n}")
+            raise ValueError(f"pmap maps {pmap.nfull} parameters, the {'formula' if model.name == 'expr' and conv is None else 'model'} has {n}")
         variant = ("_sep" if sep is not None else "_conv" if conv is not None else "_group" if group is not None else
                    "_pois" if stat is not None else "_loss" if loss is not None else "_pmap" if pmap is not None else "")
         nsolve, nunk = (nprob // group.nsets, group.nouter) if group is not None else (nprob, n)
         x, fvec, sigma, cov, chi2, rank, ib, status = self._fit_outputs(x0, m, covariance, nsolve, nunk)
-        lo, hi, plo, phi = self._fit_bounds(lower, upper, n)
+        plo, phi = _host_bounds(lower, upper, n)
         o = opts or self.options()
         dscale, sh = self._loss_scale(loss, nprob, y.device) if loss is not None else (None, 0)     # dscale, dk: alive across the call
         cv, dk = self._conv_struct(conv, nprob, y.device) if conv is not None else (None, None)
         ptr = lambda a: a.data_ptr() if a is not None else None
         obj = lambda a: a.ptr if a is not None else None
-        val = dict(head, opts=C.byref(o), nprob=nprob, m=m, t=t.data_ptr(), shared_t=shared, y=y.data_ptr(), w=ptr(weights),
+        val = dict(model.head, opts=C.byref(o), nprob=nprob, m=m, t=t.data_ptr(), shared_t=shared, y=y.data_ptr(), w=ptr(weights),
                    analytic=int(bool(analytic)), xl=plo, xu=phi, pm=obj(pmap), g=obj(group), sp=obj(sep),
                    cv=C.byref(cv) if cv is not None else None, loss=loss.kind if loss is not None else 0, scale=ptr(dscale),
                    shared_scale=sh, stat=1 if stat is not None else 0, mu_floor=stat.mu_floor if stat is not None else 0.0,
                    x=x.data_ptr(), fvec=fvec.data_ptr(), sigma=ptr(sigma), cov=ptr(cov), chi2=ptr(chi2), rank=ptr(rank), ib=ib,
                    status=status)
-        self._call(f"nlh_{model}_fit_batch{variant}", *[val[name] for name, _ in _lib.fit_args(model, variant)])
-        return (x, fvec, sigma, cov, chi2, rank, [ib[p].as_dict() for p in range(nsolve)], [int(status[p]) for p in range(nsolve)])
+        self._call(f"nlh_{model.name}_fit_batch{variant}", *[val[name] for name, _ in _lib.fit_args(model.name, variant)])
+        return (x, fvec, sigma, cov, chi2, rank) + _ib_lists(ib, status)
 
     # -- formula models ----------------------------------------------------------
     @staticmethod
@@ -703,6 +712,13 @@ class DeviceSolver:
         if weights is not None:
             _chk(weights, (nprob, m), "weights")
         return nprob, m, shared
+
+    def _expr_model(self, expr):
+        """The _Model of a formula: it has no guess."""
+        return _Model("expr", dict(expr=expr.ptr), expr.nparams, expr.nvar,
+                      lambda t, y, weights: self._expr_data(expr, t, y, weights),
+                      lambda t, y, weights: self.expr_launchers(expr, t, y, weights),
+                      lambda x, t: self.expr_eval(expr, x, t), None)
 
     def expr_launchers(self, expr, t, y, weights=None):
         """A formula model (nonlin_amd.Expr) on the data t [nvar, nprob, m] (or shared [nvar, m]; one variable: [nprob, m] or
@@ -747,22 +763,9 @@ class DeviceSolver:
         from the best candidates of a box, as in curve_fit_batch.  bins (a Binned; Binned.pixels for a formula of two
         variables): the formula is integrated or averaged over the bins y was recorded in, as in curve_fit_batch; t is then
         not read and must be None."""
-        if stat is not None and loss is not None:
-            raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
-        if bins is not None:
-            return self._bin_fit(lambda tq, zero: self.expr_launchers(expr, tq, zero), expr.nparams, expr.nvar, t, y, weights, x0, bins,
-                                 lower, upper, analytic, covariance, opts, pmap, loss, stat, group, conv, sep, starts)
-        nprob, m, shared = self._expr_data(expr, t, y, weights)
-        n = expr.nparams
-        if starts is not None:
-            if x0 is not None:
-                raise ValueError("starts excludes x0: the scan makes the starting values")
-            return self._starts_fit("expr", dict(expr=expr.ptr), lambda w: self.expr_launchers(expr, t, y, w), n, m, t, shared, y, weights,
-                                    starts, lower, upper, analytic, covariance, opts, pmap, loss, stat, group, conv, sep)
-        _chk(x0, (nprob, n), "x0")
         # conv (a Convolve) and sep (a Separable, e.g. Separable.for_expr(expr, linear=("a", "c"))): as in curve_fit_batch
-        return self._fit("expr", dict(expr=expr.ptr), n, m, t, shared, y, weights, x0, lower, upper, analytic, covariance, opts,
-                         pmap, loss, stat, group, conv, sep)
+        return self._fit_front(self._expr_model(expr), t, y, x0, weights, starts, bins,
+                               _Keywords(lower, upper, analytic, covariance, opts, pmap, loss, stat, group, conv, sep))
 
     # -- parameter maps ------------------------------------------------------------
     def pmap_launchers(self, pmap, fcn, jac, ctx, full):
@@ -986,21 +989,16 @@ class DeviceSolver:
         torch.cuda.current_stream(v.device).synchronize()             # (dsc goes with this frame)
         return out
 
-    def _bin_fit(self, launchers, n, nvar, t, y, weights, x0, bins, lower, upper, analytic, covariance, opts, pmap, loss, stat, group,
-                 conv, sep, starts):
-        """A one-call fit with bins=: the launchers of the fit composed in the order of the library's own pipeline -- the
-        model on the nodes with a zero y, the bin pair with y (and the weights, unless conv or stat take them), then conv,
-        then stat or loss --, the solve, and the covariance.  launchers(tq, zero): the model's own pair."""
-        for name, v in (("pmap", pmap), ("group", group), ("sep", sep), ("starts", starts)):
-            if v is not None:
-                raise ValueError(f"bins excludes {name}: compose bin_launchers with the other launchers and call the solver")
+    def _bin_fit(self, model, t, y, weights, x0, bins, kw):
+        """A one-call fit with bins=: the solve and the covariance on the launcher stack of the fit (_stack, with the bin pair
+        in it), and the zero-weight rule of the header where there are weights."""
         if x0 is None:
             raise ValueError("bins excludes x0=None: there is no guess on binned data; compose bin_launchers and call starts_search")
         if t is not None:
             raise ValueError("bins excludes t: the model is evaluated at bins.nodes(); pass t=None")
-        if bins.nvar != nvar:
-            raise ValueError(f"bins are over {bins.nvar} variable(s), the model has {nvar}")
-        nprob, m = y.shape
+        if bins.nvar != model.nvar:
+            raise ValueError(f"bins are over {bins.nvar} variable(s), the model has {model.nvar}")
+        (nprob, m), n = y.shape, model.n
         _chk(y, (nprob, m), "y")
         _chk(x0, (nprob, n), "x0")
         if weights is not None:
@@ -1008,40 +1006,27 @@ class DeviceSolver:
             dof = (weights != 0).sum(dim=1) - n
             if bool((dof <= 0).any()):
                 raise ValueError("bins: a problem has no degree of freedom left (rows with non-zero weight <= parameters)")
-        tq = self.bin_nodes(bins, nprob, y.device)
-        zero = torch.zeros((nprob, bins.Q * bins.m), dtype=torch.float64, device=y.device)
-        plain = conv is None and stat is None
-        layers = [launchers(tq, zero)]                               # (every context stays alive in here)
-        layers.append(self.bin_launchers(bins, *layers[-1], y, weights if plain else None))
-        if conv is not None:
-            layers.append(self.conv_launchers(conv, *layers[-1], y, None if stat is not None else weights))
-        if stat is not None:
-            layers.append(self.pois_launchers(stat, *layers[-1], y, weights))
-        if loss is not None:
-            layers.append(self.loss_launchers(loss, *layers[-1], nprob))
-        fcn, jac, ctx = layers[-1]
-        jac = jac if analytic else None
-        x = x0.clone()
-        o = opts or self.options()
-        if lower is not None or upper is not None:
-            fvec, ibs, status = self.cls_solve_batch_device(fcn, ctx, m, x, jac=jac, opts=o, lower=lower, upper=upper)
-        else:
-            fvec, ibs, status = self.lm_solve_batch_device(fcn, ctx, m, x, jac=jac, opts=o)
-        sigma = cov = chi2 = rank = None
-        if covariance:
-            cov, sigma, rank, chi2 = self.lm_covariance_batch_device(fcn, ctx, m, x, jac=jac, scaled=stat is None)
-            if weights is not None:                                  # the header's zero-weight rule, in torch
-                f = float(m - n) / dof.to(torch.float64)
-                chi2 = chi2 * f
-                if stat is None:
-                    cov = cov * f[:, None, None]
-                    sigma = torch.sqrt(torch.diagonal(cov, dim1=1, dim2=2)).contiguous()
-            bad = torch.tensor([s != 0 for s in status], dtype=torch.bool, device=y.device)
-            nan = float("nan")
-            sigma, cov, chi2 = sigma.masked_fill(bad[:, None], nan), cov.masked_fill(bad[:, None, None], nan), chi2.masked_fill(bad, nan)
-            rank = rank.masked_fill(bad, -1)
-        for layer in reversed(layers[1:]):
-            layer[2].close()
+        with self._stack(model, None, y, weights, kw, bins) as (fcn, jac, ctx, _):
+            jac = jac if kw.analytic else None
+            x = x0.clone()
+            o = kw.opts or self.options()
+            if kw.lower is not None or kw.upper is not None:
+                fvec, ibs, status = self.cls_solve_batch_device(fcn, ctx, m, x, jac=jac, opts=o, lower=kw.lower, upper=kw.upper)
+            else:
+                fvec, ibs, status = self.lm_solve_batch_device(fcn, ctx, m, x, jac=jac, opts=o)
+            sigma = cov = chi2 = rank = None
+            if kw.covariance:
+                cov, sigma, rank, chi2 = self.lm_covariance_batch_device(fcn, ctx, m, x, jac=jac, scaled=kw.stat is None)
+                if weights is not None:                              # the header's zero-weight rule, in torch
+                    f = float(m - n) / dof.to(torch.float64)
+                    chi2 = chi2 * f
+                    if kw.stat is None:
+                        cov = cov * f[:, None, None]
+                        sigma = torch.sqrt(torch.diagonal(cov, dim1=1, dim2=2)).contiguous()
+                bad = torch.tensor([s != 0 for s in status], dtype=torch.bool, device=y.device)
+                nan = float("nan")
+                sigma, cov, chi2 = sigma.masked_fill(bad[:, None], nan), cov.masked_fill(bad[:, None, None], nan), chi2.masked_fill(bad, nan)
+                rank = rank.masked_fill(bad, -1)
         return x, fvec, sigma, cov, chi2, rank, ibs, status
 
     # -- separable fits (variable projection) --------------------------------------
@@ -1104,50 +1089,75 @@ class DeviceSolver:
         return (launcher("fcn"), launcher("jac") if jac is not None else None,
                 _Wrapped(self.lib, out, keep, f"nlh_{kind}_unwrap"))
 
+    @contextlib.contextmanager
+    def _stack(self, model, t, y, weights, kw, bins=None):
+        """The launchers of a one-call fit, composed in the order of the library's own pipeline: the model's pair -- under
+        bins on bin_nodes with a zero y --, then bin_launchers, conv_launchers, pois_launchers, loss_launchers and
+        sep_launchers for what is given.  The weights go to the Poisson pair if there is one, else to the conv pair, else to
+        the bin pair, else to the model; the layers inside get None.  Yields (fcn, jac, ctx, positions) of the outermost pair,
+        positions the nonlinear unknowns with sep (None without); on the way out every wrapped context is closed, the
+        outermost first."""
+        nprob = y.shape[0]
+        taker = "pois" if kw.stat is not None else "conv" if kw.conv is not None else "bin" if bins is not None else "model"
+        w = lambda layer: weights if layer == taker else None
+        if bins is not None:
+            t, y0 = self.bin_nodes(bins, nprob, y.device), torch.zeros((nprob, bins.Q * bins.m), dtype=torch.float64, device=y.device)
+        with contextlib.ExitStack() as made:
+            def wrapped(pair):
+                made.callback(pair[2].close)
+                return pair
+            pair = model.launchers(t, y if bins is None else y0, w("model"))
+            if bins is not None:
+                pair = wrapped(self.bin_launchers(bins, *pair, y, w("bin")))
+            if kw.conv is not None:
+                pair = wrapped(self.conv_launchers(kw.conv, *pair, y, w("conv")))
+            if kw.stat is not None:
+                pair = wrapped(self.pois_launchers(kw.stat, *pair, y, w("pois")))
+            if kw.loss is not None:
+                pair = wrapped(self.loss_launchers(kw.loss, *pair, nprob))
+            positions = None
+            if kw.sep is not None:
+                pair = wrapped(self.sep_launchers(kw.sep, *pair))
+                positions = [int(k) for k in kw.sep.tables()[1]]
+            yield pair + (positions,)
+
     def lm_solve_batch_device(self, fcn, ctx, m, x, jac=None, opts=None):
         """least_squares_solver%solve on x.shape[0] problems of a USER'S device residual (launcher fcn, context ctx).
         x [nprob, n] is updated in place.  Returns (fvec, ib_list, status_list)."""
         nprob, n = x.shape
         _chk(x, (nprob, n), "x")
         fvec = torch.empty((nprob, m), dtype=torch.float64, device=x.device)
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        ib, status = _ib_status(nprob)
         o = opts or self.options()
         self._call("nlh_lm_solve_batch_device", C.byref(o), nprob, m, n, self._devfcn(fcn), self._devfcn(jac),
                    self._ctxp(ctx), x.data_ptr(), fvec.data_ptr(), ib, status)
-        return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+        return (fvec,) + _ib_lists(ib, status)
 
     def cls_solve_batch_device(self, fcn, ctx, m, x, jac=None, opts=None, lower=None, upper=None, delta=1.0, stepscale=1.0):
         """constrained_least_squares_solver%solve on x.shape[0] problems of a user's device residual (the same box for all)."""
-        import numpy as np
         nprob, n = x.shape
         _chk(x, (nprob, n), "x")
         fvec = torch.empty((nprob, m), dtype=torch.float64, device=x.device)
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        ib, status = _ib_status(nprob)
         o = opts or self.options()
-        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64)
-        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
-        plo = None if lo is None else lo.ctypes.data_as(_lib.c_double_p)
-        phi = None if hi is None else hi.ctypes.data_as(_lib.c_double_p)
+        plo, phi = _host_bounds(lower, upper)
         self._call("nlh_cls_solve_batch_device", C.byref(o), float(delta), float(stepscale), plo, phi, nprob, m, n,
                    self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), x.data_ptr(), fvec.data_ptr(), ib, status)
-        return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+        return (fvec,) + _ib_lists(ib, status)
 
     def square_solve_batch_device(self, fcn, ctx, x, jac=None, opts=None, broyden=False, jdelta=5):
         """newton_solver%solve (or quasi_newton_solver%solve) on x.shape[0] square problems of a user's device residual."""
         nprob, n = x.shape
         _chk(x, (nprob, n), "x")
         fvec = torch.empty((nprob, n), dtype=torch.float64, device=x.device)
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        ib, status = _ib_status(nprob)
         o = opts or self.options()
         tail = (nprob, n, self._devfcn(fcn), self._devfcn(jac), self._ctxp(ctx), x.data_ptr(), fvec.data_ptr(), ib, status)
         if broyden:
             self._call("nlh_quasi_newton_solve_batch_device", C.byref(o), int(jdelta), *tail)
         else:
             self._call("nlh_newton_solve_batch_device", C.byref(o), *tail)
-        return fvec, [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+        return (fvec,) + _ib_lists(ib, status)
 
     def bfgs_solve_batch_device(self, fcn, ctx, x, grad=None, opts=None):
         """bfgs%solve for every problem with the USER'S device fcnnvar: fcn a launcher called with m = 1 (dF[npoints] = f),
@@ -1155,13 +1165,12 @@ class DeviceSolver:
         Returns (fout list, ib list, status list)."""
         nprob, n = x.shape
         _chk(x, (nprob, n), "x")
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        ib, status = _ib_status(nprob)
         fout = (C.c_double * nprob)()
         o = opts or self.options(max_evals=500)
         self._call("nlh_bfgs_solve_batch_device", C.byref(o), nprob, n, self._devfcn(fcn), self._devfcn(grad), self._ctxp(ctx),
                    x.data_ptr(), fout, ib, status)
-        return [float(v) for v in fout], [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+        return ([float(v) for v in fout],) + _ib_lists(ib, status)
 
     def nelder_mead_solve_batch_device(self, fcn, ctx, x, simplex=None, init_size=1.0, opts=None):
         """nelder_mead%solve for every problem with the USER'S device fcnnvar (fcn a launcher called with m = 1).  x [nprob][n]
@@ -1172,14 +1181,13 @@ class DeviceSolver:
         _chk(x, (nprob, n), "x")
         if simplex is not None:
             _chk(simplex, (nprob, n + 1, n), "simplex")
-        ib = (_lib.IterationBehavior * nprob)()
-        status = (C.c_int32 * nprob)()
+        ib, status = _ib_status(nprob)
         fout = (C.c_double * nprob)()
         o = opts or self.options(max_evals=500)
         self._call("nlh_nelder_mead_solve_batch_device", C.byref(o), float(init_size), nprob, n, self._devfcn(fcn),
                    self._ctxp(ctx), x.data_ptr(), simplex.data_ptr() if simplex is not None else None,
                    0 if simplex is None else 1, fout, ib, status)
-        return [float(v) for v in fout], [ib[k].as_dict() for k in range(nprob)], [int(status[k]) for k in range(nprob)]
+        return ([float(v) for v in fout],) + _ib_lists(ib, status)
 
     def _root1v_batch(self, entry, fcns, ctx, lim, x, opts):
         nprob = x.shape[0]
@@ -1551,7 +1559,6 @@ class HostModel(_lib.Owner):
     _slot, _free = "_md", "nlh_dq_model_destroy"
 
     def __init__(self, owner, A, b, gamma):
-        import numpy as np
         self.owner = owner
         self.lib = owner.lib
         A = np.ascontiguousarray(A, dtype=np.float64)
@@ -1583,15 +1590,13 @@ class HostModel(_lib.Owner):
         return int(self.lib.nlh_dq_model_device_count(self._md))
 
     def _solve(self, fn, x, opts, *extra):
-        import numpy as np
         x = np.ascontiguousarray(x, dtype=np.float64).copy()
         f = np.empty((self.nprob, self.m))
-        ib = (_lib.IterationBehavior * self.nprob)()
-        st = (C.c_int32 * self.nprob)()
+        ib, st = _ib_status(self.nprob)
         dp = lambda a: a.ctypes.data_as(_lib.c_double_p)
         rc = fn(self._hptr, C.byref(opts if opts is not None else _lib.default_options()), self._md, *extra, dp(x), dp(f), ib, st)
         self._checked(rc, fn.__name__)
-        return x, f, [ib[p].as_dict() for p in range(self.nprob)], [int(st[p]) for p in range(self.nprob)]
+        return (x, f) + _ib_lists(ib, st)
 
     def lm_solve(self, x, opts=None):
         """least_squares_solver%solve on every problem: returns (x, fvec, iteration behaviours, status codes)."""
@@ -1606,33 +1611,24 @@ class HostModel(_lib.Owner):
 
     def cls_solve(self, x, lower=None, upper=None, delta=1.0, stepscale=1.0, opts=None):
         """constrained_least_squares_solver%solve on every problem inside the box [lower, upper] (n entries each, or None)."""
-        import numpy as np
-        lo = None if lower is None else np.ascontiguousarray(lower, dtype=np.float64)
-        hi = None if upper is None else np.ascontiguousarray(upper, dtype=np.float64)
-        for v in (lo, hi):
-            if v is not None and v.shape != (self.n,):
-                raise ValueError("bounds must have n entries")
-        dp = lambda a: None if a is None else a.ctypes.data_as(_lib.c_double_p)
-        return self._solve(self.lib.nlh_dq_model_cls_solve, x, opts, float(delta), float(stepscale), dp(lo), dp(hi))
+        return self._solve(self.lib.nlh_dq_model_cls_solve, x, opts, float(delta), float(stepscale),
+                           *_host_bounds(lower, upper, self.n, "bounds must have n entries"))
 
     def bfgs_solve(self, x, opts=None):
         """bfgs%solve on 0.5 ||F(x)||^2 of every problem: returns (x, F(x), objective values, behaviours, status codes)."""
-        import numpy as np
         x = np.ascontiguousarray(x, dtype=np.float64).copy()
         f = np.empty((self.nprob, self.m))
         fo = np.empty(self.nprob)
-        ib = (_lib.IterationBehavior * self.nprob)()
-        st = (C.c_int32 * self.nprob)()
+        ib, st = _ib_status(self.nprob)
         dp = lambda a: a.ctypes.data_as(_lib.c_double_p)
         rc = self.lib.nlh_dq_model_bfgs_solve(self._hptr, C.byref(opts if opts is not None else _lib.default_options()), self._md,
                                               dp(x), dp(f), dp(fo), ib, st)
         self._checked(rc, "nlh_dq_model_bfgs_solve")
-        return x, f, fo, [ib[p].as_dict() for p in range(self.nprob)], [int(st[p]) for p in range(self.nprob)]
+        return (x, f, fo) + _ib_lists(ib, st)
 
     def lm_covariance(self, x, scaled=True, tol=None):
         """Parameter covariance of every problem at x ([nprob, n] host array, not modified): returns numpy arrays (cov
         [nprob, n, n], sigma [nprob, n], rank int32 [nprob], chi2 [nprob]).  See nlh_dq_model_lm_covariance."""
-        import numpy as np
         x = np.ascontiguousarray(x, dtype=np.float64)
         if x.shape != (self.nprob, self.n):
             raise ValueError("x must be [nprob, n]")
