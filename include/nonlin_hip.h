@@ -495,6 +495,19 @@ int32_t nlh_gram_plan(int32_t m, int32_t n, int32_t *nsplit, int32_t *direct);
  * by R (upper triangle).  ipvt is 0-based.  info[k] != 0 => ill-conditioned/rank-deficient. */
 int nlh_chol_factor(nlh_handle *h, int32_t nprob, int32_t n, double *dG, const double *dg,
                     int32_t *dipvt, double *dacnorm, double *dqtf, int32_t *dinfo);
+/* The natural-order (unpivoted) blocked Cholesky of the NLH_FACTOR_AUTO policy on caller-supplied G [nprob][n][n] and
+ * g [nprob][n] (a test entry point: the solver's own launches).  form 0: one workgroup per problem, n <= 1109; form 1: the
+ * multi-CU launches, 192 <= n <= 1109; other sizes return NLH_ARRAY_SIZE_ERROR and launch nothing.  dR [nprob][n][n]
+ * receives G with its upper triangle overwritten by R (G = R^T R), dqtf = R^-T g, dacnorm = sqrt(diag G), dipvt the
+ * identity (0-based).  dinfo[k] = 0, or the 1-based index of the first pivot d with !(d > pivot_tol * acnorm^2) or
+ * !(d > 0); R and qtf of such a problem are unfinished. */
+int nlh_chol_natural(nlh_handle *h, int32_t nprob, int32_t n, const double *dG, const double *dg, double pivot_tol,
+                     int32_t form, double *dR, int32_t *dipvt, double *dacnorm, double *dqtf, int32_t *dinfo);
+/* Row signs of lmfactor for pivoted Cholesky factors (a test entry point: the solver's sign recovery before lmpar's
+ * iteration).  dJ [nprob][n][m] column-major (m >= n, not modified), dipvt 0-based as nlh_chol_factor leaves it, dR
+ * [nprob][n][n] and dqtf [nprob][n] the factors: on return R = S R~, qtf = S qtf~, dsign [nprob][n] = diag S (+-1). */
+int nlh_ne_signs(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, const double *dJ, const int32_t *dipvt,
+                 double *dR, double *dqtf, double *dsign);
 /* lmfactor itself (pivoted Householder QR, src/nonlin_least_squares.f90:569-667) plus
  * Q^T f (:241-253).  dJ is overwritten as in the reference (R strict upper, reflectors
  * below, diagonal restored to rdiag after Q^T f); dqtf [nprob][n]; dwa4 [nprob][m]. */

@@ -9,6 +9,8 @@
 //                   569-667) plus the Q^T f sweep (:241-253), one workgroup per problem.
 //   lm_head       : :229-238 (first-iteration scaling), :256-267 (scaled gradient norm),
 //                   :270-278 (gradient convergence, rescale).
+// The size edges of the three Cholesky forms (block, thread-count, tile-tail and LDS limits) are derived and tested in
+// tests/test_gpu_chol_natural.py, through the stage-level entries nlh_chol_natural and nlh_chol_factor.
 #pragma once
 #include "nlh_common.h"
 #include "nlh_lm_head.h"
@@ -178,7 +180,8 @@ template <int NB>
 __global__ void __launch_bounds__(1024)
 k_chol_nopiv(int n, const double *__restrict__ Gall, const double *__restrict__ gall,
              double *__restrict__ Rall, LmVecs v, const double *__restrict__ xall,
-             LmState *__restrict__ st, double factor, double gtol, double pivot_tol)
+             LmState *__restrict__ st, double factor, double gtol, double pivot_tol,
+             int32_t *__restrict__ info /* optional [nprob]: bad_sh, for the stage-level entry nlh_chol_natural */)
 {
     extern __shared__ double smem[];
     const int p = blockIdx.x;
@@ -353,6 +356,7 @@ k_chol_nopiv(int n, const double *__restrict__ Gall, const double *__restrict__ 
                                    tph[0] * 1e-2, tph[1] * 1e-2, tph[2] * 1e-2, tph[4] * 1e-2);
     if (tid == 0 && p == 0) printf("[chol_nopiv]   diag: load %.1f us, factor %.1f us\n", tph[5] * 1e-2, tph[6] * 1e-2);
 #endif
+    if (tid == 0 && info) info[p] = bad_sh;
     if (bad_sh) {
         if (tid == 0) s->stage = ST_NEED_PCHOL;                 // let the pivoted kernel decide (it may ask for QR)
         return;
@@ -683,7 +687,8 @@ k_chol_mc_step(int n, int jb, double *__restrict__ Rall, LmVecs v, double *__res
 #pragma unroll
             for (int i = 0; i < NB; ++i) R[(size_t)k * n + pj + i] = prev[(size_t)i * n + k];
         }
-    // (n > 528: more tiles than the prefetched two per wave)
+    // (more than 1 + 2 * 256 = 513 tiles -- 32 tile columns, 528 tiles, from n = 513 at the first step: more than the
+    // prefetched two per wave)
     for (int tix = la ? ntile : 1 + wg * nw + wid + TPW * NWG * nw; tix < ntile; tix += NWG * nw) {
         int tc = (int)((sqrtf(8.0f * (float)tix + 1.0f) - 1.0f) * 0.5f);
         while ((tc + 1) * (tc + 2) / 2 <= tix) ++tc;

@@ -1,7 +1,7 @@
 // nlh_lm.hip -- least_squares_solver: lss_solve (src/nonlin_least_squares.f90:118-391) as a batched, device-resident
 // lock-step state machine (nlh_dq_lm_solve_batch), with host callbacks (nlh_lm_solve, nlh_fd_jacobian = vfh_jac_fcn,
 // src/nonlin_multi_eqn_mult_var.f90:198-277), and its stages as entry points of their own (nlh_gram, nlh_chol_factor,
-// nlh_qr_factor, nlh_lmfactor_exact, nlh_lmpar).
+// nlh_chol_natural, nlh_ne_signs, nlh_qr_factor, nlh_lmfactor_exact, nlh_lmpar).
 #include "nlh_internal.h"
 #include <chrono>
 #include "nlh_kernels_gram.h"
@@ -14,6 +14,8 @@
 static __global__ void k_lmpar_standalone(int n, double *Rall, int ldr, const int32_t *ipvt_all, const double *diag_all,
                                    const double *qtf_all, const double *delta_all, const double *tailsq_all,
                                    double *par_all, double *x_all, double *sdiag_all, double *Wall, int ringcap);
+static __global__ void k_ne_signs_standalone(int m, int n, const double *Jall, const int32_t *ipvt_all, double *Rall, double *qtf_all,
+                                             double *Wall, double *sign_all);
 
 
 
@@ -30,6 +32,7 @@ void nlh_lm_init_device(int lds_max)
     hipFuncSetAttribute((const void *)k_lmpar<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     hipFuncSetAttribute((const void *)k_lmpar<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     hipFuncSetAttribute((const void *)k_lmpar_standalone, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    hipFuncSetAttribute((const void *)k_ne_signs_standalone, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
 }
 
 
@@ -303,6 +306,64 @@ int64_t nlh_qrx_second_matrix_bytes(nlh_handle *h)
     return (int64_t)b;
 }
 
+// ---------------------------------------------------------------------------
+// Host rules of the natural-order Cholesky (k_chol_nopiv / k_chol_mc_*), shared by the solver (lm_factor_and_step) and
+// the stage-level entry nlh_chol_natural, so that both launch the same instances.
+// ---------------------------------------------------------------------------
+constexpr int CHOL_NB = 16;
+// dynamic LDS of k_chol_nopiv: the panel, the diagonal block, the gradient, the block's qtf entries, reduction scratch
+static inline size_t chol_nopiv_lds(int n) { return sizeof(double) * ((size_t)CHOL_NB * n + CHOL_NB * CHOL_NB + n + CHOL_NB + 64); }
+// the natural-order forms serve n while that panel fits 150 KB: n <= 1109
+static inline bool chol_natural_serves(int n) { return chol_nopiv_lds(n) <= 150 * 1024; }
+// the multi-CU form: from n = 192
+static inline bool chol_mc_serves(int n) { return chol_natural_serves(n) && n >= 192; }
+// ... and only for a handful of problems (its launches cover every problem of the batch, active or not: only for batches
+// that are small themselves).  NLH_CHOL_MC = largest number of active problems (read per call: tests switch between the forms)
+static inline bool chol_mc_chosen(int n, int nactive, int nprob)
+{
+    const char *mc_e = getenv("NLH_CHOL_MC");
+    const int mc_max = mc_e ? atoi(mc_e) : 8;
+    return chol_mc_serves(n) && nactive <= mc_max && nprob <= 4 * std::max(mc_max, 1);
+}
+// more problems than CUs: 512-thread workgroups, two of which fit a CU (128 VGPRs each), so that the latency-bound
+// phases of one factorisation overlap the MFMA phase of the other
+static inline int chol_nopiv_threads(int n, int nactive)
+{
+    const int ft = factor_threads(n);
+    return (ft == 1024 && nactive > 256) ? 512 : ft;
+}
+static inline size_t chol_mc_step_lds(int n) { return sizeof(double) * ((size_t)CHOL_NB * n + 2 * (CHOL_NB * CHOL_NB + 2 * CHOL_NB)); }
+
+static void launch_chol_nopiv(nlh_handle *h, int nprob, int n, int nactive, const double *G, const double *g, double *R, const LmVecs &v,
+                              const double *x, LmState *st, double factor, double gtol, double pivot_tol, int32_t *info)
+{
+    hipLaunchKernelGGL(k_chol_nopiv<CHOL_NB>, dim3(nprob), dim3(chol_nopiv_threads(n, nactive)), chol_nopiv_lds(n), h->stream, n, G, g, R, v, x,
+                       st, factor, gtol, pivot_tol, info);
+}
+
+// a launch per panel step over many CUs instead of one workgroup per problem; same bits (nlh_kernels_factor.h).
+// bad_out (optional): where the flags of the bad pivots are (device, [nprob])
+static int launch_chol_mc(nlh_handle *h, int nprob, int n, const double *G, const double *g, double *R, const LmVecs &v,
+                          const double *x, LmState *st, double factor, double gtol, double pivot_tol, const int32_t **bad_out)
+{
+    constexpr int NB = CHOL_NB;
+    int rc2;
+    if ((rc2 = ensure(h, h->cholmc, sizeof(double) * (size_t)nprob * 2 * (NB * n + NB * NB + NB) + sizeof(int32_t) * (size_t)nprob + 64))) return rc2;
+    double *side = (double *)h->cholmc.p;
+    double *fact = side + (size_t)nprob * 2 * NB * n;
+    int32_t *bad = (int32_t *)(fact + (size_t)nprob * 2 * (NB * NB + NB));
+    hipLaunchKernelGGL(k_chol_mc_begin<NB>, dim3(64, nprob), dim3(256), 0, h->stream, n, G, g, R, v,
+                       fact, bad, (const LmState *)st, pivot_tol);
+    const size_t shm = chol_mc_step_lds(n);
+    for (int jb = 0; jb < n; jb += NB)
+        hipLaunchKernelGGL(k_chol_mc_step<NB>, dim3(CHOLMC_NWG + 2, nprob), dim3(512), shm, h->stream, n, jb, R, v, side, fact, bad,
+                           (const LmState *)st, pivot_tol);
+    hipLaunchKernelGGL(k_chol_mc_end<NB>, dim3(nprob), dim3(factor_threads(n)), sizeof(double) * (size_t)n, h->stream, n, R, v, (const double *)side,
+                       (const int32_t *)bad, x, st, factor, gtol);
+    if (bad_out) *bad_out = bad;
+    return 0;
+}
+
 // One pass over the factorisation + lmpar stages for every problem whose Jacobian is in
 // w.J (stage ST_HAVE_JAC or ST_NEED_QR) or whose factors are ready (inner-loop repeat).
 static int lm_factor_and_step(nlh_handle *h, const nlh_options *o, int nprob, int m, int n, LmWs &w,
@@ -358,36 +419,15 @@ static int lm_factor_and_step(nlh_handle *h, const nlh_options *o, int nprob, in
         !lds_fits((const void *)k_qr_factor, sh3)) return NLH_ARRAY_SIZE_ERROR;
     int rc = launch_gram(h, nprob, m, n, w.J, dfvec, w.G, w.g, w.st, ST_HAVE_JAC);
     if (rc) return rc;
-    constexpr int NB = 16;
     {   // fast path: blocked Cholesky in natural order, G -> R
         Timed t(h, NLH_K_CHOL);
-        size_t sh = sizeof(double) * ((size_t)NB * n + NB * NB + n + NB + 64);
-        // a handful of problems (BASELINE config 5's one 65536 x 512 problem): a launch per panel step over many CUs
-        // instead of one workgroup per problem; same bits (nlh_kernels_factor.h)
-        const char *mc_e = getenv("NLH_CHOL_MC");                   // (read per call: tests switch between the two forms)
-        const int mc_max = mc_e ? atoi(mc_e) : 8;
         const int na = nact < 0 ? nprob : nact;
-        // (its launches cover every problem of the batch, active or not: only for batches that are small themselves)
-        if (sh <= 150 * 1024 && n >= 192 && na <= mc_max && nprob <= 4 * std::max(mc_max, 1)) {
+        // a handful of problems (BASELINE config 5's one 65536 x 512 problem): the multi-CU form
+        if (chol_mc_chosen(n, na, nprob)) {
             int rc2;
-            if ((rc2 = ensure(h, h->cholmc, sizeof(double) * (size_t)nprob * 2 * (NB * n + NB * NB + NB) + sizeof(int32_t) * (size_t)nprob + 64))) return rc2;
-            double *side = (double *)h->cholmc.p;
-            double *fact = side + (size_t)nprob * 2 * NB * n;
-            int32_t *bad = (int32_t *)(fact + (size_t)nprob * 2 * (NB * NB + NB));
-            hipLaunchKernelGGL(k_chol_mc_begin<NB>, dim3(64, nprob), dim3(256), 0, h->stream, n, (const double *)w.G, (const double *)w.g, w.R, w.v,
-                               fact, bad, (const LmState *)w.st, o->ne_pivot_tol);
-            const size_t shm = sizeof(double) * ((size_t)NB * n + 2 * (NB * NB + 2 * NB));
-            for (int jb = 0; jb < n; jb += NB)
-                hipLaunchKernelGGL(k_chol_mc_step<NB>, dim3(CHOLMC_NWG + 2, nprob), dim3(512), shm, h->stream, n, jb, w.R, w.v, side, fact, bad,
-                                   (const LmState *)w.st, o->ne_pivot_tol);
-            hipLaunchKernelGGL(k_chol_mc_end<NB>, dim3(nprob), dim3(ft), sizeof(double) * (size_t)n, h->stream, n, w.R, w.v, (const double *)side, (const int32_t *)bad, dx,
-                               w.st, o->factor, o->gtol);
-        } else if (sh <= 150 * 1024) {
-            // more problems than CUs: 512-thread workgroups, two of which fit a CU (128 VGPRs each), so that the
-            // latency-bound phases of one factorisation overlap the MFMA phase of the other
-            const int ct = (ft == 1024 && (nact < 0 ? nprob : nact) > 256) ? 512 : ft;
-            hipLaunchKernelGGL(k_chol_nopiv<NB>, dim3(nprob), dim3(ct), sh, h->stream, n, w.G, w.g, w.R, w.v, dx, w.st,
-                               o->factor, o->gtol, o->ne_pivot_tol);
+            if ((rc2 = launch_chol_mc(h, nprob, n, w.G, w.g, w.R, w.v, dx, w.st, o->factor, o->gtol, o->ne_pivot_tol, nullptr))) return rc2;
+        } else if (chol_natural_serves(n)) {
+            launch_chol_nopiv(h, nprob, n, na, w.G, w.g, w.R, w.v, dx, w.st, o->factor, o->gtol, o->ne_pivot_tol, nullptr);
         } else {    // panel does not fit LDS: go straight to the pivoted (unblocked) factorisation
             size_t sh2 = sizeof(double) * (size_t)(3 * n + 64);
             hipLaunchKernelGGL(k_chol_factor, dim3(nprob), dim3(ft), sh2, h->stream, n, w.R, w.G, w.g, w.v, dx, w.st,
@@ -830,6 +870,76 @@ int nlh_chol_factor(nlh_handle *h, int32_t nprob, int32_t n, double *dG, const d
         hipLaunchKernelGGL(k_chol_factor, dim3(nprob), dim3(factor_threads(n)), sh, h->stream, n, dG,
                            (const double *)nullptr, dg, v, (const double *)nullptr, (LmState *)nullptr, dinfo,
                            o.factor, o.gtol, 0.0, 1, -1);
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// The natural-order blocked Cholesky of the normal-equations policy on caller-supplied G and g (parity tests): the
+// launches of lm_factor_and_step -- same instances, threads, LDS and side buffers -- on a workspace in which the
+// kernels' closing lm_head is harmless (states at ST_HAVE_JAC with fnorm = 0: the gradient test ends them at once;
+// iterate, diag and diag_prev are scratch).  form 0: k_chol_nopiv, form 1: k_chol_mc_*.
+int nlh_chol_natural(nlh_handle *h, int32_t nprob, int32_t n, const double *dG, const double *dg, double pivot_tol,
+                     int32_t form, double *dR, int32_t *dipvt, double *dacnorm, double *dqtf, int32_t *dinfo)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (nprob <= 0) return 0;
+    if (n < 1 || (form != 0 && form != 1)) return NLH_INVALID_INPUT_ERROR;
+    if (!(form == 1 ? chol_mc_serves(n) : chol_natural_serves(n))) return NLH_ARRAY_SIZE_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t stb = (sizeof(LmState) * (size_t)nprob + 63) / 64 * 64, vb = sizeof(double) * (size_t)nprob * n;
+    int rc = ensure(h, h->misc, stb + 3 * vb);
+    if (rc) return rc;
+    HIPCHK(h, hipMemsetAsync(h->misc.p, 0, stb + 3 * vb, h->stream));
+    LmState *st = (LmState *)h->misc.p;
+    double *x = (double *)((char *)h->misc.p + stb);
+    LmVecs v;
+    memset(&v, 0, sizeof v);
+    v.ipvt = dipvt; v.acnorm = dacnorm; v.qtf = dqtf; v.diag = x + (size_t)nprob * n; v.diag_prev = x + 2 * (size_t)nprob * n;
+    hipLaunchKernelGGL(k_stage_advance, dim3((nprob + 255) / 256), dim3(256), 0, h->stream, nprob, st, (int)ST_NEED_JAC, (int)ST_HAVE_JAC, 0);
+    {
+        Timed t(h, NLH_K_CHOL);
+        if (form == 1) {
+            const int32_t *bad = nullptr;
+            if ((rc = launch_chol_mc(h, nprob, n, dG, dg, dR, v, x, st, 100.0, 0.0, pivot_tol, &bad))) return rc;
+            HIPCHK(h, hipMemcpyAsync(dinfo, bad, sizeof(int32_t) * (size_t)nprob, hipMemcpyDeviceToDevice, h->stream));
+        } else {
+            launch_chol_nopiv(h, nprob, n, nprob, dG, dg, dR, v, x, st, 100.0, 0.0, pivot_tol, dinfo);
+        }
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// ne_recover_signs on caller-supplied J, pivot order and Cholesky factors (parity tests): R and qtf receive lmfactor's
+// row signs in place, dsign [nprob][n] the signs themselves.  Threads and LDS vectors as in k_lmpar<false>.
+static __global__ void __launch_bounds__(1024)
+k_ne_signs_standalone(int m, int n, const double *Jall, const int32_t *ipvt_all, double *Rall, double *qtf_all, double *Wall,
+                      double *sign_all)
+{
+    extern __shared__ double smem[];
+    const int p = blockIdx.x, tid = threadIdx.x, BS = blockDim.x;
+    double *xs = smem, *sdiag = smem + n, *wa1 = smem + 2 * n;
+    ne_recover_signs(m, n, Jall + (size_t)p * m * n, ipvt_all + (size_t)p * n, Rall + (size_t)p * n * n, qtf_all + (size_t)p * n,
+                     Wall + (size_t)p * n * n, xs, sdiag, wa1);
+    for (int j = tid; j < n; j += BS) sign_all[(size_t)p * n + j] = xs[j];
+}
+
+int nlh_ne_signs(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, const double *dJ, const int32_t *dipvt, double *dR,
+                 double *dqtf, double *dsign)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (nprob <= 0) return 0;
+    if (n < 1 || m < n) return NLH_INVALID_INPUT_ERROR;
+    const size_t sh = sizeof(double) * (size_t)(6 * n + 72);
+    if (!lds_fits((const void *)k_ne_signs_standalone, sh)) return NLH_ARRAY_SIZE_ERROR;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = ensure(h, h->misc, sizeof(double) * (size_t)nprob * n * n);
+    if (rc) return rc;
+    {
+        Timed t(h, NLH_K_LMPAR);
+        hipLaunchKernelGGL(k_ne_signs_standalone, dim3(nprob), dim3(lmpar_threads(n)), sh, h->stream, m, n, dJ, dipvt, dR, dqtf,
+                           (double *)h->misc.p, dsign);
     }
     HIPCHK(h, hipGetLastError());
     return 0;

@@ -1271,6 +1271,34 @@ class DeviceSolver:
                                               acnorm.data_ptr(), qtf.data_ptr(), info.data_ptr()), "nlh_chol_factor")
         return ipvt, acnorm, qtf, info
 
+    def chol_natural(self, G, g, pivot_tol=0.0, form=0):
+        """The natural-order blocked Cholesky of the normal-equations policy on G [nprob, n, n], g [nprob, n] (neither is
+        modified).  form 0: one workgroup per problem, form 1: the multi-CU launches.  Returns (R, ipvt0, acnorm, qtf,
+        info): R[p, c, r], r <= c, is R(r, c), the strict lower triangle is G's; info[p] is 0 or the 1-based index of
+        the first bad pivot."""
+        nprob, n, _ = G.shape
+        _chk(G, (nprob, n, n), "G"); _chk(g, (nprob, n), "g")
+        dev = G.device
+        R = torch.empty_like(G)
+        ipvt = torch.empty((nprob, n), dtype=torch.int32, device=dev)
+        acnorm = torch.empty((nprob, n), dtype=torch.float64, device=dev)
+        qtf = torch.empty((nprob, n), dtype=torch.float64, device=dev)
+        info = torch.empty((nprob,), dtype=torch.int32, device=dev)
+        self.h.check(self.lib.nlh_chol_natural(self.h.ptr, nprob, n, G.data_ptr(), g.data_ptr(), float(pivot_tol), int(form),
+                                               R.data_ptr(), ipvt.data_ptr(), acnorm.data_ptr(), qtf.data_ptr(),
+                                               info.data_ptr()), "nlh_chol_natural")
+        return R, ipvt, acnorm, qtf, info
+
+    def ne_signs(self, J, ipvt, R, qtf):
+        """lmfactor's row signs for the pivoted Cholesky factors of J^T J (chol_factor's ipvt0, R in G's upper triangle and
+        qtf): R and qtf are signed in place.  J [nprob, n, m], m >= n.  Returns the signs [nprob, n] (+-1)."""
+        nprob, n, m = J.shape
+        _chk(J, (nprob, n, m), "J"); _chk(R, (nprob, n, n), "R"); _chk(qtf, (nprob, n), "qtf")
+        sign = torch.empty((nprob, n), dtype=torch.float64, device=J.device)
+        self.h.check(self.lib.nlh_ne_signs(self.h.ptr, nprob, m, n, J.data_ptr(), ipvt.data_ptr(), R.data_ptr(),
+                                           qtf.data_ptr(), sign.data_ptr()), "nlh_ne_signs")
+        return sign
+
     def qr_factor(self, J, f):
         """lmfactor + Q^T f.  J [nprob, n, m] is overwritten.  Returns (ipvt0, rdiag, acnorm, qtf, wa4)."""
         nprob, n, m = J.shape

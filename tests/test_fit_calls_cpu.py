@@ -64,7 +64,9 @@ def test_fit_calls_match_the_parent(recorded, group):
 
 
 # entry points added since the golden was recorded, with their signatures: nothing else may differ from it
-ADDED = {"nlh_expr_plan": "i i i i i i I I I LP_c_long I LP_c_long"}
+ADDED = {"nlh_expr_plan": "i i i i i i I I I LP_c_long I LP_c_long",
+         "nlh_chol_natural": "i p i i p p d i p p p p p",
+         "nlh_ne_signs": "i p i i i p p p p p"}
 
 
 def test_signature_table_matches_the_parent():

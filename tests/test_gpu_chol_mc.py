@@ -13,7 +13,8 @@ import gram_cases as GC
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("nb,m,n", [(1, 3000, 512), (3, 2048, 256), (2, 1500, 200), (1, 4100, 500), (1, 2000, 700)])
+@pytest.mark.parametrize("nb,m,n", [(1, 3000, 512), (3, 2048, 256), (2, 1500, 200), (1, 4100, 500), (1, 2000, 700),
+                                    (1, 1500, 193), (1, 1400, 1109)])   # an odd n (scalar loads), the last n the forms serve
 def test_multi_cu_cholesky_same_bits_as_single_workgroup(ds, nb, m, n):
     A, b, xt, x0 = ds.generate(nb, m, n, seed0=4242)
     res = {}
