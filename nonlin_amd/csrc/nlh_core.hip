@@ -1,6 +1,6 @@
 // nlh_core.hip -- the handle, options, kernel timing, the synthetic generator, the launches of the residual
 // family every solver shares (vecfcn of the device model, the n perturbed evaluations of vfh_jac_fcn,
-// src/nonlin_multi_eqn_mult_var.f90:198-277), worker handles for host-loop batches, print_status
+// src/nonlin_multi_eqn_mult_var.f90:198-277), worker handles for sub-batches, print_status
 // (src/nonlin_helper.f90:17-33).  There is no CPU fallback: without a device every compute entry point fails.
 #include "nlh_internal.h"
 #include "nlh_kernels_model.h"
@@ -158,6 +158,7 @@ void nlh_destroy(nlh_handle *h)
     for (auto *b : h->bufs) if (b->p) hipFree(b->p);
     if (h->pinned) hipHostFree(h->pinned);
     if (h->staging) hipHostFree(h->staging);
+    if (h->cbstage) hipHostFree(h->cbstage);
     if (h->lu_side) { hipStreamSynchronize(h->lu_side); hipStreamDestroy(h->lu_side); }
     if (h->lu_panel_done) hipEventDestroy(h->lu_panel_done);
     for (auto e : h->lu_bulk_done) if (e) hipEventDestroy(e);
@@ -380,9 +381,6 @@ int staged_call(nlh_handle *h, std::initializer_list<HostArray> arrays, const st
 }
 
 
-// Host-loop solvers (Newton, quasi-Newton, constrained least squares, bfgs) over a batch of independent problems:
-// the problems are dealt to a few host threads, each with a private handle (own HIP stream and workspace), so the
-// latency-bound kernels of different problems overlap on the device.  NLH_WORKERS sets the thread count (default 8).
 // Private handles (own non-blocking stream + workspace) for work the caller's handle deals out to host threads.
 int ensure_workers(nlh_handle *h, int T)
 {
@@ -392,42 +390,6 @@ int ensure_workers(nlh_handle *h, int T)
         if (hipStreamCreateWithFlags(&wk->stream, hipStreamNonBlocking) != hipSuccess) { delete wk; h->err = "hipStreamCreate"; return NLH_ERR_HIP; }
         wk->own_stream = true;
         h->workers.push_back(wk);
-    }
-    return 0;
-}
-
-int run_problems(nlh_handle *h, int nprob, const std::function<int(nlh_handle *, int)> &solve_one)
-{
-    int T = 8;
-    if (const char *e = getenv("NLH_WORKERS")) T = atoi(e);
-    T = std::max(1, std::min(T, nprob));
-    if (T == 1) {
-        for (int p = 0; p < nprob; ++p) {
-            const int rc = solve_one(h, p);
-            if (rc != 0) return rc;
-        }
-        return 0;
-    }
-    { const int rcw = ensure_workers(h, T); if (rcw) return rcw; }
-    HIPCHK(h, hipStreamSynchronize(h->stream));                 // inputs written on the caller's stream are complete
-    std::atomic<int> next(0), err(0);
-    std::vector<std::thread> pool;
-    for (int t = 0; t < T; ++t)
-        pool.emplace_back([&, t]() {
-            nlh_handle *wk = h->workers[t];
-            if (hipSetDevice(wk->device) != hipSuccess) { err = NLH_ERR_HIP; return; }
-            for (;;) {
-                const int p = next.fetch_add(1);
-                if (p >= nprob || err.load() != 0) break;
-                const int rc = solve_one(wk, p);
-                if (rc != 0) { err = rc; break; }
-            }
-            hipStreamSynchronize(wk->stream);
-        });
-    for (auto &th : pool) th.join();
-    if (err.load() != 0) {
-        for (auto *wk : h->workers) if (!wk->err.empty()) { h->err = wk->err; break; }
-        return err.load();
     }
     return 0;
 }

@@ -187,9 +187,18 @@ static int dv_select(nlh_handle *h, int nprob, const LmState *st, int want, size
     if ((rc = ensure(h, h->dvIdx, sizeof(int32_t) * ((size_t)nprob + 16 + extra_ints)))) return rc;
     if ((rc = ensure_pinned(h, 64))) return rc;
     int32_t *dcnt = (int32_t *)h->dvIdx.p;
+    int32_t *hcnt = (int32_t *)h->pinned + DV_PINNED_SLOT;
+    if (nprob == 1 && st) {
+        // one problem (a single solve behind host callbacks, a batch of one): its stage is the answer and nobody reads a
+        // list -- every caller takes the problems' own order when all of them are due
+        if (known >= 0) { *cnt = known; return 0; }
+        HIPCHK(h, hipMemcpyAsync(hcnt, &st[0].stage, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        *cnt = *hcnt == want ? 1 : 0;
+        return 0;
+    }
     hipLaunchKernelGGL(k_dv_compact, dim3(1), dim3(1024), 0, h->stream, nprob, st, want, dv_list(h), dcnt);
     if (known >= 0) { *cnt = known; return 0; }
-    int32_t *hcnt = (int32_t *)h->pinned + DV_PINNED_SLOT;
     HIPCHK(h, hipMemcpyAsync(hcnt, dcnt, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     *cnt = *hcnt;
@@ -198,6 +207,7 @@ static int dv_select(nlh_handle *h, int nprob, const LmState *st, int want, size
 
 int launcher_failed(nlh_handle *h, int rc, const char *what, const char *which)
 {
+    if (h->cb_failed) { h->cb_failed = false; return rc; }      // a host-callback launcher's own failure: its text, its code
     h->err = std::string(what) + ": the user's " + which + " returned " + std::to_string(rc);
     return NLH_ERR_HIP;
 }
@@ -212,7 +222,16 @@ int residual_eval(nlh_handle *h, const ResidualSource &rs, int nprob, int m, int
     int rc;
     int cnt = nprob;
     const bool all = st == nullptr;
-    if (!all) {
+    // One problem behind host callbacks: its stage comes down with the point in the launcher's own download, and the
+    // launcher calls the user's function only if the problem is due -- no read-back of its own for the stage.
+    HostCallbacks *hc = (!all && nprob == 1 && rs.fcn == host_callback_fcn) ? (HostCallbacks *)rs.ctx : nullptr;
+    if (hc) {
+        if ((rc = ensure(h, h->dvIdx, sizeof(int32_t) * 32))) return rc;
+        if ((rc = ensure_pinned(h, 64))) return rc;
+        int32_t *hstage = (int32_t *)h->pinned + DV_PINNED_SLOT;
+        HIPCHK(h, hipMemcpyAsync(hstage, &st[0].stage, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        hc->stage = hstage; hc->want = want;
+    } else if (!all) {
         if ((rc = dv_select(h, nprob, st, want, (size_t)nprob, &cnt))) return rc;
         if (cnt == 0) return 0;
     } else if ((rc = ensure(h, h->dvIdx, sizeof(int32_t) * ((size_t)2 * nprob + 16)))) return rc;
@@ -225,8 +244,9 @@ int residual_eval(nlh_handle *h, const ResidualSource &rs, int nprob, int m, int
         if ((rc = ensure(h, h->dvF, sizeof(double) * (size_t)cnt * m))) return rc;
         X = (const double *)h->dvX.p; F = (double *)h->dvF.p;
     }
-    hipLaunchKernelGGL(k_dv_gather_x, dim3(cnt), dim3(64), 0, h->stream, cnt, n, direct ? (const int32_t *)nullptr : (const int32_t *)list,
-                       (int)rs.pbase, x, direct ? (double *)nullptr : (double *)h->dvX.p, dprob);
+    if (!hc)                                                    // (the host-callback launchers read no problem index)
+        hipLaunchKernelGGL(k_dv_gather_x, dim3(cnt), dim3(64), 0, h->stream, cnt, n, direct ? (const int32_t *)nullptr : (const int32_t *)list,
+                           (int)rs.pbase, x, direct ? (double *)nullptr : (double *)h->dvX.p, dprob);
     {
         Timed t(h, NLH_K_DQ_RESIDUAL);
         const int urc = rs.fcn(rs.ctx, (void *)h->stream, cnt, dprob, n, X, m, F);
@@ -336,6 +356,62 @@ int residual_jacobian(nlh_handle *h, const ResidualSource &rs, int nprob, int m,
         }
     }
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// a user's host callbacks as launchers (nlh_internal.h: HostCallbacks)
+// ---------------------------------------------------------------------------
+// The points of the call in pinned memory [npoints][n], `out` doubles of results per point behind them.  A buffer of its
+// own: h->pinned holds the drivers' round read-backs and dv_select's count while a launcher runs.  The upload of the results
+// is left in flight: whatever reads them is behind it on the stream, and so is the next call's download into this buffer,
+// which the host waits for before it writes here again.
+static int host_callback_run(HostCallbacks *c, hipStream_t s, int32_t npoints, int32_t n, const double *dX, size_t out, double *dOut,
+                             const std::function<void(const double *x, double *res)> &one)
+{
+    nlh_handle *h = c->h;
+    const int32_t *stage = c->stage;
+    c->stage = nullptr;
+    auto fail = [&](int code, const char *text) { h->err = text; h->cb_failed = true; return code; };
+    // the user's function runs on the thread that entered the library: one problem is never dealt to a worker
+    if (std::this_thread::get_id() != c->caller) return fail(NLH_ERR_HIP, "host callback: a single solve left its caller's thread");
+    const size_t nx = (size_t)npoints * n, no = (size_t)npoints * out, bytes = sizeof(double) * (nx + no);
+    if (bytes > h->cbstage_bytes) {
+        if (h->cbstage && hipStreamSynchronize(s) != hipSuccess) return fail(NLH_ERR_HIP, "host callback: hipStreamSynchronize");   // (an upload may still read it)
+        if (h->cbstage) hipHostFree(h->cbstage);
+        h->cbstage = nullptr; h->cbstage_bytes = 0;
+        if (hipHostMalloc(&h->cbstage, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(NLH_OUT_OF_MEMORY_ERROR, "hipHostMalloc (host callback staging)"); }
+        h->cbstage_bytes = bytes;
+    }
+    double *hx = (double *)h->cbstage, *ho = hx + nx;
+    if (hipMemcpyAsync(hx, dX, sizeof(double) * nx, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(NLH_ERR_HIP, "host callback: download of the points");
+    if (stage && *stage != c->want) return 0;                   // the one problem is not at this stage: nothing to evaluate
+    for (int32_t k = 0; k < npoints; ++k) one(hx + (size_t)k * n, ho + (size_t)k * out);
+    if (hipMemcpyAsync(dOut, ho, sizeof(double) * no, hipMemcpyHostToDevice, s) != hipSuccess) return fail(NLH_ERR_HIP, "host callback: upload of the results");
+    return 0;
+}
+
+int host_callback_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *, int32_t n, const double *dX, int32_t m, double *dF)
+{
+    HostCallbacks *c = (HostCallbacks *)ctx;
+    return host_callback_run(c, (hipStream_t)hip_stream, npoints, n, dX, (size_t)m, dF, [&](const double *x, double *f) {
+        if (c->sfcn) *f = c->sfcn(c->ctx, n, x);
+        else c->fcn(c->ctx, n, x, m, f);
+    });
+}
+
+int host_callback_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *, int32_t n, const double *dX, int32_t m, double *dJ)
+{
+    HostCallbacks *c = (HostCallbacks *)ctx;
+    return host_callback_run(c, (hipStream_t)hip_stream, npoints, n, dX, (size_t)m * n, dJ, [&](const double *x, double *j) {
+        if (c->grad) c->grad(c->ctx, n, x, j);
+        else c->jac(c->ctx, n, x, m, j);
+    });
+}
+
+ResidualSource HostCallbacks::source()
+{
+    return ResidualSource::launchers(host_callback_fcn, (jac || grad) ? host_callback_jac : (nlh_device_jacfcn) nullptr, this);
 }
 
 // ---------------------------------------------------------------------------

@@ -93,8 +93,11 @@ struct nlh_handle {
     DevBuf cholmc;                     // side buffer of the multi-CU Cholesky (solved panels, bad-pivot flags)
     void *staging = nullptr;           // pinned staging of a device-set share's rows of the caller's host arrays
     size_t staging_bytes = 0;
+    void *cbstage = nullptr;           // pinned staging of the host-callback launchers (HostCallbacks): a call's points and results
+    size_t cbstage_bytes = 0;
+    bool cb_failed = false;            // a host-callback launcher failed on its own account: err holds the text, its code is the library's
     bool qrx_open_on = false; hipEvent_t qrx_a{}, qrx_b{}; int qrx_kid = 0;   // open bracket of a nlh_qrx.hip launch
-    std::vector<nlh_handle *> workers;   // private handles (own stream + workspace) for concurrent host-loop solves
+    std::vector<nlh_handle *> workers;   // private handles (own stream + workspace) for the sub-batches of a dealt LM batch
     hipStream_t lu_side = nullptr;       // the blocked LU's look-ahead: the bulk of a step's update runs here, under the next panel
     hipEvent_t lu_panel_done = nullptr, lu_bulk_done[2] = {nullptr, nullptr};
 };
@@ -136,7 +139,6 @@ struct Timed {
     }
 };
 int ensure_workers(nlh_handle *h, int T);
-int run_problems(nlh_handle *h, int nprob, const std::function<int(nlh_handle *, int)> &solve_one);
 
 // per-unit kernel attributes (dynamic LDS limits), called by nlh_create on the handle's device
 void nlh_lm_init_device(int lds_max);
@@ -258,6 +260,40 @@ int residual_jacobian(nlh_handle *h, const ResidualSource &rs, int nprob, int m,
 
 void launch_sumsq_part(nlh_handle *h, int nprob, int m, int n, const double *f, double *part);   // nlh_lm.hip
 
+// A user's HOST callbacks as launchers (nlh_devfcn.hip): what lets a lock-step driver with nprob = 1 stand behind the
+// single solves of the drop-in path (nlh_lm_solve, nlh_quasi_newton_solve, nlh_cls_solve, nlh_bfgs_solve,
+// nlh_fd_jacobian).  A call copies the points to the host, synchronises the stream, calls the user's function once per point
+// in ascending point order on the calling thread -- which must be the thread that made the context: a driver that dealt
+// the problem to a worker is refused -- and uploads the results (left in flight: their readers are behind them on the
+// stream).  A forward-difference Jacobian is n
+// such points: the reference's n calls, in its order (src/nonlin_multi_eqn_mult_var.f90:267-273).  Either the vector pair
+// (fcn, jac) or the scalar pair (sfcn, grad: fcnnvar / gradientfcn, the m = 1 case with a 1 x n Jacobian) is set.
+struct HostCallbacks {
+    nlh_handle *h;
+    nlh_vecfcn fcn;
+    nlh_jacfcn jac;
+    nlh_fcnnvar sfcn;
+    nlh_gradfcn grad;
+    void *ctx;
+    std::thread::id caller;
+    // armed by residual_eval for one call: the one problem's stage comes down with the point, and the user's function is
+    // called only if it is `want` (no separate read-back of the stage before the call)
+    const int32_t *stage = nullptr;
+    int32_t want = 0;
+    static HostCallbacks vector(nlh_handle *h, nlh_vecfcn fcn, nlh_jacfcn jac, void *ctx)
+    {
+        return {h, fcn, jac, nullptr, nullptr, ctx, std::this_thread::get_id(), nullptr, 0};
+    }
+    static HostCallbacks scalar(nlh_handle *h, nlh_fcnnvar sfcn, nlh_gradfcn grad, void *ctx)
+    {
+        return {h, nullptr, nullptr, sfcn, grad, ctx, std::this_thread::get_id(), nullptr, 0};
+    }
+    // the residual source a driver takes: the Jacobian launcher only when the user gave a Jacobian / gradient
+    ResidualSource source();
+};
+int host_callback_fcn(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dF);
+int host_callback_jac(void *ctx, void *hip_stream, int32_t npoints, const int32_t *dprob, int32_t n, const double *dX, int32_t m, double *dJ);
+
 // nlh_square.hip
 void launch_lu_factor(nlh_handle *h, int nprob, int n, double *dA, int32_t *dipvt, int32_t *dinfo, const LmState *st = nullptr,
                       int want = -1);
@@ -267,7 +303,7 @@ void launch_house_steps(nlh_handle *h, int nprob, int rows, int ncA, int ncE, do
 
 static const int RB = 256;   // rows per block of the residual kernels
 
-// host-side scalar helpers of the solvers' O(n) logic (the reference's operation order)
+// host-side scalar helpers of nlh_newton_solve's O(n) logic (the reference's operation order)
 
 static inline double h_dot(int n, const double *a, const double *b)
 {

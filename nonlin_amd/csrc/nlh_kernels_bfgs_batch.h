@@ -7,7 +7,7 @@
 // product is ONE ordered chain of adds (nt_ordered_sum), NORM2 is the flang runtime's algorithm, maxima are exact in any
 // order.  The dense kernels (R^T R, B dx, the Cholesky update / downdate / factorisation, the two triangular solves) are
 // the ones of nlh_kernels_bfgs.h with a problem index and a stage gate.  Given those, every decision and every iterate
-// is bit-identical to the host loop (bfgs_core) and to the CPU path.
+// is bit-identical to the CPU path.
 #pragma once
 #include <cfloat>
 #include "nlh_kernels_newton.h"

@@ -5,8 +5,7 @@
 // the trust-region update and the projected backtracking (:1055-1123), the convergence tests (:1125-1149) -- runs here,
 // one workgroup per problem, in the reference's operation order: every dot product is ONE ordered chain of adds
 // (nt_ordered_sum), NORM2 is the flang runtime's algorithm, minima / maxima are exact in any order.  Given bit-identical
-// Jacobian, QR and residual kernels, every decision and every iterate is bit-identical to the host loop (cls_core) and to
-// the CPU path.
+// Jacobian, QR and residual kernels, every decision and every iterate is bit-identical to the CPU path.
 #pragma once
 #include <cfloat>
 #include "nlh_kernels_newton.h"

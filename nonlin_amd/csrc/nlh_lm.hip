@@ -713,7 +713,7 @@ int nlh_lm_solve_batch_device_h(nlh_handle *h, const nlh_options *o, int32_t npr
 }
 
 // ===========================================================================
-// Host-callback LM: the same kernels with nprob = 1; residuals come from fcn.
+// Host-callback LM: the lock-step driver on one problem, the user's vecfcn / jacobianfcn behind the host-callback launchers.
 // ===========================================================================
 int nlh_lm_solve(nlh_handle *h, const nlh_options *o, int32_t m, int32_t n, nlh_vecfcn fcn,
                  nlh_jacfcn jacfcn, void *ctx, double *x, double *fvec, nlh_iteration_behavior *ib)
@@ -721,90 +721,19 @@ int nlh_lm_solve(nlh_handle *h, const nlh_options *o, int32_t m, int32_t n, nlh_
     if (!h) return NLH_ERR_BAD_HANDLE;
     if (ib) memset(ib, 0, sizeof *ib);                          // :177-185
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;              // :188
-    int rc = check_opts_lm(o, m, n);
+    const int rc = check_opts_lm(o, m, n);
     if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->device));
-    LmWs w;
-    if ((rc = lm_workspace(h, 1, m, n, w, true))) return rc;
-    if ((rc = ensure(h, h->xdev, sizeof(double) * n))) return rc;
-    if ((rc = ensure(h, h->fdev, sizeof(double) * m))) return rc;
-    const size_t pin_bytes = 256 + sizeof(double) * ((size_t)m * n + 2 * (size_t)m + 2 * (size_t)n);
-    if ((rc = ensure_pinned(h, pin_bytes))) return rc;
-    LmState *hs = (LmState *)h->pinned;
-    double *hP = (double *)((char *)h->pinned + 256);   // m*n panel / Jacobian staging
-    double *hf = hP + (size_t)m * n;                     // m
-    double *hx = hf + m;                                 // n
-    double *dx = (double *)h->xdev.p, *dfvec = (double *)h->fdev.p;
-    hipStream_t s = h->stream;
-
-    fcn(ctx, n, x, m, fvec);                                    // :211
-    HIPCHK(h, hipMemcpyAsync(dx, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(dfvec, fvec, sizeof(double) * m, hipMemcpyHostToDevice, s));
-    launch_sumsq_part(h, 1, m, n, dfvec, w.part);
-    if (o->factor_policy == NLH_FACTOR_EXACT)
-        hipLaunchKernelGGL(k_lm_init_exact, dim3(1), dim3(256), 0, s, m, dfvec, w.st, (int)ST_NEED_JAC);
-    else
-        hipLaunchKernelGGL(k_lm_init, dim3(1), dim3(64), 0, s, 1, w.nblk, w.part, w.st, (int)ST_NEED_JAC);
-    HIPCHK(h, hipStreamSynchronize(s));
-
-    const int max_rounds = o->max_evals + 8;
-    int last_printed_iter = -1;
-    for (int round = 0; round < max_rounds; ++round) {
-        HIPCHK(h, hipMemcpyAsync(hs, w.st, sizeof(LmState), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (hs->stage == ST_DONE) break;
-        if (hs->stage == ST_NEED_JAC) {
-            if (round > 0 && o->print_status && hs->iter != last_printed_iter) {   // :372-374
-                print_status(hs->iter, hs->neval, hs->njac, hs->xnorm, hs->fnorm);
-                last_printed_iter = hs->iter;
-            }
-            // vfh_jac_fcn (:221).  x and fvec on the host are kept equal to the device copies.
-            if (jacfcn) {
-                jacfcn(ctx, n, x, m, hP);
-                HIPCHK(h, hipMemcpyAsync(w.J, hP, sizeof(double) * (size_t)m * n, hipMemcpyHostToDevice, s));
-            } else {
-                for (int j = 0; j < n; ++j) {                   // src/nonlin_multi_eqn_mult_var.f90:267-273
-                    const double temp = x[j];
-                    double hh = NLH_SQRT_EPS * fabs(temp);
-                    if (hh == 0.0) hh = NLH_SQRT_EPS;
-                    x[j] = temp + hh;
-                    fcn(ctx, n, x, m, hP + (size_t)j * m);
-                    x[j] = temp;
-                }
-                HIPCHK(h, hipMemcpyAsync(w.P, hP, sizeof(double) * (size_t)m * n, hipMemcpyHostToDevice, s));
-                launch_fd(h, 1, m, n, w.P, dfvec, dx, w.J, nullptr, -1);      // :274
-            }
-            hipLaunchKernelGGL(k_stage_advance, dim3(1), dim3(64), 0, s, 1, w.st, (int)ST_NEED_JAC,
-                               o->factor_policy != NLH_FACTOR_AUTO ? (int)ST_NEED_QR : (int)ST_HAVE_JAC, 1);
-        }
-        if ((rc = lm_factor_and_step(h, o, 1, m, n, w, dx, dfvec))) return rc;
-        HIPCHK(h, hipMemcpyAsync(hs, w.st, sizeof(LmState), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(hx, w.v.wa2, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (hs->stage == ST_DONE) break;                       // gradient convergence (:270-273)
-        if (hs->stage != ST_TRIAL_READY) { h->err = "lm: unexpected stage"; return NLH_ERR_HIP; }
-        fcn(ctx, n, hx, m, hf);                                 // :297
-        HIPCHK(h, hipMemcpyAsync(w.wa4, hf, sizeof(double) * m, hipMemcpyHostToDevice, s));
-        launch_sumsq_part(h, 1, m, n, w.wa4, w.part);
-        hipLaunchKernelGGL(k_stage_advance, dim3(1), dim3(64), 0, s, 1, w.st, (int)ST_TRIAL_READY, (int)ST_TRIAL_DONE, 0);
-        const int iter_before = hs->iter;
-        lm_update(h, o, 1, m, n, w, dx, dfvec);
-        HIPCHK(h, hipMemcpyAsync(hs, w.st, sizeof(LmState), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (hs->iter != iter_before) {                          // accepted: mirror x, fvec on the host (:341-345)
-            memcpy(x, hx, sizeof(double) * n);
-            memcpy(fvec, hf, sizeof(double) * m);
-        }
-    }
-    HIPCHK(h, hipMemcpyAsync(hs, w.st, sizeof(LmState), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    HIPCHK(h, hipGetLastError());
-    if (ib) fill_ib(*hs, ib);
-    return (hs->flag != 0 || hs->stage != ST_DONE) ? NLH_CONVERGENCE_ERROR : 0;
+    HostCallbacks cb = HostCallbacks::vector(h, fcn, jacfcn, ctx);
+    int32_t status = 0;
+    const int rcs = staged_call(h, {{x, sizeof(double) * (size_t)n, true, true, &h->xdev}, {fvec, sizeof(double) * (size_t)m, false, true, &h->fdev}},
+                                [&](void *const *d) {   // (one lock-step batch of one: no sub-batch, no worker thread)
+                                    return lm_solve_range(h, o, 1, m, n, cb.source(), (double *)d[0], (double *)d[1], ib, &status);
+                                });
+    return rcs ? rcs : status;
 }
 
 // ===========================================================================
-// vecfcn_helper%jacobian for host callbacks.
+// vecfcn_helper%jacobian for host callbacks: nlh_fd_jacobian_device on the host-callback launchers (x is never written).
 // ===========================================================================
 int nlh_fd_jacobian(nlh_handle *h, int32_t m, int32_t n, nlh_vecfcn fcn, nlh_jacfcn jacfcn, void *ctx,
                     double *x, const double *fv, double *jac)
@@ -812,35 +741,12 @@ int nlh_fd_jacobian(nlh_handle *h, int32_t m, int32_t n, nlh_vecfcn fcn, nlh_jac
     if (!h) return NLH_ERR_BAD_HANDLE;
     if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;              // :240
     if (jacfcn) { jacfcn(ctx, n, x, m, jac); return 0; }       // :241-243
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc;
+    HostCallbacks cb = HostCallbacks::vector(h, fcn, nullptr, ctx);
     const size_t mn = (size_t)m * n;
-    if ((rc = ensure(h, h->J, sizeof(double) * mn))) return rc;
-    if ((rc = ensure(h, h->P, sizeof(double) * mn))) return rc;
-    if ((rc = ensure(h, h->xdev, sizeof(double) * n))) return rc;
-    if ((rc = ensure(h, h->fdev, sizeof(double) * m))) return rc;
-    if ((rc = ensure_pinned(h, sizeof(double) * (mn + m)))) return rc;
-    double *hP = (double *)h->pinned, *hf0 = hP + mn;
-    if (fv) memcpy(hf0, fv, sizeof(double) * m);
-    else fcn(ctx, n, x, m, hf0);                                // :257-259
-    for (int j = 0; j < n; ++j) {                               // :267-273
-        const double temp = x[j];
-        double hh = NLH_SQRT_EPS * fabs(temp);
-        if (hh == 0.0) hh = NLH_SQRT_EPS;
-        x[j] = temp + hh;
-        fcn(ctx, n, x, m, hP + (size_t)j * m);
-        x[j] = temp;
-    }
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(h->P.p, hP, sizeof(double) * mn, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->fdev.p, hf0, sizeof(double) * m, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->xdev.p, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
-    launch_fd(h, 1, m, n, (const double *)h->P.p, (const double *)h->fdev.p, (const double *)h->xdev.p,
-              (double *)h->J.p, nullptr, -1);
-    HIPCHK(h, hipMemcpyAsync(jac, h->J.p, sizeof(double) * mn, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    HIPCHK(h, hipGetLastError());
-    return 0;
+    return staged_call(h, {{x, sizeof(double) * (size_t)n, true, false, &h->xdev}, {(void *)fv, fv ? sizeof(double) * (size_t)m : 0, fv != nullptr, false, &h->wa4},
+                           {jac, sizeof(double) * mn, false, true, &h->J}}, [&](void *const *d) {
+        return nlh_fd_jacobian_device(h, 1, m, n, host_callback_fcn, nullptr, &cb, (const double *)d[0], fv ? (const double *)d[1] : nullptr, (double *)d[2]);
+    });
 }
 
 int nlh_gram(nlh_handle *h, int32_t nprob, int32_t m, int32_t n, const double *dJ, const double *df, double *dG,

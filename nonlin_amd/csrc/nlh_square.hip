@@ -1,6 +1,7 @@
 // nlh_square.hip -- newton_solver (ns_solve, src/nonlin_solve.f90:452-638) and quasi_newton_solver (qns_solve, :156-427)
-// with ls_search_mimo (src/nonlin_linesearch.f90:152-326): host loops around device kernels for one problem with host
-// callbacks, lock-step device state machines for batches; lu_factor / solve_lu (call sites :570, :577), the Householder
+// with ls_search_mimo (src/nonlin_linesearch.f90:152-326): lock-step device state machines, for batches and -- quasi-Newton,
+// one problem, the callbacks behind the host-callback launchers -- for a single solve; Newton's single solve with host
+// callbacks as a host loop around device kernels; lu_factor / solve_lu (call sites :570, :577), the Householder
 // steps every QR of the library runs (also behind constrained least squares and polynomial fits), and their entry points.
 #include "nlh_internal.h"
 #include "nlh_kernels_model.h"
@@ -187,10 +188,15 @@ static int launch_lu_solve(nlh_handle *h, hipStream_t s, int nprob, int n, const
 }
 
 // ===========================================================================
-// Newton: ns_solve as a host loop; Jacobian, gradient, LU on the device.
+// Newton with host callbacks: ns_solve as a host loop; Jacobian, gradient, LU on the device.
 // The O(n) line-search and convergence arithmetic stays on the host in the
 // reference's exact order (sequential dot products), so given the same search
 // direction every accept/backtrack decision matches the CPU path.
+// The one solver that keeps a host loop: on the lock-step driver every trial point of the search is a device round trip
+// and the ordered sums of k_nt_step_begin / k_nt_trial are serial chains of n adds on one lane, which the drop-in row of
+// bench.py (n = 1024, compiled callbacks) does not afford (profiles/host_solves_ab.md).  Quasi-Newton, least squares
+// free and bounded, and BFGS run the drivers.  This is the only host copy of the search (ls_search_mimo) and of the three
+// convergence tests; tests/test_gpu_solvers.py holds it and square_lockstep to the same bits.
 // ===========================================================================
 struct NewtonEval {
     // evaluate F at host x -> host f (device copy of f kept in dfvec when keep_dev)
@@ -362,10 +368,10 @@ static int newton_core(nlh_handle *h, const nlh_options *o, int n, NewtonEval &e
 }
 
 
+
 // ===========================================================================
-// Quasi-Newton (Broyden): qns_solve as a host loop; B, Q, R live on the device.
-// Same division of labour as Newton: O(n) vector logic on the host in the reference's order,
-// every O(n^2)/O(n^3) operation in the kernels of nlh_kernels_broyden.h.
+// The Householder QR with Q formed and its rank-one update (quasi-Newton; the steps also serve constrained least squares
+// and polynomial fits).
 // ===========================================================================
 
 // B (column-major) -> Q, R: Householder QR with Q formed (qr_factor(b, q = q, r = r), :289)
@@ -477,188 +483,6 @@ static void launch_qn_update(nlh_handle *h, int nprob, int n, double *dQ, double
     hipLaunchKernelGGL(k_qn_rot_q, g1, dim3(256), sizeof(double) * 2 * n, s, n, dQ, dc, dsn, 0, gst, gwant);
 }
 
-static int quasi_newton_core(nlh_handle *h, const nlh_options *o, int jdelta, int n, NewtonEval &ev, double *x,
-                             double *fvec, nlh_iteration_behavior *ib)
-{
-    int rc;
-    const size_t nn = (size_t)n * n;
-    if (n > QN_MAX_N) return NLH_ARRAY_SIZE_ERROR;
-    if ((rc = ensure(h, h->J, sizeof(double) * nn))) return rc;
-    if ((rc = ensure(h, h->qnQ, sizeof(double) * nn))) return rc;
-    if ((rc = ensure(h, h->qnR, sizeof(double) * nn))) return rc;
-    if ((rc = ensure(h, h->qnV, sizeof(double) * ((size_t)16 * n + 8)))) return rc;
-    double *dB = (double *)h->J.p, *dQ = (double *)h->qnQ.p, *dRt = (double *)h->qnR.p;
-    double *dv = (double *)h->qnV.p;
-    double *ddx = dv, *ddf = dv + n, *dsv = dv + 2 * n, *dwcs = dv + 3 * n /* 3n */, *dgrad = dv + 6 * n,
-           *dstep = dv + 7 * n, *dfv = dv + 8 * n, *dvb = dv + 9 * n /* 4n + 4 */;
-    hipStream_t s = h->stream;
-    std::vector<double> dx(n), df(n), fvold(n), xold(n);
-    int restart = 1, xcnvrg = 0, fcnvrg = 0, gcnvrg = 0, neval = 0, iter = 0, njac = 0, flag = 0, jcount = 0;
-    int ls_zero_diff = 0;                                       // lib%converge_on_zero_diff: .false. after every search (:318 of linesearch)
-    double f, fold, stpmax, xnorm = 0, fnorm = 0, test;
-    rc = 0;
-
-    if ((rc = ev.fcn(x, fvec))) return rc;                      // :261-270
-    f = 0.5 * h_dot(n, fvec, fvec);
-    neval += 1;
-    test = 0.0;
-    for (int i = 0; i < n; ++i) test = fmax(fabs(fvec[i]), test);
-    if (test < o->ftol) fcnvrg = 1;
-
-    if (!fcnvrg) {
-        stpmax = 100.0 * fmax(h_norm2(n, x), (double)n);        // :276
-        for (;;) {                                              // :279-411
-            iter += 1;
-            if (restart) {                                      // :284-292
-                if ((rc = ev.jac(x, fvec, dB))) break;
-                njac += 1;
-                launch_qn_qr(h, 1, n, dB, dQ, dRt, dvb);
-                jcount = 0;
-            } else {                                            // :294-310
-                for (int i = 0; i < n; ++i) df[i] = fvec[i] - fvold[i];
-                for (int i = 0; i < n; ++i) dx[i] = x[i] - xold[i];
-                const double x2 = h_dot(n, dx.data(), dx.data());
-                HIPCHK(h, hipMemcpyAsync(ddx, dx.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
-                HIPCHK(h, hipMemcpyAsync(ddf, df.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
-                hipLaunchKernelGGL(k_qn_resid, dim3((n + 255) / 256, 1), dim3(256), sizeof(double) * n, s, n, dB, ddx, ddf, x2, (const double *)nullptr, dsv, (const LmState *)nullptr, -1);
-                hipLaunchKernelGGL(k_qn_rank1, dim3((n + 255) / 256, n, 1), dim3(256), 0, s, n, dB, dsv, ddx, (const LmState *)nullptr, -1);
-                launch_qn_update(h, 1, n, dQ, dRt, dsv, ddx, dwcs);
-                jcount += 1;
-            }
-            // grad = B^T f (:313), step = -R^-1 Q^T f (:322-328)
-            HIPCHK(h, hipMemcpyAsync(dfv, fvec, sizeof(double) * n, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_qn_colsdot, dim3((n + 15) / 16, 1), dim3(256), 0, s, n, n, dB, dfv, dgrad, 1.0, (const LmState *)nullptr, -1);
-            hipLaunchKernelGGL(k_qn_colsdot, dim3((n + 15) / 16, 1), dim3(256), 0, s, n, n, dQ, dfv, dstep, -1.0, (const LmState *)nullptr, -1);
-            hipLaunchKernelGGL(k_qn_solve_upper, dim3(1), dim3(std::min(1024, ((n + 63) / 64) * 64)), sizeof(double) * n, s, n, dRt, dstep, (size_t)n * n, (size_t)n, (const LmState *)nullptr, -1);
-            HIPCHK(h, hipMemcpyAsync(dx.data(), dgrad, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipMemcpyAsync(df.data(), dstep, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipStreamSynchronize(s));
-
-            memcpy(xold.data(), x, sizeof(double) * n);         // :316-318
-            memcpy(fvold.data(), fvec, sizeof(double) * n);
-            fold = f;
-
-            double temp = h_dot(n, dx.data(), df.data());       // :332-339
-            if (temp >= 0.0) {
-                restart = 1;
-                if (o->print_status) print_status(iter, neval, njac, xnorm, fnorm);
-                if (iter > 10 * o->max_evals + 100) { flag = 1; break; }    // the reference would spin here
-                continue;
-            }
-
-            if (o->use_line_search) {                           // :342-351
-                temp = h_dot(n, df.data(), df.data());
-                if (temp > stpmax) {
-                    const double sc = stpmax / temp;
-                    for (int i = 0; i < n; ++i) df[i] = df[i] * sc;
-                }
-                const double mag = h_norm2(n, df.data());       // limit_search_vector
-                if (mag != 0.0 && mag > stpmax) {
-                    const double sc = stpmax / mag;
-                    for (int i = 0; i < n; ++i) df[i] = sc * df[i];
-                }
-                int lcount = 0;
-                rc = line_search(o, ev, n, xold.data(), dx.data(), df.data(), x, fvec, fold, &f, &lcount);
-                neval += lcount;
-                ls_zero_diff = 0;
-                if (rc) break;
-            } else {                                            // :353-357
-                for (int i = 0; i < n; ++i) x[i] = x[i] + df[i];
-                if ((rc = ev.fcn(x, fvec))) break;
-                f = 0.5 * h_dot(n, fvec, fvec);
-                neval += 1;
-            }
-
-            // test_convergence (:360-367); the gradient test runs only if the search reported a zero slope
-            int check = 0;
-            xcnvrg = fcnvrg = gcnvrg = 0;
-            {
-                const double fc = 0.5 * h_dot(n, fvec, fvec);
-                fnorm = 0.0; xnorm = 0.0;
-                for (int i = 0; i < n; ++i) fnorm = fmax(fabs(fvec[i]), fnorm);
-                if (fnorm < o->ftol) { fcnvrg = 1; check = 1; }
-                else {
-                    for (int i = 0; i < n; ++i) {
-                        const double t = fabs(x[i] - xold[i]) / fmax(fabs(x[i]), 1.0);
-                        xnorm = fmax(t, xnorm);
-                    }
-                    if (xnorm < o->xtol) { xcnvrg = 1; check = 1; }
-                    else if (ls_zero_diff && o->use_line_search) {
-                        double tg = 0.0;
-                        const double den = fmax(fc, 0.5 * (double)n);
-                        for (int i = 0; i < n; ++i) tg = fmax(tg, fabs(dx[i]) * fmax(fabs(x[i]), 1.0) / den);
-                        if (tg < o->gtol) gcnvrg = 1;
-                    }
-                }
-            }
-            if (!check) {                                       // :368-391
-                if (gcnvrg) {
-                    if (restart) { rc = NLH_SPURIOUS_CONVERGENCE_ERROR; break; }
-                    restart = 1;
-                } else {
-                    restart = jcount >= jdelta ? 1 : 0;
-                }
-            } else {
-                break;
-            }
-            if (o->print_status) print_status(iter, neval, njac, xnorm, fnorm);   // :398-400
-            if (neval >= o->max_evals) { flag = 1; break; }     // :403-406
-        }
-    }
-    if (ib) {                                                   // :414-422
-        ib->iter_count = iter; ib->fcn_count = neval; ib->jacobian_count = njac; ib->gradient_count = 0;
-        ib->converge_on_fcn = fcnvrg; ib->converge_on_chng = xcnvrg; ib->converge_on_zero_diff = gcnvrg;
-    }
-    if (rc) return rc;
-    return flag ? NLH_CONVERGENCE_ERROR : 0;
-}
-
-
-int nlh_newton_solve(nlh_handle *h, const nlh_options *o, int32_t n, nlh_vecfcn fcn, nlh_jacfcn jacfcn,
-                     void *ctx, double *x, double *fvec, nlh_iteration_behavior *ib)
-{
-    if (!h) return NLH_ERR_BAD_HANDLE;
-    if (ib) memset(ib, 0, sizeof *ib);
-    if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;              // :518
-    if (!o || n < 1) return NLH_INVALID_INPUT_ERROR;
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    const size_t nn = (size_t)n * n;
-    if ((rc = ensure(h, h->P, sizeof(double) * nn))) return rc;
-    if ((rc = ensure(h, h->xdev, sizeof(double) * n))) return rc;
-    if ((rc = ensure(h, h->wa4, sizeof(double) * n))) return rc;
-    if ((rc = ensure_pinned(h, sizeof(double) * (nn + n)))) return rc;
-    double *hP = (double *)h->pinned;
-    hipStream_t s = h->stream;
-    NewtonEval ev;
-    ev.fcn = [&](const double *xx, double *ff) -> int { fcn(ctx, n, xx, n, ff); return 0; };
-    ev.jac = [&](double *xx, const double *f0, double *dJ) -> int {
-        if (jacfcn) {
-            jacfcn(ctx, n, xx, n, hP);
-            HIPCHK(h, hipMemcpyAsync(dJ, hP, sizeof(double) * nn, hipMemcpyHostToDevice, s));
-            return 0;
-        }
-        for (int j = 0; j < n; ++j) {                           // vfh_jac_fcn :267-273
-            const double temp = xx[j];
-            double hh = NLH_SQRT_EPS * fabs(temp);
-            if (hh == 0.0) hh = NLH_SQRT_EPS;
-            xx[j] = temp + hh;
-            fcn(ctx, n, xx, n, hP + (size_t)j * n);
-            xx[j] = temp;
-        }
-        HIPCHK(h, hipMemcpyAsync(h->P.p, hP, sizeof(double) * nn, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->wa4.p, f0, sizeof(double) * n, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->xdev.p, xx, sizeof(double) * n, hipMemcpyHostToDevice, s));
-        launch_fd(h, 1, n, n, (const double *)h->P.p, (const double *)h->wa4.p, (const double *)h->xdev.p, dJ, nullptr, -1);
-        HIPCHK(h, hipStreamSynchronize(s));   // hP is reused by the next call
-        return 0;
-    };
-    rc = newton_core(h, o, n, ev, x, fvec, ib);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = hipGetErrorString(e); return NLH_ERR_HIP; }
-    return rc;
-}
-
 // newton_solver%solve / quasi_newton_solver%solve for a batch of device-model problems: the lock-step state machine of
 // nlh_kernels_newton.h.  A round serves every problem in whatever stage it is.  Newton: the ones that want a Jacobian
 // get J (analytic or forward differences), grad = J^T F in the reference's row order, the LU of J in place (the
@@ -707,9 +531,9 @@ static int square_lockstep(nlh_handle *h, const nlh_options *o, bool broyden, in
     no.broyden = broyden ? 1 : 0; no.jdelta = jdelta; no.pad = 0;
     const int pb = (nprob + 255) / 256;
     const bool echo = o->print_status && nprob == 1;             // the status block is a single solve's (:611-613)
-    auto jacobian = [&]() -> int {                               // for the problems in stage NT_NEED_JAC
+    auto jacobian = [&](int known) -> int {                      // for the problems in stage NT_NEED_JAC (known: how many, or -1)
         if (rs.user())                                           // the user's jacobianfcn, or vfh_jac_fcn on the user's vecfcn
-            return residual_jacobian(h, rs, nprob, n, n, dx, dfvec, dJ, dP, st, NT_NEED_JAC, false, false, true);
+            return residual_jacobian(h, rs, nprob, n, n, dx, dfvec, dJ, dP, st, NT_NEED_JAC, false, false, true, known);
         if (analytic) {
             Timed t(h, NLH_K_DQ_JACOBIAN);
             hipLaunchKernelGGL(k_dq_jacobian<RB>, dim3((n + RB - 1) / RB, nprob), dim3(RB), sizeof(double) * n, s,
@@ -727,11 +551,11 @@ static int square_lockstep(nlh_handle *h, const nlh_options *o, bool broyden, in
     hipLaunchKernelGGL(k_nt_start, dim3(nprob), dim3(256), 0, s, n, no, (const double *)dx, (const double *)dfvec, st, ns);
     int need_jac = nprob, update = 0;                            // upper bounds until the first read-back
     // a round advances every live problem by one evaluation at least (or, quasi-Newton, turns an iteration without a
-    // descent direction into a restart: bounded by 10 max_evals + 100 iterations as in the host loop)
+    // descent direction into a restart: bounded by 10 max_evals + 100 iterations, where the reference would spin)
     const long max_rounds = broyden ? 11L * o->max_evals + (long)o->ls_max_evals + 128 : (long)o->max_evals + (long)o->ls_max_evals + 8;
     for (long round = 0; round < max_rounds; ++round) {
         if (!broyden && need_jac > 0) {
-            if ((rc = jacobian())) return rc;
+            if ((rc = jacobian(round > 0 ? need_jac : -1))) return rc;   // (exact after the first read-back)
             {
                 Timed t(h, NLH_K_JTF);                           // :565-567
                 hipLaunchKernelGGL(k_jtf_exact, dim3((n + 255) / 256, nprob), dim3(256), 0, s, n, n, (const double *)dJ,
@@ -746,7 +570,7 @@ static int square_lockstep(nlh_handle *h, const nlh_options *o, bool broyden, in
         }
         if (broyden && (need_jac > 0 || update > 0)) {
             if (need_jac > 0) {                                  // :284-292: B = J(x), QR with Q formed
-                if ((rc = jacobian())) return rc;
+                if ((rc = jacobian(round > 0 ? need_jac : -1))) return rc;   // (exact after the first read-back)
                 launch_qn_qr(h, nprob, n, dJ, dQ, dRt, dvb, st, NT_NEED_JAC);
                 hipLaunchKernelGGL(k_nt_advance, dim3(pb), dim3(256), 0, s, nprob, st, (int)NT_NEED_JAC, (int)NT_DIR);
             }
@@ -870,13 +694,13 @@ int nlh_quasi_newton_solve_batch_device_h(nlh_handle *h, const nlh_options *o, i
     return square_device_h(h, o, true, jdelta, nprob, n, fcn, jacfcn, ctx, x, fvec, ib, status);
 }
 
-// quasi_newton_solver%solve -- qns_solve, src/nonlin_solve.f90:156-427
-int nlh_quasi_newton_solve(nlh_handle *h, const nlh_options *o, int32_t jdelta, int32_t n, nlh_vecfcn fcn,
-                           nlh_jacfcn jacfcn, void *ctx, double *x, double *fvec, nlh_iteration_behavior *ib)
+// newton_solver%solve -- ns_solve, src/nonlin_solve.f90:452-638 -- with host callbacks: the host loop above
+int nlh_newton_solve(nlh_handle *h, const nlh_options *o, int32_t n, nlh_vecfcn fcn, nlh_jacfcn jacfcn,
+                     void *ctx, double *x, double *fvec, nlh_iteration_behavior *ib)
 {
     if (!h) return NLH_ERR_BAD_HANDLE;
     if (ib) memset(ib, 0, sizeof *ib);
-    if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;              // :240
+    if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;              // :518
     if (!o || n < 1) return NLH_INVALID_INPUT_ERROR;
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
@@ -893,7 +717,6 @@ int nlh_quasi_newton_solve(nlh_handle *h, const nlh_options *o, int32_t jdelta, 
         if (jacfcn) {
             jacfcn(ctx, n, xx, n, hP);
             HIPCHK(h, hipMemcpyAsync(dJ, hP, sizeof(double) * nn, hipMemcpyHostToDevice, s));
-            HIPCHK(h, hipStreamSynchronize(s));
             return 0;
         }
         for (int j = 0; j < n; ++j) {                           // vfh_jac_fcn :267-273
@@ -908,13 +731,32 @@ int nlh_quasi_newton_solve(nlh_handle *h, const nlh_options *o, int32_t jdelta, 
         HIPCHK(h, hipMemcpyAsync(h->wa4.p, f0, sizeof(double) * n, hipMemcpyHostToDevice, s));
         HIPCHK(h, hipMemcpyAsync(h->xdev.p, xx, sizeof(double) * n, hipMemcpyHostToDevice, s));
         launch_fd(h, 1, n, n, (const double *)h->P.p, (const double *)h->wa4.p, (const double *)h->xdev.p, dJ, nullptr, -1);
-        HIPCHK(h, hipStreamSynchronize(s));
+        HIPCHK(h, hipStreamSynchronize(s));   // hP is reused by the next call
         return 0;
     };
-    rc = quasi_newton_core(h, o, jdelta, n, ev, x, fvec, ib);
+    rc = newton_core(h, o, n, ev, x, fvec, ib);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { h->err = hipGetErrorString(e); return NLH_ERR_HIP; }
     return rc;
+}
+
+// quasi_newton_solver%solve -- qns_solve, src/nonlin_solve.f90:156-427 -- with the user's HOST vecfcn / jacobianfcn: the
+// lock-step driver on one problem, the callbacks behind the host-callback launchers.
+int nlh_quasi_newton_solve(nlh_handle *h, const nlh_options *o, int32_t jdelta, int32_t n, nlh_vecfcn fcn, nlh_jacfcn jacfcn, void *ctx,
+                           double *x, double *fvec, nlh_iteration_behavior *ib)
+{
+    if (!h) return NLH_ERR_BAD_HANDLE;
+    if (ib) memset(ib, 0, sizeof *ib);
+    if (!fcn) return NLH_UNDEFINED_FUNCTION_ERROR;              // :240
+    if (!o || n < 1) return NLH_INVALID_INPUT_ERROR;
+    if (n > QN_MAX_N) return NLH_ARRAY_SIZE_ERROR;
+    HostCallbacks cb = HostCallbacks::vector(h, fcn, jacfcn, ctx);
+    const size_t bytes = sizeof(double) * (size_t)n;
+    int32_t status = 0;
+    const int rc = staged_call(h, {{x, bytes, true, true, &h->xdev}, {fvec, bytes, false, true, &h->fdev}}, [&](void *const *d) {
+        return square_lockstep(h, o, true, jdelta, 1, n, cb.source(), 0, (double *)d[0], (double *)d[1], ib, &status);
+    });
+    return rc ? rc : status;
 }
 
 int nlh_dq_quasi_newton_solve_batch(nlh_handle *h, const nlh_options *o, int32_t jdelta, int32_t nprob, int32_t n,

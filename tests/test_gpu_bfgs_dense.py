@@ -268,7 +268,7 @@ def _chain(n):
 
 
 def test_bfgs_one_problem_path_beyond_the_lds_bound_bitwise(oracle):
-    """bfgs%solve for one problem (the host loop) at n = 640, to convergence on the gradient: the factorisations go through
+    """bfgs%solve for one problem (the lock-step driver behind the host callbacks) at n = 640, to convergence on the gradient: the factorisations go through
     the same dispatch -- the first iteration's, and later ones of a dense B (the oracle counts them); a launch that was
     refused would leave the stale factor and the iterates would part from the oracle's.  Status, counts, x and f."""
     import nonlin_amd as nl
