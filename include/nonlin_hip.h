@@ -1797,4 +1797,10 @@ const char *nlh_kernel_name(int32_t kernel_id);
  * nonlin_hip_boot_pois.h, a part of this ABI that this header includes in the same way. ---- */
 #include "nonlin_hip_boot_pois.h"
 
+/* ---- profile-likelihood intervals: the third statement of a fit's uncertainty, beside sigma and the bootstrap -- a pair of
+ * wrapping launchers that pins one parameter per wrapped problem at its own value on shared data, and the lock-step root
+ * finder over the pinned refits of every end.  The entry points and their stated arithmetic are in nonlin_hip_profile.h, a
+ * part of this ABI that this header includes in the same way. ---- */
+#include "nonlin_hip_profile.h"
+
 #endif /* NONLIN_HIP_H */

@@ -6,6 +6,8 @@ from ._lib import Starts, STARTS_MAX_N, STARTS_MAX_KEEP, STARTS_MAX_CAND  # noqa
 from ._lib import PoissonBootstrap, BOOT_POIS_MAX_MEAN  # noqa: F401  (parametric count replicas for stat= fits)
 from ._lib import Bootstrap, BOOT_RESIDUAL, BOOT_WILD, BOOT_PAIRS, BOOT_MAX_ROWS, BOOT_MAX_REP  # noqa: F401  (resampled-data intervals)
 from ._lib import Binned, BinStruct, bin_rule, BIN_MAX_Q, BIN_MAX_ORDER  # noqa: F401  (bin-integrated fits)
+from ._lib import (Profile, PROFILE_OK, PROFILE_OPEN, PROFILE_OPEN_AT_BOUND, PROFILE_ON_BOUND, PROFILE_MAXIT,  # noqa: F401
+                   PROFILE_FIT_FAILED, PROFILE_NO_START, PROFILE_NOT_FREE, PROFILE_LOWER, PROFILE_FLAGS)  # (profile-likelihood intervals)
 from .api import (  # noqa: F401
     NonlinError, iteration_behavior, vecfcn_helper, equation_solver, least_squares_solver,
     line_search, line_search_solver, newton_solver, quasi_newton_solver,

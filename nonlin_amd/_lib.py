@@ -408,6 +408,27 @@ BOOT_POIS_SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+class ProfileState(C.Structure):
+    """nlh_profile_state (include/nonlin_hip_profile.h): the addresses of the device arrays of a profile's root finder."""
+    _fields_ = [(k, C.c_void_p) for k in ("C0", "delta", "xhat", "width", "bound", "theta", "a", "ga", "b", "gb", "end",
+                                          "phase", "flag", "last", "nexp", "nev", "nfail")]
+
+
+# The entry points of include/nonlin_hip_profile.h, the part of the ABI that holds the profile-likelihood intervals -- the pin
+# pair and the root finder --: bound beside BOOT_POIS_SYMBOLS.
+PROFILE_SYMBOLS = {
+    "nlh_pin_wrap": (C.c_int, [_H, C.c_int32, DEVFCN, DEVFCN, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.POINTER(C.c_void_p)]),
+    "nlh_pin_set": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_pin_unwrap": _RELEASE,
+    "nlh_pin_device_fcn": _LAUNCHER,
+    "nlh_pin_device_jac": _LAUNCHER,
+    "nlh_profile_start_batch_device": (C.c_int, [_H, DEVFCN, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_double, C.c_int32, c_double_p, c_double_p, C.POINTER(ProfileState)]),
+    "nlh_profile_step_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ProfileState),
+                                         C.c_double, C.c_double, C.c_int32, C.c_int32, c_int32_p]),
+}
+
 KERNEL_IDS = {
     "dq_residual": 0, "dq_panel": 1, "fd_jacobian": 2, "gram": 3, "gram_reduce": 4, "jtf": 5,
     "chol": 6, "lmpar": 7, "qr": 8, "update": 9, "lu": 10, "dq_jacobian": 11, "qrx_pass": 12, "qrx_pivot": 13,
@@ -438,7 +459,7 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SYMBOLS.items()) + list(GUESS_SYMBOLS.items()) + list(STARTS_SYMBOLS.items()) + list(BOOT_SYMBOLS.items()) +
-                              list(BIN_SYMBOLS.items()) + list(BOOT_POIS_SYMBOLS.items())):
+                              list(BIN_SYMBOLS.items()) + list(BOOT_POIS_SYMBOLS.items()) + list(PROFILE_SYMBOLS.items())):
         fn = getattr(lib, name)       # AttributeError if the ABI and this table drift
         fn.restype = res
         fn.argtypes = args
@@ -965,6 +986,49 @@ class PoissonBootstrap:
         out = np.empty(mu.shape, dtype=np.float64)
         rc = load().nlh_boot_poisson_draws(self.seed, *args, len(mu), mu.ctypes.data_as(c_double_p), out.ctypes.data_as(c_double_p))
         return out if rc == 0 else None
+
+
+# the flags of a profile's ends (include/nonlin_hip_profile.h: NLH_PROFILE_*): one code, plus the bit PROFILE_LOWER
+(PROFILE_OK, PROFILE_OPEN, PROFILE_OPEN_AT_BOUND, PROFILE_ON_BOUND, PROFILE_MAXIT, PROFILE_FIT_FAILED, PROFILE_NO_START,
+ PROFILE_NOT_FREE) = range(8)
+PROFILE_LOWER = 16
+PROFILE_FLAGS = ("OK", "OPEN", "OPEN_AT_BOUND", "ON_BOUND", "MAXIT", "FIT_FAILED", "NO_START", "NOT_FREE")
+PROFILE_EXPAND, PROFILE_BRACKET, PROFILE_DONE = 0, 1, 2
+
+
+class Profile:
+    """The profile-likelihood interval of a fit (include/nonlin_hip_profile.h: nlh_profile_*; host data only, needs no GPU): every
+    parameter in turn is moved away from its fitted value, all the others are refitted at each trial value, and the interval ends
+    where the cost has risen by a fixed amount -- MINUIT's MINOS, lmfit's conf_interval.  It is asymmetric when the problem is, and
+    open when the data do not bound the parameter.  level: the coverage, inside (0, 1).  crit: the rise that defines the end, in
+    units of the cost's scale -- None: the squared normal quantile of (1 + level)/2 (3.84 at 0.95); with few degrees of freedom
+    pass a squared Student-t quantile; 1.0 is the Delta = 1 convention.  tol: an end is found when the rise is within tol*delta of
+    delta.  xtol: or when its bracket is below xtol*sqrt(crit)*sigma.  max_expand: doublings of the first step sqrt(crit)*sigma before an
+    end is declared open.  maxit: evaluations per end at the most.  E.g.
+        Profile(level=0.68, crit=1.0)
+    Raises ValueError for malformed values."""
+
+    def __init__(self, level=0.95, crit=None, tol=0.01, xtol=1e-3, max_expand=8, maxit=30):
+        import math
+        import statistics
+
+        def number(name, v, lo_open, hi_open=None):
+            if isinstance(v, (bool, str)) or not hasattr(v, "__float__") or not math.isfinite(float(v)) or not float(v) > lo_open or \
+                    (hi_open is not None and not float(v) < hi_open):
+                raise ValueError(f"Profile: {name} must be a finite number above {lo_open}" +
+                                 (f" and below {hi_open}" if hi_open is not None else "") + f", not {v!r}")
+            return float(v)
+        self.level = number("level", level, 0.0, 1.0)
+        if crit is None:
+            z = statistics.NormalDist().inv_cdf((1.0 + self.level) / 2.0)
+            crit = z * z
+        self.crit = number("crit", crit, 0.0)
+        self.tol = number("tol", tol, 0.0, 1.0)
+        self.xtol = number("xtol", xtol, 0.0, 1.0)
+        for name, v, least in (("max_expand", max_expand, 0), ("maxit", maxit, 1)):
+            if isinstance(v, bool) or not isinstance(v, int) or not least <= v < (1 << 31):
+                raise ValueError(f"Profile: {name} must be an integer of at least {least}, not {v!r}")
+        self.max_expand, self.maxit = int(max_expand), int(maxit)
 
 
 class Loss:

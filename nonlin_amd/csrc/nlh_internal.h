@@ -26,6 +26,8 @@
 //   nlh_starts.hip     starts: the candidates of a box, the batched scan over any residual launcher, cost / pick / take
 //   nlh_boot.hip       bootstrap: the generator's draws, the resampling kernels, the summary of the refits
 //   nlh_bin.hip        bin-integrated fits: the Gauss-Legendre rules, the wrapping launchers, apply
+//   nlh_pin.hip        the pin pair: the wrapping launchers that hold one parameter per wrapped problem at its own value
+//   nlh_profile.hip    profile-likelihood intervals: the start and the lock-step step of the root finder over all ends
 //   nlh_model.hip      device sets, device residual models behind host arrays
 //   nlh_qrx.hip        the exact lmfactor
 // Kernels live in the nlh_kernels_*.h headers with internal linkage: a unit compiles the ones it launches.  nlh_launch.h:
@@ -87,7 +89,8 @@ struct nlh_handle {
            guessA, guessP, guessH,        // starting values (nlh_guess.hip): alpha / span / flags, the decays' panel, host-array staging
            startsC, startsX, startsF, startsS, startsH,   // starts (nlh_starts.hip): the candidate table, a chunk's points and problems, its
                                           // residuals, its costs, host-array staging
-           bootV;                         // bootstrap (nlh_boot.hip): which replicas of which problems are valid
+           bootV,                         // bootstrap (nlh_boot.hip): which replicas of which problems are valid
+           profW;                         // profile intervals (nlh_profile.hip): the residuals at the fit, the box, the count of running ends
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     DevBuf cholmc;                     // side buffer of the multi-CU Cholesky (solved panels, bad-pivot flags)

@@ -1,6 +1,7 @@
-// nlh_launch.h -- the host side of the (point, row) kernels' two workgroup forms (nlh_kernels_place.h), and what the seven
+// nlh_launch.h -- the host side of the (point, row) kernels' two workgroup forms (nlh_kernels_place.h), and what the eight
 // pairs of wrapping launchers -- parameter maps (nlh_pmap.hip), robust losses (nlh_loss.hip), Poisson fits (nlh_pois.hip),
-// global fits (nlh_group.hip), instrument responses (nlh_conv.hip), separable fits (nlh_sep.hip), bins (nlh_bin.hip) -- share: WrapCtx, the base
+// global fits (nlh_group.hip), instrument responses (nlh_conv.hip), separable fits (nlh_sep.hip), bins (nlh_bin.hip), pins
+// (nlh_pin.hip) -- share: WrapCtx, the base
 // of their contexts, with how one is made and what its launchers refuse; the per-stream scratch of a context, its cap, the
 // column groups and grid of a column-split Jacobian kernel, and the slice loop of a call.
 // Every environment variable is read at every call (tests set them between calls).
@@ -57,7 +58,7 @@ static inline int device_cus(int device)
     return hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0 ? cus : 1;
 }
 
-// The base of the seven wrapping contexts: what a layer around an inner launcher pair (fcn, jac -- NULL: none --, inner) holds
+// The base of the eight wrapping contexts: what a layer around an inner launcher pair (fcn, jac -- NULL: none --, inner) holds
 // whatever it computes.  Each nlh_*_ctx derives from it alone and adds its own fields, so a context's address is its base's:
 // the launchers read magic -- one value per kind -- through the void * they are handed, and nlh_model.hip and nlh_fit.hip
 // hold a layer of any kind as a WrapCtx * (nlh_internal.h: wrap_layer, wrap_release).  tables: the kind's own device

@@ -810,6 +810,214 @@ class DeviceSolver:
                    fail.data_ptr() if fail is not None else None, cf.data_ptr(), sf.data_ptr())
         return cf, sf
 
+    # -- profile-likelihood intervals ------------------------------------------------
+    @staticmethod
+    def _pin_tables(src, pos, theta):
+        """nend of the three tables of a pin pair, checked: src, pos int32 and theta float64, contiguous GPU tensors [nend]."""
+        nend = theta.shape[0] if theta.dim() == 1 else -1
+        _chk(theta, (nend,), "theta")
+        for name, v in (("src", src), ("pos", pos)):
+            if not (v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and tuple(v.shape) == (nend,)):
+                raise ValueError(f"{name}: expected a contiguous int32 GPU tensor of shape ({nend},)")
+        return nend
+
+    def pin_launchers(self, fcn, jac, ctx, N, src, pos, theta):
+        """One parameter per wrapped problem held at its own value, the data shared, for any launcher pair: wraps (fcn, jac,
+        ctx) over N unknowns in the pin pair (nlh_pin_wrap) and returns (fcn, jac, ctx) for lm_solve_batch_device,
+        cls_solve_batch_device and fd_jacobian_device, which then work on x [nend, N - 1]: wrapped problem w is the inner
+        problem src[w] (int32) with its unknown pos[w] (int32) held at theta[w]; the others keep their order.  Only copies
+        happen, and no data are replicated: the inner launchers are called with src as their problem list.  jac is None
+        without an inner Jacobian launcher.  An entry of src or pos out of range is the caller's error.  Keep the returned ctx
+        alive while solving; ctx.close() frees it (so does garbage collection)."""
+        nend = self._pin_tables(src, pos, theta)
+        return self._wrap("pin", [(fcn, jac, ctx), (src, pos, theta)], fcn, jac, ctx, (int(N),),
+                          (nend, src.data_ptr(), pos.data_ptr(), theta.data_ptr()))
+
+    def pin_set(self, pin_ctx, src, pos, theta):
+        """Swaps the three tables of a pin pair, and with them the number of wrapped problems, between solves (nlh_pin_set)."""
+        nend = self._pin_tables(src, pos, theta)
+        rc = self.lib.nlh_pin_set(pin_ctx.ptr, nend, src.data_ptr(), pos.data_ptr(), theta.data_ptr())
+        if rc:
+            raise ValueError(f"nlh_pin_set returned {rc}")
+        pin_ctx._keep[1] = (src, pos, theta)
+
+    def _profile_state(self, nprob, n):
+        """(the tensors of a profile's state by name, the nlh_profile_state that holds their addresses)."""
+        dev, nend = self.device, nprob * n * 2
+        st = {k: torch.empty((nprob,) if k in ("C0", "delta") else (nend,),
+                             dtype=torch.float64 if i < 11 else torch.int32, device=dev)
+              for i, (k, _) in enumerate(_lib.ProfileState._fields_)}
+        return st, _lib.ProfileState(**{k: v.data_ptr() for k, v in st.items()})
+
+    def profile_start(self, fcn, ctx, m, x, sigma, prof, dof=None, scaled=True, lower=None, upper=None):
+        """The start of a Profile's root finder at the fit x, sigma [nprob, n] of the UNPINNED launcher (fcn, ctx) over m rows
+        (nlh_profile_start_batch_device): the state, a dict of device tensors by the names of nlh_profile_state -- C0, delta
+        [nprob]; xhat, width, bound, theta, a, ga, b, gb, end (float64) and phase, flag, last, nexp, nev, nfail (int32), each
+        [nprob * n * 2], end (p*n + j)*2 + s.  dof: int32 [nprob] or None (m - n); lower, upper: one box [n] or None."""
+        nprob, n = x.shape
+        _chk(x, (nprob, n), "x"); _chk(sigma, (nprob, n), "sigma")
+        if dof is not None and not (dof.is_cuda and dof.dtype == torch.int32 and dof.is_contiguous() and tuple(dof.shape) == (nprob,)):
+            raise ValueError(f"dof: expected a contiguous int32 GPU tensor of shape ({nprob},)")
+        st, cs = self._profile_state(nprob, n)
+        plo, phi = _host_bounds(lower, upper, n)
+        self._call("nlh_profile_start_batch_device", self._devfcn(fcn), self._ctxp(ctx), nprob, int(m), n, x.data_ptr(), sigma.data_ptr(),
+                   dof.data_ptr() if dof is not None else None, prof.crit, int(bool(scaled)), plo, phi, C.byref(cs))
+        st["_struct"] = cs
+        return st
+
+    def profile_step(self, state, act, cost, fail, prof):
+        """One step of the root finder for the active ends act [nact] (int32) with the costs cost [nact] of their refits and
+        fail [nact] (int32, non-zero: the refit did not end well) or None (nlh_profile_step_batch): the state is updated in
+        place; returns how many ends are still running."""
+        nact = act.shape[0]
+        _chk(cost, (nact,), "cost")
+        for name, v in (("act", act), ("fail", fail)):
+            if v is not None and not (v.is_cuda and v.dtype == torch.int32 and v.is_contiguous() and tuple(v.shape) == (nact,)):
+                raise ValueError(f"{name}: expected a contiguous int32 GPU tensor of shape ({nact},)")
+        nprob = state["C0"].shape[0]
+        n = state["theta"].shape[0] // (2 * nprob) if nprob else 1
+        left = C.c_int32()
+        self._call("nlh_profile_step_batch", nprob, n, nact, act.data_ptr(), cost.data_ptr(), fail.data_ptr() if fail is not None else None,
+                   C.byref(state["_struct"]), prof.tol, prof.xtol, prof.max_expand, prof.maxit, C.byref(left))
+        return int(left.value)
+
+    def profile_batch_device(self, fcn, jac, ctx, m, x, sigma, prof, dof=None, scaled=True, lower=None, upper=None, opts=None):
+        """The profile-likelihood intervals (a Profile) of the fit x with the standard errors sigma [nprob, n] of ANY launcher pair
+        (fcn, jac, ctx) over m rows -- a user's, a model's, or one composed with the wrapping launchers: (lo, hi [nprob, n],
+        flags, nev [nprob, n, 2] int32).  For every problem, parameter and side the root finder of nlh_profile_* looks for the
+        value of the parameter at which the cost of the refit of all the others has risen by delta = crit * C0 / dof (scaled;
+        dof: int32 [nprob], None: m - n) or crit (scaled=False: a deviance): start, then rounds of -- the tables of the active
+        ends (pin_set), ONE lm_solve_batch_device over all of them through the pin pair, each from the solution of its latest
+        successful refit (at first x without the pinned entry), starts_cost of the fvec, step -- until no end is left.  With
+        lower / upper (one box [n]) the refits are cls_solve_batch_device's, one call per parameter on the box without its
+        entry, and an interval ends at the bound.  jac=None: forward differences over the N - 1 unknowns.  A refit whose
+        status is not 0 counts as failed.  flags holds a PROFILE_* code per end plus the bit PROFILE_LOWER; lo / hi are -Inf /
+        +Inf for an open end and NaN where there is none.  The ends are chunked so that the refits' fvec stays within 256 MiB
+        (the environment variable NLH_PROFILE_ENDS, read at every call, sets the ends of a chunk instead: tests); the result does
+        not depend on the chunks.  n = 1 raises ValueError."""
+        nprob, n = x.shape
+        if n < 2:
+            raise ValueError("profile: a model of one parameter has no other to refit (n = 1 is not implemented)")
+        plo, phi = _host_bounds(lower, upper, n)                      # (the shapes, before any device work)
+        st = self.profile_start(fcn, ctx, m, x, sigma, prof, dof, scaled, lower, upper)
+        dev, nend = x.device, nprob * n * 2
+        e = torch.arange(nend, dtype=torch.int64, device=dev)
+        src, pos = (e // (2 * n)).to(torch.int32), ((e // 2) % n).to(torch.int32)
+        keep = torch.tensor([[k for k in range(n) if k != j] for j in range(n)], dtype=torch.int64, device=dev)     # [n, n - 1]
+        warm = x[:, None, None, :].expand(nprob, n, 2, n).reshape(nend, n).gather(1, keep[pos.long()])
+        per = max(1, (256 << 20) // (8 * m))
+        env = os.environ.get("NLH_PROFILE_ENDS")
+        if env is not None and int(env) >= 1:
+            per = int(env)
+        o = opts or self.options()
+        bounded = lower is not None or upper is not None
+        box = [tuple(None if b is None else np.delete(np.asarray(b, dtype=np.float64), j) for b in (lower, upper)) for j in range(n)]
+        seed = (src[:1].contiguous(), pos[:1].contiguous(), st["theta"][:1].contiguous())
+        pfcn, pjac, pctx = self.pin_launchers(fcn, jac, ctx, n, *seed)
+        try:
+            while True:
+                act = (st["phase"] != _lib.PROFILE_DONE).nonzero().reshape(-1)
+                nact = act.shape[0]
+                if nact == 0:
+                    break
+                cost = torch.empty((nact,), dtype=torch.float64, device=dev)
+                fail = torch.empty((nact,), dtype=torch.int32, device=dev)
+                for c0 in range(0, nact, per):
+                    ch = act[c0:c0 + per]
+                    groups = [ch[pos[ch] == j] for j in range(n)] if bounded else [ch]
+                    for j, sel in enumerate(groups):
+                        if sel.shape[0] == 0:
+                            continue
+                        self.pin_set(pctx, src[sel].contiguous(), pos[sel].contiguous(), st["theta"][sel].contiguous())
+                        xw = warm[sel].contiguous()
+                        if bounded:
+                            fvec, _, status = self.cls_solve_batch_device(pfcn, pctx, m, xw, jac=pjac, opts=o, lower=box[j][0], upper=box[j][1])
+                        else:
+                            fvec, _, status = self.lm_solve_batch_device(pfcn, pctx, m, xw, jac=pjac, opts=o)
+                        cs = self.starts_cost(fvec)
+                        bad = torch.tensor([s != 0 for s in status], dtype=torch.bool, device=dev)
+                        good = ~bad & torch.isfinite(cs)
+                        warm[sel[good]] = xw[good]
+                        where = (ch[:, None] == sel[None, :]).nonzero()[:, 0] + c0 if bounded else torch.arange(c0, c0 + sel.shape[0], device=dev)
+                        cost[where] = cs
+                        fail[where] = bad.to(torch.int32)
+                self.profile_step(st, act.to(torch.int32), cost, fail, prof)
+        finally:
+            pctx.close()
+        end = st["end"].reshape(nprob, n, 2)
+        return (end[:, :, 0].contiguous(), end[:, :, 1].contiguous(), st["flag"].reshape(nprob, n, 2), st["nev"].reshape(nprob, n, 2))
+
+    def _profile_fit(self, model, t, y, x, sigma, prof, weights, kw, bins=None, starts=None):
+        """The one-call profile behind curve_profile_batch and expr_profile_batch: profile_batch_device on the launcher stack of
+        the fit (_stack), through pmap_launchers with pmap=, with scaled = stat is None and dof the rows with non-zero weight
+        minus the free parameters."""
+        if starts is not None:
+            raise ValueError("a profile excludes starts: it starts from the fit x")
+        for name, v in (("sep", kw.sep), ("group", kw.group)):
+            if v is not None:
+                raise ValueError(f"a profile excludes {name}: compose the launchers and call profile_batch_device")
+        if kw.stat is not None and kw.loss is not None:
+            raise ValueError("stat and loss exclude each other: a Poisson fit has no robust loss")
+        if not isinstance(prof, _lib.Profile):
+            raise ValueError("prof: expected a Profile")
+        if bins is not None:
+            if t is not None:
+                raise ValueError("bins excludes t: the model is evaluated at bins.nodes(); pass t=None")
+            if bins.nvar != model.nvar:
+                raise ValueError(f"bins are over {bins.nvar} variable(s), the model has {model.nvar}")
+            nprob, m = y.shape
+            _chk(y, (nprob, m), "y")
+            if weights is not None:
+                _chk(weights, (nprob, m), "weights")
+        else:
+            nprob, m, _ = model.data(t, y, weights)
+        n, pmap, dev = model.n, kw.pmap, y.device
+        _chk(x, (nprob, n), "x"); _chk(sigma, (nprob, n), "sigma")
+        if pmap is not None and pmap.nfull != n:
+            raise ValueError(f"pmap maps {pmap.nfull} parameters, the model has {n}")
+        nfree = pmap.nfree if pmap is not None else n
+        if nfree < 2:
+            raise ValueError("profile: a model of one free parameter has no other to refit (n = 1 is not implemented)")
+        _host_bounds(kw.lower, kw.upper, n)
+        rows = (weights != 0).sum(dim=1) if weights is not None else torch.full((nprob,), m, dtype=torch.int64, device=dev)
+        dof = (rows - nfree).to(torch.int32)
+        with self._stack(model, t, y, weights, kw, bins) as (fcn, jac, ctx, _):
+            jac = jac if kw.analytic else None
+            if pmap is None:
+                return self.profile_batch_device(fcn, jac, ctx, m, x, sigma, prof, dof, kw.stat is None, kw.lower, kw.upper, kw.opts)
+            free = torch.from_numpy(pmap.tables()[4][:nfree].astype("int64")).to(dev)
+            cut = lambda b: None if b is None else np.asarray(b, dtype=np.float64)[free.cpu().numpy()]
+            mfcn, mjac, mctx = self.pmap_launchers(pmap, fcn, jac, ctx, x)
+            try:
+                lo_f, hi_f, fl_f, nev_f = self.profile_batch_device(mfcn, mjac, mctx, m, self.pmap_gather(pmap, x), sigma[:, free].contiguous(),
+                                                                    prof, dof, kw.stat is None, cut(kw.lower), cut(kw.upper), kw.opts)
+            finally:
+                mctx.close()
+            lo, hi = (torch.full((nprob, n), float("nan"), dtype=torch.float64, device=dev) for _ in range(2))
+            flags = torch.full((nprob, n, 2), _lib.PROFILE_NOT_FREE, dtype=torch.int32, device=dev)
+            nev = torch.zeros((nprob, n, 2), dtype=torch.int32, device=dev)
+            lo[:, free], hi[:, free], flags[:, free], nev[:, free] = lo_f, hi_f, fl_f, nev_f
+            return lo, hi, flags, nev
+
+    def curve_profile_batch(self, kind, t, y, x, sigma, prof, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
+                            opts=None, pmap=None, loss=None, stat=None, conv=None, bins=None, sep=None, group=None, starts=None):
+        """The profile-likelihood intervals (a Profile) of curve_fit_batch's fit x with its standard errors sigma [nprob, n] of the
+        data t, y: (lo, hi [nprob, n], flags, nev [nprob, n, 2] int32), as profile_batch_device returns them, on the launchers
+        the fit itself ran on -- the caller's weights, bounds, loss, stat and conv.  Every parameter in turn is held at trial
+        values while all the others are refitted; the interval ends where the cost has risen by crit * chi2 (least squares:
+        scaled, dof the rows with non-zero weight minus the free parameters) or by crit (stat=Poisson(): the deviance).  No data
+        are replicated: all 2 n ends of all problems refit against the nprob data sets.  pmap: the ends are those of the free
+        parameters; lo and hi are NaN with flag PROFILE_NOT_FREE at fixed and tied positions, whose values x holds.  bins (a
+        Binned): as in curve_fit_batch, with t=None.  sep=, group= and starts= raise ValueError."""
+        return self._profile_fit(self._curve_model(kind, ncomp, baseline), t, y, x, sigma, prof, weights,
+                                 _Keywords(lower, upper, analytic, False, opts, pmap, loss, stat, group, conv, sep), bins, starts)
+
+    def expr_profile_batch(self, expr, t, y, x, sigma, prof, weights=None, lower=None, upper=None, analytic=True, opts=None, pmap=None,
+                           loss=None, stat=None, conv=None, bins=None, sep=None, group=None, starts=None):
+        """curve_profile_batch with an Expr in the place of (kind, ncomp, baseline): the profile of expr_fit_batch's fit x."""
+        return self._profile_fit(self._expr_model(expr), t, y, x, sigma, prof, weights,
+                                 _Keywords(lower, upper, analytic, False, opts, pmap, loss, stat, group, conv, sep), bins, starts)
+
     # -- global fits ---------------------------------------------------------------
     def group_launchers(self, group, fcn, jac, ctx):
         """Parameters shared across data sets for any launcher pair: wraps (fcn, jac, ctx) -- of curve_launchers,
