@@ -161,7 +161,7 @@ void launch_lu_factor(nlh_handle *h, int nprob, int n, double *dA, int32_t *dipv
         return;
     }
     if (dinfo) hipMemsetAsync(dinfo, 0, sizeof(int32_t) * (size_t)nprob, h->stream);
-    // panels factored in registers while they have at most 2048 rows (several rows per thread, implicit interchanges),
+    // panels factored in registers while they have at most 1024 rows (several rows per thread, implicit interchanges),
     // 32-column panels in global memory before
     // NLH_LU_CONTRACT=1 (measurement only): the same kernels with every multiply-subtract pair contracted
     // into one FMA -- the pivots stay, the bits do not

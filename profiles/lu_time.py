@@ -8,7 +8,7 @@ from nonlin_amd.device import DeviceSolver
 from oracle import pyoracle as O
 ds = DeviceSolver(0)
 L = O.lib()
-print("NLH_LU_PANEL", os.environ.get("NLH_LU_PANEL"), "NLH_LU_FAST", os.environ.get("NLH_LU_FAST"))
+print("NLH_LU_PANEL", os.environ.get("NLH_LU_PANEL"), "NLH_LU_CONTRACT", os.environ.get("NLH_LU_CONTRACT"))
 for n in [int(a) for a in sys.argv[1:]] or [128, 200, 257, 300, 513, 1024, 1500]:
     rng = np.random.default_rng(n)
     a = rng.standard_normal((n, n))

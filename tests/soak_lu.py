@@ -1,6 +1,9 @@
 """Random sweep of lu_factor / solve_lu on the device against the oracle (sizes around every panel switch, ties, zero
 columns, equal rows, scaled rows, scattered NaNs): factors, interchanges, info and solution bit for bit.  Not collected by
-pytest; run on a GPU box: python tests/soak_lu.py"""
+pytest; run on a GPU box: python tests/soak_lu.py.  The default panel mode only.  The collected tests that pin every
+panel form (NLH_LU_PANEL = 0, 1, 2 and NLH_LU_CONTRACT), every size switch, the engineered interchange patterns and the
+solve's exact-zero skips are tests/test_gpu_lu_edges.py on inputs from tests/lu_cases.py (host side:
+tests/test_lu_cases_cpu.py)."""
 import sys, ctypes as C
 import os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
