@@ -1803,4 +1803,10 @@ const char *nlh_kernel_name(int32_t kernel_id);
  * part of this ABI that this header includes in the same way. ---- */
 #include "nonlin_hip_profile.h"
 
+/* ---- studentised and BCa intervals of the bootstrap: the two textbook corrections of the percentile interval -- the reduction
+ * of the refits and their standard errors to the bootstrap-t interval, the delete-one jackknife weights, the acceleration and
+ * the bias-corrected, accelerated levels.  The entry points and their stated arithmetic are in nonlin_hip_boot_ci.h, a part of
+ * this ABI that this header includes in the same way. ---- */
+#include "nonlin_hip_boot_ci.h"
+
 #endif /* NONLIN_HIP_H */

@@ -4,6 +4,7 @@ include/nonlin_hip.h.  See DESIGN.md.  There is no CPU fallback."""
 from ._lib import NonlinHipUnavailable, LIB_PATH  # noqa: F401
 from ._lib import Starts, STARTS_MAX_N, STARTS_MAX_KEEP, STARTS_MAX_CAND  # noqa: F401  (the box scan: starting values)
 from ._lib import PoissonBootstrap, BOOT_POIS_MAX_MEAN  # noqa: F401  (parametric count replicas for stat= fits)
+from ._lib import bca_levels, BOOT_INTERVALS, BCA_DEGENERATE, BCA_NO_ACCEL, BCA_BAD_DENOM, BCA_NO_REPLICA  # noqa: F401  (studentised / BCa intervals)
 from ._lib import Bootstrap, BOOT_RESIDUAL, BOOT_WILD, BOOT_PAIRS, BOOT_MAX_ROWS, BOOT_MAX_REP  # noqa: F401  (resampled-data intervals)
 from ._lib import Binned, BinStruct, bin_rule, BIN_MAX_Q, BIN_MAX_ORDER  # noqa: F401  (bin-integrated fits)
 from ._lib import (Profile, PROFILE_OK, PROFILE_OPEN, PROFILE_OPEN_AT_BOUND, PROFILE_ON_BOUND, PROFILE_MAXIT,  # noqa: F401

@@ -408,6 +408,19 @@ BOOT_POIS_SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# The entry points of include/nonlin_hip_boot_ci.h, the part of the ABI that holds the studentised and the BCa interval of the
+# bootstrap: bound beside PROFILE_SYMBOLS.
+BOOT_CI_SYMBOLS = {
+    "nlh_boot_bca_levels": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, c_double_p, c_double_p, c_double_p, c_int32_p]),
+    "nlh_boot_student_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_boot_jackknife_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nlh_boot_accel_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nlh_boot_bca_batch": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 class ProfileState(C.Structure):
     """nlh_profile_state (include/nonlin_hip_profile.h): the addresses of the device arrays of a profile's root finder."""
     _fields_ = [(k, C.c_void_p) for k in ("C0", "delta", "xhat", "width", "bound", "theta", "a", "ga", "b", "gb", "end",
@@ -459,7 +472,8 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SYMBOLS.items()) + list(GUESS_SYMBOLS.items()) + list(STARTS_SYMBOLS.items()) + list(BOOT_SYMBOLS.items()) +
-                              list(BIN_SYMBOLS.items()) + list(BOOT_POIS_SYMBOLS.items()) + list(PROFILE_SYMBOLS.items())):
+                              list(BIN_SYMBOLS.items()) + list(BOOT_POIS_SYMBOLS.items()) + list(PROFILE_SYMBOLS.items()) +
+                              list(BOOT_CI_SYMBOLS.items())):
         fn = getattr(lib, name)       # AttributeError if the ABI and this table drift
         fn.restype = res
         fn.argtypes = args
@@ -899,6 +913,24 @@ LOSS_KINDS = {"linear": LOSS_LINEAR, "huber": LOSS_HUBER, "soft_l1": LOSS_SOFT_L
 BOOT_RESIDUAL, BOOT_WILD, BOOT_PAIRS = 0, 1, 2
 BOOT_KINDS = {"residual": BOOT_RESIDUAL, "wild": BOOT_WILD, "pairs": BOOT_PAIRS}
 BOOT_MAX_ROWS, BOOT_MAX_REP = 16384, 4096
+# the intervals of the one-call bootstraps, and the flags of a BCa interval (include/nonlin_hip_boot_ci.h: NLH_BCA_*)
+BOOT_INTERVALS = ("percentile", "student", "bca")
+BCA_DEGENERATE, BCA_NO_ACCEL, BCA_BAD_DENOM, BCA_NO_REPLICA = 1, 2, 4, 8
+
+
+def bca_levels(c2, cnt, a, level=0.95):
+    """nlh_boot_bca_levels (host code, needs no GPU): (z0, alpha_lo, alpha_hi, flag) of a BCa interval from c2 = 2*#{replicas
+    below the fit} + #{equal to it}, cnt valid replicas, the acceleration a and the level -- what boot_bca computes per problem
+    and parameter --, or None when the library refuses."""
+    try:
+        args = [int(c2), int(cnt), float(a), float(level)]
+    except (TypeError, ValueError):
+        return None
+    if any(not -(1 << 31) <= v < (1 << 31) for v in args[:2]):
+        return None
+    z0, alo, ahi, flag = C.c_double(), C.c_double(), C.c_double(), C.c_int32()
+    rc = load().nlh_boot_bca_levels(*args, C.byref(z0), C.byref(alo), C.byref(ahi), C.byref(flag))
+    return (z0.value, alo.value, ahi.value, int(flag.value)) if rc == 0 else None
 
 
 class Bootstrap:
@@ -908,12 +940,19 @@ class Bootstrap:
     "wild" (every residual keeps its row and takes a random sign: noise whose size varies along the rows), "pairs" (rows are
     drawn with replacement: a row drawn c times weighs sqrt(c) times its weight) or a BOOT_* constant.  seed: any integer,
     taken mod 2^64; a replica depends on (seed, problem, replica) alone.  level: the coverage of the percentile interval,
-    inside (0, 1).  centre: subtract the mean residual before drawing ("residual" only).  E.g.
+    inside (0, 1).  centre: subtract the mean residual before drawing ("residual" only).  interval: which interval the one-call
+    bootstraps return (include/nonlin_hip_boot_ci.h) -- "percentile" (the quantiles of the refits), "student" (bootstrap-t: the
+    quantiles of (x* - x)/sigma*, which needs every refit's covariance and the fit's own sigma) or "bca" (bias-corrected and
+    accelerated: the percentile levels moved by the share of refits below x and by the skewness of m delete-one refits per data
+    set).  E.g.
         Bootstrap(nrep=200, kind="wild", seed=7)
     Raises ValueError for what the library refuses."""
 
-    def __init__(self, nrep=200, kind="residual", seed=0, level=0.95, centre=True):
+    def __init__(self, nrep=200, kind="residual", seed=0, level=0.95, centre=True, interval="percentile"):
         import numpy as np
+        if not isinstance(interval, str) or interval not in BOOT_INTERVALS:
+            raise ValueError(f"Bootstrap: unknown interval {interval!r} (one of {', '.join(BOOT_INTERVALS)})")
+        self.interval = interval
         if isinstance(kind, str):
             if kind.lower() not in BOOT_KINDS:
                 raise ValueError(f"Bootstrap: unknown kind {kind!r} (one of {', '.join(BOOT_KINDS)})")
@@ -958,18 +997,18 @@ class PoissonBootstrap:
     GPU): every replica holds counts y* ~ Poisson(mu) drawn from the fitted values mu, and is refitted with the same deviance
     (stat=Poisson()).  For counting data the kinds of Bootstrap are wrong -- a resampled residual added to a fitted value is
     not a count and can be negative --, and at low counts, where the likelihood is skewed, the linearised x +- 1.96 sigma is
-    least trustworthy.  nrep, seed and level are Bootstrap's; a replica depends on (seed, problem, replica, mu) alone.  A
+    least trustworthy.  nrep, seed, level and interval are Bootstrap's; a replica depends on (seed, problem, replica, mu) alone.  A
     fitted value that is a NaN, negative or above BOOT_POIS_MAX_MEAN = 2^24 on an unmasked row makes its problem's bootstrap
     invalid (above 2^24 counts are Gaussian to 2.5e-4: Bootstrap("wild") with weights 1/sqrt(mu) serves).  E.g.
         PoissonBootstrap(nrep=200, seed=7)
     Raises ValueError for what the library refuses."""
 
-    def __init__(self, nrep=200, seed=0, level=0.95):
+    def __init__(self, nrep=200, seed=0, level=0.95, interval="percentile"):
         try:
-            base = Bootstrap(nrep=nrep, seed=seed, level=level)        # the shared fields: Bootstrap's validation
+            base = Bootstrap(nrep=nrep, seed=seed, level=level, interval=interval)     # the shared fields: Bootstrap's validation
         except ValueError as exc:
             raise ValueError("Poisson" + str(exc)) from None
-        self.nrep, self.seed, self.level = base.nrep, base.seed, base.level
+        self.nrep, self.seed, self.level, self.interval = base.nrep, base.seed, base.level, base.interval
 
     def draws(self, p, b, first, mu):
         """nlh_boot_poisson_draws: the draws of the rows first .. first + len(mu) - 1 of the stream of problem p and replica b

@@ -476,6 +476,62 @@ class DeviceSolver:
                    hi.data_ptr(), nvalid.data_ptr())
         return lo, hi, mean, sd, nvalid
 
+    # -- studentised and BCa intervals (include/nonlin_hip_boot_ci.h) --------------------
+    def boot_student(self, xs, sigs, x, sigma, level=0.95):
+        """(lo, hi [nprob, n], nvalid_t [nprob, n] int32): the bootstrap-t interval of the fit x with standard errors sigma
+        [nprob, n] from the refits xs and their own standard errors sigs [nrep, nprob, n] (nlh_boot_student_batch).  A replica
+        counts for a parameter when its whole row of xs is finite and its sigs there is finite and > 0; the quantiles T of
+        (xs - x)/sigs give lo = x - T_hi sigma, hi = x - T_lo sigma.  No such replica, or an x or sigma that will not do: NaN."""
+        nrep, nprob, n = xs.shape
+        _chk(xs, (nrep, nprob, n), "xs"); _chk(sigs, (nrep, nprob, n), "sigs"); _chk(x, (nprob, n), "x"); _chk(sigma, (nprob, n), "sigma")
+        lo, hi = (torch.empty((nprob, n), dtype=torch.float64, device=xs.device) for _ in range(2))
+        nvalid_t = torch.empty((nprob, n), dtype=torch.int32, device=xs.device)
+        self._call("nlh_boot_student_batch", nrep, nprob, n, xs.data_ptr(), sigs.data_ptr(), x.data_ptr(), sigma.data_ptr(), float(level),
+                   lo.data_ptr(), hi.data_ptr(), nvalid_t.data_ptr())
+        return lo, hi, nvalid_t
+
+    def boot_jackknife(self, weights, nprob, m, row0=0, nrows=None):
+        """The delete-one weights of the rows row0 .. row0 + nrows - 1 (nrows=None: up to m) of nprob data sets of m rows
+        (nlh_boot_jackknife_batch): wout [nrows, nprob, m], deletion-major, so that wout.reshape(nrows * nprob, m) is the
+        weights of a batch for a fit -- the caller's weights [nprob, m] (None: 1.0) with row row0 + r set to 0.0."""
+        nprob, m, row0 = int(nprob), int(m), int(row0)
+        nrows = m - row0 if nrows is None else int(nrows)
+        if weights is not None:
+            _chk(weights, (nprob, m), "weights")
+        wout = torch.empty((max(nrows, 0), nprob, m), dtype=torch.float64, device=self.device)
+        self._call("nlh_boot_jackknife_batch", nprob, m, row0, nrows, weights.data_ptr() if weights is not None else None, wout.data_ptr())
+        return wout
+
+    def boot_accel(self, xjack, weights=None):
+        """(accel [nprob, n], njack [nprob] int32): the acceleration of a BCa interval from the delete-one refits xjack
+        [m, nprob, n] (nlh_boot_accel_batch): a = sum d^3 / (6 (sum d^2)^1.5), d = mean - xjack_i, over the deletions of rows
+        of non-zero weight whose refit is finite, njack of them.  Fewer than two, or no spread: 0.0."""
+        m, nprob, n = xjack.shape
+        _chk(xjack, (m, nprob, n), "xjack")
+        if weights is not None:
+            _chk(weights, (nprob, m), "weights")
+        accel = torch.empty((nprob, n), dtype=torch.float64, device=xjack.device)
+        njack = torch.empty((nprob,), dtype=torch.int32, device=xjack.device)
+        self._call("nlh_boot_accel_batch", m, nprob, n, xjack.data_ptr(), weights.data_ptr() if weights is not None else None,
+                   accel.data_ptr(), njack.data_ptr())
+        return accel, njack
+
+    def boot_bca(self, xs, x, accel, level=0.95):
+        """(lo, hi, z0, alpha_lo, alpha_hi [nprob, n], flags [nprob, n] int32, nvalid [nprob] int32): the BCa interval of the fit
+        x [nprob, n] from the refits xs [nrep, nprob, n] and boot_accel's accel (nlh_boot_bca_batch): the quantiles of the valid
+        replicas at the levels alpha, which are the percentile levels moved by z0 -- from the share of replicas below x -- and
+        by accel.  flags: a sum of nonlin_amd.BCA_DEGENERATE (every replica on one side of x: the percentile interval),
+        BCA_NO_ACCEL (accel not finite: taken as 0), BCA_BAD_DENOM (an end's adjustment has no meaning: that end keeps its
+        percentile level) and BCA_NO_REPLICA (nothing to work with: NaN)."""
+        nrep, nprob, n = xs.shape
+        _chk(xs, (nrep, nprob, n), "xs"); _chk(x, (nprob, n), "x"); _chk(accel, (nprob, n), "accel")
+        lo, hi, z0, alo, ahi = (torch.empty((nprob, n), dtype=torch.float64, device=xs.device) for _ in range(5))
+        flags = torch.empty((nprob, n), dtype=torch.int32, device=xs.device)
+        nvalid = torch.empty((nprob,), dtype=torch.int32, device=xs.device)
+        self._call("nlh_boot_bca_batch", nrep, nprob, n, xs.data_ptr(), x.data_ptr(), accel.data_ptr(), float(level), lo.data_ptr(),
+                   hi.data_ptr(), z0.data_ptr(), alo.data_ptr(), ahi.data_ptr(), flags.data_ptr(), nvalid.data_ptr())
+        return lo, hi, z0, alo, ahi, flags, nvalid
+
     @staticmethod
     def _replicas(r, t, shared, weights, x, kw):
         """(t, weights, x, kw) of a chunk of r replicas, replica-major: what is per problem -- t unless shared, the weights, x,
@@ -488,13 +544,18 @@ class DeviceSolver:
         return (t if shared else t.repeat(1, r, 1) if t.dim() == 3 else t.repeat(r, 1),
                 weights.repeat(r, 1) if weights is not None else None, x.repeat(r, 1), kw._replace(loss=loss, conv=conv))
 
-    def _boot_fit(self, model, t, y, x, boot, weights, kw):
+    def _boot_fit(self, model, t, y, x, boot, weights, kw, sigma=None):
         """The one-call bootstrap behind curve_boot_batch and expr_boot_batch: the fitted values -- model.eval(x, t), through
         conv_apply with conv --, then chunks of replicas whose y* stays within 256 MiB (the environment variable
         NLH_BOOT_REPS, read at every call, sets the replicas of a chunk instead: tests), each chunk one _fit call without
         covariance from x repeated, and the summary of what the fits returned, NaN where a fit's status is not 0.  A
         PoissonBootstrap takes boot_poisson's replicas and passes stat on to the refits; the refits of a problem with a bad
-        fitted value are set to NaN on the device."""
+        fitted value are set to NaN on the device.
+        boot.interval "percentile" makes exactly these calls.  "student": the refits run with covariance, their sigma is kept
+        (NaN where the status is not 0), and boot_student replaces lo and hi.  "bca": after the replicas the m delete-one
+        refits of every data set run through the same _fit from x, in chunks of deletions by the same rule -- y and what is per
+        problem repeated as for replicas, the weights boot_jackknife's (of the caller's weights, or mask) --, then boot_accel
+        and boot_bca.  Both return summary's mean, sd and nvalid, and a dict of what they computed on the way."""
         nprob, m, shared = model.data(t, y, weights)
         n, stat, group, conv = model.n, kw.stat, kw.group, kw.conv
         pois = isinstance(boot, _lib.PoissonBootstrap)
@@ -508,7 +569,12 @@ class DeviceSolver:
         pairs = not pois and boot.kind == _lib.BOOT_PAIRS
         if pairs and conv is not None:
             raise ValueError('kind "pairs" excludes conv: a convolution needs every row')
+        kind = getattr(boot, "interval", "percentile")
+        if kind == "student" and sigma is None:
+            raise ValueError('interval "student" needs sigma=: the standard errors [nprob, n] of the fit x')
         _chk(x, (nprob, n), "x")
+        if kind == "student":
+            _chk(sigma, (nprob, n), "sigma")
         mu = None
         if not pairs:
             mu = model.eval(x, t)
@@ -518,8 +584,9 @@ class DeviceSolver:
         env = os.environ.get("NLH_BOOT_REPS")
         if env is not None and int(env) >= 1:
             per = int(env)
-        refit = kw._replace(covariance=False, group=None)
+        refit = kw._replace(covariance=kind == "student", group=None)
         xs = torch.empty((boot.nrep, nprob, n), dtype=torch.float64, device=y.device)
+        sigs = torch.empty_like(xs) if kind == "student" else None
         for rep0 in range(0, boot.nrep, per):
             r = min(per, boot.nrep - rep0)
             if pois:
@@ -530,12 +597,30 @@ class DeviceSolver:
             out = self._fit(model, tc, shared, ystar.reshape(r * nprob, m), wstar.reshape(r * nprob, m) if pairs else wc, xc, kc)
             bad = torch.tensor([s != 0 for s in out[7]], dtype=torch.bool, device=y.device)
             xs[rep0:rep0 + r] = out[0].masked_fill(bad[:, None], float("nan")).reshape(r, nprob, n)
+            if sigs is not None:
+                sigs[rep0:rep0 + r] = out[2].masked_fill(bad[:, None], float("nan")).reshape(r, nprob, n)
             if pois:                                                 # a problem with a bad fitted value has no valid replica
                 xs[rep0:rep0 + r].masked_fill_((nbad > 0)[None, :, None], float("nan"))
-        return self.boot_summary(xs, boot.level) + (xs,)
+        summary = self.boot_summary(xs, boot.level)
+        if kind == "percentile":
+            return summary + (xs,)
+        if kind == "student":
+            lo, hi, nvalid_t = self.boot_student(xs, sigs, x, sigma, boot.level)
+            return (lo, hi) + summary[2:] + (xs, dict(sigs=sigs, nvalid_t=nvalid_t))
+        xjack = torch.empty((m, nprob, n), dtype=torch.float64, device=y.device)
+        for row0 in range(0, m, per):
+            r = min(per, m - row0)
+            wj = self.boot_jackknife(weights, nprob, m, row0, r)
+            tc, _, xc, kc = self._replicas(r, t, shared, None, x, refit)
+            out = self._fit(model, tc, shared, y.repeat(r, 1), wj.reshape(r * nprob, m), xc, kc)
+            bad = torch.tensor([s != 0 for s in out[7]], dtype=torch.bool, device=y.device)
+            xjack[row0:row0 + r] = out[0].masked_fill(bad[:, None], float("nan")).reshape(r, nprob, n)
+        accel, njack = self.boot_accel(xjack, weights)
+        lo, hi, z0, alo, ahi, flags, _ = self.boot_bca(xs, x, accel, boot.level)
+        return (lo, hi) + summary[2:] + (xs, dict(xjack=xjack, njack=njack, accel=accel, z0=z0, alpha_lo=alo, alpha_hi=ahi, flags=flags))
 
     def curve_boot_batch(self, kind, t, y, x, boot, ncomp=1, baseline=-1, weights=None, lower=None, upper=None, analytic=True,
-                         opts=None, pmap=None, loss=None, stat=None, group=None, conv=None, sep=None):
+                         opts=None, pmap=None, loss=None, stat=None, group=None, conv=None, sep=None, sigma=None):
         """The bootstrap of curve_fit_batch's fit x [nprob, n] of the data t, y (a Bootstrap: nlh_boot_resample_batch, the fit
         itself, nlh_boot_summary_batch): boot.nrep replicas of every data set are made from the fitted values and the data,
         each is fitted exactly as the keywords say -- the caller's bounds, pmap, loss, conv and sep, started from x, without
@@ -547,15 +632,25 @@ class DeviceSolver:
         Counts: boot a PoissonBootstrap together with stat=Poisson() (nlh_boot_poisson_batch) -- the replicas are counts drawn
         from Poisson(fitted values), each refitted with stat and the caller's bounds, pmap, conv and mask; a problem whose
         fitted values hold a NaN, a negative value or one above 2^24 on an unmasked row comes back with nvalid 0 and NaN.  A
-        PoissonBootstrap without stat=, or with group=, raises ValueError."""
+        PoissonBootstrap without stat=, or with group=, raises ValueError.
+        boot.interval (of either kind of boot) chooses the interval; "percentile" is everything above.  "student": sigma= is
+        required -- the fit's own standard errors [nprob, n], curve_fit_batch's sigma; without it ValueError --, every refit
+        runs WITH covariance, and lo, hi are the bootstrap-t interval x - T sigma from the quantiles T of (x* - x)/sigma* over
+        the replicas whose sigma* is finite and > 0 (a fixed parameter of a pmap has none: NaN).  "bca": after the replicas
+        every data set is refitted m more times, each with one row's weight (or mask entry) set to 0 -- m extra fits per data
+        set, so the cost grows with the SQUARE of m: 128 rows at 200 replicas make 328 fits per data set --, and lo, hi are
+        the quantiles at the bias-corrected and accelerated levels.  Both return (lo, hi, mean, sd, nvalid, xs, info): mean,
+        sd and nvalid are the summary's, info a dict -- sigs [nrep, nprob, n] and nvalid_t [nprob, n] for "student"; xjack
+        [m, nprob, n], njack [nprob], accel, z0, alpha_lo, alpha_hi and flags [nprob, n] (BCA_* bits) for "bca".  conv= is
+        allowed with both: a zero weight removes a row of the residual, not of the convolution."""
         return self._boot_fit(self._curve_model(kind, ncomp, baseline), t, y, x, boot, weights,
-                              _Keywords(lower, upper, analytic, False, opts, pmap, loss, stat, group, conv, sep))
+                              _Keywords(lower, upper, analytic, False, opts, pmap, loss, stat, group, conv, sep), sigma)
 
     def expr_boot_batch(self, expr, t, y, x, boot, weights=None, lower=None, upper=None, analytic=True, opts=None, pmap=None,
-                        loss=None, stat=None, group=None, conv=None, sep=None):
+                        loss=None, stat=None, group=None, conv=None, sep=None, sigma=None):
         """curve_boot_batch with an Expr in the place of (kind, ncomp, baseline): the bootstrap of expr_fit_batch's fit x."""
         return self._boot_fit(self._expr_model(expr), t, y, x, boot, weights,
-                              _Keywords(lower, upper, analytic, False, opts, pmap, loss, stat, group, conv, sep))
+                              _Keywords(lower, upper, analytic, False, opts, pmap, loss, stat, group, conv, sep), sigma)
 
     @staticmethod
     def _fit_outputs(x0, m, covariance, nsolve, nunk):
